@@ -19,9 +19,20 @@ Other workloads print their OWN line (never mixed into the headline metric):
   --workload resnet  the ResNet-152 feature extractor of the step: crops/s of the batched trunk
   --workload fcmf-large  BASELINE configs[4] geometry (XLM-R-large, seq 256, 100 ROIs); --dtype fp8 = its e4m3 MFMA path, bf16 for comparison
 
-One JSON line on stdout (rank 0).  `roofline` describes the dominant kernel (the bf16 MFMA GEMM family):
-achieved = executed GEMM FLOPs / summed launch durations measured with HIP events on the launch stream during the
-last timed step.  `cpu_baseline` times the CPU oracle (a port, not the product) on config C0 (B=4) on this host.
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times exactly --steps steps and prints the line; the
+figures below take extra work and are measured only with --full (null or absent otherwise):
+  `roofline`      the dominant kernel (the bf16 MFMA GEMM family): achieved = executed GEMM FLOPs / summed launch
+                  durations measured with HIP events on the launch stream during the last timed step
+  `h2d*`, `*_with_h2d`  (fcmf, single GPU) extra steps fed through the drivers' DevicePrefetcher from pageable host batches
+  `cpu_baseline`  (fcmf, single GPU, unless --no-cpu-baseline) the CPU oracle (a port, not the product) on config C0 (B=4)
+
+--dump-outputs DIR writes, as DIR/<name>.npy (float32; a fixed, seeded sample of the larger arrays), what the timed step
+function computes from inputs that are the same in every run: for the training workloads it runs the step on a fresh copy
+of the seeded initial state up to the first step with a learning rate above 0 (see replay_until_learning) and writes that
+step's loss, logits (fcmf), and every trainable parameter after its AdamW update with the step's gradient, at up to 4096
+seeded positions each (`param_sample`, `grad_sample`); resnet, a forward pass over weights that never change, writes the
+trunk features of its last timed step, which has those same inputs.  Two runs or builds with the same arguments can be
+compared output for output.
 """
 import argparse
 import glob
@@ -31,6 +42,7 @@ import os
 import sys
 import tempfile
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(ROOT, "multimodal-aspect-category-sentiment-analysis_amd")
@@ -164,8 +176,10 @@ def gemm_roofline(trace):
 
 
 def timed_loop(step, args, world, dev, trace=True):
-    """W warm-up steps, then EXACTLY K steps between barrier + synchronize pairs; MAX over ranks"""
+    """W warm-up steps, then EXACTLY K steps between barrier + synchronize pairs; MAX over ranks.  The GEMM trace of the
+    last timed step (the roofline) is taken with --full only."""
     from fcmf_framework import ops
+    trace = trace and args.full
     for _ in range(args.warmup):
         step()
     if world > 1:
@@ -189,6 +203,65 @@ def timed_loop(step, args, world, dev, trace=True):
     return dt, tr, out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+PARAM_SAMPLE = 4096
+
+
+def seeded_sample(t, n, seed):
+    """t flattened, or n of its elements at fixed seeded positions (sorted) when it holds more"""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= n:
+        return flat
+    idx = torch.randint(flat.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def param_samples(model):
+    """every trainable parameter and its gradient (zeros where the step produced none), at up to PARAM_SAMPLE positions each
+    (registration order; positions seeded by the parameter's name), concatenated"""
+    ps, gs = [], []
+    for name, p in model.named_parameters():
+        if p.requires_grad:
+            seed = zlib.crc32(name.encode())
+            ps.append(seeded_sample(p, PARAM_SAMPLE, seed).float())
+            gs.append(seeded_sample(p.grad if p.grad is not None else torch.zeros_like(p), PARAM_SAMPLE, seed).float())
+    return {"param_sample": torch.cat(ps), "grad_sample": torch.cat(gs)}
+
+
+def replay_until_learning(opt, step):
+    """--dump-outputs: run `step` on a fresh copy of the seeded initial state up to and including the first step whose learning
+    rate is not 0 (the linear warmup starts at 0), and return what that step returned: its update moves the parameters.
+    Not the last timed step: the parameter-gradient reductions accumulate with float atomics, and AdamW amplifies their
+    rounding differences along the timed trajectory, so its later steps never see the same inputs twice."""
+    while True:
+        lr = max(g["lr"] for g in opt.param_groups)
+        out = step()
+        if lr > 0:
+            return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 (float64 stays float64)"""
+    import numpy as np
+    out = {k: (t.detach().double() if t.dtype == torch.float64 else t.detach().float()).cpu().numpy() for k, t in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def fcmf_initial_model(cfg, NI, NR):
+    """the benchmark's seeded, random-init FCMF, on the CPU"""
+    from fcmf_framework.fcmf_multimodal import FCMF
+    from fcmf_framework.roberta import RobertaConfig, RobertaModel
+    torch.manual_seed(42)
+    with tempfile.TemporaryDirectory(prefix="hf_") as hf:      # read once, by the constructor
+        RobertaModel(RobertaConfig(**cfg)).save_pretrained(hf)
+        return FCMF(hf, num_labels=4, num_imgs=NI, num_roi=NR)
+
+
 # ---------------------------------------------------------------------------------------
 LARGE_CFG = dict(vocab_size=250002, hidden_size=1024, num_hidden_layers=24, num_attention_heads=16,
                  intermediate_size=4096, max_position_embeddings=514, type_vocab_size=1, pad_token_id=1,
@@ -199,57 +272,66 @@ def run_fcmf(args, rank, world, dev, large=False):
     import synthetic_data as synth
     from fcmf_framework import ops
     from fcmf_framework.dp import GradArena, GradReducer
-    from fcmf_framework.fcmf_multimodal import FCMF
     from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup
-    from fcmf_framework.roberta import RobertaConfig, RobertaModel
 
     CFG = LARGE_CFG if large else BASE_CFG
     S, NI, NR, A, B = (256, 7, 100, 6, args.batch) if large else (128, 7, 36, 6, args.batch)
-    torch.manual_seed(42)
-    hf = tempfile.mkdtemp(prefix="hf_")
-    RobertaModel(RobertaConfig(**CFG)).save_pretrained(hf)
-    model = FCMF(hf, num_labels=4, num_imgs=NI, num_roi=NR).to(dev)
-    model.train(not args.no_dropout)
-    ops.manual_seed(42 + rank)
-    ops.set_compute_dtype(torch.float32 if args.dtype == "fp32" else torch.bfloat16)
-    ops.set_fp8(args.dtype == "fp8")     # forward + dX GEMMs on e4m3 operands (BASELINE configs[4]); everything else as in bf16
-    opt = FusedAdamW(param_groups(model), lr=7e-4)
-    sched = get_linear_schedule_with_warmup(opt, int(0.1 * 1000), 1000)
-    red = arena = None
-    if world > 1 or args.dp_one_rank or not args.no_arena:
-        arena = GradArena.for_model(model)     # as run_multimodal_fcmf.py does (leaves out bert.cell.pooler: it never gets a gradient)
-        if world > 1 or args.dp_one_rank:
-            red = GradReducer(arena, exchange=args.dp_exchange, native=args.dp_native, group_mb=args.dp_group_mb,
-                              single_rank=args.dp_one_rank)
-            red.broadcast_parameters(0)
-    host = synth.synth_batch(B, CFG, S=S, num_imgs=NI, num_roi=NR, num_aspects=A, seed=42 + rank)
-    batch = {k: v.to(dev) for k, v in host.items()}
 
-    def step(batch=batch):
-        if arena is not None:
-            arena.zero()
-        else:
-            opt.zero_grad(set_to_none=True)
-        logits = model.forward_aspects(batch["input_ids"], batch["visual_embeds_att"], batch["roi_embeds_att"],
-                                       batch["roi_coors"], batch["token_type_ids"], batch["attention_mask"],
-                                       batch["added_attention_mask"])
-        loss = model.loss_aspects(logits, batch["labels"])
-        loss.backward()
-        if red is not None:
-            red.finish()
-        opt.step(max_grad_norm=1.0)
-        sched.step()
-        return loss
+    def setup():
+        """the benchmark's seeded initial state (model, optimizer, schedule, gradient arena, batch) and its training step"""
+        model = fcmf_initial_model(CFG, NI, NR).to(dev)
+        model.train(not args.no_dropout)
+        ops.manual_seed(42 + rank)
+        ops.set_compute_dtype(torch.float32 if args.dtype == "fp32" else torch.bfloat16)
+        ops.set_fp8(args.dtype == "fp8")     # forward + dX GEMMs on e4m3 operands (BASELINE configs[4]); everything else as in bf16
+        opt = FusedAdamW(param_groups(model), lr=7e-4)
+        sched = get_linear_schedule_with_warmup(opt, int(0.1 * 1000), 1000)
+        red = arena = None
+        if world > 1 or args.dp_one_rank or not args.no_arena:
+            arena = GradArena.for_model(model)     # as run_multimodal_fcmf.py does (leaves out bert.cell.pooler: it never gets a gradient)
+            if world > 1 or args.dp_one_rank:
+                red = GradReducer(arena, exchange=args.dp_exchange, native=args.dp_native, group_mb=args.dp_group_mb,
+                                  single_rank=args.dp_one_rank)
+                red.broadcast_parameters(0)
+        host = synth.synth_batch(B, CFG, S=S, num_imgs=NI, num_roi=NR, num_aspects=A, seed=42 + rank)
+        batch = {k: v.to(dev) for k, v in host.items()}
 
+        def step(batch=batch):
+            if arena is not None:
+                arena.zero()
+            else:
+                opt.zero_grad(set_to_none=True)
+            logits = model.forward_aspects(batch["input_ids"], batch["visual_embeds_att"], batch["roi_embeds_att"],
+                                           batch["roi_coors"], batch["token_type_ids"], batch["attention_mask"],
+                                           batch["added_attention_mask"])
+            loss = model.loss_aspects(logits, batch["labels"])
+            loss.backward()
+            if red is not None:
+                red.finish()
+            opt.step(max_grad_norm=1.0)
+            sched.step()
+            return loss, logits
+        return model, opt, step, red, host
+
+    def dump():
+        """--dump-outputs, on every rank (the step may hold collectives): see replay_until_learning"""
+        m, o, st, _, _ = setup()
+        loss, logits = replay_until_learning(o, st)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dict(loss=loss.reshape(1), logits=logits, **param_samples(m)))
+
+    model, _, step, red, host = setup()
     from fcmf_framework.ops import deferred_dw
     dw0 = (deferred_dw.batched_launches, deferred_dw.batched_matrices)
-    dt, trace, loss = timed_loop(step, args, world, dev)
+    dt, trace, (loss, _) = timed_loop(step, args, world, dev)
     comm = red.stats() if red is not None else None
     if comm is not None:
         n = max(1, args.steps)
         comm["dw_batched_launches_per_step"] = round((deferred_dw.batched_launches - dw0[0]) / n, 1)
         comm["dw_matrices_per_batched_launch"] = round((deferred_dw.batched_matrices - dw0[1]) / max(1, deferred_dw.batched_launches - dw0[0]), 2)
     if rank != 0:
+        if args.dump_outputs:
+            dump()
         return None
     # host -> HBM: (1) the bare copy of one batch from pinned memory; (2) the step loop fed through the drivers' DevicePrefetcher --
     # every step consumes a FRESH host batch (pinned producer buffers, copy stream, one batch ahead): `value_with_h2d` is that
@@ -258,7 +340,7 @@ def run_fcmf(args, rank, world, dev, large=False):
     #  rehearsal of round 3 caught rank 0 waiting for them here)
     h2d_ms = ms_step_pf = None
     n_pf = max(3, min(args.steps, 8))
-    if world == 1:
+    if world == 1 and args.full:
         from device_prefetch import DevicePrefetcher
         pinned = {k: v.pin_memory() for k, v in host.items()}
         torch.cuda.synchronize()
@@ -306,7 +388,7 @@ def run_fcmf(args, rank, world, dev, large=False):
         "value_with_h2d": None if ms_step_pf is None else round(world * B / (ms_step_pf * 1e-3), 2),
         "ms_per_step_with_h2d": None if ms_step_pf is None else round(ms_step_pf, 2),
         "h2d": (f"{n_pf} steps, each on a PAGEABLE host batch through device_prefetch.DevicePrefetcher (worker thread copies it into the pinned staging ring, copy stream, one batch ahead; timed after the ring is allocated)"
-                if world == 1 else "measured on single-GPU runs only"),
+                if ms_step_pf is not None else "measured with --full on single-GPU runs only"),
         "roofline": gemm_roofline(trace),
     }
     if comm is not None:
@@ -314,8 +396,10 @@ def run_fcmf(args, rank, world, dev, large=False):
         dwk = (rl.get("per_kernel") or {}).get("gemm_bf16_dw_batched_kernel")
         comm["dw_batched_tflops"] = dwk["tflops"] if dwk else None      # the batched weight-gradient kernel keeps running under DP
         out["dp"] = comm
-    if world == 1 and not args.no_cpu_baseline and not large:
+    if args.full and world == 1 and not args.no_cpu_baseline and not large:
         out["cpu_baseline"] = cpu_baseline()
+    if args.dump_outputs:
+        dump()
     return out
 
 
@@ -330,44 +414,58 @@ def run_iaog(args, rank, world, dev):
     from fcmf_framework.roberta import RobertaConfig, RobertaModel
     cfg = BASE_CFG
     V, NI, NR, B, S, Ld = cfg["vocab_size"], 7, 4, args.batch, 128, args.dec_len
-    hf = tempfile.mkdtemp(prefix="hf_")
-    torch.manual_seed(42)
-    RobertaModel(RobertaConfig(**cfg)).save_pretrained(hf)
-    ops.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
-    ops.manual_seed(42 + rank)
-    model = FCMFSeq2Seq(V, 20, hf, NI, NR, 1.0)
-    model.decoder.embedding = torch.nn.Embedding(V, model.decoder.num_hiddens)       # run_pretraining_fcmf.py:189
-    model = model.to(dev).train(not args.no_dropout)
-    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
-    opt = FusedAdamW([{'params': [p for n, p in named if not any(nd in n for nd in NO_DECAY)], 'weight_decay': 1e-5},
-                      {'params': [p for n, p in named if any(nd in n for nd in NO_DECAY)], 'weight_decay': 0.0}], lr=3e-5)
-    arena = GradArena.for_model(model)      # one memset per step instead of a zero fill per weight gradient
-    red = None
-    if world > 1 or args.dp_one_rank:
-        red = GradReducer(arena, exchange=args.dp_exchange, native=args.dp_native, group_mb=args.dp_group_mb,
-                          single_rank=args.dp_one_rank)
-        red.broadcast_parameters(0)
-    b = synth.synth_batch(B, cfg, S=S, num_imgs=NI, num_roi=NR, num_aspects=1, seed=3 + rank, coord_dtype=torch.float32)
-    b = {k: v.to(dev) for k, v in b.items()}
-    dec = torch.randint(3, V, (B, Ld), generator=torch.Generator().manual_seed(1 + rank)).to(dev)
-    lab = torch.roll(dec, -1, dims=1)
-    lab[:, -1] = -100
 
-    def step():
-        if arena is not None:
-            arena.zero()
-        else:
-            opt.zero_grad(set_to_none=True)
-        loss = model.forward_loss(b["input_ids"][:, 0], dec, lab, b["visual_embeds_att"], b["roi_embeds_att"], b["roi_coors"],
-                                  b["token_type_ids"][:, 0], b["attention_mask"][:, 0], b["added_attention_mask"][:, 0])
-        loss.backward()
-        if red is not None:
-            red.finish()
-        opt.step(max_grad_norm=1.0)
-        return loss
+    def setup():
+        """the benchmark's seeded initial state and its training step"""
+        with tempfile.TemporaryDirectory(prefix="hf_") as hf:      # read once, by the constructor
+            torch.manual_seed(42)
+            RobertaModel(RobertaConfig(**cfg)).save_pretrained(hf)
+            ops.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
+            ops.manual_seed(42 + rank)
+            model = FCMFSeq2Seq(V, 20, hf, NI, NR, 1.0)
+        model.decoder.embedding = torch.nn.Embedding(V, model.decoder.num_hiddens)       # run_pretraining_fcmf.py:189
+        model = model.to(dev).train(not args.no_dropout)
+        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+        opt = FusedAdamW([{'params': [p for n, p in named if not any(nd in n for nd in NO_DECAY)], 'weight_decay': 1e-5},
+                          {'params': [p for n, p in named if any(nd in n for nd in NO_DECAY)], 'weight_decay': 0.0}], lr=3e-5)
+        arena = GradArena.for_model(model)      # one memset per step instead of a zero fill per weight gradient
+        red = None
+        if world > 1 or args.dp_one_rank:
+            red = GradReducer(arena, exchange=args.dp_exchange, native=args.dp_native, group_mb=args.dp_group_mb,
+                              single_rank=args.dp_one_rank)
+            red.broadcast_parameters(0)
+        b = synth.synth_batch(B, cfg, S=S, num_imgs=NI, num_roi=NR, num_aspects=1, seed=3 + rank, coord_dtype=torch.float32)
+        b = {k: v.to(dev) for k, v in b.items()}
+        dec = torch.randint(3, V, (B, Ld), generator=torch.Generator().manual_seed(1 + rank)).to(dev)
+        lab = torch.roll(dec, -1, dims=1)
+        lab[:, -1] = -100
 
+        def step():
+            if arena is not None:
+                arena.zero()
+            else:
+                opt.zero_grad(set_to_none=True)
+            loss = model.forward_loss(b["input_ids"][:, 0], dec, lab, b["visual_embeds_att"], b["roi_embeds_att"], b["roi_coors"],
+                                      b["token_type_ids"][:, 0], b["attention_mask"][:, 0], b["added_attention_mask"][:, 0])
+            loss.backward()
+            if red is not None:
+                red.finish()
+            opt.step(max_grad_norm=1.0)
+            return loss
+        return model, opt, step, red
+
+    def dump():
+        """--dump-outputs, on every rank (the step may hold collectives): see replay_until_learning"""
+        m, o, st, _ = setup()
+        replay_loss = replay_until_learning(o, st)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dict(loss=replay_loss.reshape(1), **param_samples(m)))
+
+    model, _, step, red = setup()
     dt, trace, loss = timed_loop(step, args, world, dev)
     comm = red.stats() if red is not None else None
+    if args.dump_outputs:
+        dump()
     if rank != 0:
         return None
     return {
@@ -403,6 +501,8 @@ def run_resnet(args, rank, world, dev):
     dt, trace, y = timed_loop(step, args, world, dev)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"features": seeded_sample(y, 1 << 22, 0)})      # [B*NI, 49, 2048]: 16 MB of it
     crops = NI * B
     gflop_per_crop = 2 * 11.51         # ResNet-152 forward at 224x224: 11.5 GMACs (He et al. 2016 table 1: 11.3e9 FLOPs = MACs)
     ms = dt / args.steps * 1e3
@@ -473,7 +573,12 @@ def main():
     ap.add_argument("--dec_len", type=int, default=12, help="IAOG decoder length")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp8"],
                     help="fp8: e4m3 forward / dX GEMMs (v_mfma_scale_f32_16x16x128_f8f6f4) with bf16 weight-gradient GEMMs: --workload fcmf-large")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (GEMM trace of the last timed step), "
+                         "host-to-device steps through the prefetcher, CPU baseline")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write what the step computes from the seeded initial state to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-dropout", action="store_true")
     ap.add_argument("--no-arena", dest="no_arena", action="store_true",
                     help="single GPU: per-weight gradient tensors instead of the flat gradient arena the drivers use (always on for --gpus > 1)")
@@ -491,6 +596,8 @@ def main():
     ap.add_argument("--launch-check", dest="launch_check", action="store_true",
                     help="only the N-rank rendezvous + one collective, no GPU work (CPU test of the launch path)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: one process per GPU, started here (before anything touches the GPU)

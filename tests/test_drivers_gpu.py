@@ -256,3 +256,47 @@ def test_bench_over_rccl_prints_exactly_one_json_line(dev):
     dp = doc["dp"]
     assert dp["buckets"] >= 10 and 2 <= dp["launch_groups"] < dp["buckets"] and dp["exposed_comm_ms_per_step"] is not None
     assert doc["value"] > 0 and doc["loss"] == doc["loss"]
+
+
+def test_bench_plain_run_full_run_and_dumped_outputs(tmp_path, dev):
+    """a plain `bench.py` line times the steps and nothing else (no GEMM trace, no host-to-device steps, no CPU baseline);
+    --full adds them.  --dump-outputs writes float32 .npy files of the training step replayed on a fresh copy of the seeded
+    initial state up to the first step with a learning rate above 0: two runs dump the same forward (bitwise) and gradients /
+    updated parameters that differ only by the reduction order of the float atomics, and the AdamW update has moved the
+    parameters away from their initial values"""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    docs, dumps = {}, {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        d = tmp_path / mode
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8",
+                            "--dump-outputs", str(d)] + extra, env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = r.stdout.strip().splitlines()
+        assert len(out) == 1 and out[0].startswith("{"), r.stdout[:2000]
+        docs[mode] = json.loads(out[0])
+        dumps[mode] = {f[:-len(".npy")]: np.load(d / f) for f in os.listdir(d)}
+    p, f = docs["plain"], docs["full"]
+    assert p["steps"] == 2 and p["warmup"] == 1 and p["ms_per_step"] > 0 and p["value"] > 0
+    assert p["roofline"] is None and p["value_with_h2d"] is None and "cpu_baseline" not in p
+    assert f["roofline"]["launches"] > 0 and f["value_with_h2d"] > 0
+    a, b = dumps["plain"], dumps["full"]
+    assert sorted(a) == sorted(b) == ["grad_sample", "logits", "loss", "param_sample"]
+    assert a["logits"].shape == (8, 6, 4) and a["loss"].shape == (1,) and a["param_sample"].shape == a["grad_sample"].shape
+    for k in a:
+        assert a[k].dtype == np.float32 and a[k].shape == b[k].shape and np.isfinite(a[k]).all(), k
+    assert np.array_equal(a["loss"], b["loss"]) and np.array_equal(a["logits"], b["logits"])
+    ga, gb = a["grad_sample"], b["grad_sample"]
+    assert np.abs(ga - gb).max() <= 1e-4 * np.abs(gb).max()
+    # the dumped step's learning rate is the schedule's second, at most 7e-4 / 100: an AdamW update at its second step is at
+    # most ~1.4 x that, so two runs differ by less than two opposite updates
+    assert np.abs(a["param_sample"] - b["param_sample"]).max() <= 2e-5
+    import bench
+    p0 = bench.param_samples(bench.fcmf_initial_model(bench.BASE_CFG, 7, 36))["param_sample"].numpy()
+    moved = np.abs(a["param_sample"] - p0)
+    assert p0.shape == a["param_sample"].shape
+    assert (moved > 0).mean() > 0.5 and moved.max() <= 1e-4, ((moved > 0).mean(), moved.max())

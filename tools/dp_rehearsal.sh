@@ -5,6 +5,6 @@
 # step, one JSON line from rank 0, exit code 0.
 #   tools/dp_rehearsal.sh [workload] [tag]  ->  gpurun_out/<tag>_dp2_gloo_rehearsal_<workload>.json
 W=${1:-fcmf}; TAG=${2:-r04}
-FCMF_BENCH_SINGLE_DEVICE=1 timeout -k 10 500 python bench.py --workload $W --gpus 2 --steps 3 --warmup 1 --backend gloo --no-cpu-baseline \
+FCMF_BENCH_SINGLE_DEVICE=1 timeout -k 10 500 python bench.py --full --workload $W --gpus 2 --steps 3 --warmup 1 --backend gloo --no-cpu-baseline \
   > gpurun_out/${TAG}_dp2_gloo_rehearsal_$W.json 2> gpurun_out/${TAG}_dp2_$W.err
 echo "rc $?"

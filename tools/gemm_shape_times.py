@@ -1,5 +1,5 @@
 """Diagnostic: every distinct (kernel, M, N, K, epilogue) GEMM of one benchmark step with its launches and summed HIP-event time
-(the weight-gradient GEMMs that go through ops.deferred_dw are launched by its flush, not here: see bench.py's per_kernel line).
+(the weight-gradient GEMMs that go through ops.deferred_dw are launched by its flush, not here: see the per_kernel table of `bench.py --full`).
 python tools/gemm_shape_times.py [bench args]  ->  stderr"""
 import importlib
 import os

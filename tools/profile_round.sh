@@ -17,5 +17,5 @@ rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmcW_$TAG 
 python3 $ROOT/tools/pmc_traffic.py $(find $OUT/pmcF_$TAG -name "*counter_collection.csv" | head -1) $(find $OUT/pmcW_$TAG -name "*counter_collection.csv" | head -1) > $OUT/${TAG}_pmc_traffic.json
 rm -rf $OUT/prof_$TAG $OUT/pmcF_$TAG $OUT/pmcW_$TAG
 cd $ROOT
-python3 bench.py --steps 20 --warmup 3 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --full --steps 20 --warmup 3 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 echo done

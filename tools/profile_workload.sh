@@ -8,7 +8,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_$W -o $
 cp $(find $OUT/prof_${TAG}_$W -name "${TAG}_kernel_stats.csv" | head -1) $OUT/${TAG}_${W}_kernel_stats.csv
 rm -rf $OUT/prof_${TAG}_$W
 cd $ROOT
-python3 bench.py --workload $W "$@" > $OUT/${TAG}_bench_$W.json 2> $OUT/${TAG}_bench_$W.err
+python3 bench.py --full --workload $W "$@" > $OUT/${TAG}_bench_$W.json 2> $OUT/${TAG}_bench_$W.err
 python3 - $OUT/${TAG}_${W}_kernel_stats.csv <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
