@@ -274,6 +274,17 @@ def maxpool3x3s2_nhwc(x):
     return y
 
 
+def maxpool3x3s2_bwd_nhwc(x, dy):
+    """gradient of maxpool3x3s2_nhwc: dy [N, Ho, Wo, C] -> dx [N, H, W, C]; each window's gradient goes to its FIRST maximum
+    (scan order r, then s: torch's tie rule)"""
+    N, Hh, Ww, C = x.shape
+    if dy.shape != (N, (Hh - 1) // 2 + 1, (Ww - 1) // 2 + 1, C) or dy.dtype != x.dtype or not (x.is_contiguous() and dy.is_contiguous()):
+        raise H.HipLibraryError(f"maxpool3x3s2_bwd_nhwc: dy {tuple(dy.shape)} {dy.dtype} does not match x {tuple(x.shape)} {x.dtype}")
+    dx = torch.empty_like(x)
+    H.check(H.lib().fcmf_maxpool3x3s2_bwd(H.ptr(x), H.ptr(dy), H.ptr(dx), N, Hh, Ww, C, H.dt(x), H.stream()), "fcmf_maxpool3x3s2_bwd")
+    return dx
+
+
 def adaptive_avgpool_nhwc(x, oh, ow, tokens=False):
     """float32 [N, C, oh, ow] (tokens=False: the reference's layout) or [N, oh*ow, C] (tokens=True)"""
     N, Hh, Ww, C = x.shape
@@ -617,9 +628,7 @@ class ResNet(nn.Module):
             g = r["blk"].backward_rec(r, g, grads)
         stem = tape[0]
         z = stem["z"]
-        N, Hh, Ww, C = z.shape
-        dz = torch.empty_like(z)
-        H.check(H.lib().fcmf_maxpool3x3s2_bwd(H.ptr(z), H.ptr(g), H.ptr(dz), N, Hh, Ww, C, H.dt(z), H.stream()), "fcmf_maxpool3x3s2_bwd")
+        dz = maxpool3x3s2_bwd_nhwc(z, g)
         dy, _ = batchnorm_bwd_nhwc_(self.bn1, stem["s"], dz, stem["y"], z, grads)
         conv2d_bwd_nhwc(self.conv1, stem["v"], dy, grads, need_dx=False, src_strides=stem["v"].stride())
 

@@ -237,6 +237,7 @@ def test_fine_tune_cnn_bf16_runs_and_is_close(dev):
     cos = (a @ b / (a.norm() * b.norm())).item()
     # gradients through 22 train-mode BatchNorm backward passes with bf16 activations (each subtracts two batch means from
     # bf16-rounded gradients): the direction is preserved (measured cos 0.963), the norm to 4 digits
+    # (rounding-limited: one bf16 block is within 8e-3 of float64, test_resnet_bwd_gpu.test_bottleneck_bwd_matches_oracle_autograd)
     assert cos > 0.93 and 0.9 < (a.norm() / b.norm()).item() < 1.1, (cos, (a.norm() / b.norm()).item())
 
 
