@@ -269,6 +269,16 @@ int fcmf_xent_bwd(const void* logits, int64_t ld, const int64_t* labels, void* d
 int fcmf_xent_mean(const float* loss_rows, const int64_t* labels, int n, int64_t ignore_index,
                    float mult, float* out2, void* stream);
 
+/* torch.nn.BCEWithLogitsLoss() (mean over n x C) of the multi-label photo-category head (image_processing/
+ * run_image_categories.py:175,186), in one launch of one workgroup (classifier heads: n x C of a few thousand):
+ *   logits [n, C] of `dtype` (row stride ld elements), target float32 [n, C] (row stride ldt; may be NULL when only probs
+ *   is asked for);
+ *   loss (float32 [1], may be NULL) <- mean of max(x,0) - x*y + log1p(exp(-|x|)), summed in a fixed order in float64;
+ *   dlogits (may be NULL, `dtype`, row stride ldd) <- (sigmoid(x) - y) * (dloss ? *dloss : 1) / (n*C);
+ *   probs (float32 [n, C] dense, may be NULL) <- sigmoid(x). */
+int fcmf_bce_logits(const void* logits, int64_t ld, const float* target, int64_t ldt, int n, int C, const float* dloss,
+                    float* loss, void* dlogits, int64_t ldd, float* probs, int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Additive attention mask of a 0 / 1 int64 mask [rows, >= cols] with row stride ld (elements):
  * out[r][c] = (1 - mask[r][c]) * value as float32 [rows, cols]  (fcmf_pretraining.py:53-56,97-100,133-136: value = -10000;
@@ -471,6 +481,33 @@ int fcmf_maxpool3x3s2_bwd(const void* x, const void* dy, void* dx, int N, int H,
 /* F.adaptive_avg_pool2d backward: dy float32 in the forward's output layout (0 = [N,C,oh,ow], 1 = [N,oh*ow,C]) */
 int fcmf_adaptive_avgpool_bwd(const float* dy, void* dx, int N, int H, int W, int C, int oh, int ow, int layout,
                               int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Crop + antialiased resize + flip + normalise of uint8 photos (the category classifiers' preprocessing,
+ * image_processing/run_image_categories.py:35-41 and run_roi_categories.py:34-45: v2.Resize((S,S), antialias=True),
+ * RandomHorizontalFlip, ConvertImageDtype, Normalize), for a batch of crops of different photos and sizes in one call.
+ * Photos are packed into one DEVICE byte buffer `src` of `src_bytes` bytes; crop i is described by descs[i] (DEVICE array):
+ *   offset      byte offset of its photo in src;  H, W its size;  sC, sH, sW element (= byte) strides of channel, row and
+ *               column (CHW: W*H, W, 1; HWC as PIL decodes it: 1, 3*W, 3);
+ *   r0:r1, c0:c1 the crop box as the reference slices it (image[:, x1:x2, y1:y2]: the first index is rows); ends past the photo
+ *               are clipped as in a Python slice;
+ *   flip        != 0: out[..., x] = resized[..., S-1-x].
+ * out [n, 3, S, S] contiguous, float32 or bfloat16 (`dtype`) = (rint(resize(crop)) clamped to [0, 255] / 255 - mean[c]) / std[c]
+ * with resize = F.interpolate(mode="bilinear", antialias=True, align_corners=False) on the float values (review_batches.to_crop).
+ * mean / std: HOST float[3].  scratch: caller-owned DEVICE float32 of >= n * 3 * max_rows * S elements (the horizontally resampled
+ * rows); max_rows >= the clipped height of every crop.  A crop that is empty, starts below 0 or reaches past src_bytes, or is
+ * taller than max_rows, yields NaN (host wrappers reject those before the launch). */
+typedef struct {
+  int64_t offset;
+  int H, W;
+  int64_t sC, sH, sW;
+  int r0, r1, c0, c1;
+  int flip, reserved;
+} fcmf_crop_desc;
+
+int fcmf_crop_resize_normalize(const uint8_t* src, int64_t src_bytes, const fcmf_crop_desc* descs, int n, int max_rows, int S,
+                               const float* mean, const float* std, float* scratch, int64_t scratch_bytes, void* out,
+                               int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Data-parallel gradient exchange (reference: torch.distributed.init_process_group("nccl") + DistributedDataParallel,

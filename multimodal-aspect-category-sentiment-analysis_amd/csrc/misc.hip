@@ -48,6 +48,36 @@ __global__ __launch_bounds__(256) void xent_mean_kernel(const float* __restrict_
   }
 }
 
+// binary cross entropy with logits, mean over n x C (torch.nn.BCEWithLogitsLoss): ONE workgroup, so the mean is summed in a
+// fixed order (float64 per thread, then a tree); dlogits / probs ride along in the same pass
+template <typename T>
+__global__ __launch_bounds__(256) void bce_logits_kernel(const T* __restrict__ logits, int64_t ld, const float* __restrict__ target,
+                                                         int64_t ldt, int n, int C, const float* __restrict__ dloss,
+                                                         float* __restrict__ loss, T* __restrict__ dlogits, int64_t ldd,
+                                                         float* __restrict__ probs) {
+  __shared__ double ssum[256];
+  const int64_t total = (int64_t)n * C;
+  const float sc = (dloss ? *dloss : 1.0f) / (float)total;
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < total; i += 256) {
+    const int r = (int)(i / C), c = (int)(i - (int64_t)r * C);
+    const float x = to_f32<T>(logits[(int64_t)r * ld + c]), y = target ? target[(int64_t)r * ldt + c] : 0.f;
+    const float e = expf(-fabsf(x));
+    if (loss) s += (double)(fmaxf(x, 0.f) - x * y + log1pf(e));
+    const float sg = x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+    if (dlogits) dlogits[(int64_t)r * ldd + c] = from_f32<T>((sg - y) * sc);
+    if (probs) probs[i] = sg;
+  }
+  if (!loss) return;
+  ssum[threadIdx.x] = s;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) ssum[threadIdx.x] += ssum[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = (float)(ssum[0] / (double)total);
+}
+
 // additive attention mask from a 0 / 1 integer mask: out[r][c] = (mask[r][c] - 1) * (-value)  (= (1 - mask) * value)
 __global__ __launch_bounds__(256) void additive_mask_kernel(const int64_t* __restrict__ mask, int64_t ld, float* __restrict__ out,
                                                             int rows, int cols, float value) {
@@ -430,6 +460,23 @@ extern "C" int fcmf_xent_mean(const float* loss_rows, const int64_t* labels, int
   if (!loss_rows || !labels || !out2 || n < 0) return FCMF_ERR_ARG;
   hipLaunchKernelGGL(xent_mean_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), loss_rows, labels, n,
                      ignore_index, mult, out2);
+  FCMF_CHECK_LAUNCH();
+  return FCMF_OK;
+}
+
+extern "C" int fcmf_bce_logits(const void* logits, int64_t ld, const float* target, int64_t ldt, int n, int C, const float* dloss,
+                               float* loss, void* dlogits, int64_t ldd, float* probs, int dtype, void* stream) {
+  if (!logits || (!target && (loss || dlogits)) || n < 0 || C <= 0 || ld < C || (target && ldt < C) || (dlogits && ldd < C))
+    return FCMF_ERR_ARG;
+  if (n == 0) return FCMF_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (dtype == FCMF_F32)
+    hipLaunchKernelGGL((bce_logits_kernel<float>), dim3(1), dim3(256), 0, st, (const float*)logits, ld, target, ldt, n, C, dloss, loss,
+                       (float*)dlogits, ldd, probs);
+  else if (dtype == FCMF_BF16)
+    hipLaunchKernelGGL((bce_logits_kernel<bf16_t>), dim3(1), dim3(256), 0, st, (const bf16_t*)logits, ld, target, ldt, n, C, dloss, loss,
+                       (bf16_t*)dlogits, ldd, probs);
+  else return FCMF_ERR_UNSUPPORTED;
   FCMF_CHECK_LAUNCH();
   return FCMF_OK;
 }

@@ -33,6 +33,14 @@ class AttnDesc(ctypes.Structure):
     ]
 
 
+class CropDesc(ctypes.Structure):
+    """mirror of fcmf_crop_desc (64 bytes)"""
+    _fields_ = [
+        ("offset", _i64), ("H", _i), ("W", _i), ("sC", _i64), ("sH", _i64), ("sW", _i64),
+        ("r0", _i), ("r1", _i), ("c0", _i), ("c1", _i), ("flip", _i), ("reserved", _i),
+    ]
+
+
 # name -> argtypes (restype is int unless noted); must list EVERY symbol of include/fcmf_hip.h
 SIGNATURES = {
     "fcmf_abi_version": [],
@@ -69,6 +77,8 @@ SIGNATURES = {
     "fcmf_xent_fwd": [_vp, _i64, _vp, _vp, _vp, _i, _i, _i64, _i, _vp],
     "fcmf_xent_bwd": [_vp, _i64, _vp, _vp, _i64, _vp, _f, _i, _i, _i64, _i, _vp],
     "fcmf_xent_mean": [_vp, _vp, _i, _i64, _f, _vp, _vp],
+    "fcmf_bce_logits": [_vp, _i64, _vp, _i64, _i, _i, _vp, _vp, _vp, _i64, _vp, _i, _vp],
+    "fcmf_crop_resize_normalize": [_vp, _i64, _vp, _i, _i, _i, _c.POINTER(_f), _c.POINTER(_f), _vp, _i64, _vp, _i, _vp],
     "fcmf_additive_mask": [_vp, _i64, _vp, _i, _i, _f, _vp],
     "fcmf_cast": [_vp, _vp, _i64, _i, _i, _vp],
     "fcmf_cast_transpose": [_vp, _vp, _i, _i, _vp],

@@ -1447,3 +1447,51 @@ def additive_mask(m, value):
 
 def cross_entropy(logits, labels, ignore_index=-100, mult=1.0):
     return XentFn.apply(logits, labels, int(ignore_index), float(mult))
+
+
+def _rows2d(logits):
+    lg = logits if logits.stride(-1) == 1 else logits.contiguous()
+    return lg.reshape(-1, lg.shape[-1]) if lg.dim() != 2 else lg
+
+
+class BCELogitsFn(torch.autograd.Function):
+    """torch.nn.BCEWithLogitsLoss() (mean over every element) of logits [N, C] against float targets: fcmf_bce_logits, one
+    launch forward (the loss) and one backward ((sigmoid - target) * g / (N C)), no torch arithmetic"""
+
+    @staticmethod
+    def forward(ctx, logits, target):
+        lg = _rows2d(logits)
+        tg = target.reshape(lg.shape).float().contiguous()
+        H.require_cuda(lg, tg)
+        n, C = lg.shape
+        loss = torch.empty((), dtype=torch.float32, device=lg.device)
+        H.check(H.lib().fcmf_bce_logits(H.ptr(lg), lg.stride(0), H.ptr(tg), C, n, C, None, H.ptr(loss), None, C, None, H.dt(lg),
+                                        H.stream()), "fcmf_bce_logits")
+        ctx.save_for_backward(lg, tg)
+        ctx.lshape = logits.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, tg = ctx.saved_tensors
+        n, C = lg.shape
+        d = torch.empty((n, C), dtype=lg.dtype, device=lg.device)
+        gs = g.float().contiguous()
+        H.check(H.lib().fcmf_bce_logits(H.ptr(lg), lg.stride(0), H.ptr(tg), C, n, C, H.ptr(gs), None, H.ptr(d), C, None, H.dt(lg),
+                                        H.stream()), "fcmf_bce_logits")
+        return d.view(ctx.lshape), None
+
+
+def bce_with_logits(logits, target):
+    return BCELogitsFn.apply(logits, target)
+
+
+def sigmoid(logits):
+    """float32 sigmoid of [N, C] logits (evaluating a multi-label head): the `probs` output of fcmf_bce_logits"""
+    lg = _rows2d(logits.detach())
+    H.require_cuda(lg)
+    n, C = lg.shape
+    probs = torch.empty((n, C), dtype=torch.float32, device=lg.device)
+    H.check(H.lib().fcmf_bce_logits(H.ptr(lg), lg.stride(0), None, C, n, C, None, None, None, C, H.ptr(probs), H.dt(lg),
+                                    H.stream()), "fcmf_bce_logits")
+    return probs.view(logits.shape)
