@@ -7,7 +7,7 @@ The reference wraps the model in torch DDP with find_unused_parameters=True over
 * `GradArena`: every parameter's gradient is a view of ONE flat float32 buffer, laid out in the order backward
   produces gradients (reverse registration order; q/k/v weights of a fused attention block adjacent so that their
   [3H, H] weight-gradient GEMM writes one slice).  The backward kernels write straight into the slices
-  (`ops.alloc_grad`): one memset per step replaces the per-tensor zero fills, autograd adopts the slices as
+  (`ops.grad_dest`): one memset per step replaces the per-tensor zero fills, autograd adopts the slices as
   `p.grad` without copying, and a bucket of gradients is a contiguous range of the buffer.
 * `GradReducer`: all-reduces (RCCL, `torch.distributed` backend "nccl" on ROCm; gloo in the CPU tests) each bucket
   IN PLACE -- no concatenation, no copy-back -- on a side stream as soon as the last gradient of the bucket has been
@@ -27,7 +27,7 @@ class GradArena:
         """params: the parameters that receive gradients, in registration order.  blocks: lists of parameters that
         must sit next to each other, in the given order (fused q|k|v weight / bias gradients).  pad_rows: a large 2-D parameter
         whose row count is no multiple of this (the 64001-row tied vocabulary matrix) gets zeroed SLACK rows behind its slice, so
-        that the MFMA weight-gradient GEMM -- which writes whole 32-row groups -- can accumulate straight into it (`take_rows`)."""
+        that the MFMA weight-gradient GEMM -- which writes whole 32-row groups -- can accumulate straight into it (`claim(p, rows=...)`)."""
         params = [p for p in params if p.requires_grad]
         seen, uniq = set(), []
         for p in params:                      # tied parameters (decoder.dense.weight) appear once
@@ -129,75 +129,68 @@ class GradArena:
         p = self._slice_param.get(slice_ptr)
         return 0 if p is None else self.fwd_uses.get(p.data_ptr(), 0)
 
-    def take(self, param):
-        """the slice of `param` if nothing has claimed it in this step (else None: the caller uses a temporary and
-        autograd accumulates it into the slice in place)"""
+    def _resolve(self, param):
+        """the arena's parameter behind `param`, or None ("not here").  Matched by address AND element count: a [3H, H] view of
+        the fused q|k|v block shares the query weight's pointer.  Not across micro-steps of a gradient accumulation: once p.grad
+        is set, every producer of a pass must return a tensor (a temporary that autograd adds), or the post-accumulate hook that
+        drives the bucket exchange would not fire."""
         p = self._by_ptr.get(param.data_ptr())
-        # (matched by address: a [3H, H] view of the fused q|k|v block shares the query weight's pointer -- the element
-        #  count tells them apart; blocks go through take_block)
-        if p is None or p.numel() != param.numel() or id(p) in self._taken or p.grad is not None:
+        if p is None or p.numel() != param.numel() or p.grad is not None:
             return None
-        self._taken.add(id(p))
-        return self.view[id(p)]
+        return p
 
-    def retake(self, param):
-        """the slice of `param` if an EARLIER producer of this backward pass has already claimed it (a weight applied several
-        times in the forward: the fusion layer runs 7 + 1 times): the caller accumulates into it IN PLACE and hands autograd
+    def claim(self, params, rows=None):
+        """-> None ("not here": the caller uses a zero-filled temporary that autograd adds) or (buf, first).
+        params: one parameter -> buf is its slice; with `rows` (a producer that writes rows >= shape[0] rows of a 2-D parameter:
+        the padded vocabulary projection) the [rows, cols] buffer that starts at the slice and runs into its zeroed slack, None if
+        the slack does not cover it.  A list of parameters -> ONE flat buffer covering their slices, which must be adjacent in
+        the given order (fused q|k|v, the IAOG decoder's per-head weights) and all in the same state.
+        first: this call claimed the slice(s) -- the caller hands autograd aliases of them (`grad_alias`, or views of buf).  Not
+        first: an EARLIER producer of this backward pass has claimed them (a weight applied several times in the forward: the
+        fusion layer runs 7 + 1 times, the tied vocabulary matrix): the caller accumulates into buf IN PLACE and hands autograd
         `None` for this use -- the first producer's tensor, which autograd holds until every use has reported, is this very
         memory.  (Round 3 gave later producers a zero-filled temporary that autograd then added: a fill and an add launch per
-        parameter and use.)  Not across micro-steps: once p.grad is set, the first producer of a pass must return a tensor, or
-        the post-accumulate hook that drives the bucket exchange would not fire."""
-        p = self._by_ptr.get(param.data_ptr())
-        if p is None or p.numel() != param.numel() or id(p) not in self._taken or p.grad is not None:
-            return None
-        return self.view[id(p)]
-
-    def take_rows(self, param, rows):
-        """(buffer [rows, cols] starting at the slice of the 2-D `param` and running into its slack, what to hand autograd) for a
-        producer that writes `rows` >= param.shape[0] rows (the padded vocabulary projection); None if the slack does not cover it.
-        First producer of the pass: autograd gets the slice; a later one: None (accumulated in place, see retake)."""
-        p = self._by_ptr.get(param.data_ptr())
-        if p is None or p.dim() != 2 or p.numel() != param.numel() or p.grad is not None:
-            return None
-        cols = p.shape[1]
-        if (rows - p.shape[0]) * cols > self.slack.get(id(p), 0) or rows < p.shape[0]:
-            return None
-        off = self.offset[id(p)]
-        buf = self.flat[off:off + rows * cols].view(rows, cols)
-        if id(p) in self._taken:
-            return buf, None
-        self._taken.add(id(p))
-        return buf, self.view[id(p)].view_as(p)      # (a fresh alias: autograd adopts only a tensor object it alone holds)
-
-    def retake_block(self, params):
-        ps = [self._by_ptr.get(q.data_ptr()) for q in params]
-        if any(p is None or id(p) not in self._taken or p.grad is not None for p in ps):
-            return None
-        off = self.offset[id(ps[0])]
-        for a, b in zip(ps, ps[1:]):
-            if self.offset[id(b)] != self.offset[id(a)] + a.numel():
+        parameter and use.)"""
+        if isinstance(params, (list, tuple)):
+            ps = [self._resolve(q) for q in params]
+            if any(p is None for p in ps):
                 return None
-        return self.flat[off:off + sum(p.numel() for p in ps)]
+            first = id(ps[0]) not in self._taken
+            off = end = self.offset[id(ps[0])]
+            for p in ps:
+                if self.offset[id(p)] != end or (id(p) not in self._taken) != first:
+                    return None
+                end += p.numel()
+            buf = self.flat[off:end]
+        else:
+            p = self._resolve(params)
+            if p is None:
+                return None
+            ps = (p,)
+            first = id(p) not in self._taken
+            if rows is None:
+                buf = self.view[id(p)]
+            else:
+                if p.dim() != 2 or rows < p.shape[0] or (rows - p.shape[0]) * p.shape[1] > self.slack.get(id(p), 0):
+                    return None
+                off = self.offset[id(p)]
+                buf = self.flat[off:off + rows * p.shape[1]].view(rows, p.shape[1])
+        if first:
+            self._taken.update(id(p) for p in ps)
+        return buf, first
 
-    def untake(self, params):
-        """give back slices claimed by take / take_block that nothing was written to (a kernel refused the shape)"""
+    def release(self, params):
+        """give back claimed slices that nothing was written to (a kernel refused the shape)"""
         for q in params:
             p = self._by_ptr.get(q.data_ptr())
             if p is not None:
                 self._taken.discard(id(p))
 
-    def take_block(self, params):
-        """one tensor covering the adjacent slices of `params` (or None)"""
-        ps = [self._by_ptr.get(q.data_ptr()) for q in params]
-        if any(p is None or id(p) in self._taken or p.grad is not None for p in ps):
-            return None
-        off = self.offset[id(ps[0])]
-        for a, b in zip(ps, ps[1:]):
-            if self.offset[id(b)] != self.offset[id(a)] + a.numel():
-                return None
-        for p in ps:
-            self._taken.add(id(p))
-        return self.flat[off:off + sum(p.numel() for p in ps)]
+    def grad_alias(self, param, shape=None):
+        """a FRESH tensor object over the slice of `param` to hand autograd: it adopts a gradient as p.grad without a copy only
+        when it is the sole holder of the tensor object -- the arena's own view objects would be cloned"""
+        v = self.view[id(self._by_ptr[param.data_ptr()])]
+        return v.view(v.shape if shape is None else shape)
 
     def adopt(self, p):
         """make p.grad the arena slice (copying a gradient that was produced elsewhere into it)"""

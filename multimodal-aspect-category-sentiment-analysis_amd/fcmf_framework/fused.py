@@ -94,7 +94,7 @@ class _SideGemms:
 
     def __init__(self, device):
         self.dev = device
-        self.on = USE_SIDE_STREAM and ops._gemm_trace is None   # event timing assumes one stream
+        self.on = USE_SIDE_STREAM and not ops.tracing()   # event timing assumes one stream
         self.used = False
 
     def launch(self, tensors, *a, **kw):
@@ -259,45 +259,30 @@ def _post_bwd(dy, c, saved, wo, w1, w2, g1, g2, p, seeds, G, side):
     return dc, dz1
 
 
-def _grad_arena(device, Hd, I, with_qkv, params=None):
-    """all float32 gradient buffers of one layer: the parameters' slices of the step's flat gradient arena when one is
-    active (dp.GradArena: zeroed once per step), else views of ONE zero fill.  params: name -> Parameter (or the
-    [q, k, v] list for "wqkv" / "bqkv")."""
-    sizes = [("wo", (Hd, Hd)), ("w1", (I, Hd)), ("w2", (Hd, I)), ("bo", (Hd,)), ("b1", (I,)), ("b2", (Hd,)),
-             ("g1", (Hd,)), ("be1", (Hd,)), ("g2", (Hd,)), ("be2", (Hd,))]
-    if with_qkv:
-        sizes = [("wqkv", (3 * Hd, Hd)), ("bqkv", (3 * Hd,))] + sizes
-    arena = ops.grad_arena() if params is not None else None
-    out = {"_inplace": set()}       # names whose buffer is the slice an EARLIER use of the same (shared) parameter returned: autograd gets None
-    if arena is not None:
-        for n, s in sizes:
-            q = params.get(n)
-            v = None
-            if isinstance(q, (list, tuple)):
-                v = arena.take_block(q)
-                if v is None:
-                    v = arena.retake_block(q)
-                    if v is not None:
-                        out["_inplace"].add(n)
-            elif q is not None:
-                v = arena.take(q)
-                if v is None:
-                    v = arena.retake(q)
-                    if v is not None:
-                        out["_inplace"].add(n)
-            if v is not None:
-                out[n] = v.view(s)
-        sizes = [(n, s) for n, s in sizes if n not in out]
-        if not sizes:
-            return out
-    total = sum(math.prod(s) for _, s in sizes)
-    flat = torch.zeros(total, dtype=torch.float32, device=device)
-    off = 0
-    for n, s in sizes:
-        k = math.prod(s)
-        out[n] = flat[off:off + k].view(s)
-        off += k
-    return out
+def _layer_grads(device, Hd, I, params):
+    """all float32 gradient buffers of one layer.  params: name -> Parameter (or the [q, k, v] list for "wqkv" / "bqkv").
+    -> (G: name -> buffer to accumulate into, R: name -> what to hand autograd for it), both from ops.grad_dest: the
+    parameters' slices of the step's flat gradient arena when one is active (dp.GradArena: zeroed once per step); the names that
+    are not there share ONE zero fill."""
+    shapes = dict(wqkv=(3 * Hd, Hd), bqkv=(3 * Hd,), wo=(Hd, Hd), w1=(I, Hd), w2=(Hd, I), bo=(Hd,), b1=(I,), b2=(Hd,),
+                  g1=(Hd,), be1=(Hd,), g2=(Hd,), be2=(Hd,))
+    G, R = {}, {}
+    for n, q in params.items():
+        G[n], R[n] = ops.grad_dest(q, shapes[n], temp=False)
+    rest = [n for n in params if G[n] is None]
+    if rest:
+        flat = torch.zeros(sum(math.prod(shapes[n]) for n in rest), dtype=torch.float32, device=device)
+        off = 0
+        for n in rest:
+            k = math.prod(shapes[n])
+            G[n] = R[n] = flat[off:off + k].view(shapes[n])
+            off += k
+    return G, R
+
+
+def _split3(g, Hd):
+    """the fused q|k|v gradient [3H, ...] as the three parameters' gradients (None: accumulated in place)"""
+    return (None, None, None) if g is None else (g[:Hd], g[Hd:2 * Hd], g[2 * Hd:])
 
 
 class PostAttentionFn(torch.autograd.Function):
@@ -318,14 +303,13 @@ class PostAttentionFn(torch.autograd.Function):
     def backward(ctx, dy):
         c2, wo, w1, w2, g1, g2, bo, be1, b1, b2, be2, *saved = ctx.saved_tensors
         p, s0, s1, cshape, rshape = ctx.cfg
-        G = _grad_arena(c2.device, c2.shape[1], w1.shape[0], False,
-                        dict(wo=wo, w1=w1, w2=w2, bo=bo, b1=b1, b2=b2, g1=g1, be1=be1, g2=g2, be2=be2))
+        G, R = _layer_grads(c2.device, c2.shape[1], w1.shape[0],
+                            dict(wo=wo, w1=w1, w2=w2, bo=bo, b1=b1, b2=b2, g1=g1, be1=be1, g2=g2, be2=be2))
         side = _SideGemms(c2.device)
         dc, dres = _post_bwd(dy.reshape(c2.shape).contiguous(), c2, saved, wo, w1, w2, g1, g2, p, (s0, s1), G, side)
         side.join()
-        r = lambda n: None if n in G["_inplace"] else G[n]      # (accumulated in place: see dp.GradArena.retake)
-        return (dc.view(cshape), dres.view(rshape), r("wo"), r("bo"), r("g1"), r("be1"), r("w1"), r("b1"), r("w2"), r("b2"),
-                r("g2"), r("be2"), None, None, None, None)
+        return (dc.view(cshape), dres.view(rshape), R["wo"], R["bo"], R["g1"], R["be1"], R["w1"], R["b1"], R["w2"], R["b2"],
+                R["g2"], R["be2"], None, None, None, None)
 
 
 class SelfLayerFn(torch.autograd.Function):
@@ -358,9 +342,9 @@ class SelfLayerFn(torch.autograd.Function):
         heads, p_h, p_a, seed_a, s0, s1, xshape = ctx.cfg
         G_, T, Hd = xshape
         M, dt = G_ * T, x2.dtype
-        G = _grad_arena(x2.device, Hd, w1.shape[0], True,
-                        dict(wqkv=[wq, wk, wv], bqkv=[bq, bk, bv], wo=wo, w1=w1, w2=w2, bo=bo, b1=b1, b2=b2, g1=g1, be1=be1,
-                             g2=g2, be2=be2))
+        G, R = _layer_grads(x2.device, Hd, w1.shape[0],
+                            dict(wqkv=[wq, wk, wv], bqkv=[bq, bk, bv], wo=wo, w1=w1, w2=w2, bo=bo, b1=b1, b2=b2, g1=g1, be1=be1,
+                                 g2=g2, be2=be2))
         side = _SideGemms(x2.device)
         dc, dz1 = _post_bwd(dy.reshape(M, Hd).contiguous(), c, saved, wo, w1, w2, g1, g2, p_h, (s0, s1), G, side)
         dqkv = self_attention_bwd(qkv, mk, c, lse, dc, G_, T, Hd, heads, p_a, seed_a, bias_grad=G["bqkv"])
@@ -370,10 +354,7 @@ class SelfLayerFn(torch.autograd.Function):
         ops.gemm_dx(dqkv, wm if wm.data_ptr() == wq.data_ptr() else None, wqkv, dx, M, Hd, 3 * Hd, aux=dz1, epi=H.EPI_ADD, owner=wq)   # + residual gradient
         side.launch((dqkv, x2), dqkv, x2, G["wqkv"], 3 * Hd, Hd, M, 3 * Hd, Hd, Hd, 1, 1, acc=True)
         side.join()
-        W, b = G["wqkv"], G["bqkv"]
-        r = lambda n: None if n in G["_inplace"] else G[n]      # (accumulated in place: see dp.GradArena.retake)
-        Ws = (None, None, None) if "wqkv" in G["_inplace"] else (W[:Hd], W[Hd:2 * Hd], W[2 * Hd:])
-        bs = (None, None, None) if "bqkv" in G["_inplace"] else (b[:Hd], b[Hd:2 * Hd], b[2 * Hd:])
-        return (dx.view(xshape), None, Ws[0], bs[0], Ws[1], bs[1], Ws[2], bs[2], r("wo"), r("bo"),
-                r("g1"), r("be1"), r("w1"), r("b1"), r("w2"), r("b2"), r("g2"), r("be2"),
+        Ws, bs = _split3(R["wqkv"], Hd), _split3(R["bqkv"], Hd)
+        return (dx.view(xshape), None, Ws[0], bs[0], Ws[1], bs[1], Ws[2], bs[2], R["wo"], R["bo"],
+                R["g1"], R["be1"], R["w1"], R["b1"], R["w2"], R["b2"], R["g2"], R["be2"],
                 None, None, None, None, None, None, None)

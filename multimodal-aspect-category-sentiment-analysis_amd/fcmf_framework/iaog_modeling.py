@@ -337,8 +337,7 @@ class _ScaledEmbedding(torch.autograd.Function):
                                              H.dt(out), H.stream()), "fcmf_embed_scale_fwd")
         ctx.save_for_backward(idc)
         ctx.scale = scale
-        ctx.weight = weight if (weight.dtype == torch.float32 and weight.is_contiguous()) else None
-        ctx.wshape = weight.shape
+        ctx.weight = weight
         return out
 
     @staticmethod
@@ -346,9 +345,9 @@ class _ScaledEmbedding(torch.autograd.Function):
         from . import _hip as H
         (ids,) = ctx.saved_tensors
         d = dy.contiguous()
-        dw = ops.alloc_grad(ctx.weight, ctx.wshape) if ctx.weight is not None else \
-            torch.zeros(ctx.wshape, dtype=torch.float32, device=dy.device)
-        H.check(H.lib().fcmf_embed_scale_bwd(H.ptr(d), H.ptr(ids), H.ptr(dw), ids.numel(), ctx.wshape[1], ctx.wshape[0], None, float(ctx.scale),
+        V, Hd = ctx.weight.shape
+        dw, _ = ops.grad_dest(ctx.weight, (V, Hd), in_place=False, device=dy.device)      # (never in place: a claimed slice gives a temporary that autograd adds)
+        H.check(H.lib().fcmf_embed_scale_bwd(H.ptr(d), H.ptr(ids), H.ptr(dw), ids.numel(), Hd, V, None, float(ctx.scale),
                                              H.dt(d), H.stream()), "fcmf_embed_scale_bwd")      # (ids outside the table made the forward's rows NaN: the loss already says so)
         return None, dw, None, None, None
 

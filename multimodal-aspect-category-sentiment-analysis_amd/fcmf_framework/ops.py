@@ -298,42 +298,40 @@ def grad_arena():
     return _grad_arena
 
 
-def alloc_grad(param, shape=None):
-    """zero-initialised float32 buffer for the gradient of `param` (viewed as `shape`): the parameter's arena
-    slice if an arena is active and the slice is still unclaimed in this step, else a fresh zero tensor"""
+def grad_dest(param, shape, *, rows=None, in_place=True, temp=True, device=None):
+    """where a backward writes the float32 gradient of `param` -> (buf, ret): the kernel ACCUMULATES into `buf` (zero, or holding
+    what earlier producers of this pass wrote), the backward returns `ret` to autograd.  param: a Parameter viewed as `shape`, or a
+    list of Parameters whose gradients lie back to back in one buffer of `shape` (fused q|k|v: the caller splits `ret`), or None.
+    rows: the producer writes `rows` >= shape[0] rows (the padded vocabulary projection): `buf` is [rows, shape[1]].
+    * an arena is active and the slice is unclaimed in this pass (dp.GradArena.claim): `buf` is the slice, `ret` an alias of it that
+      autograd adopts as p.grad -- no fill, no copy;
+    * an earlier producer of a shared weight has claimed it: `buf` is the slice again and `ret` None (accumulated in place); with
+      in_place=False (the embedding tables) such a producer gets a temporary instead;
+    * no arena, "not here", or not a float32 contiguous tensor of prod(shape) elements: one zero-filled temporary on `device`
+      (default: the parameter's) that autograd adds -- or (None, None) with temp=False, for a caller that fills all its
+      temporaries at once."""
     a = _grad_arena
     if a is not None and param is not None:
-        v = a.take(param)
-        if v is not None:
-            return v if shape is None else v.view(shape)
-    return torch.zeros(tuple(param.shape) if shape is None else shape, dtype=torch.float32, device=param.device)
-
-
-def alloc_grad_ex(param, shape=None):
-    """-> (buffer to ACCUMULATE the gradient of `param` into, what to hand autograd for it).  First producer of the pass: the
-    parameter's zeroed arena slice, returned to autograd; a later producer of the same pass (shared weights): the same slice,
-    accumulated in place, and `None` for autograd (dp.GradArena.retake); no arena: a fresh zero tensor."""
-    a = _grad_arena
-    if a is not None and param is not None:
-        v = a.take(param)
-        if v is not None:
-            v = v if shape is None else v.view(shape)
-            return v, v
-        v = a.retake(param)
-        if v is not None:
-            return (v if shape is None else v.view(shape)), None
-    z = torch.zeros(tuple(param.shape) if shape is None else shape, dtype=torch.float32, device=param.device)
-    return z, z
-
-
-def alloc_grad_block(params, shape):
-    """one zero-initialised buffer covering the gradients of `params` back to back (fused q|k|v)"""
-    a = _grad_arena
-    if a is not None:
-        v = a.take_block(params)
-        if v is not None:
-            return v.view(shape)
-    return torch.zeros(shape, dtype=torch.float32, device=params[0].device)
+        if isinstance(param, (list, tuple)):
+            ok = all(q.dtype == torch.float32 and q.is_contiguous() for q in param) and sum(q.numel() for q in param) == math.prod(shape)
+        else:
+            ok = param.dtype == torch.float32 and param.is_contiguous() and param.numel() == math.prod(shape)
+        got = a.claim(param, rows) if ok else None
+        if got is not None and (got[1] or in_place):
+            buf, first = got
+            if rows is None:
+                buf = buf.view(shape)
+                return buf, (buf if first else None)
+            return buf, (a.grad_alias(param, shape) if first else None)
+    if not temp:
+        return None, None
+    if device is None:
+        device = (param[0] if isinstance(param, (list, tuple)) else param).device
+    if rows is None:
+        buf = torch.zeros(shape, dtype=torch.float32, device=device)
+        return buf, buf
+    buf = torch.zeros((rows,) + tuple(shape[1:]), dtype=torch.float32, device=device)
+    return buf, buf[:shape[0]]
 
 
 def as_compute(w, dtype):
@@ -400,9 +398,14 @@ def gemm_trace_end():
     return [(name, fl, e0.elapsed_time(e1)) for name, fl, e0, e1 in tr]
 
 
+def tracing():
+    return _gemm_trace is not None
+
+
 class trace_launch:
-    """`with trace_launch(flops):` around a direct library call that multiplies on the GEMM context of the current stream (the trunk's
-    implicit-GEMM convolutions): recorded like `gemm` when a trace is open, free otherwise"""
+    """`with trace_launch(flops):` around a library call that multiplies on the GEMM context of the current stream (`gemm`, the
+    trunk's implicit-GEMM convolutions): records (kernel name, flops, start event, end event) when a trace is open and the call
+    did not raise, free otherwise.  A call that launched nothing sets `.flops = None`: nothing is recorded."""
 
     def __init__(self, flops):
         self.flops = flops
@@ -414,7 +417,7 @@ class trace_launch:
         return self
 
     def __exit__(self, *exc):
-        if _gemm_trace is not None and exc[0] is None:
+        if _gemm_trace is not None and exc[0] is None and self.flops is not None:
             self.e1.record()
             _gemm_trace.append((H.lib().fcmf_gemm_ctx_last_kernel(H.gemm_ctx()).decode(), float(self.flops), self.e0, self.e1))
         return False
@@ -453,7 +456,7 @@ class _DeferredDW:
             return False
         # A weight applied SEVERAL times (the mm layer's key / value weights: text keys, ROI keys, the fusion layer) has several
         # producers, but since round 4 every one of them accumulates in place into the slice the first one claimed and hands
-        # autograd None (alloc_grad_ex / GradArena.retake): nothing is added by the engine, so they may all wait for the flush and
+        # autograd None (grad_dest / GradArena.claim): nothing is added by the engine, so they may all wait for the flush and
         # batch with the same-shape gradients of the text encoder.  (A destination outside the arena -- the temporaries of a
         # gradient-accumulation micro-step -- never gets here.)
         n = arena.uses(C.data_ptr())
@@ -496,14 +499,9 @@ class _DeferredDW:
             with torch.cuda.device(key[0]):
                 ctx = H.gemm_ctx(workspace=True)
                 arr = lambda i: (ctypes.c_void_p * len(es))(*[e[i] if i == 2 else e[i].data_ptr() for e in es])
-                if _gemm_trace is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                H.check(H.lib().fcmf_gemm_dw_batched(ctx, len(es), arr(0), arr(1), arr(2), M, N, K, lda, ldb, ldc, int(acc), H.stream()),
-                        "fcmf_gemm_dw_batched")
-                if _gemm_trace is not None:
-                    e1.record()
-                    _gemm_trace.append((H.lib().fcmf_gemm_ctx_last_kernel(ctx).decode(), 2.0 * M * N * K * len(es), e0, e1))
+                with trace_launch(2.0 * M * N * K * len(es)):
+                    H.check(H.lib().fcmf_gemm_dw_batched(ctx, len(es), arr(0), arr(1), arr(2), M, N, K, lda, ldb, ldc, int(acc), H.stream()),
+                            "fcmf_gemm_dw_batched")
             self.batched_launches += 1
             self.batched_matrices += len(es)
 
@@ -523,14 +521,9 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, ta, tb, bias=None, aux=None, epi=H.EPI
     if deferred_dw.wanted(A, B, C, ta, tb, bias, aux, epi, colsum) and deferred_dw.push(A, B, C, M, N, K, lda, ldb, ldc, acc):
         return
     ctx = H.gemm_ctx(workspace=acc or C.dtype == torch.float32)   # (weight-gradient GEMMs: the context owns the split-K scratch of this stream)
-    if _gemm_trace is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    H.check(H.lib().fcmf_gemm(ctx, H.ptr(A), H.ptr(B), H.ptr(C), H.ptr(bias), H.ptr(aux), H.ptr(colsum), M, N, K, lda, ldb, ldc,
-                              int(ta), int(tb), H.dt(A), H.dt(C), epi, int(acc), H.stream()), "fcmf_gemm")
-    if _gemm_trace is not None:
-        e1.record()
-        _gemm_trace.append((H.lib().fcmf_gemm_ctx_last_kernel(ctx).decode(), 2.0 * M * N * K, e0, e1))
+    with trace_launch(2.0 * M * N * K):
+        H.check(H.lib().fcmf_gemm(ctx, H.ptr(A), H.ptr(B), H.ptr(C), H.ptr(bias), H.ptr(aux), H.ptr(colsum), M, N, K, lda, ldb, ldc,
+                                  int(ta), int(tb), H.dt(A), H.dt(C), epi, int(acc), H.stream()), "fcmf_gemm")
 
 
 # (see _DeferredDW.wanted; measured on one box, 20 steps, twice each: 36.76 / 36.85 ms off, 36.70 / 36.67 ms on -- 168 instead of 176 GEMM
@@ -556,24 +549,18 @@ def head_weight_grad(x2, dy2, params):
     M, N = x2.shape[0], len(params) * nh * d
     if E < 256 or N < 256 or dy2.shape[1] != N or not dy2.is_contiguous():
         return None
-    flat = a.take_block(list(params)) if len(params) > 1 else a.take(params[0])
-    if flat is None:
+    got = a.claim(list(params))
+    if got is None or not got[1]:          # (a second producer would have to ACCUMULATE: the blocked kernel overwrites)
         return None
-    ctx = H.gemm_ctx(workspace=True)
-    if _gemm_trace is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = H.lib().fcmf_gemm_colblocks(ctx, H.ptr(x2), H.ptr(dy2), H.ptr(flat), E, N, M, _ld(x2), N, d, 1, 1, d, E * d, 0, H.stream())
-    if rc == H.ERR_UNSUPPORTED:
-        a.untake(params)
-        return None
-    H.check(rc, "fcmf_gemm_colblocks")
-    if _gemm_trace is not None:
-        e1.record()
-        _gemm_trace.append((H.lib().fcmf_gemm_ctx_last_kernel(ctx).decode(), 2.0 * E * N * M, e0, e1))
-    # (FRESH aliases: autograd adopts a gradient as p.grad without a copy only when it is the sole holder of the tensor object --
-    #  the arena's own view objects would be cloned)
-    return [a.view[id(a._by_ptr[p.data_ptr()])].view(nh, E, d) for p in params]
+    with trace_launch(2.0 * E * N * M) as t:
+        rc = H.lib().fcmf_gemm_colblocks(H.gemm_ctx(workspace=True), H.ptr(x2), H.ptr(dy2), H.ptr(got[0]), E, N, M, _ld(x2), N, d, 1, 1,
+                                         d, E * d, 0, H.stream())
+        if rc == H.ERR_UNSUPPORTED:
+            t.flops = None
+            a.release(params)
+            return None
+        H.check(rc, "fcmf_gemm_colblocks")
+    return [a.grad_alias(p, (nh, E, d)) for p in params]
 
 
 def quant_fp8_rows(x, rows, K, ldx, out=None):
@@ -594,15 +581,9 @@ def _fp8_ok(M, N, K, ldc, *tensors):
 
 
 def gemm_fp8(xq, sx, wq, sw, C, M, N, K, bias=None, aux=None, epi=H.EPI_NONE, colsum=None):
-    ctx = H.gemm_ctx()
-    if _gemm_trace is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    H.check(H.lib().fcmf_gemm_fp8(ctx, H.ptr(xq), H.ptr(sx), H.ptr(wq), H.ptr(sw), H.ptr(C), H.ptr(bias), H.ptr(aux), H.ptr(colsum),
-                                  M, N, K, K, K, N, epi, H.stream()), "fcmf_gemm_fp8")
-    if _gemm_trace is not None:
-        e1.record()
-        _gemm_trace.append((H.lib().fcmf_gemm_ctx_last_kernel(ctx).decode(), 2.0 * M * N * K, e0, e1))
+    with trace_launch(2.0 * M * N * K):
+        H.check(H.lib().fcmf_gemm_fp8(H.gemm_ctx(), H.ptr(xq), H.ptr(sx), H.ptr(wq), H.ptr(sw), H.ptr(C), H.ptr(bias), H.ptr(aux), H.ptr(colsum),
+                                      M, N, K, K, K, N, epi, H.stream()), "fcmf_gemm_fp8")
 
 
 def gemm_nt(x, weight, w_compute, y, M, N, K, ldx, bias=None, aux=None, epi=H.EPI_NONE, colsum=None, owner=None, xq=None):
@@ -678,15 +659,12 @@ def _linear_bwd(x, w, dy, need_dx=True, need_dw=True, need_db=True, dx_epi=H.EPI
         dx = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
         gemm_dx(dy, master, w, dx, M, K, N, aux=dx_aux, epi=dx_epi)
     if need_dw:
-        if master is not None and master.dtype == torch.float32 and master.is_contiguous() and tuple(master.shape) == (N, K):
-            dwbuf, dw = alloc_grad_ex(master, (N, K))         # (dw = None: accumulated in place into the slice an earlier use returned)
-        else:
-            dwbuf = dw = torch.zeros((N, K), dtype=torch.float32, device=dy.device)
+        dwbuf, dw = grad_dest(master, (N, K), device=dy.device)   # (dw = None: accumulated in place into the slice an earlier use returned)
         gemm(dy, x, dwbuf, N, K, M, N, _ld(x), K, 1, 1, acc=True)
     if need_db:
         if bias_param is not None and bias_param.dtype == torch.float32 and tuple(bias_param.shape) == (N,):
             # straight into the parameter's (already zero) arena slice: no output tensor, no memset inside fcmf_colsum
-            dbbuf, db = alloc_grad_ex(bias_param, (N,))
+            dbbuf, db = grad_dest(bias_param, (N,))
             H.check(H.lib().fcmf_colsum(H.ptr(dy), H.ptr(dbbuf), M, N, N, H.dt(dy), 1, H.stream()), "fcmf_colsum")
         else:
             db = colsum(dy, M, N, N)
@@ -978,12 +956,7 @@ class VocabCrossEntropyFn(torch.autograd.Function):
             # the tied vocabulary matrix: its arena slice has zeroed slack rows up to Vp (dp.GradArena pad_rows), so the padded product
             # accumulates straight into it -- no 196 MB zero fill, and the embedding lookup's gradient (the other producer of the tied
             # matrix) adds to the same memory in place instead of through a 196 MB autograd add
-            got = _grad_arena.take_rows(weight, Vp) if (_grad_arena is not None and weight.dtype == torch.float32 and weight.is_contiguous()) else None
-            if got is not None:
-                dwp, dw = got
-            else:
-                dwp = torch.zeros((Vp, K), dtype=torch.float32, device=x2.device)
-                dw = dwp[:V]
+            dwp, dw = grad_dest(weight, (V, K), rows=Vp, device=x2.device)
             gemm(d, x2, dwp, Vp, K, M, Vp, _ld(x2), K, 1, 1, acc=True)
         if has_bias and ctx.needs_input_grad[2]:
             db = colsum(d, M, Vp, Vp)[:V]
@@ -1065,8 +1038,8 @@ class AddLNFn(torch.autograd.Function):
         dy2 = dy.reshape(rows, Hd).contiguous()
         dz = torch.empty_like(z)
         dx = torch.empty_like(z) if ctx.p > 0 else None
-        dgbuf, dg = alloc_grad_ex(gamma, (Hd,))       # the arena slices (already zero) where an arena is active: no fill launches
-        dbbuf, db = alloc_grad_ex(beta, (Hd,))          # (dg / db = None: a later use of shared parameters, accumulated in place)
+        dgbuf, dg = grad_dest(gamma, (Hd,))       # the arena slices (already zero) where an arena is active: no fill launches
+        dbbuf, db = grad_dest(beta, (Hd,))          # (dg / db = None: a later use of shared parameters, accumulated in place)
         H.check(H.lib().fcmf_add_ln_bwd(H.ptr(dy2), H.ptr(z), H.ptr(gamma), H.ptr(mean), H.ptr(rstd), H.ptr(dz),
                                         H.ptr(dx), H.ptr(dgbuf), H.ptr(dbbuf), 0, H.ptr(ln_workspace(rows, Hd, z.device)), rows, Hd, ctx.p, ctx.seed, H.dt(z),
                                         H.stream()), "fcmf_add_ln_bwd")
@@ -1135,10 +1108,7 @@ class EmbedLNFn(torch.autograd.Function):
                                           ntok, Hd, eps, p, seed, H.dt(y), H.stream()), "fcmf_embed_ln_fwd")
         ctx.save_for_backward(ids, pos, tt, z, gamma, mean, rstd)
         ctx.p, ctx.seed, ctx.pad_id = p, seed, pad_id
-        ctx.word = word if (word.dtype == torch.float32 and word.is_contiguous()) else None   # (the Parameter: arena lookup)
-        ok = lambda t: t if (t is not None and t.dtype == torch.float32 and t.is_contiguous()) else None
-        ctx.tabs = (ok(ptab), ok(ttab), ok(gamma), ok(beta))                                     # (likewise: their arena slices)
-        ctx.shapes = (word.shape, ptab.shape, ttab.shape)
+        ctx.params = (word, ptab, ttab, gamma, beta)       # (the Parameters: grad_dest looks up their arena slices)
         return y.view(*ids.shape, Hd)
 
     @staticmethod
@@ -1152,19 +1122,16 @@ class EmbedLNFn(torch.autograd.Function):
             H.check(L.fcmf_dropout(H.ptr(d), H.ptr(o), d.numel(), ctx.p, ctx.seed, H.dt(d), H.stream()), "fcmf_dropout")
             d = o
         dz = torch.empty_like(z)
-        ptab, ttab, gpar, bpar = ctx.tabs
-        zeros = lambda shape: torch.zeros(shape, dtype=torch.float32, device=z.device)
-        dg = alloc_grad(gpar, (Hd,)) if gpar is not None else zeros(Hd)        # (arena slices: already zero, no fill launches)
-        db = alloc_grad(bpar, (Hd,)) if bpar is not None else zeros(Hd)
+        word, ptab, ttab, gpar, bpar = ctx.params
+        # (arena slices: already zero, no fill launches.  Only the word table accumulates in place -- dword = None: the tied
+        #  matrix's slice was claimed by the vocabulary projection; the others get a temporary that autograd adds)
+        dg, _ = grad_dest(gpar, (Hd,), in_place=False, device=z.device)
+        db, _ = grad_dest(bpar, (Hd,), in_place=False, device=z.device)
         H.check(L.fcmf_add_ln_bwd(H.ptr(d), H.ptr(z), H.ptr(gamma), H.ptr(mean), H.ptr(rstd), H.ptr(dz), 0, H.ptr(dg),
                                   H.ptr(db), 0, H.ptr(ln_workspace(ntok, Hd, z.device)), ntok, Hd, 0.0, 0, H.dt(z), H.stream()), "fcmf_add_ln_bwd")
-        ws, ps, ts = ctx.shapes
-        if ctx.word is not None:
-            dwordbuf, dword = alloc_grad_ex(ctx.word, ws)      # (dword = None: the tied matrix's slice was claimed by the vocabulary projection)
-        else:
-            dwordbuf = dword = torch.zeros(ws, dtype=torch.float32, device=z.device)
-        dpos = alloc_grad(ptab, ps) if ptab is not None else zeros(ps)
-        dtt = alloc_grad(ttab, ts) if ttab is not None else zeros(ts)
+        dwordbuf, dword = grad_dest(word, word.shape, device=z.device)
+        dpos, _ = grad_dest(ptab, ptab.shape, in_place=False, device=z.device)
+        dtt, _ = grad_dest(ttab, ttab.shape, in_place=False, device=z.device)
         two_d = ids.dim() == 2 and pos.is_contiguous()
         fused = False
         if two_d and (tt is None or tt.is_contiguous()):

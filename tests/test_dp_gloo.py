@@ -143,8 +143,10 @@ def test_grad_arena_layout_for_fcmf_model():
                 for trio in ((m.query.weight, m.key.weight, m.value.weight), (m.query.bias, m.key.bias, m.value.bias)):
                     offs = [arena.offset[id(p)] for p in trio]
                     assert offs[0] % ALIGN == 0 and offs[1] == offs[0] + trio[0].numel() and offs[2] == offs[1] + trio[1].numel()
-                    blk = arena.take_block(list(trio))
-                    assert blk is not None and blk.numel() == 3 * trio[0].numel() and arena.take_block(list(trio)) is None
+                    blk, first = arena.claim(list(trio))
+                    assert first and blk.numel() == 3 * trio[0].numel()
+                    again = arena.claim(list(trio))                   # claimed once: a second producer is never `first`
+                    assert again is not None and not again[1] and again[0].data_ptr() == blk.data_ptr()
         assert nblocks >= synth.TINY_CFG["num_hidden_layers"] + 2          # text encoder layers + text2img + mm_attention
         # backward order: the classifier (registered last) comes first, the word embeddings last
         assert arena.offset[id(named["classifier.weight"])] < arena.offset[id(named["encoder.bert.cell.embeddings.word_embeddings.weight"])]
@@ -363,9 +365,9 @@ def test_bare_bench_command_launches_its_own_ranks():
 
 
 def test_grad_arena_slack_rows_behind_a_ragged_vocabulary_matrix():
-    """GradArena pad_rows / take_rows: a large 2-D parameter whose row count is no multiple of 32 (the 64001-row tied vocabulary matrix)
+    """GradArena pad_rows / claim(rows=): a large 2-D parameter whose row count is no multiple of 32 (the 64001-row tied vocabulary matrix)
     gets zeroed slack rows behind its slice; the first producer that writes whole 32-row groups gets a [rows32, cols] buffer that starts
-    at the slice and hands autograd the slice itself, a later producer of the same pass gets the buffer and None (accumulate in place);
+    at the slice and hands autograd a fresh alias of the slice, a later producer of the same pass gets the buffer and is not `first` (accumulate in place);
     the next parameter's slice starts behind the slack.  CPU, no kernels."""
     sys.path.insert(0, PKG)
     from fcmf_framework.dp import ALIGN, GradArena
@@ -376,16 +378,91 @@ def test_grad_arena_slack_rows_behind_a_ragged_vocabulary_matrix():
         rows32 = (8201 + 31) // 32 * 32
         assert arena.slack[id(a)] == (rows32 - 8201) * 4 and id(b) not in arena.slack
         assert arena.offset[id(b)] >= arena.offset[id(a)] + rows32 * 4 and arena.offset[id(b)] % ALIGN == 0
-        assert arena.take_rows(a, rows32 + 32) is None                      # more rows than the slack covers
-        buf, ret = arena.take_rows(a, rows32)
+        assert arena.claim(a, rows=rows32 + 32) is None                     # more rows than the slack covers
+        buf, first = arena.claim(a, rows=rows32)
+        ret = arena.grad_alias(a)
+        assert first
         assert tuple(buf.shape) == (rows32, 4) and buf.data_ptr() == arena.view[id(a)].data_ptr()
         assert ret.data_ptr() == arena.view[id(a)].data_ptr() and ret is not arena.view[id(a)] and ret.shape == a.shape
-        buf2, ret2 = arena.take_rows(a, rows32)                              # a second producer of the same pass
-        assert buf2.data_ptr() == buf.data_ptr() and ret2 is None
-        assert arena.take(a) is None and arena.retake(a) is not None
+        buf2, first2 = arena.claim(a, rows=rows32)                           # a second producer of the same pass
+        assert buf2.data_ptr() == buf.data_ptr() and first2 is False
+        got = arena.claim(a)                                                 # (no first claim any more, but the slice to accumulate into)
+        assert got is not None and got[1] is False and got[0].data_ptr() == buf.data_ptr()
         buf.fill_(1.0)
         arena.zero()
         assert float(arena.flat.abs().sum()) == 0.0                          # the slack is zeroed with the slices
-        assert arena.take_rows(b, 32) is None                                # small parameters have no slack
+        assert arena.claim(b, rows=32) is None                               # small parameters have no slack
+    finally:
+        arena.deactivate()
+
+
+def test_grad_arena_claim_state_table():
+    """GradArena.claim / release / grad_alias, state by state: s a single parameter, [k, q] a block packed back to back, r a ragged
+    2-D parameter with slack rows, x a parameter the arena does not know.  For every state: returned or not, `first` or not, the
+    buffer's address and element count, and which claim marks changed.  CPU, no kernels."""
+    sys.path.insert(0, PKG)
+    from fcmf_framework.dp import GradArena
+    s, k, q = (torch.nn.Parameter(torch.randn(*sh)) for sh in ((2, 3, 8), (5, 8), (5, 8)))
+    r = torch.nn.Parameter(torch.randn(8201, 4))
+    x = torch.nn.Parameter(torch.randn(8, 8))
+    arena = GradArena([r, k, q, s], blocks=[[k, q]])
+    try:
+        rows32 = (8201 + 31) // 32 * 32
+        addr = lambda p: arena.flat.data_ptr() + 4 * arena.offset[id(p)]
+        marks = lambda: tuple(id(p) in arena._taken for p in (s, k, q, r))
+        none = (False, False, False, False)
+
+        def expect(got, first, ptr, numel, shape=None):
+            assert got is not None and got[1] is first and got[0].data_ptr() == ptr and got[0].numel() == numel
+            assert shape is None or tuple(got[0].shape) == shape
+
+        assert arena.offset[id(q)] == arena.offset[id(k)] + k.numel() and arena.slack[id(r)] == (rows32 - 8201) * 4
+        for _ in range(2):                                           # the second round: after zero(), everything as at the start
+            assert marks() == none and not arena.fwd_uses
+            # unknown address, element count differs (a view that shares the parameter's pointer), wrong order, rows out of range
+            assert arena.claim(x) is None and arena.claim([k, x]) is None and arena.claim(x, rows=8) is None
+            assert arena.claim(s.detach()[:1]) is None and arena.claim([k.detach()[:2], q]) is None and arena.claim(r.detach()[:32], rows=32) is None
+            assert arena.claim([q, k]) is None and arena.claim([k, s]) is None and arena.claim([s, k, q]) is None           # (s: 48 elements, k starts on the next 64-element boundary)
+            assert arena.claim(r, rows=8200) is None and arena.claim(r, rows=rows32 + 1) is None and arena.claim(k, rows=6) is None
+            assert arena.claim(s, rows=2) is None and arena.claim(s, rows=8) is None                        # not 2-D
+            assert marks() == none
+            # unclaimed -> first, marked; claimed -> the same buffer, not first, marks unchanged
+            expect(arena.claim(s), True, addr(s), 48, (2, 3, 8))
+            assert marks() == (True, False, False, False)
+            expect(arena.claim(s), False, addr(s), 48, (2, 3, 8))
+            expect(arena.claim([k, q]), True, addr(k), 80, (80,))
+            assert marks() == (True, True, True, False)
+            expect(arena.claim([k, q]), False, addr(k), 80, (80,))
+            expect(arena.claim(q), False, addr(q), 40)                  # (a member on its own: claimed with its block)
+            expect(arena.claim(r, rows=rows32), True, addr(r), rows32 * 4, (rows32, 4))
+            assert marks() == (True, True, True, True)
+            expect(arena.claim(r, rows=rows32), False, addr(r), rows32 * 4, (rows32, 4))
+            expect(arena.claim(r, rows=8201), False, addr(r), 8201 * 4, (8201, 4))
+            expect(arena.claim(r), False, addr(r), 8201 * 4, (8201, 4))
+            assert arena.claim(r, rows=rows32 + 32) is None and marks() == (True, True, True, True)
+            # release -> as unclaimed; a block with some members claimed and some not -> not here, no mark changes
+            arena.release([q, x])
+            assert marks() == (True, True, False, True)
+            assert arena.claim([k, q]) is None and marks() == (True, True, False, True)
+            expect(arena.claim(q), True, addr(q), 40, (5, 8))
+            expect(arena.claim([k, q]), False, addr(k), 80)
+            arena.release([s, k, q, r])
+            assert marks() == none
+            expect(arena.claim(s), True, addr(s), 48)
+            # p.grad is not None (a later micro-step of a gradient accumulation): not here, claimed or not, marks unchanged
+            s.grad, k.grad, r.grad = torch.zeros(2, 3, 8), torch.zeros(5, 8), torch.zeros(8201, 4)
+            before = marks()
+            assert arena.claim(s) is None and arena.claim(k) is None and arena.claim([k, q]) is None
+            assert arena.claim(r) is None and arena.claim(r, rows=rows32) is None and marks() == before
+            expect(arena.claim(q), True, addr(q), 40)
+            # grad_alias: a new object over the slice every time, in the parameter's shape or the one asked for
+            for p in (s, k, q, r):
+                v, w = arena.grad_alias(p), arena.grad_alias(p, (p.numel(),))
+                assert v is not w and v is not arena.view[id(p)] and v.data_ptr() == w.data_ptr() == addr(p)
+                assert v.shape == p.shape and tuple(w.shape) == (p.numel(),)
+            arena.note_forward(s.data_ptr())
+            arena.flat.fill_(1.0)
+            arena.zero()
+            assert float(arena.flat.abs().sum()) == 0.0 and all(p.grad is None for p in (s, k, q, r))
     finally:
         arena.deactivate()

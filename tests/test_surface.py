@@ -159,3 +159,66 @@ def test_drivers_accept_the_published_command_lines():
     assert (b.encoder_learning_rate, b.classifier_head_learning_rate, b.alpha) == (7e-5, 7e-4, 1.0)
     c = pt.build_parser().parse_args(_argv(REF_PRETRAIN_FLAGS))
     assert c.list_aspect == ['Location'] and c.beam_size == 2 and c.fine_tune_cnn and c.ddp
+
+
+def test_grad_dest_states_on_cpu_parameters():
+    """ops.grad_dest, the one place that decides where a backward writes a parameter gradient and what autograd is handed for it, over
+    CPU parameters (no kernel is launched): every state of a parameter's arena slice x in_place x arena active or not, and tensors
+    that are not eligible (bf16, a non-contiguous view, a wrong element count)."""
+    from fcmf_framework import ops
+    from fcmf_framework.dp import GradArena
+    w, k, q = (torch.nn.Parameter(torch.randn(*s)) for s in ((6, 8), (5, 8), (5, 8)))
+    r = torch.nn.Parameter(torch.randn(8201, 4))
+    rows32 = (8201 + 31) // 32 * 32
+    old = ops.grad_arena()
+    arena = GradArena([r, k, q, w], blocks=[[k, q]])
+    in_arena = lambda t: arena.flat.data_ptr() <= t.data_ptr() < arena.flat.data_ptr() + 4 * arena.total
+    addr = lambda p: arena.view[id(p)].data_ptr()
+
+    def temporary(buf, ret, shape, rows=None):
+        assert not in_arena(buf) and buf.dtype == torch.float32 and float(buf.abs().sum()) == 0.0
+        assert tuple(buf.shape) == ((rows,) + tuple(shape[1:]) if rows else tuple(shape)) and tuple(ret.shape) == tuple(shape)
+        assert ret is buf if rows is None else (ret is not buf and ret.data_ptr() == buf.data_ptr())
+
+    try:
+        for in_place in (True, False):
+            arena.zero()
+            # unclaimed: the slice, and autograd gets it (rows: a distinct alias of the slice in the parameter's shape)
+            buf, ret = ops.grad_dest(w, (6, 8), in_place=in_place)
+            assert buf.data_ptr() == addr(w) and ret is buf and ret is not arena.view[id(w)] and tuple(buf.shape) == (6, 8)
+            buf, ret = ops.grad_dest([k, q], (10, 8), in_place=in_place)
+            assert buf.data_ptr() == addr(k) and ret is buf and tuple(buf.shape) == (10, 8)
+            buf, ret = ops.grad_dest(r, (8201, 4), rows=rows32, in_place=in_place)
+            assert buf.data_ptr() == addr(r) and tuple(buf.shape) == (rows32, 4)
+            assert ret is not buf and ret is not arena.view[id(r)] and ret.data_ptr() == addr(r) and tuple(ret.shape) == (8201, 4)
+            # claimed by an earlier producer of the pass: in place and None -- or, with in_place=False, a temporary that autograd adds
+            for p, shape, rows in ((w, (48,), None), ([k, q], (80,), None), (r, (8201, 4), rows32), (r, (8201, 4), None)):
+                buf, ret = ops.grad_dest(p, shape, rows=rows, in_place=in_place)
+                if in_place:
+                    assert ret is None and buf.data_ptr() == addr(p[0] if isinstance(p, list) else p)
+                    assert tuple(buf.shape) == ((rows32, 4) if rows else shape)
+                else:
+                    temporary(buf, ret, shape, rows)
+            # p.grad is set (a later micro-step of a gradient accumulation): a temporary, claimed or not
+            w.grad = torch.zeros(6, 8)
+            temporary(*ops.grad_dest(w, (6, 8), in_place=in_place), (6, 8))
+            arena.release([w])
+            temporary(*ops.grad_dest(w, (6, 8), in_place=in_place), (6, 8))
+            # not eligible: never the arena, whatever the state
+            arena.zero()
+            for t, shape in ((w.detach().bfloat16(), (6, 8)), (w.detach().t(), (8, 6)), (w, (6, 4)), (w.detach()[:3], (6, 8)), ([k, q], (5, 8))):
+                temporary(*ops.grad_dest(t, shape, in_place=in_place), shape)
+            assert not arena._taken
+            assert ops.grad_dest(w.detach().t(), (8, 6), temp=False) == (None, None)
+            assert ops.grad_dest(None, (3,), device="cpu")[0].shape == (3,)
+        # no arena: one zero fill each
+        arena.deactivate()
+        assert ops.grad_arena() is None
+        for in_place in (True, False):
+            temporary(*ops.grad_dest(w, (6, 8), in_place=in_place), (6, 8))
+            temporary(*ops.grad_dest([k, q], (10, 8), in_place=in_place), (10, 8))
+            temporary(*ops.grad_dest(r, (8201, 4), rows=rows32, in_place=in_place), (8201, 4), rows32)
+            assert ops.grad_dest(w, (6, 8), in_place=in_place, temp=False) == (None, None)
+    finally:
+        arena.deactivate()
+        ops.set_grad_arena(old)
