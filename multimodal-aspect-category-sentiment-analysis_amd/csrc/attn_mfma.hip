@@ -692,28 +692,19 @@ extern "C" int fcmf_attn_mfma_fwd(const void* q, const void* k, const void* v, c
   const dim3 grid(G * heads, (Tq + AT - 1) / AT);
   if (Tk > AT) {
     const int smem = 4 * TILE_B;
-    static bool attr2 = false;
-    if (!attr2) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_mfma_fwd256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr2 = true; }
-    hipLaunchKernelGGL(attn_mfma_fwd256_kernel, grid, dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
-    FCMF_CHECK_LAUNCH();
-    return FCMF_OK;
+    static bool attr2 = false;      // (this kernel's dynamic LDS is one constant: its limit is raised once)
+    return fcmf_launch_flagged(&attr2, attn_mfma_fwd256_kernel, grid, dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
   }
   const int ntiles = (int)(grid.x * grid.y);
   static const bool no_persist = getenv("FCMF_ATTN_NO_PERSIST") != nullptr;      // A/B switch for benchmarks
   if (ntiles >= 4 * 512 && !no_persist) {       // enough tiles for every resident workgroup (2 per CU) to walk several
     const int smem = 2 * (2 * TILE_B + 512);
-    static bool attr3 = false;
-    if (!attr3) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_mfma_fwd_persist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr3 = true; }
-    hipLaunchKernelGGL(attn_mfma_fwd_persist_kernel, dim3(512), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P, ntiles, (int)grid.y);
-    FCMF_CHECK_LAUNCH();
-    return FCMF_OK;
+    static bool attr3 = false;      // (this kernel's dynamic LDS is one constant: its limit is raised once)
+    return fcmf_launch_flagged(&attr3, attn_mfma_fwd_persist_kernel, dim3(512), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P, ntiles, (int)grid.y);
   }
   const int smem = 2 * TILE_B;
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_mfma_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr = true; }
-  hipLaunchKernelGGL(attn_mfma_fwd_kernel, grid, dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
-  FCMF_CHECK_LAUNCH();
-  return FCMF_OK;
+  static bool attr = false;      // (this kernel's dynamic LDS is one constant: its limit is raised once)
+  return fcmf_launch_flagged(&attr, attn_mfma_fwd_kernel, grid, dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
 }
 
 extern "C" int fcmf_attn_mfma_bwd(const void* q, const void* k, const void* v, const float* mask, const void* out,
@@ -731,16 +722,10 @@ extern "C" int fcmf_attn_mfma_bwd(const void* q, const void* k, const void* v, c
   P.scale = scale; P.p = dropout_p; P.seed = seed; P.colsum = colsum;
   if (Tk > AT || Tq > AT) {
     const int smem = 9 * TILE_B;   // 2 x (Q, dO) + 2 x (K, V) tiles + the two 8 KiB chunk images = 144 KiB: one workgroup per CU
-    static bool attr2 = false;
-    if (!attr2) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_mfma_bwd256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr2 = true; }
-    hipLaunchKernelGGL(attn_mfma_bwd256_kernel, dim3(G * heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
-    FCMF_CHECK_LAUNCH();
-    return FCMF_OK;
+    static bool attr2 = false;      // (this kernel's dynamic LDS is one constant: its limit is raised once)
+    return fcmf_launch_flagged(&attr2, attn_mfma_bwd256_kernel, dim3(G * heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
   }
   const int smem = 5 * TILE_B;   // Q, K, V, dO tiles + the two 8 KiB chunk images = 80 KiB: two workgroups per CU
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_mfma_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem); attr = true; }
-  hipLaunchKernelGGL(attn_mfma_bwd_kernel, dim3(G * heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
-  FCMF_CHECK_LAUNCH();
-  return FCMF_OK;
+  static bool attr = false;      // (this kernel's dynamic LDS is one constant: its limit is raised once)
+  return fcmf_launch_flagged(&attr, attn_mfma_bwd_kernel, dim3(G * heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
 }

@@ -1247,10 +1247,7 @@ extern "C" int fcmf_attn_small_fwd(const fcmf_attn_desc* desc, void* out, float*
     if (after_k < over) smem += over - after_k;
     if (smem <= TINY_LDS) {
       auto k = desc->T1 > 64 ? attn_tiny_fwd_kernel<true> : attn_tiny_fwd_kernel<false>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      hipLaunchKernelGGL(k, dim3(desc->G * desc->heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
-      FCMF_CHECK_LAUNCH();
-      return FCMF_OK;
+      return fcmf_launch(k, dim3(desc->G * desc->heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
     }
   }
   if (rows_flat_ok(desc) && desc->T1 + desc->T2 <= 384 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
@@ -1273,22 +1270,13 @@ extern "C" int fcmf_attn_small_fwd(const fcmf_attn_desc* desc, void* out, float*
   const size_t smem = base + (size_t)P.RB * per_row;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   dim3 grid(desc->G * desc->heads);
-#define FCMF_ATTN_FWD(TT, KPL, DC)                                                                                         \
-  do {                                                                                                                     \
-    auto k = attn_small_fwd_kernel<TT, KPL, DC>;                                                                           \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);    \
-    hipLaunchKernelGGL(k, grid, dim3(256), smem, st, P);                                                                   \
-  } while (0)
+#define FCMF_ATTN_FWD(TT, KPL, DC) fcmf_launch(attn_small_fwd_kernel<TT, KPL, DC>, grid, dim3(256), smem, st, P)
 #define FCMF_ATTN_FWD_T(TT)                                                                                                \
-  do {                                                                                                                     \
-    if (desc->d == 64) { if (kpl == 4) FCMF_ATTN_FWD(TT, 4, 64); else FCMF_ATTN_FWD(TT, 8, 64); }                          \
-    else               { if (kpl == 4) FCMF_ATTN_FWD(TT, 4, 0); else FCMF_ATTN_FWD(TT, 8, 0); }                            \
-  } while (0)
-  if (desc->dtype == FCMF_F32) FCMF_ATTN_FWD_T(float); else FCMF_ATTN_FWD_T(bf16_t);
+  (desc->d == 64 ? (kpl == 4 ? FCMF_ATTN_FWD(TT, 4, 64) : FCMF_ATTN_FWD(TT, 8, 64))                                        \
+                 : (kpl == 4 ? FCMF_ATTN_FWD(TT, 4, 0) : FCMF_ATTN_FWD(TT, 8, 0)))
+  return desc->dtype == FCMF_F32 ? FCMF_ATTN_FWD_T(float) : FCMF_ATTN_FWD_T(bf16_t);
 #undef FCMF_ATTN_FWD_T
 #undef FCMF_ATTN_FWD
-  FCMF_CHECK_LAUNCH();
-  return FCMF_OK;
 }
 
 static int attn_small_bwd_impl(const fcmf_attn_desc* desc, const void* out, const void* dout, const float* lse,
@@ -1324,20 +1312,14 @@ static int attn_small_bwd_impl(const fcmf_attn_desc* desc, const void* out, cons
     const size_t row = sizeof(float) * 2 * (size_t)(desc->T1 + 1);      // one row of the two [rows][T + 1] f32 arrays
     if (desc->R <= TINY_MAX && desc->T1 <= TINY_MAX && opnd + desc->R * row <= TINY_LDS) {
       const size_t smem = opnd + desc->R * row;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_tiny_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      hipLaunchKernelGGL(attn_tiny_bwd_kernel, dim3(desc->G * desc->heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
-      FCMF_CHECK_LAUNCH();
-      return FCMF_OK;
+      return fcmf_launch(attn_tiny_bwd_kernel, dim3(desc->G * desc->heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
     }
     if (opnd + 16 * row <= TINY_LDS) {                   // row blocks of >= 16 rows, as even as the LDS allows
       const int fit = (int)((TINY_LDS - opnd) / row);
       const int nblk = (desc->R + fit - 1) / fit;
       P.RB = (desc->R + nblk - 1) / nblk;
       const size_t smem = opnd + P.RB * row;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_tiny_bwd_blocked_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      hipLaunchKernelGGL(attn_tiny_bwd_blocked_kernel, dim3(desc->G * desc->heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
-      FCMF_CHECK_LAUNCH();
-      return FCMF_OK;
+      return fcmf_launch(attn_tiny_bwd_blocked_kernel, dim3(desc->G * desc->heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
     }
   }
   if (rows_flat_ok(desc) && !dbias && (desc->T2 == 0 || grouped) && (desc->T1 == 0 || dv1) &&
@@ -1349,14 +1331,8 @@ static int attn_small_bwd_impl(const fcmf_attn_desc* desc, const void* out, cons
       hipStream_t st = reinterpret_cast<hipStream_t>(stream);
       hipLaunchKernelGGL(attn_rows_flat_bwd_kernel, dim3(desc->G * desc->heads), dim3(256), smem, st, P);
       FCMF_CHECK_LAUNCH();
-      if (grouped) {
-        dim3 grid2((desc->G / desc->group_div) * desc->R, 4);
-        auto k = attn_private_grad_kernel<bf16_t>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-        hipLaunchKernelGGL(k, grid2, dim3(256), smem2, st, P);
-        FCMF_CHECK_LAUNCH();
-      }
-      return FCMF_OK;
+      if (!grouped) return FCMF_OK;
+      return fcmf_launch(attn_private_grad_kernel<bf16_t>, dim3((desc->G / desc->group_div) * desc->R, 4), dim3(256), smem2, st, P);
     }
   }
   const int nsh = desc->T1 < 128 ? desc->T1 : 128;
@@ -1372,35 +1348,16 @@ static int attn_small_bwd_impl(const fcmf_attn_desc* desc, const void* out, cons
   const int nchunks = desc->T1 > 0 ? (desc->T1 + 127) / 128 : 1;
   dim3 grid(desc->G * desc->heads, nchunks);
   const bool one = P.RB >= desc->R;
-#define LAUNCH_(T, ONE, GR)                                                                                                \
-  do {                                                                                                                     \
-    auto k = attn_small_bwd_kernel<T, ONE, GR>;                                                                            \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);    \
-    hipLaunchKernelGGL(k, grid, dim3(256), smem, st, P);                                                                   \
-  } while (0)
+#define LAUNCH_(T, ONE, GR) fcmf_launch(attn_small_bwd_kernel<T, ONE, GR>, grid, dim3(256), smem, st, P)
 #define LAUNCH_T(T)                                                                                                        \
-  do {                                                                                                                     \
-    if (grouped) { if (one) LAUNCH_(T, true, true); else LAUNCH_(T, false, true); }                                        \
-    else         { if (one) LAUNCH_(T, true, false); else LAUNCH_(T, false, false); }                                      \
-  } while (0)
-  if (desc->dtype == FCMF_F32) LAUNCH_T(float); else LAUNCH_T(bf16_t);
+  (grouped ? (one ? LAUNCH_(T, true, true) : LAUNCH_(T, false, true)) : (one ? LAUNCH_(T, true, false) : LAUNCH_(T, false, false)))
+  rc = desc->dtype == FCMF_F32 ? LAUNCH_T(float) : LAUNCH_T(bf16_t);
 #undef LAUNCH_T
 #undef LAUNCH_
-  FCMF_CHECK_LAUNCH();
-  if (grouped) {
-    dim3 grid2((desc->G / desc->group_div) * desc->R, 4);    // 4 key ranges per (review, row): ~1800 workgroups on the step
-    if (desc->dtype == FCMF_F32) {
-      auto k = attn_private_grad_kernel<float>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-      hipLaunchKernelGGL(k, grid2, dim3(256), smem2, st, P);
-    } else {
-      auto k = attn_private_grad_kernel<bf16_t>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-      hipLaunchKernelGGL(k, grid2, dim3(256), smem2, st, P);
-    }
-    FCMF_CHECK_LAUNCH();
-  }
-  return FCMF_OK;
+  if (rc != FCMF_OK || !grouped) return rc;
+  const dim3 grid2((desc->G / desc->group_div) * desc->R, 4);    // 4 key ranges per (review, row): ~1800 workgroups on the step
+  if (desc->dtype == FCMF_F32) return fcmf_launch(attn_private_grad_kernel<float>, grid2, dim3(256), smem2, st, P);
+  return fcmf_launch(attn_private_grad_kernel<bf16_t>, grid2, dim3(256), smem2, st, P);
 }
 
 extern "C" int fcmf_attn_small_bwd(const fcmf_attn_desc* desc, const void* out, const void* dout, const float* lse,

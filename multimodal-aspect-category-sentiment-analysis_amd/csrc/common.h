@@ -16,6 +16,24 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
     if (e__ != hipSuccess) return FCMF_ERR_LAUNCH;                     \
   } while (0)
 
+// Launches k(args...) and returns FCMF_OK / FCMF_ERR_LAUNCH.  A launch with dynamic LDS first raises the kernel's
+// dynamic-LDS limit to `smem` (above 64 KiB the default limit refuses the launch) -- before EVERY such launch, or, with
+// `attr_set`, at the first launch through that flag only (kernels whose dynamic LDS is one constant: attn_mfma.hip).
+template <class... P, class... A>
+static int fcmf_launch_flagged(bool* attr_set, void (*k)(P...), dim3 grid, dim3 block, size_t smem, hipStream_t st, A&&... args) {
+  if (smem && !(attr_set && *attr_set)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (attr_set) *attr_set = true;
+  }
+  hipLaunchKernelGGL(k, grid, block, smem, st, static_cast<P>(args)...);
+  FCMF_CHECK_LAUNCH();
+  return FCMF_OK;
+}
+template <class... P, class... A>
+static int fcmf_launch(void (*k)(P...), dim3 grid, dim3 block, size_t smem, hipStream_t st, A&&... args) {
+  return fcmf_launch_flagged(nullptr, k, grid, block, smem, st, args...);
+}
+
 // ---- scalar conversions ----------------------------------------------------------------
 template <typename T> __device__ __forceinline__ float to_f32(T x);
 template <> __device__ __forceinline__ float to_f32<float>(float x) { return x; }

@@ -6,7 +6,10 @@
 //   gemm_bf16_kernel   : 128x128x32 block tile, 4 waves (2x2), 4-stage LDS-DMA ring, two workgroups per CU, split-K
 //                        with f32 atomics -- small / ragged / narrow outputs and tanh epilogues;
 //   gemm_generic_kernel: any dtype / any stride, exact-f32 v_mfma_f32_16x16x4_f32.  Parity path (fp32 mode) and odd
-//                        shapes (classifier N=4, box WG 64->8 ...).
+//                        shapes (classifier N=4, box WG 64->8 ...);
+//   gemm_bf16_small_kernel: 64x64 tiles where 128x128 tiles would leave most CUs empty; gemm_fp8_tile192_kernel: e4m3 operands;
+//   gemm_bf16_dw_batched_kernel: up to 32 same-shape weight gradients as one work list; splitk_reduce_*: the reduce passes.
+// Host half (end of the file): entry point -> GemmArgs -> plan_gemm (pure) -> GemmPlan -> run_plan (the only launcher).
 #include "common.h"
 #include <cstdio>
 
@@ -1459,25 +1462,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ X, fl
   }
 }
 
-// =========================================================================================
-// host dispatch
-// =========================================================================================
-template <bool A_TR, bool B_TR>
-static int launch_bf16(const GemmParams& p, int out_dtype, dim3 grid, hipStream_t st) {
-  size_t smem = NSTAGE * STAGE_BYTES;
-  if (out_dtype == FCMF_F32) {
-    auto k = gemm_bf16_kernel<A_TR, B_TR, float>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(k, grid, dim3(256), smem, st, p);
-  } else {
-    auto k = gemm_bf16_kernel<A_TR, B_TR, bf16_t>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(k, grid, dim3(256), smem, st, p);
-  }
-  FCMF_CHECK_LAUNCH();
-  return FCMF_OK;
-}
-
+// ---- __global__ entry points of the persistent body ---------------------------------------------------------------------
 // (thin __global__ wrapper: the body holds AMDGPU inline-asm constraints, which the host pass must never see
 // inside a kernel template -- it would silently drop the host-side kernel handle)
 template <bool A_TR, bool B_TR, typename TC, int EPI>
@@ -1518,56 +1503,7 @@ template <int EPI>
 __global__ __launch_bounds__(512, 1) void gemm_fp8_tile192_kernel(GemmParams p) {
   gemm_bf16_tile256_body<false, false, bf16_t, EPI, 6, 64, true>(p);
 }
-template <int EPI>
-static void launch_fp8_tile(const GemmParams& p, dim3 grid, hipStream_t st) {
-  const size_t smem = (size_t)RING_BYTES + 8 * 4096;
-  auto k = gemm_fp8_tile192_kernel<EPI>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(k, grid, dim3(512), smem, st, p);
-}
 
-template <bool A_TR, bool B_TR, typename TC, int EPI>
-static void launch_bf16_tile_typed(const GemmParams& p, dim3 grid, hipStream_t st, int tm, int kb) {
-  const size_t smem = (size_t)RING_BYTES + 8 * 4096;   // ring + per-wave transposition slices = 160 KiB
-  if constexpr (!A_TR && !B_TR && sizeof(TC) == 2) {
-    if (kb == 64) {
-      if (tm == 192) {
-        auto k = gemm_bf16_tile192k64_kernel<EPI>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(512), smem, st, p);
-      } else {
-        auto k = gemm_bf16_tile256k64_kernel<EPI>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(512), smem, st, p);
-      }
-      return;
-    }
-  }
-  if constexpr (!A_TR && sizeof(TC) == 2) {
-    if (tm == 192) {
-      auto k = gemm_bf16_tile192_kernel<B_TR, EPI>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      hipLaunchKernelGGL(k, grid, dim3(512), smem, st, p);
-      return;
-    }
-  }
-  auto k = gemm_bf16_tile256_kernel<A_TR, B_TR, TC, EPI>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(k, grid, dim3(512), smem, st, p);
-}
-
-template <bool A_TR, bool B_TR>
-static int launch_bf16_tile(const GemmParams& p, int out_dtype, dim3 grid, hipStream_t st, int tm, int kb) {
-  if (out_dtype == FCMF_F32) launch_bf16_tile_typed<A_TR, B_TR, float, FCMF_EPI_NONE>(p, grid, st, 256, 32);
-  else switch (p.epilogue) {
-    case FCMF_EPI_NONE: launch_bf16_tile_typed<A_TR, B_TR, bf16_t, FCMF_EPI_NONE>(p, grid, st, tm, kb); break;
-    case FCMF_EPI_GELU: launch_bf16_tile_typed<A_TR, B_TR, bf16_t, FCMF_EPI_GELU>(p, grid, st, tm, kb); break;
-    case FCMF_EPI_DGELU: launch_bf16_tile_typed<A_TR, B_TR, bf16_t, FCMF_EPI_DGELU>(p, grid, st, tm, kb); break;
-    default: launch_bf16_tile_typed<A_TR, B_TR, bf16_t, FCMF_EPI_ADD>(p, grid, st, tm, kb); break;
-  }
-  FCMF_CHECK_LAUNCH();
-  return FCMF_OK;
-}
 // C (+)= sum_z ws[z]: the reduce pass of the workspace split-K (partials were just written: L2 / Infinity Cache hits)
 // C (+)= sum_z ws[z] for partial tiles stored in the FRAGMENT layout (the f32 epilogue above): ws[z][tile][wave][fj][fi][lane][4].
 // One thread sums the `ksplit` copies of one 16-byte piece (coalesced KiB reads per wave) and writes it to its (row, column).
@@ -1677,235 +1613,393 @@ extern "C" const char* fcmf_gemm_ctx_last_kernel(const fcmf_gemm_ctx* ctx) { ret
 
 struct ConvGeom { int C, logC, Hp, Wp, Ho, Wo, kw, stride; int64_t in_bytes; int logP; };
 
+// =========================================================================================
+// host dispatch: entry point -> GemmArgs -> plan_gemm (pure: which kernel, grid, parameters, reduce pass, name) -> run_plan
+// =========================================================================================
+// what an entry point asks for (filled by field name from zero; the stream travels beside it)
+struct GemmArgs {
+  const void* A; const void* B; void* C;
+  const float* bias; void* aux; float* colsum;
+  int M, N, K;
+  int64_t lda, ldb, ldc;
+  int trans_a, trans_b, in_dtype, out_dtype, epilogue, accumulate;
+  const ConvGeom* cv;              // implicit-GEMM convolution: A is the NHWC activation
+  float* colstats;                 // block statistics of the output (fcmf_gemm_colstats)
+  int cblk; int64_t cblk_stride;   // column-blocked output (fcmf_gemm_colblocks)
+};
+
+enum GemmKernel { GK_NONE, GK_GENERIC, GK_TILE128, GK_SMALL, GK_NARROW, GK_PERSISTENT, GK_FP8, GK_DW_BATCHED };
+enum GemmReduce { RED_NONE, RED_ROWS, RED_FRAG, RED_FRAG_BATCHED };
+struct GemmPlan {
+  GemmKernel kernel;               // GK_NONE: nothing to launch (an empty output)
+  int tm, kb, trans_a, trans_b, in_dtype, out_dtype, epilogue;   // what selects the kernel's instantiation
+  dim3 grid, block;
+  size_t smem;
+  GemmParams p;                    // every kernel but the generic one
+  GenericParams g;                 // GK_GENERIC
+  const BatchPtrs* batch;          // GK_DW_BATCHED: the chunk's pointer tables (the caller's)
+  GemmReduce reduce;               // pass over the split-K partial tiles in p.ws
+  int reduce_blocks, cblk;
+  int64_t cblk_stride;
+  char name[96];
+};
+
+constexpr size_t PERSIST_SMEM = (size_t)RING_BYTES + 8 * 4096;   // ring + per-wave transposition slices = 160 KiB
+
+static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+static const char* const epi_names[] = {"NONE", "GELU", "TANH", "DGELU", "DTANH", "ADD"};
+
+static void plan_begin(GemmPlan* pl, const GemmArgs& a, GemmKernel kernel) {
+  pl->kernel = kernel; pl->tm = 0; pl->kb = 32;
+  pl->trans_a = a.trans_a; pl->trans_b = a.trans_b; pl->in_dtype = a.in_dtype; pl->out_dtype = a.out_dtype; pl->epilogue = a.epilogue;
+  pl->batch = nullptr; pl->reduce = RED_NONE; pl->reduce_blocks = 0; pl->cblk = a.cblk; pl->cblk_stride = a.cblk_stride;
+}
+
+static int64_t c_extent_bytes(const GemmArgs& a) { return (((int64_t)a.M - 1) * a.ldc + a.N) * 2; }   // (of a 2-byte output)
+
+// the kernels' parameter block from zero: the problem, the convolution geometry and the operand extents (elem_bytes per operand element)
+static GemmParams base_params(const GemmArgs& a, int elem_bytes) {
+  GemmParams p{};
+  p.A = a.A; p.B = a.B; p.C = a.C; p.bias = a.bias; p.aux = a.aux; p.colsum = a.colsum; p.colstats = a.colstats;
+  p.M = a.M; p.N = a.N; p.K = a.K; p.lda = a.lda; p.ldb = a.ldb; p.ldc = a.ldc;
+  p.epilogue = a.epilogue; p.accumulate = a.accumulate; p.ksplit = 1;
+  if (const ConvGeom* cv = a.cv) {
+    p.cv_C = cv->C; p.cv_logC = cv->logC; p.cv_Hp = cv->Hp; p.cv_Wp = cv->Wp; p.cv_Ho = cv->Ho; p.cv_Wo = cv->Wo;
+    p.cv_kw = cv->kw; p.cv_inv_kw = (65536 + cv->kw - 1) / cv->kw; p.cv_stride = cv->stride; p.cv_logP = cv->logP;
+  }
+  // bytes addressable through each operand: (rows - 1) * ld + contiguous extent
+  p.a_bytes = a.cv ? (unsigned)a.cv->in_bytes : (unsigned)((((int64_t)(a.trans_a ? a.K : a.M) - 1) * a.lda + (a.trans_a ? a.M : a.K)) * elem_bytes);
+  p.b_bytes = (unsigned)((((int64_t)(a.trans_b ? a.K : a.N) - 1) * a.ldb + (a.trans_b ? a.N : a.K)) * elem_bytes);
+  const int64_t c_extent = c_extent_bytes(a);
+  p.c_bytes = (unsigned)(c_extent < (1ll << 31) ? c_extent : 0);
+  return p;
+}
+
+// The work list of the persistent kernels: `tiles` output tiles x the slices of a `ksplit`-way split of the nk k-tiles (whole
+// k-tiles per slice, so the split may come out smaller than asked), walked by one workgroup per CU.  Returns the grid.
+static dim3 persistent_list(const fcmf_gemm_ctx& cfg, GemmParams& p, int tiles, int nk, int ksplit, bool bf16_out) {
+  p.ktiles_per_split = (nk + ksplit - 1) / ksplit;
+  p.ksplit = (nk + p.ktiles_per_split - 1) / p.ktiles_per_split;
+  p.tiles = tiles;
+  p.total_items = tiles * p.ksplit;
+  p.nt_out = bf16_out && (int64_t)p.M * p.N * 2 >= cfg.nt_min_bytes;
+  return dim3(p.total_items < cfg.num_cus ? p.total_items : cfg.num_cus);
+}
+static void plan_persistent_launch(GemmPlan* pl, dim3 grid) { pl->grid = grid; pl->block = dim3(512); pl->smem = PERSIST_SMEM; }
+
+// reduce pass over fragment-layout partial tiles (one thread per 16-byte piece of a tile)
+static void plan_frag_reduce(GemmPlan* pl, GemmReduce kind) {
+  const int64_t total4 = (int64_t)pl->p.tiles * (GB * GB / 4);
+  pl->reduce = kind;
+  pl->reduce_blocks = (int)((total4 + 255) / 256 < 4096 ? (total4 + 255) / 256 : 4096);
+}
+
+// ---- split-K choices --------------------------------------------------------------------------------------------------
+// persistent kernel, fewer tiles than CUs: one work item per CU, each at least min_kt k-tiles deep
+static int persistent_ksplit(int slots, int tiles, int nk, int kb) {
+  int ksplit = slots / tiles;
+  const int min_kt = (nk * (kb / 32) >= 64 ? 8 : 6) / (kb / 32);   // >= 256 (192) k per work item: short contractions (K = 768 rows) split 4 ways
+  if (ksplit > nk / min_kt) ksplit = nk / min_kt > 0 ? nk / min_kt : 1;
+  if (ksplit > 64) ksplit = 64;
+  return ksplit;
+}
+// 128 x 128 kernel, accumulating f32 output whose grid cannot fill the chip (weight gradients: K = number of tokens).
+// (unsplit, 36 lone workgroups of 24 k-tiles were measured SLOWER than 6-way split + float atomics on the IAOG
+// decoder's 768 x 768 x 768-row weight gradients: a single workgroup per CU has nothing to overlap its latencies with)
+static int tile128_ksplit(int tiles, int nk) {
+  int ksplit = 512 / tiles;   // one round of <= 512 resident blocks (256 CUs x 2)
+  if (ksplit > nk / 4) ksplit = nk / 4 > 0 ? nk / 4 : 1;
+  if (ksplit > 32) ksplit = 32;
+  return ksplit;
+}
+// generic kernel, accumulating f32 output of `blocks` < 128 tiles: contraction range per blockIdx.z, or 0 for no split
+static int generic_kchunk(int K, int blocks) {
+  int ks = 256 / blocks;                               // about one workgroup per CU
+  if (ks > K / 32) ks = K / 32;                        // >= 32 contraction steps each
+  return ks > 1 ? ((K + ks - 1) / ks + 15) / 16 * 16 : 0;   // multiple of the kernel's 16-deep k step
+}
+
 // shapes of the narrow-output layouts of the persistent kernel (N <= 64: 8 x 1 waves of 32 rows; N <= 128: 4 x 2 waves of 64 rows)
 static bool narrow_shape(int M, int N, int K) { return N >= 32 && N <= 128 && N % 8 == 0 && K % 64 == 0 && M >= 8192; }
 
-// rows per block of the statistics fcmf_gemm_colstats / fcmf_conv_gemm_colstats emit for an [M, N] output contracted over K:
-// 128 (256-column tiles), 256 (narrow layouts: one block per tile), 0 where no kernel emits them (the GEMM call then returns FCMF_ERR_UNSUPPORTED)
-extern "C" int fcmf_gemm_colstats_block_rows(const fcmf_gemm_ctx* ctx, int M, int N, int K) {
-  const fcmf_gemm_ctx& cfg = ctx ? *ctx : g_default_ctx;
-  if (cfg.force_tile == 0 && cfg.kb64 && narrow_shape(M, N, K)) return 256;
-  return (M >= 256 && N >= 256 && N % 8 == 0) ? 128 : 0;
+// what the MFMA kernels' loaders need of the operands
+static bool mfma_operands_ok(const GemmArgs& a) {
+  // contiguous extents that the 16-byte loaders walk must be multiples of 8 elements
+  const int a_contig = a.trans_a ? a.M : a.K, b_contig = a.trans_b ? a.N : a.K;
+  return a.in_dtype == FCMF_BF16 && al16(a.A) && al16(a.B) && al16(a.C) && (!a.aux || al16(a.aux)) &&
+         (!a.bias || al16(a.bias)) && (a.lda % 8 == 0) && (a.ldb % 8 == 0) && (a_contig % 8 == 0) &&
+         (b_contig % 8 == 0) && (a.N % 4 == 0) && (a.ldc % 4 == 0) && a.K > 0 &&
+         // K-contiguous operands cannot zero-fill a partial k-tile; 32-bit byte offsets
+         (a.trans_a || a.K % BK == 0) && (a.trans_b || a.K % BK == 0) &&
+         (a.cv || ((int64_t)(a.trans_a ? a.K : a.M) * a.lda) < (1ll << 30)) &&      // (cv: A's extent is the activation's, checked by the caller)
+         (((int64_t)(a.trans_b ? a.K : a.N) * a.ldb) < (1ll << 30));
 }
 
-static int gemm_impl(fcmf_gemm_ctx* ctx, const void* A, const void* B, void* C, const float* bias, void* aux, float* colsum,
-                     int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int trans_a, int trans_b, int in_dtype,
-                     int out_dtype, int epilogue, int accumulate, void* stream, const ConvGeom* cv, float* colstats = nullptr,
-                     int cblk = 0, int64_t cblk_stride = 0) {
-  if (!A || !B || !C || M < 0 || N < 0 || K < 0) return FCMF_ERR_ARG;
-  const fcmf_gemm_ctx& cfg = ctx ? *ctx : g_default_ctx;
-  char name_sink[96];
-  char* const last_kernel = ctx ? ctx->last_kernel : name_sink;
-  constexpr size_t NAME = sizeof(name_sink);
-  if (M == 0 || N == 0) return FCMF_OK;
-  if (accumulate && out_dtype != FCMF_F32) return FCMF_ERR_ARG;
-  if ((epilogue == FCMF_EPI_DGELU || epilogue == FCMF_EPI_DTANH || epilogue == FCMF_EPI_ADD) && !aux) return FCMF_ERR_ARG;
-  if (colsum && accumulate) return FCMF_ERR_ARG;   // column sums are those of the final C, not of split-K partials
-  if (in_dtype != FCMF_F32 && in_dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
-  if (out_dtype != FCMF_F32 && out_dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  // contiguous extents that the 16-byte loaders walk must be multiples of 8 elements
-  const int a_contig = trans_a ? M : K, b_contig = trans_b ? N : K;
-  const bool fast = in_dtype == FCMF_BF16 && al16(A) && al16(B) && al16(C) && (!aux || al16(aux)) &&
-                    (!bias || al16(bias)) && (lda % 8 == 0) && (ldb % 8 == 0) && (a_contig % 8 == 0) &&
-                    (b_contig % 8 == 0) && (N % 4 == 0) && (ldc % 4 == 0) && K > 0 &&
-                    // K-contiguous operands cannot zero-fill a partial k-tile; 32-bit byte offsets
-                    (trans_a || K % BK == 0) && (trans_b || K % BK == 0) &&
-                    (cv || ((int64_t)(trans_a ? K : M) * lda) < (1ll << 30)) && (((int64_t)(trans_b ? K : N) * ldb) < (1ll << 30));   // (cv: A's extent is the activation's, checked by the caller)
-  if (fast) {
-    GemmParams p{A, B, C, bias, aux, M, N, K, lda, ldb, ldc, epilogue, accumulate, 1, 0, 0, 0, 0, colsum, 0, 0, nullptr, 0, nullptr, nullptr,
-                 0, 0, 0, 0, 0, 0, 0, 0, 0, colstats, 0, 0};
-    if (cv) { p.cv_C = cv->C; p.cv_logC = cv->logC; p.cv_Hp = cv->Hp; p.cv_Wp = cv->Wp; p.cv_Ho = cv->Ho; p.cv_Wo = cv->Wo; p.cv_kw = cv->kw; p.cv_inv_kw = (65536 + cv->kw - 1) / cv->kw; p.cv_stride = cv->stride; p.cv_logP = cv->logP; }
-    // bytes addressable through each operand: (rows - 1) * ld + contiguous extent
-    p.a_bytes = cv ? (unsigned)cv->in_bytes : (unsigned)((((int64_t)(trans_a ? K : M) - 1) * lda + (trans_a ? M : K)) * 2);
-    p.b_bytes = (unsigned)((((int64_t)(trans_b ? K : N) - 1) * ldb + (trans_b ? N : K)) * 2);
-    const int64_t c_extent = (((int64_t)M - 1) * ldc + N) * 2;
-    p.c_bytes = (unsigned)(c_extent < (1ll << 31) ? c_extent : 0);
-    const int nk = (K + BK - 1) / BK;
-    // 256x256 persistent ping-pong kernel for the big problems; 128x128 for small / ragged / narrow outputs,
-    // f32 outputs with an activation epilogue and tanh epilogues (poolers)
-    const bool tile_ok = (N % 8 == 0) && (ldc % 8 == 0) && (out_dtype == FCMF_BF16 || epilogue == FCMF_EPI_NONE) &&
-                         epilogue != FCMF_EPI_TANH && epilogue != FCMF_EPI_DTANH &&
-                         (out_dtype == FCMF_F32 || c_extent < (1ll << 31));
-    // (weight gradients: the 256x256 kernel's row-wise f32 epilogue / 256-byte atomics beat the 128x128 kernel's
-    // fragment-layout atomics from K = 1024 up -- 25 vs 97 us at 768x768x2048)
-    // f32 outputs WITHOUT accumulate (a fresh weight-gradient buffer: no zero fill needed) may still split K when the context
-    // owns a workspace: the reduce pass then writes the sum instead of adding it
-    const bool splittable = epilogue == FCMF_EPI_NONE && out_dtype == FCMF_F32 && !colsum &&
-                            (accumulate || (cfg.ws != nullptr && !bias));
-    bool large = tile_ok && M >= 256 && N >= 256 &&
-                 ((int64_t)M * N >= (int64_t)256 * 256 * 64 || (splittable && K >= 512));
-    if (cfg.force_tile == 128) large = false;
-    if (cfg.force_tile == 256 || cfg.force_tile == 192) large = tile_ok;
-    if (cblk) {      // column-blocked output: written by the fragment-layout reduce pass only (f32, split K through the workspace)
-      if (!(tile_ok && splittable && out_dtype == FCMF_F32 && cfg.ws && M >= 256 && N >= 256 && cblk % 4 == 0 && N % cblk == 0)) return FCMF_ERR_UNSUPPORTED;
-      large = true;
-    }
-    // narrow outputs with many rows (the trunk's 64- / 128-channel convolutions): the persistent kernel's 4 x 2 / 8 x 1 wave layouts
-    const bool narrow = cfg.force_tile == 0 && cfg.kb64 && tile_ok && !colsum && !aux && !accumulate && !trans_a && !trans_b &&
-                        out_dtype == FCMF_BF16 && epilogue == FCMF_EPI_NONE && narrow_shape(M, N, K);
-    if (narrow) {
-      p.ksplit = 1; p.ktiles_per_split = K / 64;
-      p.tiles = (M + GB - 1) / GB; p.total_items = p.tiles;
-      p.ws = nullptr;
-      p.nt_out = (int64_t)M * N * 2 >= cfg.nt_min_bytes;
-      const dim3 grid(p.total_items < cfg.num_cus ? p.total_items : cfg.num_cus);
-      const size_t smem = (size_t)RING_BYTES + 8 * 4096;
-      snprintf(last_kernel, NAME, "gemm_bf16_tile256k64_n%d_kernel", N <= 64 ? 64 : 128);
-      if (N <= 64) {
-        auto k = gemm_bf16_tile256k64_n64_kernel;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(512), smem, st, p);
-      } else {
-        auto k = gemm_bf16_tile256k64_n128_kernel;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(512), smem, st, p);
-      }
-      FCMF_CHECK_LAUNCH();
-      return FCMF_OK;
-    }
-    if (colstats) {       // block statistics exist in the 256-row bf16 kernels only: the caller falls back to a statistics pass
-      // (they were built into the 128 x 128 kernel too -- the trunk's 64 / 128-channel layers -- and measured: its epilogue, a
-      //  fragment-layout one, pays as much for the rounding, the 128 shuffles and two barriers as the separate pass costs)
-      if (!(tile_ok && M >= 256 && N >= 256 && out_dtype == FCMF_BF16 && !trans_a && !trans_b && epilogue == FCMF_EPI_NONE &&
-            !accumulate && !aux))
-        return FCMF_ERR_UNSUPPORTED;
-      large = true;
-    }
-    if (large) {
-      const int slots = cfg.num_cus;
-      // block tile rows: 256, or 192 where that removes a nearly empty last round (cost model: rounds x
-      // (k-loop time scaled by the tile rows + a fixed per-tile cost of ~8 k-tiles))
-      int tm = 256;
-      if (!trans_a && out_dtype == FCMF_BF16 && !accumulate) {
-        auto cost = [&](int rows) {
-          const int64_t t = (int64_t)((M + rows - 1) / rows) * ((N + GB - 1) / GB);
-          return (double)((t + slots - 1) / slots) * (nk * (rows / 256.0) + 8.0);
-        };
-        if (cost(192) < 0.97 * cost(256) && !colstats) tm = 192;
-      }
-      if (cfg.force_tile == 192 && !trans_a && out_dtype == FCMF_BF16 && !accumulate && !colstats) tm = 192;
-      const int tiles_l = ((M + tm - 1) / tm) * ((N + GB - 1) / GB);
-      // 64-deep k-tiles where both operands are K-contiguous (whole-line DMA), the output is bf16 and K allows it
-      // (weight gradients -- token-major operands, 512-B DMA rows already -- measured 4-8 % SLOWER on 64-deep k-tiles)
-      const int kb = (cfg.kb64 && !trans_a && !trans_b && out_dtype == FCMF_BF16 && !accumulate && K % 64 == 0) ? 64 : 32;
-      const int nk = (K + kb - 1) / kb;      // (shadows the 32-deep count above: the kernel counts k-tiles of ITS depth)
-      int ksplit = 1;
-      if (splittable && tiles_l < slots) {
-        ksplit = slots / tiles_l;
-        const int min_kt = (nk * (kb / 32) >= 64 ? 8 : 6) / (kb / 32);   // >= 256 (192) k per work item: short contractions (K = 768 rows) split 4 ways
-        if (ksplit > nk / min_kt) ksplit = nk / min_kt > 0 ? nk / min_kt : 1;
-        if (ksplit > 64) ksplit = 64;
-      }
-      p.ktiles_per_split = (nk + ksplit - 1) / ksplit;
-      p.ksplit = (nk + p.ktiles_per_split - 1) / p.ktiles_per_split;
-      p.tiles = tiles_l;
-      p.total_items = tiles_l * p.ksplit;
-      dim3 grid(p.total_items < slots ? p.total_items : slots);
-      p.ws = nullptr;
-      p.nt_out = out_dtype == FCMF_BF16 && (int64_t)M * N * 2 >= cfg.nt_min_bytes;
-      // (partial tiles are whole 256 x 256 fragment-layout tiles when the GEMM has neither bias nor column sums: size by tiles)
-      const bool frag_ws = !bias && !colsum;
-      const int64_t ws_need = frag_ws ? (int64_t)p.ksplit * tiles_l * GB * GB * 4 : (int64_t)p.ksplit * M * N * 4;
-      if (p.ksplit > 1 && out_dtype == FCMF_F32 && cfg.ws && cfg.ws_bytes >= ws_need) p.ws = cfg.ws;
-      if (p.ksplit > 1 && !accumulate && !p.ws) {       // (no workspace of that size: float atomics would need a zeroed C)
-        p.ksplit = 1; p.ktiles_per_split = nk; p.total_items = tiles_l;
-      }
-      if (cblk && !(p.ksplit > 1 && p.ws && frag_ws)) return FCMF_ERR_UNSUPPORTED;   // (only the reduce pass knows the blocked layout)
-      {
-        static const char* const epi_names[] = {"NONE", "GELU", "TANH", "DGELU", "DTANH", "ADD"};
-        if (kb == 64) snprintf(last_kernel, NAME, "gemm_bf16_tile%dk64_kernel<%s>", tm, epi_names[epilogue]);
-        else if (tm == 192) snprintf(last_kernel, NAME, "gemm_bf16_tile192_kernel<%d,%s>", trans_b, epi_names[epilogue]);
-        else snprintf(last_kernel, NAME, "gemm_bf16_tile256_kernel<%d,%d,%s,%s>", trans_a, trans_b, out_dtype == FCMF_F32 ? "f32" : "bf16", epi_names[epilogue]);
-      }
-      int rc;
-      if (!trans_a && !trans_b) rc = launch_bf16_tile<false, false>(p, out_dtype, grid, st, tm, kb);
-      else if (!trans_a && trans_b) rc = launch_bf16_tile<false, true>(p, out_dtype, grid, st, tm, kb);
-      else if (trans_a && !trans_b) rc = launch_bf16_tile<true, false>(p, out_dtype, grid, st, tm, kb);
-      else rc = launch_bf16_tile<true, true>(p, out_dtype, grid, st, tm, kb);
-      if (rc == FCMF_OK && p.ws) {
-        if (frag_ws) {
-          const int64_t total4 = (int64_t)tiles_l * (GB * GB / 4);
-          const int blocks = (int)((total4 + 255) / 256 < 4096 ? (total4 + 255) / 256 : 4096);
-          hipLaunchKernelGGL(splitk_reduce_frag_kernel, dim3(blocks), dim3(256), 0, st, p.ws, reinterpret_cast<float*>(C), M, N, ldc,
-                             p.ksplit, tiles_l, (N + GB - 1) / GB, accumulate, cblk, cblk_stride);
-        } else {
-          const int64_t total4 = (int64_t)M * N / 4;
-          const int blocks = (int)((total4 + 255) / 256 < 2048 ? (total4 + 255) / 256 : 2048);
-          hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p.ws, reinterpret_cast<float*>(C), M, N, ldc,
-                             p.ksplit, accumulate);
-        }
-        FCMF_CHECK_LAUNCH();
-      }
-      return rc;
-    }
-    if (colstats) return FCMF_ERR_UNSUPPORTED;
-    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    // small outputs (128 x 128 tiles would leave more than half of the CUs without a workgroup): the 64 x 64 kernel
-    if (cfg.force_tile == 0 && cfg.kb64 && !trans_a && !trans_b && !cv && K % 64 == 0 && tiles <= cfg.num_cus / 2 &&
-        (int64_t)M * N >= 64 * 64 && !(accumulate && epilogue == FCMF_EPI_NONE && nk >= 64)) {      // (long-K accumulations: split-K below)
-      p.ksplit = 1; p.ktiles_per_split = K / 64;
-      const dim3 grid(((M + SMALL_T - 1) / SMALL_T) * ((N + SMALL_T - 1) / SMALL_T));
-      const size_t smem = (size_t)NSTAGE * SMALL_STAGE_BYTES;
-      snprintf(last_kernel, NAME, "gemm_bf16_small_kernel<%s>", out_dtype == FCMF_F32 ? "f32" : "bf16");
-      if (out_dtype == FCMF_F32) {
-        auto k = gemm_bf16_small_kernel<float>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, p);
-      } else {
-        auto k = gemm_bf16_small_kernel<bf16_t>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k, grid, dim3(256), smem, st, p);
-      }
-      FCMF_CHECK_LAUNCH();
-      return FCMF_OK;
-    }
-    int ksplit = 1;
-    // split K only where the output grid cannot fill the chip and C is an f32 accumulator
-    // (weight gradients: K = number of tokens).
-    // (unsplit, 36 lone workgroups of 24 k-tiles were measured SLOWER than 6-way split + float atomics on the IAOG
-    // decoder's 768 x 768 x 768-row weight gradients: a single workgroup per CU has nothing to overlap its latencies with)
-    if (accumulate && epilogue == FCMF_EPI_NONE && tiles < 512) {
-      ksplit = 512 / tiles;   // one round of <= 512 resident blocks (256 CUs x 2)
-      if (ksplit > nk / 4) ksplit = nk / 4 > 0 ? nk / 4 : 1;
-      if (ksplit > 32) ksplit = 32;
-    }
-    p.ksplit = ksplit;
-    p.ktiles_per_split = (nk + ksplit - 1) / ksplit;
-    p.ksplit = (nk + p.ktiles_per_split - 1) / p.ktiles_per_split;
-    dim3 grid(tiles, 1, p.ksplit);
-    snprintf(last_kernel, NAME, "gemm_bf16_kernel<%d,%d,%s>", trans_a, trans_b, out_dtype == FCMF_F32 ? "f32" : "bf16");
-    if (!trans_a && !trans_b) return launch_bf16<false, false>(p, out_dtype, grid, st);
-    if (!trans_a && trans_b) return launch_bf16<false, true>(p, out_dtype, grid, st);
-    if (trans_a && !trans_b) return launch_bf16<true, false>(p, out_dtype, grid, st);
-    return launch_bf16<true, true>(p, out_dtype, grid, st);
-  }
-  if (cv || colstats) return FCMF_ERR_UNSUPPORTED;      // (the any-stride kernel has no implicit-convolution addressing, no block statistics)
-  GenericParams g{A, B, C, bias, aux, M, N, K,
-                  trans_a ? 1 : lda, trans_a ? lda : 1, trans_b ? 1 : ldb, trans_b ? ldb : 1, ldc,
-                  epilogue, accumulate, colsum, 0};
-  dim3 grid((N + 63) / 64, (M + 63) / 64);
-  if (accumulate && out_dtype == FCMF_F32 && epilogue == FCMF_EPI_NONE && !bias && !colsum && grid.x * grid.y < 128 && K >= 128) {
-    int ks = 256 / (int)(grid.x * grid.y);               // about one workgroup per CU
-    if (ks > K / 32) ks = K / 32;                        // >= 32 contraction steps each
-    if (ks > 1) {
-      g.kchunk = ((K + ks - 1) / ks + 15) / 16 * 16;     // multiple of the kernel's 16-deep k step
-      grid.z = (K + g.kchunk - 1) / g.kchunk;
-    }
-  }
-  snprintf(last_kernel, NAME, "gemm_generic_kernel");
-  if (in_dtype == FCMF_F32 && out_dtype == FCMF_F32)
-    hipLaunchKernelGGL((gemm_generic_kernel<float, float>), grid, dim3(256), 0, st, g);
-  else if (in_dtype == FCMF_BF16 && out_dtype == FCMF_BF16)
-    hipLaunchKernelGGL((gemm_generic_kernel<bf16_t, bf16_t>), grid, dim3(256), 0, st, g);
-  else if (in_dtype == FCMF_BF16 && out_dtype == FCMF_F32)
-    hipLaunchKernelGGL((gemm_generic_kernel<bf16_t, float>), grid, dim3(256), 0, st, g);
-  else
-    hipLaunchKernelGGL((gemm_generic_kernel<float, bf16_t>), grid, dim3(256), 0, st, g);
-  FCMF_CHECK_LAUNCH();
+// narrow outputs with many rows (the trunk's 64- / 128-channel convolutions): the persistent kernel's 4 x 2 / 8 x 1 wave layouts
+static int plan_narrow(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl) {
+  plan_begin(pl, a, GK_NARROW);
+  pl->tm = 256; pl->kb = 64;
+  pl->p = base_params(a, 2);
+  plan_persistent_launch(pl, persistent_list(cfg, pl->p, (a.M + GB - 1) / GB, a.K / 64, 1, true));
+  snprintf(pl->name, sizeof pl->name, "gemm_bf16_tile256k64_n%d_kernel", a.N <= 64 ? 64 : 128);
   return FCMF_OK;
+}
+
+// block tile rows of the persistent kernel: 256, or 192 where that removes a nearly empty last round (cost model: rounds x
+// (k-loop time scaled by the tile rows + a fixed per-tile cost of ~8 k-tiles))
+static int persistent_tile_rows(const fcmf_gemm_ctx& cfg, const GemmArgs& a) {
+  if (a.trans_a || a.out_dtype != FCMF_BF16 || a.accumulate || a.colstats) return 256;
+  if (cfg.force_tile == 192) return 192;
+  auto cost = [&](int rows) {
+    const int64_t t = (int64_t)((a.M + rows - 1) / rows) * ((a.N + GB - 1) / GB);
+    return (double)((t + cfg.num_cus - 1) / cfg.num_cus) * ((a.K + BK - 1) / BK * (rows / 256.0) + 8.0);
+  };
+  return cost(192) < 0.97 * cost(256) ? 192 : 256;
+}
+
+// 256 (192) x 256 persistent ping-pong kernel.  `splittable`: K may be split (an f32 accumulator, or a fresh f32 output that a
+// workspace reduce pass writes)
+static int plan_persistent(const fcmf_gemm_ctx& cfg, const GemmArgs& a, bool splittable, GemmPlan* pl) {
+  plan_begin(pl, a, GK_PERSISTENT);
+  GemmParams& p = pl->p;
+  p = base_params(a, 2);
+  const int slots = cfg.num_cus, tm = persistent_tile_rows(cfg, a);
+  const int tiles = ((a.M + tm - 1) / tm) * ((a.N + GB - 1) / GB);
+  // 64-deep k-tiles where both operands are K-contiguous (whole-line DMA), the output is bf16 and K allows it
+  // (weight gradients -- token-major operands, 512-B DMA rows already -- measured 4-8 % SLOWER on 64-deep k-tiles)
+  const int kb = (cfg.kb64 && !a.trans_a && !a.trans_b && a.out_dtype == FCMF_BF16 && !a.accumulate && a.K % 64 == 0) ? 64 : 32;
+  const int nk = (a.K + kb - 1) / kb;      // (the kernel counts k-tiles of ITS depth)
+  const int ksplit = splittable && tiles < slots ? persistent_ksplit(slots, tiles, nk, kb) : 1;
+  const dim3 grid = persistent_list(cfg, p, tiles, nk, ksplit, a.out_dtype == FCMF_BF16);
+  // (partial tiles are whole 256 x 256 fragment-layout tiles when the GEMM has neither bias nor column sums: size by tiles)
+  const bool frag_ws = !a.bias && !a.colsum;
+  const int64_t ws_need = frag_ws ? (int64_t)p.ksplit * tiles * GB * GB * 4 : (int64_t)p.ksplit * a.M * a.N * 4;
+  if (p.ksplit > 1 && a.out_dtype == FCMF_F32 && cfg.ws && cfg.ws_bytes >= ws_need) p.ws = cfg.ws;
+  // (no workspace of that size: float atomics would need a zeroed C.  The grid keeps the size it had with the split, as it
+  //  always has: workgroups beyond the work list find no item)
+  if (p.ksplit > 1 && !a.accumulate && !p.ws) persistent_list(cfg, p, tiles, nk, 1, a.out_dtype == FCMF_BF16);
+  if (a.cblk && !(p.ksplit > 1 && p.ws && frag_ws)) return FCMF_ERR_UNSUPPORTED;   // (only the reduce pass knows the blocked layout)
+  pl->tm = tm; pl->kb = kb;
+  plan_persistent_launch(pl, grid);
+  if (p.ws && frag_ws) plan_frag_reduce(pl, RED_FRAG);
+  else if (p.ws) {
+    const int64_t total4 = (int64_t)a.M * a.N / 4;
+    pl->reduce = RED_ROWS;
+    pl->reduce_blocks = (int)((total4 + 255) / 256 < 2048 ? (total4 + 255) / 256 : 2048);
+  }
+  if (kb == 64) snprintf(pl->name, sizeof pl->name, "gemm_bf16_tile%dk64_kernel<%s>", tm, epi_names[a.epilogue]);
+  else if (tm == 192) snprintf(pl->name, sizeof pl->name, "gemm_bf16_tile192_kernel<%d,%s>", a.trans_b, epi_names[a.epilogue]);
+  else snprintf(pl->name, sizeof pl->name, "gemm_bf16_tile256_kernel<%d,%d,%s,%s>", a.trans_a, a.trans_b, a.out_dtype == FCMF_F32 ? "f32" : "bf16", epi_names[a.epilogue]);
+  return FCMF_OK;
+}
+
+// the MFMA kernels: 256x256 persistent ping-pong kernel for the big problems; 128x128 for small / ragged / narrow outputs,
+// f32 outputs with an activation epilogue and tanh epilogues (poolers); 64x64 where 128x128 tiles leave the chip empty
+static int plan_mfma(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl) {
+  const int M = a.M, N = a.N, K = a.K;
+  const bool tile_ok = (N % 8 == 0) && (a.ldc % 8 == 0) && (a.out_dtype == FCMF_BF16 || a.epilogue == FCMF_EPI_NONE) &&
+                       a.epilogue != FCMF_EPI_TANH && a.epilogue != FCMF_EPI_DTANH &&
+                       (a.out_dtype == FCMF_F32 || c_extent_bytes(a) < (1ll << 31));
+  // (weight gradients: the 256x256 kernel's row-wise f32 epilogue / 256-byte atomics beat the 128x128 kernel's
+  // fragment-layout atomics from K = 1024 up -- 25 vs 97 us at 768x768x2048)
+  // f32 outputs WITHOUT accumulate (a fresh weight-gradient buffer: no zero fill needed) may still split K when the context
+  // owns a workspace: the reduce pass then writes the sum instead of adding it
+  const bool splittable = a.epilogue == FCMF_EPI_NONE && a.out_dtype == FCMF_F32 && !a.colsum &&
+                          (a.accumulate || (cfg.ws != nullptr && !a.bias));
+  const bool plain_bf16 = a.out_dtype == FCMF_BF16 && !a.trans_a && !a.trans_b && a.epilogue == FCMF_EPI_NONE && !a.accumulate && !a.aux;
+  bool large = tile_ok && M >= 256 && N >= 256 &&
+               ((int64_t)M * N >= (int64_t)256 * 256 * 64 || (splittable && K >= 512));
+  if (cfg.force_tile == 128) large = false;
+  if (cfg.force_tile == 256 || cfg.force_tile == 192) large = tile_ok;
+  if (a.cblk) {      // column-blocked output: written by the fragment-layout reduce pass only (f32, split K through the workspace)
+    if (!(tile_ok && splittable && a.out_dtype == FCMF_F32 && cfg.ws && M >= 256 && N >= 256 && a.cblk % 4 == 0 && N % a.cblk == 0)) return FCMF_ERR_UNSUPPORTED;
+    large = true;
+  }
+  if (cfg.force_tile == 0 && cfg.kb64 && tile_ok && !a.colsum && plain_bf16 && narrow_shape(M, N, K)) return plan_narrow(cfg, a, pl);
+  if (a.colstats) {       // block statistics exist in the 256-row bf16 kernels only: the caller falls back to a statistics pass
+    // (they were built into the 128 x 128 kernel too -- the trunk's 64 / 128-channel layers -- and measured: its epilogue, a
+    //  fragment-layout one, pays as much for the rounding, the 128 shuffles and two barriers as the separate pass costs)
+    if (!(tile_ok && M >= 256 && N >= 256 && plain_bf16)) return FCMF_ERR_UNSUPPORTED;
+    large = true;
+  }
+  if (large) return plan_persistent(cfg, a, splittable, pl);
+
+  GemmParams& p = pl->p;
+  p = base_params(a, 2);
+  const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN), nk = (K + BK - 1) / BK;
+  // small outputs (128 x 128 tiles would leave more than half of the CUs without a workgroup): the 64 x 64 kernel
+  if (cfg.force_tile == 0 && cfg.kb64 && !a.trans_a && !a.trans_b && !a.cv && K % 64 == 0 && tiles <= cfg.num_cus / 2 &&
+      (int64_t)M * N >= 64 * 64 && !(a.accumulate && a.epilogue == FCMF_EPI_NONE && nk >= 64)) {      // (long-K accumulations: split-K below)
+    plan_begin(pl, a, GK_SMALL);
+    pl->tm = SMALL_T; pl->kb = SMALL_KB;
+    p.ktiles_per_split = K / 64;
+    pl->grid = dim3(((M + SMALL_T - 1) / SMALL_T) * ((N + SMALL_T - 1) / SMALL_T)); pl->block = dim3(256);
+    pl->smem = (size_t)NSTAGE * SMALL_STAGE_BYTES;
+    snprintf(pl->name, sizeof pl->name, "gemm_bf16_small_kernel<%s>", a.out_dtype == FCMF_F32 ? "f32" : "bf16");
+    return FCMF_OK;
+  }
+  plan_begin(pl, a, GK_TILE128);
+  pl->tm = BM;
+  // split K only where the output grid cannot fill the chip and C is an f32 accumulator
+  const int ksplit = a.accumulate && a.epilogue == FCMF_EPI_NONE && tiles < 512 ? tile128_ksplit(tiles, nk) : 1;
+  p.ktiles_per_split = (nk + ksplit - 1) / ksplit;
+  p.ksplit = (nk + p.ktiles_per_split - 1) / p.ktiles_per_split;
+  pl->grid = dim3(tiles, 1, p.ksplit); pl->block = dim3(256);
+  pl->smem = NSTAGE * STAGE_BYTES;
+  snprintf(pl->name, sizeof pl->name, "gemm_bf16_kernel<%d,%d,%s>", a.trans_a, a.trans_b, a.out_dtype == FCMF_F32 ? "f32" : "bf16");
+  return FCMF_OK;
+}
+
+// any dtype / any stride: the exact-f32 kernel
+static int plan_generic(const GemmArgs& a, GemmPlan* pl) {
+  plan_begin(pl, a, GK_GENERIC);
+  GenericParams& g = pl->g;
+  g = GenericParams{};
+  g.A = a.A; g.B = a.B; g.C = a.C; g.bias = a.bias; g.aux = a.aux; g.colsum = a.colsum;
+  g.M = a.M; g.N = a.N; g.K = a.K;
+  g.a_si = a.trans_a ? 1 : a.lda; g.a_sk = a.trans_a ? a.lda : 1; g.b_sj = a.trans_b ? 1 : a.ldb; g.b_sk = a.trans_b ? a.ldb : 1; g.ldc = a.ldc;
+  g.epilogue = a.epilogue; g.accumulate = a.accumulate;
+  pl->grid = dim3((a.N + 63) / 64, (a.M + 63) / 64); pl->block = dim3(256);
+  pl->smem = 0;
+  const int blocks = (int)(pl->grid.x * pl->grid.y);
+  if (a.accumulate && a.out_dtype == FCMF_F32 && a.epilogue == FCMF_EPI_NONE && !a.bias && !a.colsum && blocks < 128 && a.K >= 128) {
+    g.kchunk = generic_kchunk(a.K, blocks);
+    if (g.kchunk) pl->grid.z = (a.K + g.kchunk - 1) / g.kchunk;
+  }
+  snprintf(pl->name, sizeof pl->name, "gemm_generic_kernel");
+  return FCMF_OK;
+}
+
+// Pure: reads the context's settings and the arguments, touches neither the device nor the context.
+static int plan_gemm(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl) {
+  if (!a.A || !a.B || !a.C || a.M < 0 || a.N < 0 || a.K < 0) return FCMF_ERR_ARG;
+  plan_begin(pl, a, GK_NONE);
+  if (a.M == 0 || a.N == 0) return FCMF_OK;
+  if (a.accumulate && a.out_dtype != FCMF_F32) return FCMF_ERR_ARG;
+  if ((a.epilogue == FCMF_EPI_DGELU || a.epilogue == FCMF_EPI_DTANH || a.epilogue == FCMF_EPI_ADD) && !a.aux) return FCMF_ERR_ARG;
+  if (a.colsum && a.accumulate) return FCMF_ERR_ARG;   // column sums are those of the final C, not of split-K partials
+  if (a.in_dtype != FCMF_F32 && a.in_dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
+  if (a.out_dtype != FCMF_F32 && a.out_dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
+  if (mfma_operands_ok(a)) return plan_mfma(cfg, a, pl);
+  if (a.cv || a.colstats) return FCMF_ERR_UNSUPPORTED;      // (the any-stride kernel has no implicit-convolution addressing, no block statistics)
+  return plan_generic(a, pl);
+}
+
+// ---- plan -> launches (the only place that names kernel instantiations) -------------------------------------------------
+template <bool A_TR, bool B_TR, typename TC, int EPI>
+static int launch_persistent_typed(const GemmPlan& pl, hipStream_t st) {
+  if constexpr (!A_TR && !B_TR && sizeof(TC) == 2) {
+    if (pl.kb == 64 && pl.tm == 192) return fcmf_launch(gemm_bf16_tile192k64_kernel<EPI>, pl.grid, pl.block, pl.smem, st, pl.p);
+    if (pl.kb == 64) return fcmf_launch(gemm_bf16_tile256k64_kernel<EPI>, pl.grid, pl.block, pl.smem, st, pl.p);
+  }
+  if constexpr (!A_TR && sizeof(TC) == 2) {
+    if (pl.tm == 192) return fcmf_launch(gemm_bf16_tile192_kernel<B_TR, EPI>, pl.grid, pl.block, pl.smem, st, pl.p);
+  }
+  return fcmf_launch(gemm_bf16_tile256_kernel<A_TR, B_TR, TC, EPI>, pl.grid, pl.block, pl.smem, st, pl.p);
+}
+template <bool A_TR, bool B_TR>
+static int launch_persistent(const GemmPlan& pl, hipStream_t st) {
+  if (pl.out_dtype == FCMF_F32) return launch_persistent_typed<A_TR, B_TR, float, FCMF_EPI_NONE>(pl, st);
+  switch (pl.epilogue) {
+    case FCMF_EPI_NONE: return launch_persistent_typed<A_TR, B_TR, bf16_t, FCMF_EPI_NONE>(pl, st);
+    case FCMF_EPI_GELU: return launch_persistent_typed<A_TR, B_TR, bf16_t, FCMF_EPI_GELU>(pl, st);
+    case FCMF_EPI_DGELU: return launch_persistent_typed<A_TR, B_TR, bf16_t, FCMF_EPI_DGELU>(pl, st);
+    default: return launch_persistent_typed<A_TR, B_TR, bf16_t, FCMF_EPI_ADD>(pl, st);
+  }
+}
+template <bool A_TR, bool B_TR>
+static int launch_tile128(const GemmPlan& pl, hipStream_t st) {
+  if (pl.out_dtype == FCMF_F32) return fcmf_launch(gemm_bf16_kernel<A_TR, B_TR, float>, pl.grid, pl.block, pl.smem, st, pl.p);
+  return fcmf_launch(gemm_bf16_kernel<A_TR, B_TR, bf16_t>, pl.grid, pl.block, pl.smem, st, pl.p);
+}
+static int launch_fp8(const GemmPlan& pl, hipStream_t st) {
+  switch (pl.epilogue) {
+    case FCMF_EPI_NONE: return fcmf_launch(gemm_fp8_tile192_kernel<FCMF_EPI_NONE>, pl.grid, pl.block, pl.smem, st, pl.p);
+    case FCMF_EPI_GELU: return fcmf_launch(gemm_fp8_tile192_kernel<FCMF_EPI_GELU>, pl.grid, pl.block, pl.smem, st, pl.p);
+    case FCMF_EPI_DGELU: return fcmf_launch(gemm_fp8_tile192_kernel<FCMF_EPI_DGELU>, pl.grid, pl.block, pl.smem, st, pl.p);
+    default: return fcmf_launch(gemm_fp8_tile192_kernel<FCMF_EPI_ADD>, pl.grid, pl.block, pl.smem, st, pl.p);
+  }
+}
+static int launch_generic(const GemmPlan& pl, hipStream_t st) {
+  if (pl.in_dtype == FCMF_F32 && pl.out_dtype == FCMF_F32) return fcmf_launch(gemm_generic_kernel<float, float>, pl.grid, pl.block, 0, st, pl.g);
+  if (pl.in_dtype == FCMF_BF16 && pl.out_dtype == FCMF_BF16) return fcmf_launch(gemm_generic_kernel<bf16_t, bf16_t>, pl.grid, pl.block, 0, st, pl.g);
+  if (pl.in_dtype == FCMF_BF16 && pl.out_dtype == FCMF_F32) return fcmf_launch(gemm_generic_kernel<bf16_t, float>, pl.grid, pl.block, 0, st, pl.g);
+  return fcmf_launch(gemm_generic_kernel<float, bf16_t>, pl.grid, pl.block, 0, st, pl.g);
+}
+// one of the four operand orientations of a launcher template
+#define FCMF_BY_TRANS(fn, pl, st)                                                                        \
+  ((pl).trans_a ? ((pl).trans_b ? fn<true, true>(pl, st) : fn<true, false>(pl, st))                      \
+                : ((pl).trans_b ? fn<false, true>(pl, st) : fn<false, false>(pl, st)))
+
+static int run_plan(const GemmPlan& pl, hipStream_t st) {
+  const GemmParams& p = pl.p;
+  int rc = FCMF_OK;
+  switch (pl.kernel) {
+    case GK_NONE: return FCMF_OK;
+    case GK_GENERIC: rc = launch_generic(pl, st); break;
+    case GK_TILE128: rc = FCMF_BY_TRANS(launch_tile128, pl, st); break;
+    case GK_SMALL:
+      rc = pl.out_dtype == FCMF_F32 ? fcmf_launch(gemm_bf16_small_kernel<float>, pl.grid, pl.block, pl.smem, st, p)
+                                    : fcmf_launch(gemm_bf16_small_kernel<bf16_t>, pl.grid, pl.block, pl.smem, st, p);
+      break;
+    case GK_NARROW:
+      rc = p.N <= 64 ? fcmf_launch(gemm_bf16_tile256k64_n64_kernel, pl.grid, pl.block, pl.smem, st, p)
+                     : fcmf_launch(gemm_bf16_tile256k64_n128_kernel, pl.grid, pl.block, pl.smem, st, p);
+      break;
+    case GK_PERSISTENT: rc = FCMF_BY_TRANS(launch_persistent, pl, st); break;
+    case GK_FP8: rc = launch_fp8(pl, st); break;
+    case GK_DW_BATCHED: rc = fcmf_launch(gemm_bf16_dw_batched_kernel, pl.grid, pl.block, pl.smem, st, p, *pl.batch); break;
+  }
+  if (rc != FCMF_OK) return rc;
+  const dim3 rgrid(pl.reduce_blocks), rblock(256);
+  float* const C = reinterpret_cast<float*>(p.C);
+  const int tiles_n = (p.N + GB - 1) / GB;
+  switch (pl.reduce) {
+    case RED_NONE: return FCMF_OK;
+    case RED_ROWS: return fcmf_launch(splitk_reduce_kernel, rgrid, rblock, 0, st, p.ws, C, p.M, p.N, p.ldc, p.ksplit, p.accumulate);
+    case RED_FRAG:
+      return fcmf_launch(splitk_reduce_frag_kernel, rgrid, rblock, 0, st, p.ws, C, p.M, p.N, p.ldc, p.ksplit, p.tiles, tiles_n, p.accumulate,
+                         pl.cblk, pl.cblk_stride);
+    case RED_FRAG_BATCHED:
+      return fcmf_launch(splitk_reduce_frag_batched_kernel, rgrid, rblock, 0, st, p.ws, *pl.batch, p.tiles_per_mat, p.M, p.N, p.ldc, p.ksplit,
+                         p.tiles, tiles_n, p.accumulate);
+  }
+  return FCMF_OK;
+}
+
+// plan -> name -> run.  (The name is written before the launch: it stands even when the launch then fails.)
+static int run_named(fcmf_gemm_ctx* ctx, const GemmPlan& pl, void* stream) {
+  if (pl.kernel == GK_NONE) return FCMF_OK;
+  if (ctx) snprintf(ctx->last_kernel, sizeof ctx->last_kernel, "%s", pl.name);
+  return run_plan(pl, reinterpret_cast<hipStream_t>(stream));
+}
+static int gemm_impl(fcmf_gemm_ctx* ctx, const GemmArgs& a, void* stream) {
+  GemmPlan pl;
+  const int rc = plan_gemm(ctx ? *ctx : g_default_ctx, a, &pl);
+  return rc == FCMF_OK ? run_named(ctx, pl, stream) : rc;
+}
+
+// bf16 row-major A [M, K] x W [N, K]^T -> bf16, no epilogue: the GEMM of the convolution / statistics entry points
+static GemmArgs plain_bf16_args(const void* A, const void* B, void* C, int M, int N, int K) {
+  GemmArgs a{};
+  a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.K = K; a.lda = K; a.ldb = K; a.ldc = N;
+  a.in_dtype = FCMF_BF16; a.out_dtype = FCMF_BF16; a.epilogue = FCMF_EPI_NONE;
+  return a;
+}
+
+// rows per block of the statistics fcmf_gemm_colstats / fcmf_conv_gemm_colstats emit for an [M, N] output contracted over K:
+// 128 (256-column tiles), 256 (narrow layouts: one block per tile), 0 where no kernel emits them (the GEMM call then returns
+// FCMF_ERR_UNSUPPORTED).  Read off the plan of that GEMM.  The query carries neither addresses nor leading dimensions, so it plans
+// for aligned operands with leading dimensions small enough for every extent limit: a call whose own strides exceed a limit still
+// gets FCMF_ERR_UNSUPPORTED.
+extern "C" int fcmf_gemm_colstats_block_rows(const fcmf_gemm_ctx* ctx, int M, int N, int K) {
+  alignas(16) static char operand[16];
+  GemmArgs a = plain_bf16_args(operand, operand, operand, M, N, K);
+  a.lda = a.ldb = a.ldc = 8;
+  a.colstats = reinterpret_cast<float*>(operand);
+  GemmPlan pl;
+  if (plan_gemm(ctx ? *ctx : g_default_ctx, a, &pl) != FCMF_OK) return 0;
+  return pl.kernel == GK_NARROW ? 256 : pl.kernel == GK_PERSISTENT ? 128 : 0;
 }
 
 // ---- e4m3 GEMM ---------------------------------------------------------------------------------------------------------
@@ -1916,39 +2010,24 @@ extern "C" int fcmf_gemm_fp8(fcmf_gemm_ctx* ctx, const void* A, const float* sa,
   if (M == 0 || N == 0) return FCMF_OK;
   if ((epilogue == FCMF_EPI_DGELU || epilogue == FCMF_EPI_ADD) && !aux) return FCMF_ERR_ARG;
   if (epilogue == FCMF_EPI_TANH || epilogue == FCMF_EPI_DTANH) return FCMF_ERR_UNSUPPORTED;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  const int64_t c_extent = (((int64_t)M - 1) * ldc + N) * 2;
+  GemmArgs a{};
+  a.A = A; a.B = B; a.C = C; a.bias = bias; a.aux = aux; a.colsum = colsum;
+  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+  a.out_dtype = FCMF_BF16; a.epilogue = epilogue;
   // 128-byte k-tiles of whole cache lines; 16-byte DMA chunks; the persistent kernels' 8-column row pieces
   if (K % 128 || lda % 16 || ldb % 16 || N % 8 || ldc % 8 || !al16(A) || !al16(B) || !al16(C) || (aux && !al16(aux)) ||
-      (bias && !al16(bias)) || !al16(sb) || c_extent >= (1ll << 31) || (int64_t)M * lda >= (1ll << 31) ||
+      (bias && !al16(bias)) || !al16(sb) || c_extent_bytes(a) >= (1ll << 31) || (int64_t)M * lda >= (1ll << 31) ||
       (int64_t)N * ldb >= (1ll << 31) || M < 256 || N < 256)
     return FCMF_ERR_UNSUPPORTED;
   const fcmf_gemm_ctx& cfg = ctx ? *ctx : g_default_ctx;
-  GemmParams p{A, B, C, bias, aux, M, N, K, lda, ldb, ldc, epilogue, 0, 1, 0, 0, 0, 0, colsum, 0, 0, nullptr, 0, sa, sb, 0, 0, 0, 0, 0, 0, 0, 0, 0, nullptr, 0, 0};
-  p.a_bytes = (unsigned)(((int64_t)M - 1) * lda + K);
-  p.b_bytes = (unsigned)(((int64_t)N - 1) * ldb + K);
-  p.c_bytes = (unsigned)c_extent;
-  const int slots = cfg.num_cus, nk = K / 128;
-  constexpr int tm = 192;
-  p.tiles = ((M + tm - 1) / tm) * ((N + GB - 1) / GB);
-  p.ktiles_per_split = nk;
-  p.ksplit = 1;
-  p.total_items = p.tiles;
-  p.nt_out = (int64_t)M * N * 2 >= cfg.nt_min_bytes;
-  dim3 grid(p.total_items < slots ? p.total_items : slots);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (ctx) {
-    static const char* const epi_names[] = {"NONE", "GELU", "TANH", "DGELU", "DTANH", "ADD"};
-    snprintf(ctx->last_kernel, sizeof ctx->last_kernel, "gemm_fp8_tile%d_kernel<%s>", tm, epi_names[epilogue]);
-  }
-  switch (epilogue) {
-    case FCMF_EPI_NONE: launch_fp8_tile<FCMF_EPI_NONE>(p, grid, st); break;
-    case FCMF_EPI_GELU: launch_fp8_tile<FCMF_EPI_GELU>(p, grid, st); break;
-    case FCMF_EPI_DGELU: launch_fp8_tile<FCMF_EPI_DGELU>(p, grid, st); break;
-    default: launch_fp8_tile<FCMF_EPI_ADD>(p, grid, st); break;
-  }
-  FCMF_CHECK_LAUNCH();
-  return FCMF_OK;
+  GemmPlan pl;
+  plan_begin(&pl, a, GK_FP8);
+  pl.tm = 192; pl.kb = 128;
+  pl.p = base_params(a, 1);
+  pl.p.sa = sa; pl.p.sb = sb;
+  plan_persistent_launch(&pl, persistent_list(cfg, pl.p, ((M + pl.tm - 1) / pl.tm) * ((N + GB - 1) / GB), K / 128, 1, true));
+  snprintf(pl.name, sizeof pl.name, "gemm_fp8_tile%d_kernel<%s>", pl.tm, epi_names[epilogue]);
+  return run_named(ctx, pl, stream);
 }
 
 // x [rows, K] (bf16 / f32, row stride ldx) -> q [rows, K] e4m3 (row stride ldq bytes) with ONE scale per row:
@@ -2042,16 +2121,30 @@ extern "C" int fcmf_quant_fp8_rows(const void* x, int64_t ldx, void* q, int64_t 
 extern "C" int fcmf_gemm(fcmf_gemm_ctx* ctx, const void* A, const void* B, void* C, const float* bias, void* aux, float* colsum,
                          int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int trans_a, int trans_b, int in_dtype,
                          int out_dtype, int epilogue, int accumulate, void* stream) {
-  return gemm_impl(ctx, A, B, C, bias, aux, colsum, M, N, K, lda, ldb, ldc, trans_a, trans_b, in_dtype, out_dtype, epilogue,
-                   accumulate, stream, nullptr);
+  GemmArgs a{};
+  a.A = A; a.B = B; a.C = C; a.bias = bias; a.aux = aux; a.colsum = colsum;
+  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+  a.trans_a = trans_a; a.trans_b = trans_b; a.in_dtype = in_dtype; a.out_dtype = out_dtype;
+  a.epilogue = epilogue; a.accumulate = accumulate;
+  return gemm_impl(ctx, a, stream);
+}
+
+// bf16 operands in the given orientations -> f32, no epilogue: weight gradients
+static GemmArgs grad_args(int M, int N, int K, int trans_a, int trans_b, int accumulate) {
+  GemmArgs a{};
+  a.M = M; a.N = N; a.K = K; a.trans_a = trans_a; a.trans_b = trans_b;
+  a.in_dtype = FCMF_BF16; a.out_dtype = FCMF_F32; a.epilogue = FCMF_EPI_NONE; a.accumulate = accumulate;
+  return a;
 }
 
 extern "C" int fcmf_gemm_colblocks(fcmf_gemm_ctx* ctx, const void* A, const void* B, float* C, int M, int N, int K, int64_t lda, int64_t ldb,
                                    int64_t ldc, int trans_a, int trans_b, int col_block, int64_t col_block_stride, int accumulate,
                                    void* stream) {
   if (col_block <= 0 || col_block_stride <= 0 || ldc < col_block) return FCMF_ERR_ARG;
-  return gemm_impl(ctx, A, B, C, nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc, trans_a, trans_b, FCMF_BF16, FCMF_F32, FCMF_EPI_NONE,
-                   accumulate, stream, nullptr, nullptr, col_block, col_block_stride);
+  GemmArgs a = grad_args(M, N, K, trans_a, trans_b, accumulate);
+  a.A = A; a.B = B; a.C = C; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+  a.cblk = col_block; a.cblk_stride = col_block_stride;
+  return gemm_impl(ctx, a, stream);
 }
 
 // ---- batched weight gradients -----------------------------------------------------------------------------------------
@@ -2060,6 +2153,23 @@ extern "C" int fcmf_gemm_colblocks(fcmf_gemm_ctx* ctx, const void* A, const void
 // BATCH_MAX matrices form one work list of (matrix, tile, k-split) items for the persistent 256 x 256 kernel; the split factor
 // is chosen for whole rounds of the chip (a 768 x 768 gradient alone is 9 tiles: alone it needed a 28-way split and a 64 MB
 // partial-tile round trip).  Shapes the persistent kernel does not take, and count == 1, run as `count` fcmf_gemm calls.
+// k-split of a batched chunk for whole rounds: the smallest split whose last round is at least 92 % full (else the fullest), each
+// split at least 8 k-tiles deep, partial tiles within the context's workspace
+static int batched_ksplit(const fcmf_gemm_ctx& cfg, int tiles, int nk) {
+  const int slots = cfg.num_cus;
+  int best = 1;
+  double best_eff = 0.0;
+  const int64_t ws_tiles = cfg.ws ? cfg.ws_bytes / ((int64_t)GB * GB * 4) : 0;
+  for (int sp = 1; sp <= 16; ++sp) {
+    if (sp > 1 && ((int64_t)sp * tiles > ws_tiles || nk / sp < 8)) break;
+    const int64_t items = (int64_t)tiles * sp, rounds = (items + slots - 1) / slots;
+    const double eff = (double)items / (double)(rounds * slots);
+    if (eff > best_eff + 1e-9) { best_eff = eff; best = sp; }
+    if (eff >= 0.92) { best = sp; break; }
+  }
+  return best;
+}
+
 extern "C" int fcmf_gemm_dw_batched(fcmf_gemm_ctx* ctx, int count, const void* const* A, const void* const* B, void* const* C, int M, int N,
                                     int K, int64_t lda, int64_t ldb, int64_t ldc, int accumulate, void* stream) {
   if (count < 0 || !A || !B || !C || M < 0 || N < 0 || K < 0) return FCMF_ERR_ARG;
@@ -2067,64 +2177,40 @@ extern "C" int fcmf_gemm_dw_batched(fcmf_gemm_ctx* ctx, int count, const void* c
     if (!A[i] || !B[i] || !C[i]) return FCMF_ERR_ARG;
   if (count == 0 || M == 0 || N == 0) return FCMF_OK;
   const fcmf_gemm_ctx& cfg = ctx ? *ctx : g_default_ctx;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   bool ok = count > 1 && cfg.force_tile != 128 && K > 0 && M >= 256 && N >= 256 && lda % 8 == 0 && ldb % 8 == 0 && M % 8 == 0 && N % 8 == 0 &&
             ldc % 8 == 0 && (int64_t)K * lda < (1ll << 30) && (int64_t)K * ldb < (1ll << 30);
   for (int i = 0; ok && i < count; ++i) ok = al16(A[i]) && al16(B[i]) && al16(C[i]);
+  GemmArgs a = grad_args(M, N, K, 1, 1, accumulate);
+  a.lda = lda; a.ldb = ldb; a.ldc = ldc;
   if (!ok) {
     for (int i = 0; i < count; ++i) {
-      const int rc = gemm_impl(ctx, A[i], B[i], C[i], nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc, 1, 1, FCMF_BF16, FCMF_F32, FCMF_EPI_NONE,
-                               accumulate, stream, nullptr);
+      a.A = A[i]; a.B = B[i]; a.C = C[i];
+      const int rc = gemm_impl(ctx, a, stream);
       if (rc != FCMF_OK) return rc;
     }
     return FCMF_OK;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int slots = cfg.num_cus, tpm = ((M + GB - 1) / GB) * ((N + GB - 1) / GB), nk = (K + 31) / 32;
+  const int tpm = ((M + GB - 1) / GB) * ((N + GB - 1) / GB), nk = (K + 31) / 32;
   const int chunks = (count + BATCH_MAX - 1) / BATCH_MAX;
-  const size_t smem = (size_t)RING_BYTES + 8 * 4096;
-  auto kern = gemm_bf16_dw_batched_kernel;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   for (int c = 0, first = 0; c < chunks; ++c) {
     const int n = (count - first + (chunks - c) - 1) / (chunks - c);          // near-equal chunks
     BatchPtrs bp{};
     for (int i = 0; i < n; ++i) { bp.A[i] = A[first + i]; bp.B[i] = B[first + i]; bp.C[i] = C[first + i]; }
+    a.A = bp.A[0]; a.B = bp.B[0]; a.C = bp.C[0];
+    GemmPlan pl;
+    plan_begin(&pl, a, GK_DW_BATCHED);
+    pl.tm = 256; pl.batch = &bp;
+    pl.p = base_params(a, 2);
+    pl.p.c_bytes = 0;            // (as this path always had it: the f32 epilogue does not range-check C)
+    pl.p.tiles_per_mat = tpm;
     const int tiles = n * tpm;
-    // k-split for whole rounds: the smallest split whose last round is at least 92 % full (else the fullest), each split at least
-    // 8 k-tiles deep, partial tiles within the context's workspace
-    int best = 1;
-    double best_eff = 0.0;
-    const int64_t ws_tiles = cfg.ws ? cfg.ws_bytes / ((int64_t)GB * GB * 4) : 0;
-    for (int sp = 1; sp <= 16; ++sp) {
-      if (sp > 1 && ((int64_t)sp * tiles > ws_tiles || nk / sp < 8)) break;
-      const int64_t items = (int64_t)tiles * sp, rounds = (items + slots - 1) / slots;
-      const double eff = (double)items / (double)(rounds * slots);
-      if (eff > best_eff + 1e-9) { best_eff = eff; best = sp; }
-      if (eff >= 0.92) { best = sp; break; }
-    }
-    GemmParams p{};
-    p.A = bp.A[0]; p.B = bp.B[0]; p.C = bp.C[0];
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.epilogue = FCMF_EPI_NONE; p.accumulate = accumulate;
-    p.a_bytes = (unsigned)((((int64_t)K - 1) * lda + M) * 2);
-    p.b_bytes = (unsigned)((((int64_t)K - 1) * ldb + N) * 2);
-    p.ktiles_per_split = (nk + best - 1) / best;
-    p.ksplit = (nk + p.ktiles_per_split - 1) / p.ktiles_per_split;
-    p.tiles = tiles; p.tiles_per_mat = tpm;
-    p.total_items = tiles * p.ksplit;
-    p.ws = p.ksplit > 1 ? cfg.ws : nullptr;
-    const dim3 grid(p.total_items < slots ? p.total_items : slots);
-    hipLaunchKernelGGL(kern, grid, dim3(512), smem, st, p, bp);
-    if (p.ws) {
-      const int64_t total4 = (int64_t)tiles * (GB * GB / 4);
-      const int blocks = (int)((total4 + 255) / 256 < 4096 ? (total4 + 255) / 256 : 4096);
-      hipLaunchKernelGGL(splitk_reduce_frag_batched_kernel, dim3(blocks), dim3(256), 0, st, p.ws, bp, tpm, M, N, ldc, p.ksplit, tiles,
-                         (N + GB - 1) / GB, accumulate);
-    }
-    FCMF_CHECK_LAUNCH();
+    plan_persistent_launch(&pl, persistent_list(cfg, pl.p, tiles, nk, batched_ksplit(cfg, tiles, nk), false));
+    if (pl.p.ksplit > 1) { pl.p.ws = cfg.ws; plan_frag_reduce(&pl, RED_FRAG_BATCHED); }
+    snprintf(pl.name, sizeof pl.name, "gemm_bf16_dw_batched_kernel");
+    const int rc = run_named(ctx, pl, stream);
+    if (rc != FCMF_OK) return rc;
     first += n;
   }
-  if (ctx) snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "gemm_bf16_dw_batched_kernel");
   return FCMF_OK;
 }
 
@@ -2133,8 +2219,9 @@ extern "C" int fcmf_gemm_dw_batched(fcmf_gemm_ctx* ctx, int count, const void* c
 // fcmf_bn_apply with `pad`); no patch matrix exists: the LDS-DMA of A's k-tile t reads the tap (ky, kx) of every row's
 // receptive field straight from the activation (per-lane offset = the field's origin, fixed per work item; the tap is a
 // wave-uniform scalar offset).
-static int conv_gemm_impl(fcmf_gemm_ctx* ctx, const void* x, const void* w, void* y, float* colstats, int n, int Hp, int Wp, int C, int Ho,
-                          int Wo, int kh, int kw, int stride, int Cout, void* stream) {
+struct ConvShape { int n, Hp, Wp, C, Ho, Wo, kh, kw, stride, Cout; };
+static int conv_gemm_impl(fcmf_gemm_ctx* ctx, const void* x, const void* w, void* y, float* colstats, const ConvShape& s, void* stream) {
+  const int n = s.n, Hp = s.Hp, Wp = s.Wp, C = s.C, Ho = s.Ho, Wo = s.Wo, kh = s.kh, kw = s.kw, stride = s.stride, Cout = s.Cout;
   if (!x || !w || !y || n <= 0 || Hp <= 0 || Wp <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || Cout <= 0)
     return FCMF_ERR_ARG;
   if ((C & (C - 1)) || C < 64 || kh * kw > 64) return FCMF_ERR_UNSUPPORTED;             // k-tiles must not straddle taps
@@ -2144,13 +2231,13 @@ static int conv_gemm_impl(fcmf_gemm_ctx* ctx, const void* x, const void* w, void
   int logC = 0;
   while ((1 << logC) < C) ++logC;
   const ConvGeom cv{C, logC, Hp, Wp, Ho, Wo, kw, stride, in_bytes, logC};
-  const int K = kh * kw * C;
-  return gemm_impl(ctx, x, w, y, nullptr, nullptr, nullptr, (int)M, Cout, K, K, K, Cout, 0, 0, FCMF_BF16, FCMF_BF16, FCMF_EPI_NONE, 0,
-                   stream, &cv, colstats);
+  GemmArgs a = plain_bf16_args(x, w, y, (int)M, Cout, kh * kw * C);
+  a.cv = &cv; a.colstats = colstats;
+  return gemm_impl(ctx, a, stream);
 }
 extern "C" int fcmf_conv_gemm(fcmf_gemm_ctx* ctx, const void* x, const void* w, void* y, int n, int Hp, int Wp, int C, int Ho,
                               int Wo, int kh, int kw, int stride, int Cout, void* stream) {
-  return conv_gemm_impl(ctx, x, w, y, nullptr, n, Hp, Wp, C, Ho, Wo, kh, kw, stride, Cout, stream);
+  return conv_gemm_impl(ctx, x, w, y, nullptr, ConvShape{n, Hp, Wp, C, Ho, Wo, kh, kw, stride, Cout}, stream);
 }
 
 // The same two products with the BatchNorm statistics of the output as a by-product (ResNet trunks: every convolution feeds a
@@ -2162,13 +2249,14 @@ extern "C" int fcmf_conv_gemm(fcmf_gemm_ctx* ctx, const void* x, const void* w, 
 extern "C" int fcmf_gemm_colstats(fcmf_gemm_ctx* ctx, const void* A, const void* B, void* C, float* stats, int M, int N, int K,
                                   int64_t lda, int64_t ldb, int64_t ldc, void* stream) {
   if (!stats) return FCMF_ERR_ARG;
-  return gemm_impl(ctx, A, B, C, nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc, 0, 0, FCMF_BF16, FCMF_BF16, FCMF_EPI_NONE, 0, stream,
-                   nullptr, stats);
+  GemmArgs a = plain_bf16_args(A, B, C, M, N, K);
+  a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.colstats = stats;
+  return gemm_impl(ctx, a, stream);
 }
 extern "C" int fcmf_conv_gemm_colstats(fcmf_gemm_ctx* ctx, const void* x, const void* w, void* y, float* stats, int n, int Hp, int Wp,
                                        int C, int Ho, int Wo, int kh, int kw, int stride, int Cout, void* stream) {
   if (!stats) return FCMF_ERR_ARG;
-  return conv_gemm_impl(ctx, x, w, y, stats, n, Hp, Wp, C, Ho, Wo, kh, kw, stride, Cout, stream);
+  return conv_gemm_impl(ctx, x, w, y, stats, ConvShape{n, Hp, Wp, C, Ho, Wo, kh, kw, stride, Cout}, stream);
 }
 
 // Implicit-GEMM convolution for inputs with FEW channels (the trunk's 7x7 / stride-2 stem on RGB crops, whose patch matrix was
@@ -2192,9 +2280,9 @@ extern "C" int fcmf_conv_gemm_runs(fcmf_gemm_ctx* ctx, const void* x, const void
   while ((1 << logC) < run) ++logC;
   while ((1 << logP) < pix) ++logP;
   const ConvGeom cv{run, logC, Hp, Wp, Ho, Wo, 1, stride, in_elems * 2, logP};
-  const int K = kh * run;
-  return gemm_impl(ctx, x, w, y, nullptr, nullptr, nullptr, (int)M, Cout, K, K, K, Cout, 0, 0, FCMF_BF16, FCMF_BF16, FCMF_EPI_NONE, 0,
-                   stream, &cv, stats);
+  GemmArgs a = plain_bf16_args(x, w, y, (int)M, Cout, kh * run);
+  a.cv = &cv; a.colstats = stats;
+  return gemm_impl(ctx, a, stream);
 }
 
 extern "C" int fcmf_colsum(const void* X, float* out, int M, int N, int64_t ldx, int dtype, int accumulate,
