@@ -178,6 +178,27 @@ int fcmf_attn_mfma_bwd(const void* q, const void* k, const void* v, const float*
  * mm_modeling.py:182-184 / HF RobertaSelfAttention's three nn.Linear biases) without another pass over dqkv. */
 
 /* ---------------------------------------------------------------------------------------
+ * Attention probabilities on request: P = softmax(score) as float32, BEFORE dropout, recomputed from Q and K with exactly the
+ * score definition of fcmf_attn_desc above (the forward kernels never materialise P).  Both entry points find the row maximum
+ * and sum themselves (no lse of a forward is needed); a row whose every key carries the finfo(float32).min mask comes out
+ * uniform, 1/T, as in the forward kernels and in torch.
+ * Output element (g, slot h, r, t) at probs + g*p_sg + h*p_sh + r*T + t (elements), so one kernel writes either layout:
+ *   [G, heads, R, T]: p_sg = heads*R*T, p_sh = R*T   (HF `output_attentions`: one [B, heads, S, S] tensor per text-encoder layer,
+ *                     mm_modeling.py:440-446 -> fcmf_pretraining.py:41);
+ *   [heads*G, R, T] : p_sg = R*T, p_sh = G*R*T       (index h*G + g: the `score` the IAOG `Attention` returns and keeps as
+ *                     attention_weights, mm_modeling.py:126-132, in the order of its torch.split(output, mb_size, dim=0)).
+ * fcmf_attn_probs: VALU, FCMF_F32 / FCMF_BF16; reads desc->q / k1 / k2 with their strides (a query row stride of 0 included),
+ *   mask, bias, group_div, causal and head_quirk; IGNORES v1, v2, dropout_p, seed and the o_* strides.  Limits as
+ *   fcmf_attn_small_bwd: T1+T2 <= 512, T2 <= 128, d <= 128, FCMF_ERR_UNSUPPORTED outside them.
+ * fcmf_attn_mfma_probs: bf16, head dim 64, Tq, Tk <= 256; q / k rows as fcmf_attn_mfma_fwd reads them (row strides ldq / ldk:
+ *   the fused layers' [rows, 3*H] q|k|v buffer is read in place), mask [G, Tk] additive or NULL.  Same alignment rules as
+ *   fcmf_attn_mfma_fwd (ldq, ldk multiples of 8, 16-byte aligned q / k), FCMF_ERR_UNSUPPORTED otherwise. */
+int fcmf_attn_probs(const fcmf_attn_desc* desc /*host*/, float* probs, int64_t p_sg, int64_t p_sh, void* stream);
+int fcmf_attn_mfma_probs(const void* q, const void* k, const float* mask, float* probs, int G, int heads,
+                         int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t p_sg, int64_t p_sh,
+                         float scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * y = LayerNorm(dropout(x) + res) * gamma + beta   (eps inside the sqrt, biased variance)
  * Replaces BertSelfOutput/BertOutput/AddNorm + FCMFLayerNorm (mm_modeling.py:158-171,
  * 276-280,324-328,566-573) and HF nn.LayerNorm(eps=1e-5).

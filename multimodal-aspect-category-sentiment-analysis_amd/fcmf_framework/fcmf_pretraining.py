@@ -44,10 +44,12 @@ class FCMFEncoder(nn.Module):
 
     # ------------------------------------------------------------------------------------
     def encode_aspects(self, input_ids, visual_embeds_att, roi_embeds_att, roi_coors, token_type_ids,
-                       attention_mask, added_attention_mask):
+                       attention_mask, added_attention_mask, return_attentions=False):
         """input_ids / token_type_ids / attention_mask [B,A,S]; added_attention_mask [B,A,>=S+num_roi];
         visual_embeds_att [B,NI,49,F]; roi_embeds_att [B,NI,NR,F]; roi_coors [B,NI,NR,4].
-        Returns the fusion-layer output [B*A, 1+2*NI, H] (row b*A+a = sample b, aspect a)."""
+        Returns the fusion-layer output [B*A, 1+2*NI, H] (row b*A+a = sample b, aspect a); with return_attentions also what
+        FeatureExtractor hands back as `enc_attentions` (fcmf_pretraining.py:41): () unless ops.set_output_attentions(True), then
+        one [B*A, heads, S, S] tensor per text-encoder layer."""
         B, A, S = input_ids.shape
         Bt, NI, NR = B * A, self.num_imgs, self.num_roi
         tr = self.training
@@ -61,7 +63,11 @@ class FCMFEncoder(nn.Module):
         added = added_attention_mask.reshape(Bt, -1)
 
         # 1. text encoder on all B*A sequences at once                      (fcmf_pretraining.py:41)
-        seq = cell.encode(ids, tt, am)                                                   # [Bt,S,H]
+        enc_attentions = ()
+        if return_attentions and ops.output_attentions():
+            seq, _, enc_attentions = self.bert(ids, tt, am)                              # (+ the pooler and one launch per layer)
+        else:
+            seq = cell.encode(ids, tt, am)                                               # [Bt,S,H]
 
         cross = self.text2img_attention.layer[0]
         mm = self.mm_attention.layer[0]
@@ -103,17 +109,17 @@ class FCMFEncoder(nn.Module):
         # 5. fusion: [CLS] + image features + ROI features through the SAME mm layer (:127-140)
         fusion = torch.cat((cls.unsqueeze(1), h_feat, r_feat), dim=1)                    # [Bt,1+2NI,H]
         m_f = layers.additive_mask(added, 1 + 2 * NI)
-        return layers.transformer_layer(mm, fusion, fusion, m_f, nh, eps, p_h, p_a, tr)
+        out = layers.transformer_layer(mm, fusion, fusion, m_f, nh, eps, p_h, p_a, tr)
+        return (out, enc_attentions) if return_attentions else out
 
     def forward(self, input_ids, visual_embeds_att, roi_embeds_att, roi_coors=None, token_type_ids=None,
                 attention_mask=None, added_attention_mask=None):
-        out = self.encode_aspects(input_ids.unsqueeze(1), visual_embeds_att, roi_embeds_att, roi_coors,
-                                  None if token_type_ids is None else token_type_ids.unsqueeze(1),
-                                  None if attention_mask is None else attention_mask.unsqueeze(1),
-                                  added_attention_mask.unsqueeze(1))
-        # the reference also returns the text encoder's attention probabilities; the fused
-        # kernels never materialise them (they are unused in training)
-        return out, ()
+        # enc_attentions: the text encoder's attention probabilities when ops.set_output_attentions(True), else () -- the fused
+        # kernels never materialise them and training never reads them
+        return self.encode_aspects(input_ids.unsqueeze(1), visual_embeds_att, roi_embeds_att, roi_coors,
+                                   None if token_type_ids is None else token_type_ids.unsqueeze(1),
+                                   None if attention_mask is None else attention_mask.unsqueeze(1),
+                                   added_attention_mask.unsqueeze(1), return_attentions=True)
 
 
 class FCMFSeq2Seq(nn.Module):

@@ -146,6 +146,21 @@ def self_attention_fwd(qkv, mask, G, T, Hd, heads, p, seed):
     return out, lse
 
 
+def self_attention_probs(qkv, mask, G, T, Hd, heads, probs):
+    """fill probs (float32 [G, heads, T, T], contiguous) with the pre-dropout softmax of self_attention_fwd, read from the same
+    [G*T, 3H] q|k|v buffer in place, on the kernel family the forward chose"""
+    scale = 1.0 / math.sqrt(Hd // heads)
+    if tuple(probs.shape) != (G, heads, T, T) or probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise H.HipLibraryError(f"attention probabilities: need a contiguous float32 {(G, heads, T, T)} tensor")
+    es, base, L = qkv.element_size(), qkv.data_ptr(), H.lib()
+    if _use_mfma(qkv.dtype, Hd, heads, T):
+        H.check(L.fcmf_attn_mfma_probs(base, base + Hd * es, H.ptr(mask), H.ptr(probs), G, heads, T, T, 3 * Hd, 3 * Hd,
+                                       heads * T * T, T * T, scale, H.stream()), "fcmf_attn_mfma_probs")
+    else:
+        a = _qkv_desc(qkv, G, T, Hd, heads, mask, scale, 0.0, 0)
+        H.check(L.fcmf_attn_probs(a, H.ptr(probs), heads * T * T, T * T, H.stream()), "fcmf_attn_probs")
+
+
 def self_attention_bwd(qkv, mask, out, lse, dout, G, T, Hd, heads, p, seed, bias_grad=None):
     """-> dqkv [G*T, 3H].  bias_grad (float32 [3H], accumulated into): the column sums of dqkv = the gradient of the fused
     q|k|v bias; the MFMA kernel produces them per sequence from its f32 accumulators (no extra pass over dqkv)."""
@@ -313,11 +328,13 @@ class PostAttentionFn(torch.autograd.Function):
 
 
 class SelfLayerFn(torch.autograd.Function):
-    """the whole self-attention layer: fused QKV GEMM -> attention -> PostAttention tail"""
+    """the whole self-attention layer: fused QKV GEMM -> attention -> PostAttention tail.
+    probs (optional, float32 [G, heads, T, T]): filled with the layer's pre-dropout attention probabilities from the node's own
+    q|k|v buffer (one more launch; nothing is saved for it and the backward does not know about it)."""
 
     @staticmethod
     def forward(ctx, x, mask, wq, bq, wk, bk, wv, bv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2, heads, eps, p_h, p_a,
-                seed_a, seed0, seed1):
+                seed_a, seed0, seed1, probs=None):
         G_, T, Hd = x.shape
         M = G_ * T
         x2 = x.reshape(M, Hd)
@@ -331,6 +348,8 @@ class SelfLayerFn(torch.autograd.Function):
         ops.gemm_nt(x2, wm if wm.data_ptr() == wq.data_ptr() else None, wqkv, qkv, M, 3 * Hd, Hd, Hd, bias=bqkv, owner=wq)
         mk = None if mask is None else mask.contiguous().float()
         c, lse = self_attention_fwd(qkv, mk, G_, T, Hd, heads, p_a, seed_a)
+        if probs is not None:
+            self_attention_probs(qkv, mk, G_, T, Hd, heads, probs)
         y, saved = _post_fwd(c, x2, Hd, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2, eps, p_h, (seed0, seed1))
         ctx.save_for_backward(x2, mk, qkv, c, lse, wq, wk, wv, wo, w1, w2, g1, g2, bq, bk, bv, bo, be1, b1, b2, be2, *saved)
         ctx.cfg = (heads, p_h, p_a, seed_a, seed0, seed1, x.shape)
@@ -357,4 +376,4 @@ class SelfLayerFn(torch.autograd.Function):
         Ws, bs = _split3(R["wqkv"], Hd), _split3(R["bqkv"], Hd)
         return (dx.view(xshape), None, Ws[0], bs[0], Ws[1], bs[1], Ws[2], bs[2], R["wo"], R["bo"],
                 R["g1"], R["be1"], R["w1"], R["b1"], R["w2"], R["b2"], R["g2"], R["be2"],
-                None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None)

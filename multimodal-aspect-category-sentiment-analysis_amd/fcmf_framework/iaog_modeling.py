@@ -29,6 +29,11 @@ def _quirk_attn_fwd(qx, kx, heads, causal):
     return out, lse
 
 
+def _quirk_attn_probs(qx, kx, heads, causal, out=None):
+    """the softmax of _quirk_attn_fwd, float32 [heads*G, R, T], index slot*G + g (the reference's `score`, mm_modeling.py:126-132)"""
+    return ops.attention_probs(qx, k1=kx, heads=heads, causal=causal, head_quirk=True, slot_major=True, out=out)
+
+
 def _quirk_attn_bwd(qx, kx, out, lse, dout, heads, causal, dq_out, dk_out):
     """gradients per HEAD written into dq_out / dk_out ([G, R|T, heads*d] views with unit inner stride, any row stride): the
     attention backward produces them per output SLOT, fcmf_head_gather sums the slots that read each head
@@ -90,7 +95,8 @@ class _SelfQuirkAttentionFn(torch.autograd.Function):
     ONE dX and ONE dW GEMM (the reference: 2 x (repeat + bmm) forward, mm_modeling.py:79-92)."""
 
     @staticmethod
-    def forward(ctx, x, wk, wq, heads, causal):
+    def forward(ctx, x, wk, wq, heads, causal, probs=None):
+        """probs (optional, float32 [heads*G, T, T]): filled with the attention probabilities from the node's own [kx | qx] buffer"""
         G, T, E = x.shape
         x2 = ops._rows(x)
         HD = wk.shape[0] * wk.shape[2]
@@ -99,6 +105,8 @@ class _SelfQuirkAttentionFn(torch.autograd.Function):
         ops.gemm(x2, wl, kq, G * T, 2 * HD, E, ops._ld(x2), E, 2 * HD, 0, 0)
         kq3 = kq.view(G, T, 2 * HD)
         out, lse = _quirk_attn_fwd(kq3[:, :, HD:], kq3[:, :, :HD], heads, causal)
+        if probs is not None:
+            _quirk_attn_probs(kq3[:, :, HD:], kq3[:, :, :HD], heads, causal, out=probs)
         ctx.save_for_backward(x2, kq, out, lse, wk, wq)
         ctx.cfg = (heads, causal, x.shape)
         return out
@@ -122,11 +130,11 @@ class _SelfQuirkAttentionFn(torch.autograd.Function):
             ops.gemm(dkq, kn(), dx, G * T, E, 2 * HD, 2 * HD, 2 * HD, E, 0, 0)               # NT: both operands K-contiguous
         direct = ops.head_weight_grad(x2, dkq, [wk, wq])          # straight into the two parameters' adjacent [n_head, E, d] arena slices
         if direct is not None:
-            return dx.view(xshape), direct[0], direct[1], None, None
+            return dx.view(xshape), direct[0], direct[1], None, None, None
         dwl = torch.empty((2 * HD, E), dtype=torch.float32, device=x2.device)
         ops.gemm(dkq, x2, dwl, 2 * HD, E, G * T, 2 * HD, ops._ld(x2), E, 1, 1)                # [2*n_head*d, E] = dkq^T x
         dw = dwl.view(2, nh, d, E).permute(0, 1, 3, 2)                                        # -> the parameters' [n_head, E, d]
-        return dx.view(xshape), dw[0], dw[1], None, None
+        return dx.view(xshape), dw[0], dw[1], None, None, None
 
 
 class _HoistedKeysFn(torch.autograd.Function):
@@ -233,15 +241,20 @@ class Attention(nn.Module):
             else:
                 raise NotImplementedError("1-D memory_len (key-length fill mask) is only used by the disabled MDE")
         nh = self.n_head
+        want = ops.output_attentions()
         if same and kx is None and k.dim() == 3:
-            out = _SelfQuirkAttentionFn.apply(q, self.w_kx, self.w_qx, nh, causal)       # one GEMM for [kx | qx]
+            probs = torch.empty((nh * q.shape[0], q.shape[1], q.shape[1]), dtype=torch.float32, device=q.device) if want else None
+            out = _SelfQuirkAttentionFn.apply(q, self.w_kx, self.w_qx, nh, causal, probs)    # one GEMM for [kx | qx]
         else:
             if kx is None:
                 kx = ops.head_linear(k, self.w_kx)    # [.., nh*hd], natural head order
             qx = ops.head_linear(q, self.w_qx)
             out = _QuirkAttentionFn.apply(qx, kx, nh, causal)
-        self.attention_weights = None  # probabilities are never materialised by the fused kernel
-        return ops.linear(out, self.proj.weight, self.proj.bias), None
+            probs = _quirk_attn_probs(qx, kx, nh, causal) if want else None
+        # the reference's `score` (mm_modeling.py:126-132), [n_head*B, q_len, k_len] with index slot*B + b, when
+        # ops.set_output_attentions(True); otherwise None: the fused kernel never materialises it
+        self.attention_weights = probs
+        return ops.linear(out, self.proj.weight, self.proj.bias), probs
 
 
 class PositionWiseFFN(nn.Module):

@@ -40,9 +40,10 @@ def post_attention(layer, ctx, residual, eps, p, training):
                                  layer.output.LayerNorm.weight, layer.output.LayerNorm.bias, float(eps), p, s0, s1)
 
 
-def transformer_layer(layer, xq, xkv, add_mask, heads, eps, p_hidden, p_attn, training):
+def transformer_layer(layer, xq, xkv, add_mask, heads, eps, p_hidden, p_attn, training, probs=None):
     """Full (unpruned) post-LN layer: xq [B,Tq,H] attends to xkv [B,Tk,H]; add_mask [B,Tk] float32.
-    Self-attention (xq is xkv) runs as one fused node (fused.SelfLayerFn)."""
+    Self-attention (xq is xkv) runs as one fused node (fused.SelfLayerFn).
+    probs (optional, float32 [B, heads, Tq, Tk]): receives the layer's attention probabilities (pre-dropout softmax)."""
     sa = layer.attention.self
     if xq is xkv and xq.dim() == 3 and xq.shape[1] <= 512 and xq.shape[2] // heads <= 128:
         from .fused import SelfLayerFn
@@ -56,11 +57,13 @@ def transformer_layer(layer, xq, xkv, add_mask, heads, eps, p_hidden, p_attn, tr
                                  ao.LayerNorm.weight, ao.LayerNorm.bias, layer.intermediate.dense.weight,
                                  layer.intermediate.dense.bias, layer.output.dense.weight, layer.output.dense.bias,
                                  layer.output.LayerNorm.weight, layer.output.LayerNorm.bias, heads, float(eps), ph, pa,
-                                 sa_seed, s0, s1)
+                                 sa_seed, s0, s1, probs)
     q = ops.linear(xq, sa.query.weight, sa.query.bias)
     k = ops.linear(xkv, sa.key.weight, sa.key.bias)
     v = ops.linear(xkv, sa.value.weight, sa.value.bias)
     ctx = ops.attention(q, k1=k, v1=v, mask=add_mask, heads=heads, p=p_attn, training=training)
+    if probs is not None:
+        ops.attention_probs(q, k1=k, mask=add_mask, heads=heads, out=probs)
     return post_attention(layer, ctx, xq, eps, p_hidden, training)
 
 

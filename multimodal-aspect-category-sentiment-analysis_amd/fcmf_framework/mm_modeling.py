@@ -314,7 +314,8 @@ class FeatureExtractor(nn.Module):
 
     def forward(self, input_ids, token_type_ids, attention_mask):
         seq_out, pooled_out, enc_attentions = self.cell(input_ids=input_ids, token_type_ids=token_type_ids,
-                                                        attention_mask=attention_mask, output_attentions=True)[:3]
+                                                        attention_mask=attention_mask,
+                                                        output_attentions=ops.output_attentions())[:3]
         return seq_out, pooled_out, enc_attentions
 
 

@@ -47,6 +47,22 @@ def fp8_enabled():
     return _fp8 and _compute_dtype == torch.bfloat16
 
 
+_output_attentions = False
+
+
+def set_output_attentions(on):
+    """Opt-in attention-probability outputs: RobertaModel via FeatureExtractor returns one [B, heads, S, S] float32 tensor per text
+    layer (`enc_attentions`), the IAOG decoder's Attention keeps and returns its [n_head*B, q_len, k_len] `attention_weights`.  The
+    probabilities are recomputed from Q and K by their own kernels (fcmf_attn_probs / fcmf_attn_mfma_probs) and are the softmax
+    BEFORE dropout.  Off (the default): nothing is computed and no launch is added."""
+    global _output_attentions
+    _output_attentions = bool(on)
+
+
+def output_attentions():
+    return _output_attentions
+
+
 _seed_base = 0x5DEECE66D
 _seed_ctr = 0
 
@@ -1297,6 +1313,42 @@ def attention(q, k1=None, v1=None, k2=None, v2=None, mask=None, bias=None, heads
     p = float(p) if training else 0.0
     return AttentionFn.apply(q, k1, v1, k2, v2, mask, bias, heads, group_div, float(scale), p,
                              next_seed() if p > 0 else 0, causal)
+
+
+def attention_probs(q, k1=None, k2=None, mask=None, bias=None, heads=12, group_div=1, scale=None, causal=False,
+                    head_quirk=False, slot_major=False, out=None):
+    """softmax(score) of `attention` / fcmf_attn_desc as float32, before dropout, recomputed from q and the keys (no values, no
+    logsumexp of a forward): [G, heads, R, T1+T2], or with slot_major [heads*G, R, T1+T2] where index h*G + g is output slot h of
+    group g (with head_quirk, the order of the reference Attention's `score`, mm_modeling.py:126-132).  Same operand layouts, stride
+    normalisation and MFMA / VALU choice as AttentionFn.forward.  Detached; there is no backward.  out: a float32 tensor of that
+    shape to fill instead of a new one."""
+    H.require_cuda(q)
+    q = q.detach()
+    q = q if q.stride(2) == 1 and (q.stride(1) >= q.shape[2] or q.stride(1) == 0) else q.contiguous()
+    k1 = None if k1 is None else (k1.detach() if k1.stride(2) == 1 else k1.detach().contiguous())
+    k2 = None if k2 is None else (k2.detach() if k2.stride(3) == 1 else k2.detach().contiguous())
+    mask = None if mask is None else mask.detach().contiguous().float()
+    bias = None if bias is None else bias.detach().contiguous()
+    G, R, HD = q.shape
+    d = HD // heads
+    T = (0 if k1 is None else k1.shape[1]) + (0 if k2 is None else k2.shape[2])
+    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    shape = (heads * G, R, T) if slot_major else (G, heads, R, T)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=q.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != q.device:
+        raise H.HipLibraryError(f"attention_probs: out must be a contiguous float32 {shape} tensor on {q.device}")
+    p_sg, p_sh = (R * T, G * R * T) if slot_major else (heads * R * T, R * T)
+    mfma = (q.dtype == torch.bfloat16 and d == 64 and k2 is None and bias is None and not causal and not head_quirk
+            and k1 is not None and k1.shape[1] <= 256 and R <= 256 and q.is_contiguous() and k1.is_contiguous()
+            and USE_MFMA_ATTENTION)
+    if mfma:
+        H.check(H.lib().fcmf_attn_mfma_probs(H.ptr(q), H.ptr(k1), H.ptr(mask), H.ptr(out), G, heads, R, T, HD, HD, p_sg, p_sh,
+                                             scale, H.stream()), "fcmf_attn_mfma_probs")
+    else:
+        a = _desc(q, k1, None, k2, None, mask, bias, heads, group_div, scale, 0.0, 0, causal, head_quirk)
+        H.check(H.lib().fcmf_attn_probs(a, H.ptr(out), p_sg, p_sh, H.stream()), "fcmf_attn_probs")
+    return out
 
 
 # --------------------------------------------------------------------------------------

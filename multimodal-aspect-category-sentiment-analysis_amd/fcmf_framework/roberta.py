@@ -117,9 +117,9 @@ class RobertaLayer(nn.Module):
         self.heads = cfg.num_attention_heads
         self.eps = cfg.layer_norm_eps
 
-    def forward(self, hidden_states, add_mask):
+    def forward(self, hidden_states, add_mask, probs=None):
         return layers.transformer_layer(self, hidden_states, hidden_states, add_mask, self.heads, self.eps,
-                                        self.output.dropout.p, self.attention.self.dropout.p, self.training)
+                                        self.output.dropout.p, self.attention.self.dropout.p, self.training, probs=probs)
 
 
 class RobertaEncoder(nn.Module):
@@ -127,10 +127,18 @@ class RobertaEncoder(nn.Module):
         super().__init__()
         self.layer = nn.ModuleList([RobertaLayer(cfg) for _ in range(cfg.num_hidden_layers)])
 
-    def forward(self, x, add_mask):
+    def forward(self, x, add_mask, output_attentions=False):
+        if not output_attentions:
+            for l in self.layer:
+                x = l(x, add_mask)
+            return x
+        B, S, _ = x.shape
+        attentions = []
         for l in self.layer:
-            x = l(x, add_mask)
-        return x
+            probs = torch.empty((B, l.heads, S, S), dtype=torch.float32, device=x.device)
+            x = l(x, add_mask, probs=probs)
+            attentions.append(probs)
+        return x, tuple(attentions)
 
 
 class RobertaPooler(nn.Module):
@@ -227,7 +235,16 @@ class RobertaModel(nn.Module):
         return self.encoder(x, add_mask)
 
     def forward(self, input_ids=None, token_type_ids=None, attention_mask=None, output_attentions=False, **unused):
-        seq = self.encode(input_ids, token_type_ids, attention_mask)
-        pooled = self.pooler(seq)
-        # attention probabilities are never materialised by the fused kernels
-        return (seq, pooled, ())
+        """-> (seq, pooled, attentions).  attentions is () unless output_attentions: then one float32 [B, heads, S, S] tensor per
+        layer, recomputed from the layer's own q|k buffer by fcmf_attn_probs / fcmf_attn_mfma_probs (the fused forward kernels
+        never materialise them).  They are the softmax BEFORE dropout: HF's eager path hands out the dropped-out weights in
+        train() mode; in eval() the two coincide."""
+        if not output_attentions:
+            seq = self.encode(input_ids, token_type_ids, attention_mask)
+            return (seq, self.pooler(seq), ())
+        x = self.embeddings(input_ids, token_type_ids)
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        add_mask = layers.additive_mask(attention_mask, input_ids.shape[1], torch.finfo(torch.float32).min)
+        seq, attentions = self.encoder(x, add_mask, output_attentions=True)
+        return (seq, self.pooler(seq), attentions)
