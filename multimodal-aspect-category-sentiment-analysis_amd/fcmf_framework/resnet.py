@@ -13,12 +13,14 @@ wrappers do.  Underneath:
     `trunk(x, groups=G)` runs all G calls as one batch with per-group statistics and G running-statistics updates in
     call order -- bit-for-bit the reference's semantics without its Python loop of num_imgs * num_rois launches;
   * with if_fine_tune=False (the default of both drivers) the reference detaches the features
-    (resnet_utils.py:26-28) and the trunk runs forward only; with if_fine_tune=True (--fine_tune_cnn) `TrunkFn` records
-    what the backward needs (inputs, raw convolution outputs, normalised outputs, batch statistics) and walks the
-    network in reverse by hand: BatchNorm(+ReLU) backward kernels, dX = dY W / dW = dY^T A on the GEMM kernels (the
-    patch matrix is rebuilt, not stored), col2im, max-pool and average-pool backward.
+    (resnet_utils.py:26-28) and the trunk runs forward only, BatchNorm in place; with if_fine_tune=True (--fine_tune_cnn)
+    `TrunkFn` hands the SAME walk (`_trunk_pass`, `Bottleneck.run`) a tape that records per stage what the backward needs (input,
+    raw convolution output, normalised output, batch statistics), and walks the network in reverse by hand: BatchNorm(+ReLU)
+    backward kernels, dX = dY W / dW = dY^T A on the GEMM kernels (patch matrices rebuilt, not stored), col2im, pool backward.
 There is no torch (MIOpen) fallback: CPU tensors raise HipLibraryError.
 """
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
 
@@ -96,6 +98,32 @@ def _block_stats(rows, Cout, K, dtype, device):
     return torch.empty(((rows + br - 1) // br, Cout, 2), dtype=torch.float32, device=device), br
 
 
+def _conv_rows(shape, Cout, K, dtype, device, stats, names, with_stats, plain):
+    """the tail of every trunk convolution: y [*shape, Cout] = patch rows . W[Cout, K]^T through `with_stats(y, block buffer)` where
+    `stats` is asked and a kernel emits block statistics for the shape, else (or when the library refuses that call, which then
+    leaves nothing in an open GEMM trace) through `plain(y)`.  Both return the library's status; names = their entry points,
+    names[1] None: `plain` is ops.gemm, which traces and checks itself.  -> (y, (block statistics, rows per block) or None) if stats else y"""
+    rows = shape[0] * shape[1] * shape[2]
+    y = torch.empty((rows, Cout), dtype=dtype, device=device)
+    blocks = _block_stats(rows, Cout, K, dtype, device) if stats else None
+    flops = 2.0 * rows * Cout * K
+    if blocks is not None:
+        with ops.trace_launch(flops) as t:
+            rc = with_stats(y, blocks[0])
+            if rc == H.ERR_UNSUPPORTED:
+                blocks = t.flops = None
+        if blocks is not None:
+            H.check(rc, names[0])
+    if blocks is None and names[1] is None:
+        plain(y)
+    elif blocks is None:
+        with ops.trace_launch(flops):
+            rc = plain(y)
+        H.check(rc, names[1])
+    y = y.view(*shape, Cout)
+    return (y, blocks) if stats else y
+
+
 def conv2d_implicit(xp, conv, N, Ho, Wo, stats=False):
     """xp [N, Hp, Wp, C] (zero border included where the convolution pads) -> [N, Ho, Wo, Cout] through fcmf_conv_gemm: no patch
     matrix (the 3x3 / strided convolutions of the trunk spent 9 of 46.7 ms building them, 120 MB per crop).
@@ -104,23 +132,10 @@ def conv2d_implicit(xp, conv, N, Ho, Wo, stats=False):
     Cout, C = conv.out_channels, xp.shape[3]
     wm, Kpad = _weight_matrix(conv, xp.dtype)
     assert Kpad == kh * kw * C
-    y = torch.empty((N * Ho * Wo, Cout), dtype=xp.dtype, device=xp.device)
-    blocks = _block_stats(N * Ho * Wo, Cout, Kpad, xp.dtype, xp.device) if stats else None
-    flops = 2.0 * N * Ho * Wo * Cout * Kpad
-    if blocks is not None:
-        with ops.trace_launch(flops):
-            rc = H.lib().fcmf_conv_gemm_colstats(H.gemm_ctx(), H.ptr(xp), H.ptr(wm), H.ptr(y), H.ptr(blocks[0]), N, xp.shape[1], xp.shape[2],
-                                                 C, Ho, Wo, kh, kw, conv.stride[0], Cout, H.stream())
-        if rc == H.ERR_UNSUPPORTED:
-            blocks = None
-        else:
-            H.check(rc, "fcmf_conv_gemm_colstats")
-    if blocks is None:
-        with ops.trace_launch(flops):
-            H.check(H.lib().fcmf_conv_gemm(H.gemm_ctx(), H.ptr(xp), H.ptr(wm), H.ptr(y), N, xp.shape[1], xp.shape[2], C, Ho, Wo, kh, kw,
-                                           conv.stride[0], Cout, H.stream()), "fcmf_conv_gemm")
-    y = y.view(N, Ho, Wo, Cout)
-    return (y, blocks) if stats else y
+    L, geom = H.lib(), (N, xp.shape[1], xp.shape[2], C, Ho, Wo, kh, kw, conv.stride[0], Cout)
+    return _conv_rows((N, Ho, Wo), Cout, Kpad, xp.dtype, xp.device, stats, ("fcmf_conv_gemm_colstats", "fcmf_conv_gemm"),
+                      lambda y, b: L.fcmf_conv_gemm_colstats(H.gemm_ctx(), H.ptr(xp), H.ptr(wm), H.ptr(y), H.ptr(b), *geom, H.stream()),
+                      lambda y: L.fcmf_conv_gemm(H.gemm_ctx(), H.ptr(xp), H.ptr(wm), H.ptr(y), *geom, H.stream()))
 
 
 def _stem_runs_ok(conv, x, dt):
@@ -151,13 +166,11 @@ def conv2d_stem(v, conv, stats=False):
         w[:, :, :k, :3] = src.detach().float().permute(0, 2, 3, 1)            # [Cout, 3, ky, kx] -> [Cout, ky, kx, c]
         return ops.cast(w.view(Cout, k * 32).contiguous(), torch.bfloat16)
     wm = ops.shadows.derived(conv.weight, ("stem_runs", torch.bfloat16), build)
-    y = torch.empty((N * Ho * Wo, Cout), dtype=torch.bfloat16, device=v.device)
-    blocks = _block_stats(N * Ho * Wo, Cout, k * 32, torch.bfloat16, v.device) if stats else None
-    with ops.trace_launch(2.0 * N * Ho * Wo * Cout * k * 32):
-        H.check(H.lib().fcmf_conv_gemm_runs(H.gemm_ctx(), H.ptr(buf), H.ptr(wm), H.ptr(y), H.ptr(blocks[0]) if blocks is not None else None, N, Hh + 2 * pad, Wp, 4, 32, Ho, Wo, k, 2,
-                                            Cout, H.stream()), "fcmf_conv_gemm_runs")
-    y = y.view(N, Ho, Wo, Cout)
-    return (y, blocks) if stats else y
+
+    def runs(y, b=None):       # (one entry point: the block-statistics buffer or NULL; refused with a buffer, it is asked again without)
+        return H.lib().fcmf_conv_gemm_runs(H.gemm_ctx(), H.ptr(buf), H.ptr(wm), H.ptr(y), H.ptr(b), N, Hh + 2 * pad, Wp, 4, 32, Ho, Wo,
+                                           k, 2, Cout, H.stream())
+    return _conv_rows((N, Ho, Wo), Cout, k * 32, torch.bfloat16, v.device, stats, ("fcmf_conv_gemm_runs",) * 2, runs, runs)
 
 
 def conv2d_nhwc(x, conv, src_strides=None, stats=False):
@@ -183,20 +196,10 @@ def conv2d_nhwc(x, conv, src_strides=None, stats=False):
         sn, sh, sw, sc = src_strides if src_strides is not None else x.stride()
         H.check(H.lib().fcmf_conv_im2col(H.ptr(x), H.dt(x), H.ptr(A), H.dt(A), N, Hh, Ww, C, sn, sh, sw, sc, kh, kw, st,
                                          pad, Kpad, H.stream()), "fcmf_conv_im2col")
-    y = torch.empty((rows, Cout), dtype=dt, device=x.device)
-    blocks = _block_stats(rows, Cout, Kpad, dt, x.device) if stats else None
-    if blocks is not None:
-        with ops.trace_launch(2.0 * rows * Cout * Kpad):
-            rc = H.lib().fcmf_gemm_colstats(H.gemm_ctx(), H.ptr(A), H.ptr(wm), H.ptr(y), H.ptr(blocks[0]), rows, Cout, Kpad, Kpad, Kpad, Cout,
-                                            H.stream())
-        if rc == H.ERR_UNSUPPORTED:
-            blocks = None
-        else:
-            H.check(rc, "fcmf_gemm_colstats")
-    if blocks is None:
-        ops.gemm(A, wm, y, rows, Cout, Kpad, Kpad, Kpad, Cout, 0, 0)
-    y = y.view(N, Ho, Wo, Cout)
-    return (y, blocks) if stats else y
+    dims = (rows, Cout, Kpad, Kpad, Kpad, Cout)       # M, N, K, lda, ldb, ldc
+    return _conv_rows((N, Ho, Wo), Cout, Kpad, dt, x.device, stats, ("fcmf_gemm_colstats", None),
+                      lambda y, b: H.lib().fcmf_gemm_colstats(H.gemm_ctx(), H.ptr(A), H.ptr(wm), H.ptr(y), H.ptr(b), *dims, H.stream()),
+                      lambda y: ops.gemm(A, wm, y, *dims, 0, 0))
 
 
 def batchnorm_nhwc_(y, bn, groups=1, res=None, relu=False, out=None, save=None, out_pad=0, blocks=None):
@@ -255,6 +258,24 @@ def batchnorm_nhwc_(y, bn, groups=1, res=None, relu=False, out=None, save=None, 
     if save is not None:
         save.update(mean=mean, rstd=rstd, groups=groups, training=training, rpg=rpg)
     return z
+
+
+# tape of the recording forward.  Stage: what the backward of one convolution -> BatchNorm (+ residual, ReLU) reads: x -conv-> y -bn-> z
+# and the BatchNorm's `save` dict.  BlockRecord: one Bottleneck, its stages (conv1, conv2, conv3) and its downsample Stage or None
+Stage = namedtuple("Stage", "conv bn x y z save")
+
+
+class BlockRecord(namedtuple("BlockRecord", "block stages down")):
+    def __getitem__(self, key):       # r["z2"]: the output of stage 2, for callers that read a tape entry by the old name
+        return self.stages[int(key[1:]) - 1].z if isinstance(key, str) else super().__getitem__(key)
+
+
+def _normalise(conv, bn, x, y, blocks, groups, rec, relu=True, res=None):
+    """the BatchNorm half of a stage: y = conv(x) with its own block statistics `blocks` -> (z, Stage or None).
+    rec False: y is normalised in place; rec True: into a new tensor (the backward reads the raw y), statistics saved"""
+    save = {} if rec else None
+    z = batchnorm_nhwc_(y, bn, groups, res=res, relu=relu, out=torch.empty_like(y) if rec else None, save=save, blocks=blocks)
+    return z, (Stage(conv, bn, x, y, z, save) if rec else None)
 
 
 def flush_batch_counters(module):
@@ -486,59 +507,50 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
         self.stride = stride
 
-    def forward_nhwc(self, x, groups):
-        # (every convolution hands the statistics of its output to the BatchNorm that follows it: stats=True)
+    def run(self, x, groups, tape=None):
+        """tape is None: every BatchNorm normalises in place, nothing is kept; else (TrunkFn) raw convolution outputs are NOT
+        overwritten and a BlockRecord goes on the tape.  Every convolution hands its block statistics to its own BatchNorm."""
+        rec = tape is not None
         y1, b1 = conv2d_nhwc(x, self.conv1, stats=True)
         N, Hh, Ww, C = y1.shape
-        if _implicit_ok(C, y1.dtype) and not torch.is_grad_enabled():
+        if not rec and _implicit_ok(C, y1.dtype) and not torch.is_grad_enabled():
             # bn1 + relu write straight into the zero-bordered input of the 3x3 convolution, which then runs as an implicit GEMM
             zp = padded_activation(N, Hh, Ww, C, y1.dtype, y1.device)
             batchnorm_nhwc_(y1, self.bn1, groups, relu=True, out=zp, out_pad=1, blocks=b1)
             st = self.conv2.stride[0]
-            out, b2 = conv2d_implicit(zp, self.conv2, N, (Hh - 1) // st + 1, (Ww - 1) // st + 1, stats=True)
-        else:
-            out, b2 = conv2d_nhwc(batchnorm_nhwc_(y1, self.bn1, groups, relu=True, blocks=b1), self.conv2, stats=True)
-        out = batchnorm_nhwc_(out, self.bn2, groups, relu=True, blocks=b2)
-        out, b3 = conv2d_nhwc(out, self.conv3, stats=True)
+            y2, b2 = conv2d_implicit(zp, self.conv2, N, (Hh - 1) // st + 1, (Ww - 1) // st + 1, stats=True)
+            z1 = s1 = None      # (z1 lives in the padded buffer; this branch never records)
+        else:       # (the backward rebuilds conv2's patch matrix from the unpadded z1)
+            z1, s1 = _normalise(self.conv1, self.bn1, x, y1, b1, groups, rec)
+            y2, b2 = conv2d_nhwc(z1, self.conv2, stats=True)
+        z2, s2 = _normalise(self.conv2, self.bn2, z1, y2, b2, groups, rec)
+        y3, b3 = conv2d_nhwc(z2, self.conv3, stats=True)
+        idn, sd = x, None
         if self.downsample is not None:
             yd, bd = conv2d_nhwc(x, self.downsample[0], stats=True)
-            x = batchnorm_nhwc_(yd, self.downsample[1], groups, blocks=bd)
-        return batchnorm_nhwc_(out, self.bn3, groups, res=x, relu=True, blocks=b3)       # bn3 -> += identity -> relu, one pass
+            idn, sd = _normalise(*self.downsample, x, yd, bd, groups, rec, relu=False)
+        out, s3 = _normalise(self.conv3, self.bn3, z2, y3, b3, groups, rec, res=idn)       # bn3 -> += identity -> relu, one pass
+        if rec:
+            tape.append(BlockRecord(self, (s1, s2, s3), sd))
+        return out
 
-    def forward_rec(self, x, groups, tape):
-        """forward_nhwc that keeps what the backward needs (raw convolution outputs are NOT overwritten)"""
-        r = {"x": x, "blk": self}
-        for i, (conv, bn, src) in enumerate(((self.conv1, self.bn1, "x"), (self.conv2, self.bn2, "z1"), (self.conv3, self.bn3, "z2")), 1):
-            y, blk = conv2d_nhwc(r[src], conv, stats=True)
-            r[f"y{i}"], r[f"s{i}"] = y, {}
-            if i < 3:
-                r[f"z{i}"] = batchnorm_nhwc_(y, bn, groups, relu=True, out=torch.empty_like(y), save=r[f"s{i}"], blocks=blk)
-        idn = x
-        if self.downsample is not None:
-            (r["yd"], bd), r["sd"] = conv2d_nhwc(x, self.downsample[0], stats=True), {}
-            idn = batchnorm_nhwc_(r["yd"], self.downsample[1], groups, out=torch.empty_like(r["yd"]), save=r["sd"], blocks=bd)
-        r["z3"] = batchnorm_nhwc_(r["y3"], self.bn3, groups, res=idn, relu=True, out=torch.empty_like(r["y3"]), save=r["s3"], blocks=blk)
-        tape.append(r)
-        return r["z3"]
+    forward_rec = run         # (the recording forward under its old name: run with a tape)
 
     def backward_rec(self, r, g, grads):
-        """g: gradient wrt the block output -> gradient wrt the block input (parameter gradients into `grads`)"""
-        dy3, gres = batchnorm_bwd_nhwc_(self.bn3, r["s3"], g, r["y3"], r["z3"], grads, want_gres=True)
-        dz2 = conv2d_bwd_nhwc(self.conv3, r["z2"], dy3, grads)
-        dy2, _ = batchnorm_bwd_nhwc_(self.bn2, r["s2"], dz2, r["y2"], r["z2"], grads)
-        dz1 = conv2d_bwd_nhwc(self.conv2, r["z1"], dy2, grads)
-        dy1, _ = batchnorm_bwd_nhwc_(self.bn1, r["s1"], dz1, r["y1"], r["z1"], grads)
-        if self.downsample is not None:
-            dyd, _ = batchnorm_bwd_nhwc_(self.downsample[1], r["sd"], gres, r["yd"], None, grads)
-            conv_d = self.downsample[0]
-            if conv_d.stride[0] == 1:        # layer1.0: both branches are 1x1 / stride 1 -> the second GEMM adds the first
-                dxd = conv2d_bwd_nhwc(conv_d, r["x"], dyd, grads)
-                return conv2d_bwd_nhwc(self.conv1, r["x"], dy1, grads, add=dxd)
-            gres = conv2d_bwd_nhwc(conv_d, r["x"], dyd, grads)      # strided: col2im output, added by conv1's GEMM below
-        return conv2d_bwd_nhwc(self.conv1, r["x"], dy1, grads, add=gres)
+        """r: the BlockRecord of `run`; g: gradient wrt the block output -> gradient wrt the block input (parameter gradients into `grads`)"""
+        (s1, s2, s3), d = r.stages, r.down
+        dy3, gres = batchnorm_bwd_nhwc_(s3.bn, s3.save, g, s3.y, s3.z, grads, want_gres=True)
+        dz2 = conv2d_bwd_nhwc(s3.conv, s3.x, dy3, grads)
+        dy2, _ = batchnorm_bwd_nhwc_(s2.bn, s2.save, dz2, s2.y, s2.z, grads)
+        dz1 = conv2d_bwd_nhwc(s2.conv, s2.x, dy2, grads)
+        dy1, _ = batchnorm_bwd_nhwc_(s1.bn, s1.save, dz1, s1.y, s1.z, grads)
+        if d is not None:      # conv1's GEMM below adds this branch's dX: a GEMM output (layer1.0, 1x1 / stride 1) or col2im's (strided)
+            dyd, _ = batchnorm_bwd_nhwc_(d.bn, d.save, gres, d.y, None, grads)
+            gres = conv2d_bwd_nhwc(d.conv, d.x, dyd, grads)
+        return conv2d_bwd_nhwc(s1.conv, s1.x, dy1, grads, add=gres)
 
     def forward(self, x):
-        return _nchw(self.forward_nhwc(_nhwc(x), self.bn1.groups))
+        return _nchw(self.run(_nhwc(x), self.bn1.groups))
 
 
 class ResNet(nn.Module):
@@ -600,37 +612,30 @@ class ResNet(nn.Module):
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
     def _trunk_pass(self, x, groups, tape=None):
-        """tape is None: activations are normalised in place, nothing is kept; else: recording forward for TrunkFn"""
+        """tape is None: activations are normalised in place, nothing is kept; else: recording forward for TrunkFn, which
+        appends the stem's Stage (x = the strided view of the crops) and one BlockRecord per block"""
         xs = x if x.dtype in (torch.float32, torch.bfloat16) else x.float()
         v = xs.permute(0, 2, 3, 1)                                       # strided NHWC view of the NCHW crops
         if tape is None and _stem_runs_ok(self.conv1, v, ops.compute_dtype()):
-            y, blk = conv2d_stem(v, self.conv1, stats=True)
-        else:
-            y, blk = conv2d_nhwc(v, self.conv1, src_strides=v.stride(), stats=True)
-        if tape is None:
-            y = batchnorm_nhwc_(y, self.bn1, groups, relu=True, blocks=blk)
-            y = maxpool3x3s2_nhwc(y)
-            for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
-                for blk in layer:
-                    y = blk.forward_nhwc(y, groups)
-            return y
-        stem = {"v": v, "y": y, "s": {}}
-        stem["z"] = batchnorm_nhwc_(y, self.bn1, groups, relu=True, out=torch.empty_like(y), save=stem["s"], blocks=blk)
-        tape.append(stem)
-        y = maxpool3x3s2_nhwc(stem["z"])
+            y, b = conv2d_stem(v, self.conv1, stats=True)
+        else:       # (the backward rebuilds the patch matrix from the crops)
+            y, b = conv2d_nhwc(v, self.conv1, src_strides=v.stride(), stats=True)
+        z, stem = _normalise(self.conv1, self.bn1, v, y, b, groups, tape is not None)
+        if tape is not None:
+            tape.append(stem)
+        y = maxpool3x3s2_nhwc(z)
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
-            for blk in layer:
-                y = blk.forward_rec(y, groups, tape)
+            for block in layer:
+                y = block.run(y, groups, tape)
         return y
 
     def _trunk_backward(self, tape, g, grads):
         for r in reversed(tape[1:]):
-            g = r["blk"].backward_rec(r, g, grads)
+            g = r.block.backward_rec(r, g, grads)
         stem = tape[0]
-        z = stem["z"]
-        dz = maxpool3x3s2_bwd_nhwc(z, g)
-        dy, _ = batchnorm_bwd_nhwc_(self.bn1, stem["s"], dz, stem["y"], z, grads)
-        conv2d_bwd_nhwc(self.conv1, stem["v"], dy, grads, need_dx=False, src_strides=stem["v"].stride())
+        dz = maxpool3x3s2_bwd_nhwc(stem.z, g)
+        dy, _ = batchnorm_bwd_nhwc_(stem.bn, stem.save, dz, stem.y, stem.z, grads)
+        conv2d_bwd_nhwc(stem.conv, stem.x, dy, grads, need_dx=False, src_strides=stem.x.stride())
 
     def forward(self, x):
         """torchvision's ResNet.forward (classification head); not on the FCMF path, kept for API parity"""

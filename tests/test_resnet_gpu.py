@@ -418,3 +418,207 @@ def test_stem_convolution_without_patch_matrix(dev, N, hw, src):
         assert not buf[:, :3].any() and not buf[:, -3:].any() and not buf[:, :, :3].any() and not buf[:, :, hw + 2 + 3:].any() and not buf[..., 3].any()
     finally:
         _set(torch.float32)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the trunk's library calls, in order
+# ------------------------------------------------------------------------------------------------------------------------
+class _CallRecorder:
+    """stands in for _hip._lib: every entry point of _hip.SIGNATURES appends (name, its scalar arguments) to `calls` and
+    forwards the call.  Scalar = declared as anything but c_void_p / a POINTER: addresses are left out."""
+
+    def __init__(self, real, signatures):
+        import ctypes
+        self._real, self.calls = real, []
+        self._scalars = {n: [i for i, t in enumerate(sig) if t is not ctypes.c_void_p and not issubclass(t, ctypes._Pointer)]
+                         for n, sig in signatures.items()}
+
+    def __getattr__(self, name):
+        fn, keep = getattr(self._real, name), self._scalars.get(name)
+        if keep is None:
+            return fn
+
+        def call(*args):
+            self.calls.append((name, tuple(args[i] for i in keep)))
+            return fn(*args)
+        return call
+
+
+def _trunk_calls(dev, dtype, mode, layers=synth.RESNET_TINY_LAYERS, hw=64):
+    """[(entry point, scalar arguments)] of one trunk pass over 2 call groups x 2 crops of hw x hw.  mode: "train" / "eval" (no-grad
+    forward) or "fine_tune" (train mode, TrunkFn forward + backward)"""
+    from fcmf_framework import _hip as H
+    _set(dtype)                                  # (also drops the weight shadows: their casts are part of every recorded pass)
+    m, _ = _build(layers, dev)
+    m.train(mode != "eval")
+    x = synth.synth_crops(4, hw, seed=1).to(dev)
+    H.gemm_ctx(workspace=True)                   # (the first use of a stream creates its context and workspace: not part of the pass)
+    real = H.lib()
+    H._lib = rec = _CallRecorder(real, H.SIGNATURES)
+    try:
+        if mode == "fine_tune":
+            y = m.trunk_nhwc(x, groups=2, fine_tune=True)
+            assert y.requires_grad
+            y.backward(torch.ones_like(y))
+        else:
+            with torch.no_grad():
+                m.trunk_nhwc(x, groups=2)
+        torch.cuda.synchronize()
+    finally:
+        H._lib = real
+        _set(torch.float32)
+    return rec.calls, m
+
+
+def _calls_digest(calls):
+    import hashlib
+    return hashlib.sha256(repr(calls).encode()).hexdigest()
+
+
+# Entry-point names in call order, and the SHA-256 of repr([(name, scalar arguments), ...]).  Both were generated by running
+# _trunk_calls at the commit BEFORE the two trunk forwards became one walk (Bottleneck.run), not at the commit under test: the
+# walk has to issue what the two forwards issued.
+TRUNK_CALLS = {
+    "bf16-train": ("""
+        fcmf_pack_rgb0 fcmf_cast fcmf_gemm_colstats_block_rows fcmf_conv_gemm_runs fcmf_bn_stats_workspace
+        fcmf_bn_stats fcmf_bn_finalize_apply fcmf_maxpool3x3s2 fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_conv_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_gemm_colstats fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm_colstats
+        fcmf_bn_stats_workspace fcmf_bn_stats_blocks fcmf_bn_finalize_apply fcmf_bn_stats_workspace
+        fcmf_bn_stats_blocks fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_conv_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_gemm_colstats fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_conv_gemm_colstats fcmf_bn_stats_workspace fcmf_bn_stats_blocks fcmf_bn_finalize_apply
+        fcmf_bn_stats_workspace fcmf_bn_stats_blocks fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_conv_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply
+        fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm_colstats fcmf_bn_stats_workspace fcmf_bn_stats_blocks
+        fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm_colstats fcmf_bn_stats_workspace
+        fcmf_bn_stats_blocks fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_conv_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_gemm fcmf_cast fcmf_gemm_colstats_block_rows fcmf_conv_gemm fcmf_bn_stats_workspace fcmf_bn_stats
+        fcmf_bn_finalize_apply fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply
+        fcmf_cast fcmf_gemm_colstats_block_rows fcmf_conv_gemm fcmf_bn_stats_workspace fcmf_bn_stats
+        fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_stats_workspace
+        fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_conv_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_cast fcmf_gemm_colstats_block_rows fcmf_conv_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_bn_stats_workspace fcmf_bn_stats
+        fcmf_bn_finalize_apply
+        """, "37fd198234c00a0028e6e91c2629eed1f9fd14e45e8b0209260e645ca51386ae"),
+    "bf16-eval": ("""
+        fcmf_pack_rgb0 fcmf_cast fcmf_gemm_colstats_block_rows fcmf_conv_gemm_runs fcmf_bn_finalize_apply
+        fcmf_maxpool3x3s2 fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_finalize_apply fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_conv_gemm fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_gemm_colstats fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm_colstats fcmf_bn_finalize_apply
+        fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_finalize_apply fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_conv_gemm fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_gemm_colstats fcmf_cast fcmf_gemm_colstats_block_rows fcmf_conv_gemm_colstats fcmf_bn_finalize_apply
+        fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_finalize_apply fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_conv_gemm fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_gemm_colstats fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm_colstats
+        fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_conv_gemm fcmf_bn_finalize_apply
+        fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_cast fcmf_gemm_colstats_block_rows fcmf_conv_gemm
+        fcmf_bn_finalize_apply fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm
+        fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_conv_gemm fcmf_bn_finalize_apply
+        fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_finalize_apply fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_conv_gemm fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_conv_gemm fcmf_bn_finalize_apply fcmf_bn_finalize_apply
+        """, "64515cd344c09f5555e10b5cc903c6e7bebc9ca10b4df654ed455497a7c7abcc"),
+    "bf16-fine_tune": ("""
+        fcmf_cast fcmf_conv_im2col fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats
+        fcmf_bn_finalize_apply fcmf_maxpool3x3s2 fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast fcmf_conv_im2col
+        fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply
+        fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm_colstats fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_gemm_colstats fcmf_bn_stats_workspace fcmf_bn_stats_blocks fcmf_bn_finalize_apply
+        fcmf_bn_stats_workspace fcmf_bn_stats_blocks fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast fcmf_conv_im2col
+        fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply
+        fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm_colstats fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_conv_gemm_colstats fcmf_bn_stats_workspace fcmf_bn_stats_blocks fcmf_bn_finalize_apply
+        fcmf_bn_stats_workspace fcmf_bn_stats_blocks fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast fcmf_conv_im2col
+        fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply
+        fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm_colstats fcmf_bn_stats_workspace fcmf_bn_stats_blocks
+        fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm_colstats fcmf_bn_stats_workspace
+        fcmf_bn_stats_blocks fcmf_bn_finalize_apply fcmf_cast fcmf_conv_im2col fcmf_gemm_colstats_block_rows
+        fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_cast fcmf_gemm_colstats_block_rows fcmf_conv_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_bn_stats_workspace fcmf_bn_stats
+        fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_stats_workspace
+        fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast fcmf_conv_im2col fcmf_gemm_colstats_block_rows fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows
+        fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply
+        fcmf_cast fcmf_conv_im2col fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats
+        fcmf_bn_finalize_apply fcmf_cast fcmf_gemm_colstats_block_rows fcmf_gemm fcmf_cast
+        fcmf_gemm_colstats_block_rows fcmf_conv_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_gemm
+        fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_conv_im2col fcmf_gemm fcmf_gemm fcmf_conv_col2im
+        fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_conv_im2col fcmf_gemm fcmf_gemm
+        fcmf_conv_col2im fcmf_gemm fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_gemm fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_conv_im2col fcmf_gemm fcmf_gemm fcmf_conv_col2im
+        fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_gemm fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_gemm
+        fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_conv_im2col fcmf_gemm fcmf_gemm fcmf_conv_col2im
+        fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_conv_im2col fcmf_gemm fcmf_gemm
+        fcmf_conv_col2im fcmf_gemm fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_gemm fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_conv_im2col fcmf_gemm fcmf_gemm fcmf_conv_col2im
+        fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_gemm fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_gemm
+        fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_conv_im2col fcmf_gemm fcmf_gemm fcmf_conv_col2im
+        fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_conv_im2col fcmf_gemm fcmf_gemm
+        fcmf_conv_col2im fcmf_gemm fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_gemm fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_conv_im2col fcmf_gemm fcmf_gemm fcmf_conv_col2im
+        fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_gemm fcmf_gemm fcmf_gemm
+        fcmf_gemm fcmf_maxpool3x3s2_bwd fcmf_bn_stats_workspace fcmf_bn_bwd fcmf_conv_im2col fcmf_gemm
+        """, "9aed4056152c32730ddd2a9ccce77d7204c990099c12a63ba17e5c9005e23ac8"),
+    "fp32-train": ("""
+        fcmf_conv_im2col fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_maxpool3x3s2
+        fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_conv_im2col fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_gemm fcmf_gemm fcmf_bn_stats_workspace
+        fcmf_bn_stats fcmf_bn_finalize_apply fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_conv_im2col fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_gemm fcmf_conv_im2col fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_bn_stats_workspace fcmf_bn_stats
+        fcmf_bn_finalize_apply fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply
+        fcmf_conv_im2col fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats
+        fcmf_bn_finalize_apply fcmf_conv_im2col fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats
+        fcmf_bn_finalize_apply fcmf_gemm fcmf_conv_im2col fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats
+        fcmf_bn_finalize_apply fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_conv_im2col fcmf_gemm
+        fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats
+        fcmf_bn_finalize_apply fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply
+        fcmf_conv_im2col fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_gemm
+        fcmf_conv_im2col fcmf_gemm fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_bn_finalize
+        fcmf_bn_apply fcmf_bn_stats_workspace fcmf_bn_stats fcmf_bn_finalize_apply fcmf_bn_finalize fcmf_bn_apply
+        """, "ffa1d7d6815241a13a03406de38f5143dce09b08b490dd6e8574d3735faff40d"),
+}
+
+
+@pytest.mark.parametrize("dtype,mode", [(torch.bfloat16, "train"), (torch.bfloat16, "eval"), (torch.bfloat16, "fine_tune"), (torch.float32, "train")],
+                         ids=["bf16-train", "bf16-eval", "bf16-fine_tune", "fp32-train"])
+def test_trunk_library_call_sequence(dev, dtype, mode, request):
+    """the (1,2,2,1)-block trunk on 64x64 crops meets every fork of the walk: stem runs / patch-matrix stem, implicit 3x3 / im2col,
+    a stride-1 and a strided downsample, colstats blocks / the statistics pass on the small late maps"""
+    from fcmf_framework import resnet as R
+    calls, m = _trunk_calls(dev, dtype, mode)
+    names = [c[0] for c in calls]
+    print("MEASURED", request.node.callspec.id, len(names), _calls_digest(calls))
+    convs = [c for c in m.modules() if isinstance(c, R.Conv2d)]
+    kxk = sum(c.kernel_size[0] > 1 for c in convs)                                    # the stem and the 3x3s
+    strided_1x1 = sum(c.kernel_size[0] == 1 and c.stride[0] > 1 for c in convs)       # the downsamples of layer2..4
+    if dtype == torch.bfloat16 and mode != "fine_tune":
+        assert "fcmf_conv_im2col" not in names              # no patch matrix anywhere in a bf16 forward-only pass
+    if mode == "fine_tune":
+        # forward: one patch matrix per convolution that is not a direct GEMM (k x k; the strided 1x1 shortcuts are gathered by
+        # the implicit GEMM, grad mode being off inside TrunkFn.forward); backward: one more for each of those AND for the shortcuts
+        assert names.count("fcmf_conv_im2col") == kxk + (kxk + strided_1x1)
+    exp_names, exp_digest = TRUNK_CALLS[request.node.callspec.id]
+    assert names == exp_names.split()
+    assert _calls_digest(calls) == exp_digest
