@@ -82,8 +82,9 @@ class GradArena:
             if isinstance(m, QKVStorageMixin):
                 blocks.append([m.query.weight, m.key.weight, m.value.weight])
                 blocks.append([m.query.bias, m.key.bias, m.value.bias])
-        # IAOG decoder: the per-head projection weights whose gradients ONE column-blocked GEMM writes (ops.head_weight_grad) --
-        # [w_kx | w_qx] of every self attention, and the w_kx of ALL blocks' cross attention (their keys are hoisted into one GEMM)
+        # IAOG decoder: the per-head projection weights whose gradients ONE column-blocked GEMM writes (ops.head_project_bwd ->
+        # ops.head_weight_grad) -- [w_kx | w_qx] of every self attention, and the w_kx of ALL blocks' cross attention (ONE
+        # ops.head_linear projects the encoder output by all of them: IAOGDecoder.project_encoder)
         for m in model.modules():
             blks = getattr(m, "blks", None)
             if blks is not None and all(hasattr(b, "attention1") and hasattr(b, "attention2") for b in blks):

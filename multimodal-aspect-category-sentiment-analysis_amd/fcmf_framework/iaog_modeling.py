@@ -15,12 +15,12 @@ import math
 import torch
 import torch.nn as nn
 
+from . import _hip as H
 from . import layers, ops
 
 
 def _quirk_attn_fwd(qx, kx, heads, causal):
     """qx [G, R, heads*d], kx [G, T, heads*d] (row strides arbitrary, unit inner stride) -> out [G, R, heads*d] dense, lse"""
-    from . import _hip as H
     G, R, HD = qx.shape
     out = torch.empty((G, R, HD), dtype=qx.dtype, device=qx.device)
     lse = torch.empty((G, heads, R), dtype=torch.float32, device=qx.device)
@@ -38,7 +38,6 @@ def _quirk_attn_bwd(qx, kx, out, lse, dout, heads, causal, dq_out, dk_out):
     """gradients per HEAD written into dq_out / dk_out ([G, R|T, heads*d] views with unit inner stride, any row stride): the
     attention backward produces them per output SLOT, fcmf_head_gather sums the slots that read each head
     (slot s of group g reads head (s*G + g) % heads, mm_modeling.py:79-85)"""
-    from . import _hip as H
     G, R, HD = qx.shape
     T, d = kx.shape[1], HD // heads
     nch = max(1, (T + 127) // 128)
@@ -75,34 +74,19 @@ class _QuirkAttentionFn(torch.autograd.Function):
         return dq, dk, None, None
 
 
-def _pair_layouts(wk, wq, dtype):
-    """[2*n_head*d, E] (nn.Linear layout: keys' rows, then queries') and its transpose [E, 2*n_head*d] for the two per-head
-    weight tensors of one decoder Attention, cached on the key parameter (both are stale after every optimizer step)"""
-    nh, E, d = wk.shape
-
-    def nk(_):
-        return ops.cast(torch.cat((wk.detach().permute(0, 2, 1).reshape(nh * d, E), wq.detach().permute(0, 2, 1).reshape(nh * d, E)), 0), dtype)
-
-    def kn(_):
-        return ops.cast(torch.cat((wk.detach().permute(1, 0, 2).reshape(E, nh * d), wq.detach().permute(1, 0, 2).reshape(E, nh * d)), 1), dtype)
-    return ops.shadows.derived(wk, ("pair_nk", dtype, wq.data_ptr()), nk), (lambda: ops.shadows.derived(wk, ("pair_kn", dtype, wq.data_ptr()), kn))
-
-
 class _SelfQuirkAttentionFn(torch.autograd.Function):
     """decoder self attention `Attention(X, X, causal)` up to (not including) `proj`, as ONE node: the key and query projections
-    of the same input are one GEMM against [w_kx | w_qx] (N = 2 * n_head * d), the attention reads the two halves of its output in
-    place, and the backward gathers the per-slot gradients straight into the halves of one [rows, 2*n_head*d] buffer that feeds
-    ONE dX and ONE dW GEMM (the reference: 2 x (repeat + bmm) forward, mm_modeling.py:79-92)."""
+    of the same input are one GEMM against [w_kx | w_qx] (ops.head_project, N = 2 * n_head * d), the attention reads the two halves
+    of its output in place, and the backward gathers the per-slot gradients straight into the halves of one [rows, 2*n_head*d]
+    buffer that feeds ONE dX and ONE dW GEMM (the reference: 2 x (repeat + bmm) forward, mm_modeling.py:79-92)."""
 
     @staticmethod
     def forward(ctx, x, wk, wq, heads, causal, probs=None):
         """probs (optional, float32 [heads*G, T, T]): filled with the attention probabilities from the node's own [kx | qx] buffer"""
-        G, T, E = x.shape
+        G, T, _ = x.shape
         x2 = ops._rows(x)
-        HD = wk.shape[0] * wk.shape[2]
-        wl = ops.shadows.head_nk([wk, wq]) if x2.dtype == torch.bfloat16 else _pair_layouts(wk, wq, x2.dtype)[0]
-        kq = torch.empty((G * T, 2 * HD), dtype=x2.dtype, device=x2.device)
-        ops.gemm(x2, wl, kq, G * T, 2 * HD, E, ops._ld(x2), E, 2 * HD, 0, 0)
+        kq = ops.head_project(x2, [wk, wq])
+        HD = kq.shape[1] // 2
         kq3 = kq.view(G, T, 2 * HD)
         out, lse = _quirk_attn_fwd(kq3[:, :, HD:], kq3[:, :, :HD], heads, causal)
         if probs is not None:
@@ -115,81 +99,13 @@ class _SelfQuirkAttentionFn(torch.autograd.Function):
     def backward(ctx, dout):
         x2, kq, out, lse, wk, wq = ctx.saved_tensors
         heads, causal, xshape = ctx.cfg
-        G, T, E = xshape
-        nh, _, d = wk.shape
-        HD = nh * d
-        kq3 = kq.view(G, T, 2 * HD)
+        HD = kq.shape[1] // 2
+        kq3 = kq.view(xshape[0], xshape[1], 2 * HD)
         dkq = torch.empty_like(kq)
-        d3 = dkq.view(G, T, 2 * HD)
+        d3 = dkq.view(kq3.shape)
         _quirk_attn_bwd(kq3[:, :, HD:], kq3[:, :, :HD], out, lse, dout, heads, causal, d3[:, :, HD:], d3[:, :, :HD])
-        dx = torch.empty((G * T, E), dtype=x2.dtype, device=x2.device)
-        if x2.dtype == torch.bfloat16:     # NN: dx = dkq W with W in the forward's [2*n_head*d, E] layout (no second re-layout)
-            ops.gemm(dkq, ops.shadows.head_nk([wk, wq]), dx, G * T, E, 2 * HD, 2 * HD, E, E, 0, 1)
-        else:
-            _, kn = _pair_layouts(wk, wq, x2.dtype)
-            ops.gemm(dkq, kn(), dx, G * T, E, 2 * HD, 2 * HD, 2 * HD, E, 0, 0)               # NT: both operands K-contiguous
-        direct = ops.head_weight_grad(x2, dkq, [wk, wq])          # straight into the two parameters' adjacent [n_head, E, d] arena slices
-        if direct is not None:
-            return dx.view(xshape), direct[0], direct[1], None, None, None
-        dwl = torch.empty((2 * HD, E), dtype=torch.float32, device=x2.device)
-        ops.gemm(dkq, x2, dwl, 2 * HD, E, G * T, 2 * HD, ops._ld(x2), E, 1, 1)                # [2*n_head*d, E] = dkq^T x
-        dw = dwl.view(2, nh, d, E).permute(0, 1, 3, 2)                                        # -> the parameters' [n_head, E, d]
-        return dx.view(xshape), dw[0], dw[1], None, None, None
-
-
-class _HoistedKeysFn(torch.autograd.Function):
-    """the key projections of ALL decoder blocks' cross attention -- every block projects the same encoder output with its own
-    w_kx (mm_modeling.py:601-605) -- as ONE GEMM (N = blocks * n_head * d) before the block loop; returns one [G, T, n_head*d]
-    view per block.  Backward: the blocks' key gradients side by side -> ONE dX and ONE dW GEMM."""
-
-    @staticmethod
-    def forward(ctx, enc, *wks):
-        G, T, E = enc.shape
-        e2 = ops._rows(enc)
-        nh, _, d = wks[0].shape
-        HD, nb = nh * d, len(wks)
-
-        def nk(_):
-            return ops.cast(torch.cat([w.detach().permute(0, 2, 1).reshape(HD, E) for w in wks], 0), e2.dtype)
-        wl = (ops.shadows.head_nk(list(wks)) if e2.dtype == torch.bfloat16
-              else ops.shadows.derived(wks[0], ("hoist_nk", e2.dtype, nb, wks[-1].data_ptr()), nk))
-        kx = torch.empty((G * T, nb * HD), dtype=e2.dtype, device=e2.device)
-        ops.gemm(e2, wl, kx, G * T, nb * HD, E, ops._ld(e2), E, nb * HD, 0, 0)
-        ctx.save_for_backward(e2, *wks)
-        ctx.cfg = (enc.shape, nb, HD)
-        k3 = kx.view(G, T, nb * HD)
-        return tuple(k3[:, :, i * HD:(i + 1) * HD] for i in range(nb))
-
-    @staticmethod
-    def backward(ctx, *grads):
-        e2, *wks = ctx.saved_tensors
-        eshape, nb, HD = ctx.cfg
-        G, T, E = eshape
-        nh, _, d = wks[0].shape
-        zero = None
-        parts = []
-        for g in grads:
-            if g is None:
-                zero = torch.zeros((G, T, HD), dtype=e2.dtype, device=e2.device) if zero is None else zero
-                g = zero
-            parts.append(g.reshape(G * T, HD))
-        dk = torch.cat(parts, 1)                                                             # [G*T, blocks*HD]
-
-        def kn(_):
-            return ops.cast(torch.cat([w.detach().permute(1, 0, 2).reshape(E, HD) for w in wks], 1), e2.dtype)
-        de = torch.empty((G * T, E), dtype=e2.dtype, device=e2.device)
-        if e2.dtype == torch.bfloat16:
-            ops.gemm(dk, ops.shadows.head_nk(list(wks)), de, G * T, E, nb * HD, nb * HD, E, E, 0, 1)       # NN
-        else:
-            wt = ops.shadows.derived(wks[0], ("hoist_kn", e2.dtype, nb, wks[-1].data_ptr()), kn)
-            ops.gemm(dk, wt, de, G * T, E, nb * HD, nb * HD, nb * HD, E, 0, 0)
-        direct = ops.head_weight_grad(e2, dk, list(wks))          # every block's w_kx: adjacent arena slices (dp.GradArena.for_model)
-        if direct is not None:
-            return (de.view(eshape),) + tuple(direct)
-        dwl = torch.empty((nb * HD, E), dtype=torch.float32, device=e2.device)
-        ops.gemm(dk, e2, dwl, nb * HD, E, G * T, nb * HD, ops._ld(e2), E, 1, 1)
-        dw = dwl.view(nb, nh, d, E).permute(0, 1, 3, 2)
-        return (de.view(eshape),) + tuple(dw[i] for i in range(nb))
+        dx, dws = ops.head_project_bwd(x2, dkq, [wk, wq], ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        return (None if dx is None else dx.view(xshape), *(dws or (None, None)), None, None, None)
 
 
 _valid_lens_cache = {}
@@ -261,8 +177,8 @@ class PositionWiseFFN(nn.Module):
     def __init__(self, ffn_num_hiddens, ffn_num_outputs, hidden_size=None):
         super().__init__()
         from . import mm_modeling as mm
-        H = hidden_size or mm.HIDDEN_SIZE
-        self.dense1 = nn.Linear(H, ffn_num_hiddens)
+        Hd = hidden_size or mm.HIDDEN_SIZE
+        self.dense1 = nn.Linear(Hd, ffn_num_hiddens)
         self.act = mm.ACT2FN[mm.HIDDEN_ACT]
         self.dense2 = nn.Linear(ffn_num_hiddens, ffn_num_outputs)
 
@@ -288,17 +204,18 @@ class TransformerDecoderBlock(nn.Module):
     def __init__(self, i, hidden_size=None, num_heads=None):
         super().__init__()
         from . import mm_modeling as mm
-        H, nh = hidden_size or mm.HIDDEN_SIZE, num_heads or mm.NUM_ATTENTION_HEADS
+        Hd, nh = hidden_size or mm.HIDDEN_SIZE, num_heads or mm.NUM_ATTENTION_HEADS
         p = mm.ATTENTION_PROBS_DROPOUT_PROB
         self.i = i
-        self.attention1 = Attention(H, H // nh, nh, 'scaled_dot_product', p)
-        self.addnorm1 = AddNorm(H, p)
-        self.attention2 = Attention(H, H // nh, nh, 'scaled_dot_product', p)
-        self.addnorm2 = AddNorm(H, p)
-        self.ffn = PositionWiseFFN(H, H, H)
-        self.add_norm3 = AddNorm(H, p)
+        self.attention1 = Attention(Hd, Hd // nh, nh, 'scaled_dot_product', p)
+        self.addnorm1 = AddNorm(Hd, p)
+        self.attention2 = Attention(Hd, Hd // nh, nh, 'scaled_dot_product', p)
+        self.addnorm2 = AddNorm(Hd, p)
+        self.ffn = PositionWiseFFN(Hd, Hd, Hd)
+        self.add_norm3 = AddNorm(Hd, p)
 
-    def forward(self, X, state, enc_attention_mask=None, is_train=True):
+    def forward(self, X, state, enc_attention_mask=None, is_train=True, kx=None):
+        """kx: this block's cross-attention keys when the decoder has projected them already (IAOGDecoder.project_encoder)"""
         enc_outputs, enc_valid_lens = state[0], state[1]
         if state[2][self.i] is not None:  # the reference concatenates a cache it never reads (:588-601)
             state[2][self.i] = torch.cat((state[2][self.i], X), dim=1)
@@ -310,7 +227,7 @@ class TransformerDecoderBlock(nn.Module):
         X2, _ = self.attention1(X, X, dec_valid_lens)
         Y = self.addnorm1(X, X2)
         cross_mask = enc_attention_mask if enc_attention_mask is not None else enc_valid_lens
-        Y2, _ = self.attention2(enc_outputs, Y, cross_mask, kx=getattr(self, "_hoisted_kx", None))
+        Y2, _ = self.attention2(enc_outputs, Y, cross_mask, kx=kx)
         Z = self.addnorm2(Y, Y2)
         return self.add_norm3(Z, self.ffn(Z)), state
 
@@ -319,11 +236,11 @@ class PositionalEncoding(nn.Module):
     def __init__(self, hidden_size=None):
         super().__init__()
         from . import mm_modeling as mm
-        H = hidden_size or mm.HIDDEN_SIZE
+        Hd = hidden_size or mm.HIDDEN_SIZE
         self.dropout = nn.Dropout(mm.ATTENTION_PROBS_DROPOUT_PROB)
-        P = torch.zeros((1, mm.MAX_POSITION_EMBEDDINGS, H))
+        P = torch.zeros((1, mm.MAX_POSITION_EMBEDDINGS, Hd))
         X = torch.arange(mm.MAX_POSITION_EMBEDDINGS, dtype=torch.float32).reshape(-1, 1) / torch.pow(
-            10000, torch.arange(0, H, 2, dtype=torch.float32) / H)
+            10000, torch.arange(0, Hd, 2, dtype=torch.float32) / Hd)
         P[:, :, 0::2] = torch.sin(X)
         P[:, :, 1::2] = torch.cos(X)
         self.register_buffer('P', P)
@@ -340,7 +257,6 @@ class _ScaledEmbedding(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ids, weight, pos_table, scale, out_dtype):
-        from . import _hip as H
         idc = ids.contiguous()
         n, Hd = idc.numel(), weight.shape[1]
         T = ids.shape[-1]
@@ -355,7 +271,6 @@ class _ScaledEmbedding(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from . import _hip as H
         (ids,) = ctx.saved_tensors
         d = dy.contiguous()
         V, Hd = ctx.weight.shape
@@ -385,7 +300,7 @@ class IAOGDecoder(nn.Module):
     def project_encoder(self, enc_outputs):
         """every block's cross-attention keys ( = values, mm_modeling.py:129) of an encoder output, one GEMM for all blocks;
         hand the result to forward(..., hoisted=) when the same encoder output is decoded again and again (decoding.py)"""
-        return _HoistedKeysFn.apply(layers.to_compute(enc_outputs), *[blk.attention2.w_kx for blk in self.blks])
+        return ops.HeadLinearFn.apply(layers.to_compute(enc_outputs), *[blk.attention2.w_kx for blk in self.blks])
 
     def hidden_states(self, X, state, enc_attention_mask=None, is_train=True, hoisted=None):
         """the decoder stack up to (not including) the vocabulary projection: [B, Ld, H]"""
@@ -396,13 +311,9 @@ class IAOGDecoder(nn.Module):
         # every block's cross attention projects the SAME encoder output with its own w_kx: one GEMM for all of them
         enc = layers.to_compute(state[0])
         if hoisted is None:
-            hoisted = _HoistedKeysFn.apply(enc, *[blk.attention2.w_kx for blk in self.blks]) if enc.dim() == 3 else [None] * len(self.blks)
+            hoisted = self.project_encoder(enc) if enc.dim() == 3 else [None] * len(self.blks)
         for i, blk in enumerate(self.blks):
-            blk._hoisted_kx = hoisted[i]
-            try:
-                X, state = blk(X, state, enc_attention_mask=enc_attention_mask, is_train=is_train)
-            finally:
-                blk._hoisted_kx = None
+            X, state = blk(X, state, enc_attention_mask=enc_attention_mask, is_train=is_train, kx=hoisted[i])
             self._attention_weights[0][i] = blk.attention1.attention_weights
             self._attention_weights[1][i] = blk.attention2.attention_weights
         return X

@@ -809,61 +809,88 @@ def seq_fan(seq, w1, b1, w2, b2):
     return SeqFanFn.apply(seq, w1, b1, w2, b2)
 
 
+def head_layouts(ws, dtype):
+    """the per-head weights `ws` (Parameters [n_head, E, d] of the IAOG decoder's Attention, side by side) for a kernel computing in
+    `dtype` other than bf16 (bf16: `shadows.head_nk`) -> ([len(ws)*n_head*d, E], the nn.Linear layout in natural head order, and a
+    function that builds its transpose [E, len(ws)*n_head*d], the K-contiguous operand of dx = dy W, when it is called).  Cached on
+    the PARAMETER ws[0] (`shadows.derived`), never on a temporary; the addresses of all of `ws` are part of the tag."""
+    nh, E, d = ws[0].shape
+    tag = (dtype,) + tuple(w.data_ptr() for w in ws)
+
+    def build(perm, shape, dim):
+        parts = [w.detach().permute(*perm).reshape(shape) for w in ws]
+        return cast(parts[0] if len(parts) == 1 else torch.cat(parts, dim), dtype)
+    return (shadows.derived(ws[0], ("head_nk",) + tag, lambda _: build((0, 2, 1), (nh * d, E), 0)),
+            lambda: shadows.derived(ws[0], ("head_kn",) + tag, lambda _: build((1, 0, 2), (E, nh * d), 1)))
+
+
+def head_project(x2, ws):
+    """y[:, (i*n_head + h)*d + j] = sum_e x2[:, e] * ws[i][h, e, j]: the per-head projections of the IAOG decoder `Attention`
+    (w_kx / w_qx [n_head, E, d], mm_modeling.py:57-58,79-92) of one input by every weight of `ws` as ONE GEMM against the
+    [len(ws)*n_head*d, E] re-layout of the parameters instead of the reference's B-fold `repeat` + bmm per weight.
+    x2 [M, E] (unit inner stride, any row stride) -> y [M, len(ws)*n_head*d]"""
+    ws = list(ws)
+    return _linear_fwd(x2, shadows.head_nk(ws) if x2.dtype == torch.bfloat16 else head_layouts(ws, x2.dtype)[0], None)
+
+
+def head_project_bwd(x2, dy2, ws, need_dx=True, need_dw=True):
+    """backward of head_project: dy2 [M, len(ws)*n_head*d] dense -> (dx [M, E] or None, [dw_i in the parameters' [n_head, E, d]
+    layout] or None).  ONE dX and ONE dW GEMM for all of `ws`."""
+    ws = list(ws)
+    nh, E, d = ws[0].shape
+    M, N = dy2.shape
+    dx = dws = None
+    if need_dx:
+        dx = torch.empty((M, E), dtype=dy2.dtype, device=dy2.device)
+        if dy2.dtype == torch.bfloat16:
+            gemm(dy2, shadows.head_nk(ws), dx, M, E, N, N, E, E, 0, 1)           # NN: dx = dy W with W in the forward's [N, E] layout (no second re-layout)
+        else:
+            gemm(dy2, head_layouts(ws, dy2.dtype)[1](), dx, M, E, N, N, N, E, 0, 0)   # NT: both operands K-contiguous
+    if need_dw:
+        dws = head_weight_grad(x2, dy2, ws)                                      # straight into the parameters' adjacent [n_head, E, d] arena slices
+        if dws is None:
+            dwl = torch.empty((N, E), dtype=torch.float32, device=dy2.device)    # (fresh buffer: written, not accumulated into)
+            gemm(dy2, x2, dwl, N, E, M, N, _ld(x2), E, 1, 1)                     # [len(ws)*n_head*d, E] = dy^T x
+            dws = list(dwl.view(len(ws), nh, d, E).permute(0, 1, 3, 2))          # -> the parameters' [n_head, E, d]
+    return dx, dws
+
+
 class HeadLinearFn(torch.autograd.Function):
-    """y[..., h*d + j] = sum_e x[..., e] * w[h, e, j]: the per-head projections of the IAOG decoder `Attention`
-    (w_kx / w_qx [n_head, E, d], mm_modeling.py:57-58,79-92) as ONE GEMM against the [n_head*d, E] re-layout of the
-    parameter instead of the reference's B-fold `repeat` + bmm.  The re-layouts (and their bf16 casts) are cached
-    on the PARAMETER (`shadows.derived`), never on a temporary."""
+    """head_project of x [..., E] by the per-head weights ws (every decoder block's cross-attention w_kx of the same encoder
+    output, mm_modeling.py:601-605; one w_qx) as one node: one [..., n_head*d] output per weight, views of the one product."""
 
     @staticmethod
-    def _layouts(w, dtype):
-        nh, E, d = w.shape
-
-        def nk(src):      # [n_head*d, E]: nn.Linear layout, natural head order
-            return cast(src.permute(0, 2, 1).reshape(nh * d, E), dtype)
-
-        def kn(src):      # [E, n_head*d]: its transpose, the K-contiguous operand of dx = dy W
-            return cast(src.permute(1, 0, 2).reshape(E, nh * d), dtype)
-        return shadows.derived(w, ("head_nk", dtype), nk), (lambda: shadows.derived(w, ("head_kn", dtype), kn))
-
-    @staticmethod
-    def forward(ctx, x, w):
+    def forward(ctx, x, *ws):
         x2 = _rows(x)
-        nh, E, d = w.shape
-        wl = shadows.head_nk([w]) if x2.dtype == torch.bfloat16 else HeadLinearFn._layouts(w, x2.dtype)[0]
-        y = _linear_fwd(x2, wl, None)
-        ctx.save_for_backward(x2, w)
+        y = head_project(x2, ws)
+        ctx.save_for_backward(x2, *ws)
         ctx.xshape = x.shape
-        return y.view(*x.shape[:-1], nh * d)
+        HD = y.shape[1] // len(ws)
+        y = y.view(*x.shape[:-1], len(ws) * HD)
+        return tuple(y[..., i * HD:(i + 1) * HD] for i in range(len(ws)))
 
     @staticmethod
-    def backward(ctx, dy):
-        x2, w = ctx.saved_tensors
-        nh, E, d = w.shape
-        M, N = x2.shape[0], nh * d
-        dy2 = dy.reshape(-1, N).contiguous()
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty((M, E), dtype=dy2.dtype, device=dy2.device)
-            if dy2.dtype == torch.bfloat16:
-                gemm(dy2, shadows.head_nk([w]), dx, M, E, N, N, E, E, 0, 1)      # NN: dx = dy W with W in the forward's [N, E] layout
-            else:
-                _, kn = HeadLinearFn._layouts(w, x2.dtype)
-                gemm(dy2, kn(), dx, M, E, N, N, N, E, 0, 0)                  # NT: both operands K-contiguous
-            dx = dx.view(ctx.xshape)
-        if ctx.needs_input_grad[1]:
-            direct = head_weight_grad(x2, dy2, [w])                          # straight into the parameter's [n_head, E, d] arena slice
-            if direct is not None:
-                dw = direct[0]
-            else:
-                dwl = torch.empty((N, E), dtype=torch.float32, device=dy2.device)    # (fresh buffer: written, not accumulated into)
-                gemm(dy2, x2, dwl, N, E, M, N, _ld(x2), E, 1, 1)                 # [n_head*d, E] = dy^T x
-                dw = dwl.view(nh, d, E).permute(0, 2, 1)                         # the parameter's [n_head, E, d] layout
-        return dx, dw
+    def backward(ctx, *dys):
+        x2, *ws = ctx.saved_tensors
+        M, HD = x2.shape[0], ws[0].shape[0] * ws[0].shape[2]
+        if len(dys) == 1:
+            dy2 = dys[0].reshape(-1, HD).contiguous()
+        else:                                  # the weights' output gradients side by side; an unused output counts as zeros
+            zero = None
+            parts = []
+            for g in dys:
+                if g is None:
+                    g = zero = torch.zeros((M, HD), dtype=x2.dtype, device=x2.device) if zero is None else zero
+                parts.append(g.reshape(M, HD))
+            dy2 = torch.cat(parts, 1)
+        dx, dws = head_project_bwd(x2, dy2, ws, ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:]))
+        return (None if dx is None else dx.view(ctx.xshape), *(dws or [None] * len(ws)))
 
 
-def head_linear(x, w):
-    return HeadLinearFn.apply(x, w)
+def head_linear(x, *ws):
+    """-> one tensor for one weight, a tuple of them for several (see HeadLinearFn)"""
+    ys = HeadLinearFn.apply(x, *ws)
+    return ys[0] if len(ws) == 1 else ys
 
 
 class VocabLinearFn(torch.autograd.Function):
