@@ -16,6 +16,8 @@ The ResNet-152 extractors are checkpointed next to the model under the reference
 evaluation through the reference's path rewrites (:334-346, :588-598); after training, --do_eval runs the TEST-set
 evaluation of :567-694 and writes `test_results_fcmf.txt` + `test_predictions_formatted.txt` in the reference's format.
 Batches reach the GPU through `device_prefetch.DevicePrefetcher` (pinned host memory, copy stream, one batch ahead).
+Process set-up, the checkpoint code, the extractors and the loop of one epoch are `train_harness.py`'s, shared with
+run_pretraining_fcmf.py; this file keeps the parser, the model and data, the 4 parameter groups, the loss and the evaluation.
 Extra flags (not in the reference): --bf16, --synthetic_steps N (seeded synthetic batches with
 precomputed features: no dataset / tokenizer / torchvision needed), --precomputed_features.
 The host-side batch producer (vimacsa_dataset.MACSADataset, image decoding, ResNet-152 feature
@@ -25,7 +27,6 @@ user's `vimacsa_dataset` module and torchvision exactly as the reference does.
 import argparse
 import logging
 import os
-import random
 import sys
 
 import numpy as np
@@ -40,6 +41,8 @@ from fcmf_framework.dp import GradArena, GradReducer  # noqa: E402
 from fcmf_framework.fcmf_multimodal import FCMF  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
+from train_harness import (build_extractors, init_run, load_resnets, make_features, save_extractors, save_model,  # noqa: E402
+                           split_decay, train_epoch)
 
 
 POLARITY_MAP = {0: 'None', 1: 'Negative', 2: 'Neutral', 3: 'Positive'}      # reference :28
@@ -49,42 +52,6 @@ def macro_f1(y_true, y_pred):
     from sklearn.metrics import precision_recall_fscore_support
     p, r, f, _ = precision_recall_fscore_support(y_true, y_pred, average='macro', zero_division=0)
     return p, r, f
-
-
-def save_model(path, model, optimizer, scheduler, epoch, best_score=0.0, scaler=None):
-    """checkpoint dict of the reference (run_multimodal_fcmf.py:40-58)"""
-    m = model.module if hasattr(model, 'module') else model
-    ck = {'epoch': epoch, 'best_score': best_score, 'model_state_dict': m.state_dict(),
-          'optimizer_state_dict': optimizer.state_dict(), 'scheduler_state_dict': scheduler.state_dict()}
-    if scaler is not None:
-        ck['scaler_state_dict'] = scaler.state_dict()
-    torch.save(ck, path)
-
-
-def companion_path(path, old, new):
-    """the reference's checkpoint-path rewrite (`checkpoint_path.replace("fcmf_model", "resimg_model")`, :334-335;
-    `best_path.replace("fcmf", "resimg")`, :588,594) applied to the FILE NAME only -- a directory called e.g.
-    `runs/fcmf/` must not be rewritten with it"""
-    d, f = os.path.split(path)
-    return os.path.join(d, f.replace(old, new))
-
-
-def load_resnets(path, resnet_img, resnet_roi, device, logger=None, old="fcmf_model", strict=True):
-    """restore the two extractors saved beside the model checkpoint `path` (reference :334-346 / :588-598)"""
-    loaded = []
-    for net, tag in ((resnet_img, "resimg"), (resnet_roi, "resroi")):
-        if net is None:
-            continue
-        q = companion_path(path, old, old.replace("fcmf", tag))
-        if os.path.exists(q):
-            ck = torch.load(q, map_location=device, weights_only=True)
-            net.load_state_dict(ck['model_state_dict'], strict=strict)
-            loaded.append(q)
-            if logger is not None:
-                logger.info("    Loading ResNet %s from: %s", tag, q)
-    if loaded:
-        ops.shadows.clear()                  # cached bf16 weight matrices of the trunk are stale
-    return loaded
 
 
 def build_parser():
@@ -134,20 +101,16 @@ def build_parser():
 
 
 def param_groups(model, args):
-    """4 groups by substring match on the parameter names (reference :249-287)"""
-    no_decay = ['bias', 'LayerNorm.bias', 'LayerNorm.weight']
-    head_names = ['classifier', 'text_pooler']
+    """4 groups by substring match on the parameter names (reference :249-287): encoder / head x decay / no decay"""
     enc, head = [], []
     for n, p in model.named_parameters():
-        if not p.requires_grad:
-            continue
-        (head if any(nd in n for nd in head_names) else enc).append((n, p))
-    return [
-        {'params': [p for n, p in enc if not any(nd in n for nd in no_decay)], 'weight_decay': 0.01, 'lr': args.encoder_learning_rate},
-        {'params': [p for n, p in enc if any(nd in n for nd in no_decay)], 'weight_decay': 0.0, 'lr': args.encoder_learning_rate},
-        {'params': [p for n, p in head if not any(nd in n for nd in no_decay)], 'weight_decay': 0.01, 'lr': args.classifier_head_learning_rate},
-        {'params': [p for n, p in head if any(nd in n for nd in no_decay)], 'weight_decay': 0.0, 'lr': args.classifier_head_learning_rate},
-    ]
+        if p.requires_grad:
+            (head if any(h in n for h in ('classifier', 'text_pooler')) else enc).append((n, p))
+    groups = []
+    for named, lr in ((enc, args.encoder_learning_rate), (head, args.classifier_head_learning_rate)):
+        decay, exempt = split_decay(named)
+        groups += [{'params': decay, 'weight_decay': 0.01, 'lr': lr}, {'params': exempt, 'weight_decay': 0.0, 'lr': lr}]
+    return groups
 
 
 class SyntheticBatches:
@@ -169,10 +132,7 @@ class SyntheticBatches:
                                   num_aspects=self.na, seed=self.seed + i)
             vis, roi = b["visual_embeds_att"], b["roi_embeds_att"]
             if self.pixels:          # the reference's pixel layout: float32 images, float64 ROI crops (vimacsa_dataset.py:175-199)
-                n = self.batch * self.ni
-                vis = synth.synth_crops(n, self.pixels, seed=self.seed + i).view(self.batch, self.ni, 3, self.pixels, self.pixels)
-                roi = synth.synth_crops(n * self.nr, self.pixels, seed=self.seed + i + 7919).view(
-                    self.batch, self.ni, self.nr, 3, self.pixels, self.pixels).double()
+                vis, roi = synth.synth_pixel_batch(self.batch, self.ni, self.nr, self.pixels, self.seed + i, torch.float64)
             texts = [f"synthetic review {self.seed + i}:{j}" for j in range(self.batch)]
             yield (vis, roi, b["roi_coors"], b["input_ids"], b["token_type_ids"],
                    b["attention_mask"], b["added_attention_mask"], b["labels"], texts)
@@ -180,31 +140,13 @@ class SyntheticBatches:
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if args.no_cuda or not torch.cuda.is_available():
-        raise SystemExit("run_multimodal_fcmf.py (MI355X build) has no CPU path: a ROCm GPU is required")
-    if args.ddp:
-        rank, local_rank, world = int(os.environ['RANK']), int(os.environ['LOCAL_RANK']), int(os.environ['WORLD_SIZE'])
-    else:
-        rank, local_rank, world = 0, 0, 1
-    torch.cuda.set_device(local_rank)
-    device = torch.device('cuda', local_rank)
-    master = rank == 0
     if args.gradient_accumulation_steps < 1:
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
+    fmt = logging.Formatter('%(asctime)s - %(levelname)s - %(name)s - %(message)s', datefmt='%m/%d/%Y %H:%M:%S')
+    rank, _, world, device, master, logger = init_run(args, "fcmf", "training_fcmf.log", formatter=fmt, script="run_multimodal_fcmf.py")
     args.train_batch_size = int(args.train_batch_size / args.gradient_accumulation_steps)
-    random.seed(args.seed); np.random.seed(args.seed); torch.manual_seed(args.seed); ops.manual_seed(args.seed + rank)
-    if world > 1:
-        torch.distributed.init_process_group(backend='nccl', device_id=device)   # RCCL over xGMI
-
-    logger = logging.getLogger("fcmf")
     if master:
-        os.makedirs(args.output_dir, exist_ok=True)
-        logger.setLevel(logging.INFO)
-        fmt = logging.Formatter('%(asctime)s - %(levelname)s - %(name)s - %(message)s', datefmt='%m/%d/%Y %H:%M:%S')
-        for h in (logging.FileHandler(f'{args.output_dir}/training_fcmf.log'), logging.StreamHandler()):
-            h.setFormatter(fmt); logger.addHandler(h)
         logger.info("device: %s n_gpu: %d, distributed training: %s, bf16: %s", device, world, bool(args.ddp), args.bf16 or args.fp16)
-    ops.set_compute_dtype(torch.bfloat16 if (args.bf16 or args.fp16) else torch.float32)
 
     ASPECT = args.list_aspect
     model = FCMF(pretrained_path=args.pretrained_hf_model, num_labels=args.num_polarity, num_imgs=args.num_imgs,
@@ -214,17 +156,13 @@ def main(argv=None):
     resnet_img = resnet_roi = None
     if args.synthetic_steps > 0:
         cfgd = dict(vocab_size=cfg.vocab_size, pad_token_id=cfg.pad_token_id)
-        train_loader = SyntheticBatches(cfgd, args.synthetic_steps, args.train_batch_size,
-                                        min(args.max_seq_length, 128, cfg.max_position_embeddings - 2),
-                                        args.num_imgs, args.num_rois, len(ASPECT), args.seed + 1000 * rank,
-                                        pixels=args.synthetic_pixels)
+        S = min(args.max_seq_length, 128, cfg.max_position_embeddings - 2)
+        synthetic = lambda steps, batch, seed: SyntheticBatches(cfgd, steps, batch, S, args.num_imgs, args.num_rois, len(ASPECT),
+                                                                seed, pixels=args.synthetic_pixels)
+        train_loader = synthetic(args.synthetic_steps, args.train_batch_size, args.seed + 1000 * rank)
         if args.do_eval:
-            dev_loader = SyntheticBatches(cfgd, max(1, args.synthetic_steps // 2), args.eval_batch_size,
-                                          min(args.max_seq_length, 128, cfg.max_position_embeddings - 2),
-                                          args.num_imgs, args.num_rois, len(ASPECT), args.seed + 77, pixels=args.synthetic_pixels)
-            test_loader = SyntheticBatches(cfgd, max(1, args.synthetic_steps // 2), args.eval_batch_size,
-                                           min(args.max_seq_length, 128, cfg.max_position_embeddings - 2),
-                                           args.num_imgs, args.num_rois, len(ASPECT), args.seed + 99, pixels=args.synthetic_pixels)
+            dev_loader = synthetic(max(1, args.synthetic_steps // 2), args.eval_batch_size, args.seed + 77)
+            test_loader = synthetic(max(1, args.synthetic_steps // 2), args.eval_batch_size, args.seed + 99)
     elif args.do_train or args.do_eval:
         # real data: the reference's host-side producer (tokenizer, pandas, MACSADataset, torchvision ResNet-152)
         from transformers import AutoTokenizer
@@ -255,7 +193,6 @@ def main(argv=None):
         # torchvision checkpoint (--resnet_checkpoint), else torchvision's IMAGENET1K_V2 if torchvision is importable
         # and has them cached, else random initialisation (logged): nothing is ever downloaded.
         from fcmf_framework.resnet import resnet152
-        from fcmf_framework.resnet_utils import myResNetImg, myResNetRoI
 
         def trunk():
             if args.resnet_checkpoint:
@@ -267,8 +204,7 @@ def main(argv=None):
                 if master:
                     logger.info("ResNet-152: no checkpoint given and torchvision weights unavailable (%s): random init", type(e).__name__)
                 return resnet152()
-        resnet_img = myResNetImg(trunk().to(device), args.fine_tune_cnn, device)
-        resnet_roi = myResNetRoI(trunk().to(device), args.fine_tune_cnn, device)
+        resnet_img, resnet_roi = build_extractors(trunk, args.fine_tune_cnn, device)
 
     model = model.to(device)
     if args.freeze_encoder:
@@ -300,13 +236,11 @@ def main(argv=None):
         model.load_state_dict({k: v for k, v in sd.items() if k.startswith('encoder.')}, strict=False)   # reference :385-391
         ops.shadows.clear()
 
-    def features(t_img, roi_img):
-        """pixels -> ResNet-152 features (reference :449-460) unless the batch already holds features: the reference's
-        num_imgs + num_imgs * num_rois trunk calls as two batched passes with per-call BatchNorm statistics"""
-        if resnet_img is None:
-            return t_img, roi_img
-        from fcmf_framework.resnet_utils import extract_features
-        return extract_features(resnet_img, resnet_roi, t_img, roi_img)
+    features = make_features(resnet_img, resnet_roi)
+
+    def loss_fn(batch):
+        logits, labels, _ = forward_batch(model, batch, features)
+        return model.loss_aspects(logits, labels)                     # sum over aspects of the batch-mean CE
 
     if args.do_train:
         for epoch in range(start_epoch, int(args.num_train_epochs)):
@@ -315,27 +249,10 @@ def main(argv=None):
             model.train()
             if resnet_img is not None:
                 resnet_img.train(); resnet_roi.train()                # reference :431 (BatchNorm in batch-statistics mode)
-            arena.zero()
-            for step, batch in enumerate(DevicePrefetcher(train_loader, device, float32_fields=(1,))):     # (1 = the float64 ROI crops) next batch: pinned, on the copy stream
-                t_img, roi_img, roi_coors, ids, tts, ams, added, labels, _ = batch
-                vis, roi = features(t_img, roi_img)
-                logits = model.forward_aspects(input_ids=ids, token_type_ids=tts, attention_mask=ams, added_attention_mask=added,
-                                               visual_embeds_att=vis, roi_embeds_att=roi, roi_coors=roi_coors)
-                loss = model.loss_aspects(logits, labels)            # sum over aspects of the batch-mean CE
-                if args.gradient_accumulation_steps > 1:
-                    loss = loss / args.gradient_accumulation_steps
-                boundary = (step + 1) % args.gradient_accumulation_steps == 0
-                if reducer is not None:
-                    reducer.enabled = boundary                        # all-reduce only the accumulated gradients
-                loss.backward()
-                if boundary:
-                    if reducer is not None:
-                        reducer.finish()
-                    optimizer.step(max_grad_norm=1.0)                 # clip_grad_norm_(1.0) fused into AdamW
-                    scheduler.step()
-                    arena.zero()
-                if master and step % 10 == 0:
-                    logger.info("epoch %d step %d loss %.4f", epoch, step, loss.item() * args.gradient_accumulation_steps)
+            log = lambda step, loss: logger.info("epoch %d step %d loss %.4f", epoch, step, loss)
+            # next batch: pinned, on the copy stream (field 1 = the float64 ROI crops)
+            train_epoch(DevicePrefetcher(train_loader, device, float32_fields=(1,)), loss_fn, arena=arena, reducer=reducer,
+                        optimizer=optimizer, scheduler=scheduler, accum=args.gradient_accumulation_steps, log=log if master else None)
             if master:
                 logger.info("--> Epoch %d Completed. Encoder LR %.2e Head LR %.2e", epoch,
                             optimizer.param_groups[0]['lr'], optimizer.param_groups[2]['lr'])
@@ -351,9 +268,7 @@ def main(argv=None):
                 max_f1 = max(max_f1, f1)
                 for tag in tags:                                      # reference :555-563: the model and BOTH extractors
                     save_model(f'{args.output_dir}/seed_{args.seed}_fcmf_model_{tag}.pth', model, optimizer, scheduler, epoch, max_f1)
-                    if resnet_img is not None:
-                        save_model(f'{args.output_dir}/seed_{args.seed}_resimg_model_{tag}.pth', resnet_img, optimizer, scheduler, epoch)
-                        save_model(f'{args.output_dir}/seed_{args.seed}_resroi_model_{tag}.pth', resnet_roi, optimizer, scheduler, epoch)
+                    save_extractors(args.output_dir, args.seed, tag, resnet_img, resnet_roi, optimizer, scheduler, epoch)
     # ---- 7. TEST EVALUATION (reference :567-694) ---------------------------------------------------------------------
     if args.do_eval and master and test_loader is not None:
         logger.info("===================== STARTING TEST EVALUATION =====================")
@@ -375,21 +290,31 @@ def main(argv=None):
         torch.distributed.destroy_process_group()
 
 
+def forward_batch(model, batch, features):
+    """one batch of the reference's 9-tuple (vimacsa_dataset.py:202) -> (logits [B, aspects, polarities], labels, texts)"""
+    t_img, roi_img, roi_coors, ids, tts, ams, added, labels, texts = batch
+    vis, roi = features(t_img, roi_img)
+    logits = model.forward_aspects(input_ids=ids, token_type_ids=tts, attention_mask=ams, added_attention_mask=added,
+                                   visual_embeds_att=vis, roi_embeds_att=roi, roi_coors=roi_coors)
+    return logits, labels, texts
+
+
 @torch.no_grad()
+def predict(model, loader, device, features):
+    """eval-mode forward + argmax over a loader: (predictions [B, aspects], labels [B, aspects], texts) per batch, as numpy"""
+    model.eval()
+    for batch in DevicePrefetcher(loader, device, float32_fields=(1,)):
+        logits, labels, texts = forward_batch(model, batch, features)
+        yield logits.argmax(-1).cpu().numpy(), labels.cpu().numpy(), texts
+
+
 def test_evaluate(model, loader, device, features, aspects, output_dir, logger):
     """test-set pass of the reference (:600-694): per-aspect precision / recall / macro-F1 into `test_results_fcmf.txt`, and
     one block per review with the predicted and gold polarity of every aspect into `test_predictions_formatted.txt`"""
-    model.eval()
     true = {a: [] for a in aspects}
     pred = {a: [] for a in aspects}
     formatted = []
-    for batch in DevicePrefetcher(loader, device, float32_fields=(1,)):
-        t_img, roi_img, roi_coors, ids, tts, ams, added, labels, texts = batch
-        vis, roi = features(t_img, roi_img)
-        logits = model.forward_aspects(input_ids=ids, token_type_ids=tts, attention_mask=ams, added_attention_mask=added,
-                                       visual_embeds_att=vis, roi_embeds_att=roi, roi_coors=roi_coors)
-        p = logits.argmax(-1).cpu().numpy()
-        y = labels.cpu().numpy()
+    for p, y, texts in predict(model, loader, device, features):
         logs = [{"text": t, "aspects": {}} for t in (texts if texts is not None else [""] * len(p))]
         for i, a in enumerate(aspects):
             true[a].append(y[:, i]); pred[a].append(p[:, i])
@@ -425,19 +350,12 @@ def test_evaluate(model, loader, device, features, aspects, output_dir, logger):
     return avg_f1
 
 
-@torch.no_grad()
 def evaluate(model, loader, device, features, num_aspects, logger):
     """dev-set macro-F1 averaged over aspects (reference :500-552)"""
-    model.eval()
     true, pred = [[] for _ in range(num_aspects)], [[] for _ in range(num_aspects)]
-    for batch in DevicePrefetcher(loader, device, float32_fields=(1,)):
-        t_img, roi_img, roi_coors, ids, tts, ams, added, labels, _ = batch
-        vis, roi = features(t_img, roi_img)
-        logits = model.forward_aspects(input_ids=ids, token_type_ids=tts, attention_mask=ams, added_attention_mask=added,
-                                       visual_embeds_att=vis, roi_embeds_att=roi, roi_coors=roi_coors)
-        p = logits.argmax(-1).cpu().numpy()
+    for p, y, _ in predict(model, loader, device, features):
         for a in range(num_aspects):
-            true[a] += labels[:, a].cpu().tolist()
+            true[a] += y[:, a].tolist()
             pred[a] += p[:, a].tolist()
     f1s = [macro_f1(true[a], pred[a])[2] for a in range(num_aspects)]
     logger.info("Dev macro-F1 per aspect: %s  mean %.4f", ["%.4f" % f for f in f1s], float(np.mean(f1s)))

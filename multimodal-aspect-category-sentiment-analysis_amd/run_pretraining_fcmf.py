@@ -13,16 +13,15 @@ encoder's word embeddings while `decoder.dense.weight` stays tied to them.
 reference's `iaog_model` -> `resimg_model` / `resroi_model` path rewrite (:244-255).
 Extra flags: --bf16, --synthetic_steps N (seeded synthetic batches, precomputed features), --synthetic_pixels SIZE
 (those batches carry pixel crops and the HIP ResNet-152 trunks run inside the step).
+Process set-up, the checkpoint code, the extractors and the loop of one epoch are `train_harness.py`'s, shared with
+run_multimodal_fcmf.py; this file keeps the parser, the model and data, the 2 parameter groups and the loss.
 With real data the driver imports the user's `iaog_dataset.IAOGDataset` (host-side producer,
 SURVEY.md section 8(f) "next") and torchvision, as the reference does.
 """
 import argparse
-import logging
 import os
-import random
 import sys
 
-import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -34,12 +33,8 @@ from fcmf_framework.dp import GradArena, GradReducer  # noqa: E402
 from fcmf_framework.fcmf_pretraining import FCMFSeq2Seq  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
-
-
-def save_model(path, model, optimizer, scheduler, epoch, best_score=0.0):
-    m = model.module if hasattr(model, 'module') else model
-    torch.save({'epoch': epoch, 'best_score': best_score, 'model_state_dict': m.state_dict(),
-                'optimizer_state_dict': optimizer.state_dict(), 'scheduler_state_dict': scheduler.state_dict()}, path)
+from train_harness import (build_extractors, init_run, load_resnets, make_features, save_extractors, save_model,  # noqa: E402
+                           split_decay, train_epoch)
 
 
 def build_parser():
@@ -93,25 +88,7 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if args.no_cuda or not torch.cuda.is_available():
-        raise SystemExit("run_pretraining_fcmf.py (MI355X build) has no CPU path: a ROCm GPU is required")
-    if args.ddp:
-        rank, local_rank, world = int(os.environ['RANK']), int(os.environ['LOCAL_RANK']), int(os.environ['WORLD_SIZE'])
-    else:
-        rank, local_rank, world = 0, 0, 1
-    torch.cuda.set_device(local_rank)
-    device = torch.device('cuda', local_rank)
-    master = rank == 0
-    random.seed(args.seed); np.random.seed(args.seed); torch.manual_seed(args.seed); ops.manual_seed(args.seed + rank)
-    if world > 1:
-        torch.distributed.init_process_group(backend='nccl', device_id=device)
-    logger = logging.getLogger("iaog")
-    if master:
-        os.makedirs(args.output_dir, exist_ok=True)
-        logger.setLevel(logging.INFO)
-        for h in (logging.FileHandler(f'{args.output_dir}/pretraining_iaog.log'), logging.StreamHandler()):
-            logger.addHandler(h)
-    ops.set_compute_dtype(torch.bfloat16 if (args.bf16 or args.fp16) else torch.float32)
+    rank, _, world, device, master, logger = init_run(args, "iaog", "pretraining_iaog.log", script="run_pretraining_fcmf.py")
 
     tokenizer = None
     if args.synthetic_steps <= 0:
@@ -130,19 +107,17 @@ def main(argv=None):
     r_img = r_roi = None
     if (args.synthetic_steps > 0 and args.synthetic_pixels > 0) or (args.synthetic_steps <= 0 and not args.feature_cache_dir):
         from fcmf_framework.resnet import resnet152
-        from fcmf_framework.resnet_utils import myResNetImg, myResNetRoI
         sd = torch.load(args.resnet_checkpoint, map_location='cpu', weights_only=True) if args.resnet_checkpoint else None
-        r_img = myResNetImg(resnet152(weights=sd).to(device), args.fine_tune_cnn, device).train()
-        r_roi = myResNetRoI(resnet152(weights=sd).to(device), args.fine_tune_cnn, device).train()
+        r_img, r_roi = build_extractors(lambda: resnet152(weights=sd), args.fine_tune_cnn, device)
+        r_img.train(); r_roi.train()
 
-    no_decay = ['bias', 'LayerNorm.bias', 'LayerNorm.weight']
     named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
     cnn_params = []
     if args.fine_tune_cnn and r_img is not None:                     # reference :203-207 (names: 'resnet.conv1.weight', ...)
         cnn_params = list(r_img.named_parameters()) + list(r_roi.named_parameters())
         named += cnn_params
-    groups = [{'params': [p for n, p in named if not any(nd in n for nd in no_decay)], 'weight_decay': 1e-5},
-              {'params': [p for n, p in named if any(nd in n for nd in no_decay)], 'weight_decay': 0.0}]
+    decay, exempt = split_decay(named)
+    groups = [{'params': decay, 'weight_decay': 1e-5}, {'params': exempt, 'weight_decay': 0.0}]
     optimizer = FusedAdamW(groups, lr=args.learning_rate, eps=args.adam_epsilon)
 
     if args.synthetic_steps > 0:
@@ -159,10 +134,9 @@ def main(argv=None):
                 lab = torch.roll(dec, -1, dims=1)
                 lab[:, -1] = -100                                                           # iaog_dataset.py:93-96
                 if args.synthetic_pixels:             # pixel crops in the IAOG dataset's float32 layout (iaog_dataset.py:148)
-                    S_, n_ = args.synthetic_pixels, args.train_batch_size * args.num_imgs
-                    b["visual_embeds_att"] = synth.synth_crops(n_, S_, seed=args.seed + i).view(args.train_batch_size, args.num_imgs, 3, S_, S_)
-                    b["roi_embeds_att"] = synth.synth_crops(n_ * args.num_rois, S_, seed=args.seed + i + 7919).view(
-                        args.train_batch_size, args.num_imgs, args.num_rois, 3, S_, S_)
+                    # (this seed lacks the `1000 * rank` term of the batch seed above: every rank draws the same pixels)
+                    b["visual_embeds_att"], b["roi_embeds_att"] = synth.synth_pixel_batch(
+                        args.train_batch_size, args.num_imgs, args.num_rois, args.synthetic_pixels, args.seed + i, torch.float32)
                 yield (b["visual_embeds_att"], b["roi_embeds_att"], b["roi_coors"], b["input_ids"][:, 0],
                        b["token_type_ids"][:, 0], b["attention_mask"][:, 0], b["added_attention_mask"][:, 0], dec, lab)
         steps_per_epoch = args.synthetic_steps
@@ -215,57 +189,33 @@ def main(argv=None):
     if args.resume_from_checkpoint and os.path.isfile(args.resume_from_checkpoint):
         ck = torch.load(args.resume_from_checkpoint, map_location=device, weights_only=True)
         model.load_state_dict(ck['model_state_dict'])
-        for net, tag in ((r_img, "resimg_model"), (r_roi, "resroi_model")):           # reference :244-255
-            d, f = os.path.split(args.resume_from_checkpoint)
-            q = os.path.join(d, f.replace("iaog_model", tag))
-            if net is not None and os.path.exists(q):
-                if master:
-                    logger.info("    Loading ResNet: %s", q)
-                net.load_state_dict(torch.load(q, map_location=device, weights_only=True)['model_state_dict'])
         optimizer.load_state_dict(ck['optimizer_state_dict'])
         scheduler.load_state_dict(ck['scheduler_state_dict'])
         start_epoch = ck['epoch'] + 1
         ops.shadows.clear()
+        load_resnets(args.resume_from_checkpoint, r_img, r_roi, device, logger if master else None, old="iaog_model")   # reference :244-255
 
-    def features(vis, roi):
-        """pixels -> ResNet-152 features (reference :305-317) unless the batch already holds features"""
-        if r_img is None:
-            return vis, roi
-        from fcmf_framework.resnet_utils import extract_features
-        return extract_features(r_img, r_roi, vis, roi.float())
+    features = make_features(r_img, r_roi)
+
+    def loss_fn(batch):
+        vis, roi, coors, enc_X, tt, am, added, dec_X, labels = batch
+        vis, roi = features(vis, roi)
+        # model(...) -> logits -> CrossEntropyLoss(ignore_index=-100) (reference :309-324) as one fused call
+        return model.forward_loss(enc_X, dec_X, labels, vis, roi, coors, tt, am, added, ignore_index=-100)
 
     if args.do_train:
         for epoch in range(start_epoch, int(args.num_train_epochs)):
             model.train()
             if r_img is not None:
                 r_img.train(); r_roi.train()
-            arena.zero()
-            for step, batch in enumerate(DevicePrefetcher(make_loader(), device)):
-                vis, roi, coors, enc_X, tt, am, added, dec_X, labels = batch
-                vis, roi = features(vis, roi)
-                # model(...) -> logits -> CrossEntropyLoss(ignore_index=-100) (reference :309-324) as one fused call
-                loss = model.forward_loss(enc_X, dec_X, labels, vis, roi, coors, tt, am, added, ignore_index=-100)
-                if args.gradient_accumulation_steps > 1:
-                    loss = loss / args.gradient_accumulation_steps
-                boundary = (step + 1) % args.gradient_accumulation_steps == 0
-                if reducer is not None:
-                    reducer.enabled = boundary
-                loss.backward()
-                if boundary:
-                    if reducer is not None:
-                        reducer.finish()
-                    optimizer.step(max_grad_norm=1.0)
-                    scheduler.step()
-                    arena.zero()
-                if master and step % 10 == 0:
-                    logger.info("epoch %d step %d loss %.4f", epoch, step, loss.item() * args.gradient_accumulation_steps)
+            log = lambda step, loss: logger.info("epoch %d step %d loss %.4f", epoch, step, loss)
+            train_epoch(DevicePrefetcher(make_loader(), device), loss_fn, arena=arena, reducer=reducer, optimizer=optimizer,
+                        scheduler=scheduler, accum=args.gradient_accumulation_steps, log=log if master else None)
             if world > 1:
                 torch.distributed.barrier()
             if master:
                 save_model(f'{args.output_dir}/seed_{args.seed}_iaog_model_last.pth', model, optimizer, scheduler, epoch)
-                if r_img is not None:                                                   # reference :458-459
-                    save_model(f'{args.output_dir}/seed_{args.seed}_resimg_model_last.pth', r_img, optimizer, scheduler, epoch)
-                    save_model(f'{args.output_dir}/seed_{args.seed}_resroi_model_last.pth', r_roi, optimizer, scheduler, epoch)
+                save_extractors(args.output_dir, args.seed, 'last', r_img, r_roi, optimizer, scheduler, epoch)   # reference :458-459
     arena.deactivate()
     if world > 1:
         torch.distributed.destroy_process_group()

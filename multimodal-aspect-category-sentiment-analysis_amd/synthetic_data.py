@@ -239,3 +239,12 @@ def synth_crops(n, size=224, seed=0):
     """[n, 3, size, size] float32 'normalised image' crops (what image_process.py hands the trunk)"""
     rng = np.random.Generator(np.random.PCG64(seed))
     return torch.from_numpy(rng.standard_normal((n, 3, size, size), dtype=np.float32))
+
+
+def synth_pixel_batch(B, num_imgs, num_rois, size, seed, roi_dtype):
+    """pixel crops of one synthetic batch in the datasets' layouts (vimacsa_dataset.py:175-199 float64 ROI crops,
+    iaog_dataset.py:148 float32): (images [B, num_imgs, 3, size, size] float32, ROI crops [B, num_imgs, num_rois, 3, size, size]
+    `roi_dtype`)"""
+    vis = synth_crops(B * num_imgs, size, seed=seed).view(B, num_imgs, 3, size, size)
+    roi = synth_crops(B * num_imgs * num_rois, size, seed=seed + 7919).view(B, num_imgs, num_rois, 3, size, size)
+    return vis, roi.to(roi_dtype)

@@ -1,0 +1,124 @@
+"""What run_multimodal_fcmf.py and run_pretraining_fcmf.py share: process / logger set-up, the checkpoint dictionary, the
+ResNet-152 extractors with their checkpoints beside the model's, the weight-decay split and the loop of one epoch.  Each
+driver keeps its parser, model, data, parameter groups, loss call and (fine-tuning) evaluation.  File:line citations are
+into the reference's two drivers."""
+import logging
+import os
+import random
+
+import numpy as np
+import torch
+
+from fcmf_framework import ops
+from fcmf_framework.resnet_utils import extract_features, myResNetImg, myResNetRoI
+
+NO_DECAY = ['bias', 'LayerNorm.bias', 'LayerNorm.weight']      # run_multimodal_fcmf.py:249, run_pretraining_fcmf.py:203
+
+
+def split_decay(named):
+    """(name, parameter) pairs -> (parameters that get weight decay, parameters that do not), each in the given order"""
+    decay, exempt = [], []
+    for n, p in named:
+        (exempt if any(nd in n for nd in NO_DECAY) else decay).append(p)
+    return decay, exempt
+
+
+def init_run(args, logger_name, log_file, formatter=None, script="this driver"):
+    """device, seeds, process group, logger (handlers on the master only) and compute dtype of one driver process, under torchrun's
+    RANK / LOCAL_RANK / WORLD_SIZE with --ddp (run_multimodal_fcmf.py:126-169, run_pretraining_fcmf.py:86-104)
+    -> rank, local_rank, world, device, master, logger"""
+    if args.no_cuda or not torch.cuda.is_available():
+        raise SystemExit(f"{script} (MI355X build) has no CPU path: a ROCm GPU is required")
+    rank, local_rank, world = [int(os.environ[k]) for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE')] if args.ddp else (0, 0, 1)
+    torch.cuda.set_device(local_rank)
+    device = torch.device('cuda', local_rank)
+    random.seed(args.seed); np.random.seed(args.seed); torch.manual_seed(args.seed); ops.manual_seed(args.seed + rank)
+    if world > 1:
+        torch.distributed.init_process_group(backend='nccl', device_id=device)   # RCCL over xGMI
+    logger = logging.getLogger(logger_name)
+    if rank == 0:
+        os.makedirs(args.output_dir, exist_ok=True)
+        logger.setLevel(logging.INFO)
+        for h in (logging.FileHandler(f'{args.output_dir}/{log_file}'), logging.StreamHandler()):
+            if formatter is not None:
+                h.setFormatter(formatter)
+            logger.addHandler(h)
+    ops.set_compute_dtype(torch.bfloat16 if (args.bf16 or args.fp16) else torch.float32)
+    return rank, local_rank, world, device, rank == 0, logger
+
+
+def save_model(path, model, optimizer, scheduler, epoch, best_score=0.0):
+    """checkpoint dict of the reference (run_multimodal_fcmf.py:40-58, run_pretraining_fcmf.py:27-42)"""
+    m = model.module if hasattr(model, 'module') else model
+    torch.save({'epoch': epoch, 'best_score': best_score, 'model_state_dict': m.state_dict(),
+                'optimizer_state_dict': optimizer.state_dict(), 'scheduler_state_dict': scheduler.state_dict()}, path)
+
+
+def companion_path(path, old, new):
+    """the reference's checkpoint-path rewrite (run_multimodal_fcmf.py: `checkpoint_path.replace("fcmf_model", "resimg_model")`,
+    :334-335; `best_path.replace("fcmf", "resimg")`, :588,594) applied to the FILE NAME only -- a directory called e.g.
+    `runs/fcmf/` must not be rewritten with it"""
+    d, f = os.path.split(path)
+    return os.path.join(d, f.replace(old, new))
+
+
+def load_resnets(path, resnet_img, resnet_roi, device, logger=None, old="fcmf_model", strict=True):
+    """restore the two extractors saved beside the model checkpoint `path` (run_multimodal_fcmf.py:334-346 / :588-598,
+    run_pretraining_fcmf.py:244-255): `old` is the part of the file name that `resimg...` / `resroi...` replaces"""
+    loaded = []
+    for net, tag in ((resnet_img, "resimg"), (resnet_roi, "resroi")):
+        q = companion_path(path, old, old.replace("fcmf", tag).replace("iaog", tag))
+        if net is not None and os.path.exists(q):
+            ck = torch.load(q, map_location=device, weights_only=True)
+            net.load_state_dict(ck['model_state_dict'], strict=strict)
+            loaded.append(q)
+            if logger is not None:
+                logger.info("    Loading ResNet %s from: %s", tag, q)
+    if loaded:
+        ops.shadows.clear()                  # cached bf16 weight matrices of the trunk are stale
+    return loaded
+
+
+def save_extractors(output_dir, seed, tag, resnet_img, resnet_roi, optimizer, scheduler, epoch):
+    """the extractors (if any) beside the model checkpoint (run_multimodal_fcmf.py:557-563, run_pretraining_fcmf.py:457-459)"""
+    for net, name in ((resnet_img, "resimg"), (resnet_roi, "resroi")):
+        if net is not None:
+            save_model(f'{output_dir}/seed_{seed}_{name}_model_{tag}.pth', net, optimizer, scheduler, epoch)
+
+
+def build_extractors(make_trunk, fine_tune, device):
+    """the two feature extractors, each on its own `make_trunk()` (run_multimodal_fcmf.py:224-227, run_pretraining_fcmf.py:191-194)"""
+    return myResNetImg(make_trunk().to(device), fine_tune, device), myResNetRoI(make_trunk().to(device), fine_tune, device)
+
+
+def make_features(resnet_img, resnet_roi):
+    """-> features(images, roi_crops): pixels -> ResNet-152 features, the reference's num_imgs + num_imgs * num_rois trunk calls
+    (run_multimodal_fcmf.py:445-460, run_pretraining_fcmf.py:299-317) as two batched passes; a batch of features passes through"""
+    def features(t_img, roi_img):
+        if resnet_img is None:
+            return t_img, roi_img
+        return extract_features(resnet_img, resnet_roi, t_img, roi_img.float())
+    return features
+
+
+def train_epoch(batches, loss_fn, *, arena, reducer, optimizer, scheduler, accum, log=None):
+    """one epoch (run_multimodal_fcmf.py:427-489, run_pretraining_fcmf.py:284-337): `loss_fn(batch)` accumulates over `accum`
+    steps, then the gradients are reduced across ranks (`reducer`, None on one rank), clipped to norm 1.0 and applied; a trailing
+    partial group gets no optimizer step.  `log(step, loss)`, if given, sees the undivided loss of every 10th step."""
+    arena.zero()
+    for step, batch in enumerate(batches):
+        loss = loss_fn(batch)
+        if accum > 1:
+            loss = loss / accum
+        boundary = (step + 1) % accum == 0
+        if reducer is not None:
+            reducer.enabled = boundary                        # all-reduce only the accumulated gradients
+        loss.backward()
+        if boundary:
+            if reducer is not None:
+                reducer.finish()
+            optimizer.step(max_grad_norm=1.0)                 # clip_grad_norm_(1.0) fused into AdamW
+            scheduler.step()
+            arena.zero()
+        if log is not None and step % 10 == 0:
+            log(step, loss.item() * accum)
