@@ -199,6 +199,28 @@ int fcmf_attn_mfma_probs(const void* q, const void* k, const float* mask, float*
                          float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * BERTScore greedy matching (Zhang et al. 2020 with idf = False, rescale_with_baseline = False: what the reference's
+ * `bert_score.score(preds, refs, ...)` computes from the scorer model's token embeddings, run_pretraining_fcmf.py:434,575).
+ * One launch scores N (candidate, reference) pairs:
+ *   s[i][j] = <c_i, r_j> / (|c_i| |r_j|)                      over the valid rows i < cand_len[n], j < ref_len[n] only
+ *   P = sum_i wc[i] max_j s[i][j] / sum_i wc[i]     R = sum_j wr[j] max_i s[i][j] / sum_j wr[j]     F = 2 P R / (P + R)
+ *   cand [N, Lc_max, H], ref [N, Lr_max, H] in `dtype` (FCMF_F32 / FCMF_BF16): row i of pair n at cand + n*sc + i*ldc (elements);
+ *   cand_len, ref_len int32 [N] in DEVICE memory (the host cannot see them: the kernel clamps each to [0, L*_max]); rows at or
+ *   beyond a pair's length are never read and may hold anything;
+ *   cand_w, ref_w float32 [N, L*_max] dense per-token weights, or NULL = 1 for every valid token.  A token of weight 0 (<s>, </s>)
+ *   still is a match target of the other side;   out float32 [N, 3] = P, R, F.
+ * P = R = F = 0 (never NaN / inf) when either length is 0 or either weight sum is 0; F = 0 when P + R = 0.  An all-zero row has
+ * similarity 0 to everything.
+ * Dot products and norms accumulate in float32; bf16 rows go to the MFMA as stored (products exact) and the accumulator is divided
+ * by the float32 norms afterwards; FCMF_F32 takes a VALU path.  Fixed-order reductions, no atomics: two launches on the same inputs
+ * give the same bits.
+ * Limits: Lc_max, Lr_max <= 512; H % 8 == 0; 16-byte aligned cand / ref and strides that keep every row 16-byte aligned --
+ * FCMF_ERR_UNSUPPORTED otherwise; negative sizes / strides and NULL cand, ref, lengths or out are FCMF_ERR_ARG. */
+int fcmf_bertscore(const void* cand, const void* ref, const int* cand_len, const int* ref_len, const float* cand_w,
+                   const float* ref_w, float* out, int N, int Lc_max, int Lr_max, int H, int64_t ldc, int64_t sc,
+                   int64_t ldr, int64_t sr, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * y = LayerNorm(dropout(x) + res) * gamma + beta   (eps inside the sqrt, biased variance)
  * Replaces BertSelfOutput/BertOutput/AddNorm + FCMFLayerNorm (mm_modeling.py:158-171,
  * 276-280,324-328,566-573) and HF nn.LayerNorm(eps=1e-5).

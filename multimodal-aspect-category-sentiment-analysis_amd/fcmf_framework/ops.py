@@ -1378,6 +1378,47 @@ def attention_probs(q, k1=None, k2=None, mask=None, bias=None, heads=12, group_d
     return out
 
 
+def bertscore(cand, ref, cand_len, ref_len, cand_w=None, ref_w=None):
+    """BERTScore greedy matching of N (candidate, reference) pairs in one launch (fcmf_bertscore, include/fcmf_hip.h): cand
+    [N, Lc, H] and ref [N, Lr, H] token embeddings (float32 or bf16, same dtype), cand_len / ref_len integer [N] valid rows of each
+    pair (rows beyond them are never read), cand_w / ref_w optional float32 [N, L] per-token weights (None = 1 per valid token)
+    -> float32 [N, 3] = P, R, F.  Detached; there is no backward.  Strides are normalised as attention_probs does: a unit
+    innermost stride is kept with whatever row / pair strides come with it, anything else is made contiguous."""
+    H.require_cuda(cand, ref, cand_len, ref_len, cand_w, ref_w)
+    if cand.dim() != 3 or ref.dim() != 3 or cand.shape[0] != ref.shape[0] or cand.shape[2] != ref.shape[2] or cand.dtype != ref.dtype:
+        raise H.HipLibraryError(f"bertscore: cand {tuple(cand.shape)} {cand.dtype} and ref {tuple(ref.shape)} {ref.dtype} must be "
+                                f"[N, L, H] of one N, H and dtype")
+    N, Lc, Hd = cand.shape
+    Lr = ref.shape[1]
+
+    def rows(x):
+        x = x.detach()
+        V = 16 // x.element_size()                  # (a view whose rows are not 16-byte aligned is copied, not refused)
+        keep = (x.stride(2) == 1 and x.stride(1) >= x.shape[2] and x.stride(1) % V == 0 and x.stride(0) % V == 0
+                and x.data_ptr() % 16 == 0)
+        return x if keep else x.contiguous()
+
+    def lens(l):
+        if tuple(l.shape) != (N,) or l.dtype.is_floating_point:
+            raise H.HipLibraryError(f"bertscore: lengths must be integer [{N}] tensors")
+        return l.detach().to(torch.int32).contiguous()
+
+    def weights(wt, L):
+        if wt is None:
+            return None
+        if tuple(wt.shape) != (N, L):
+            raise H.HipLibraryError(f"bertscore: weights must be [{N}, {L}], got {tuple(wt.shape)}")
+        return wt.detach().float().contiguous()
+    cand, ref = rows(cand), rows(ref)
+    cand_len, ref_len = lens(cand_len), lens(ref_len)
+    cand_w, ref_w = weights(cand_w, Lc), weights(ref_w, Lr)
+    out = torch.empty((N, 3), dtype=torch.float32, device=cand.device)
+    H.check(H.lib().fcmf_bertscore(H.ptr(cand), H.ptr(ref), H.ptr(cand_len), H.ptr(ref_len), H.ptr(cand_w), H.ptr(ref_w),
+                                   H.ptr(out), N, Lc, Lr, Hd, cand.stride(1), cand.stride(0), ref.stride(1), ref.stride(0),
+                                   H.dt(cand), H.stream()), "fcmf_bertscore")
+    return out
+
+
 # --------------------------------------------------------------------------------------
 # box geometry
 # --------------------------------------------------------------------------------------

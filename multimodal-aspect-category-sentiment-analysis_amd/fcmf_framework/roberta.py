@@ -127,14 +127,16 @@ class RobertaEncoder(nn.Module):
         super().__init__()
         self.layer = nn.ModuleList([RobertaLayer(cfg) for _ in range(cfg.num_hidden_layers)])
 
-    def forward(self, x, add_mask, output_attentions=False):
+    def forward(self, x, add_mask, output_attentions=False, num_layers=None):
+        """num_layers: stop after that many layers and return that layer's output (None or >= the depth: all of them)"""
+        layer = self.layer if num_layers is None else self.layer[:max(int(num_layers), 0)]
         if not output_attentions:
-            for l in self.layer:
+            for l in layer:
                 x = l(x, add_mask)
             return x
         B, S, _ = x.shape
         attentions = []
-        for l in self.layer:
+        for l in layer:
             probs = torch.empty((B, l.heads, S, S), dtype=torch.float32, device=x.device)
             x = l(x, add_mask, probs=probs)
             attentions.append(probs)
@@ -226,13 +228,14 @@ class RobertaModel(nn.Module):
         return new
 
     # ---- forward -----------------------------------------------------------------------
-    def encode(self, input_ids, token_type_ids=None, attention_mask=None):
-        """sequence output [B,S,H] only (the training path never uses pooled/attentions)"""
+    def encode(self, input_ids, token_type_ids=None, attention_mask=None, num_layers=None):
+        """sequence output [B,S,H] only (the training path never uses pooled/attentions); num_layers=k below the depth: the output
+        of layer k, what `bert_score` takes from a model truncated to its first k layers"""
         x = self.embeddings(input_ids, token_type_ids)
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         add_mask = layers.additive_mask(attention_mask, input_ids.shape[1], torch.finfo(torch.float32).min)
-        return self.encoder(x, add_mask)
+        return self.encoder(x, add_mask, num_layers=num_layers)
 
     def forward(self, input_ids=None, token_type_ids=None, attention_mask=None, output_attentions=False, **unused):
         """-> (seq, pooled, attentions).  attentions is () unless output_attentions: then one float32 [B, heads, S, S] tensor per

@@ -12,7 +12,12 @@ encoder's word embeddings while `decoder.dense.weight` stays tied to them.
 `seed_{seed}_resimg_model_last.pth` / `..._resroi_model_last.pth` (:457-459) and restored on resume through the
 reference's `iaog_model` -> `resimg_model` / `resroi_model` path rewrite (:244-255).
 Extra flags: --bf16, --synthetic_steps N (seeded synthetic batches, precomputed features), --synthetic_pixels SIZE
-(those batches carry pixel crops and the HIP ResNet-152 trunks run inside the step).
+(those batches carry pixel crops and the HIP ResNet-152 trunks run inside the step), --synthetic_eval_samples N.
+--do_eval is the generation evaluation the reference keeps commented out (:376-452, :462-632), in `iaog_eval.py`: after every
+epoch the master rank beam-search decodes the dev set (`dev_with_iaog.json`, or N seeded synthetic samples), scores the text against
+the labels with BERTScore (`fcmf_framework/bertscore.py`: --bert_score_model must be a LOCAL model directory), keeps
+`seed_{seed}_{iaog,resimg,resroi}_model_best.pth` by macro F1 and carries `best_score` in the `last` checkpoints; after training
+the best checkpoint decodes the test set into `iaog_test_predictions_formatted.txt`.  Without --do_eval nothing of this runs.
 Process set-up, the checkpoint code, the extractors and the loop of one epoch are `train_harness.py`'s, shared with
 run_multimodal_fcmf.py; this file keeps the parser, the model and data, the 2 parameter groups and the loss.
 With real data the driver imports the user's `iaog_dataset.IAOGDataset` (host-side producer,
@@ -37,6 +42,9 @@ from train_harness import (build_extractors, init_run, load_resnets, make_featur
                            split_decay, train_epoch)
 
 
+DEFAULT_BERT_SCORE_MODEL = 'uitnlp/visobert'      # the reference's default (:53), a hub name
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     # (reference :47-48 marks both `required`; here they are only read by the real-data branch, so --synthetic_steps runs without)
@@ -46,10 +54,12 @@ def build_parser():
     p.add_argument('--image_dir', default='../vimacsa/image')
     p.add_argument("--pretrained_hf_model", default=None, type=str, required=True)
     p.add_argument("--resume_from_checkpoint", default=None, type=str)
-    # accepted exactly as the reference declares them (run_pretraining_fcmf.py:53,57,60,66,82); --bert_score_model / --beam_size /
-    # --resnet_label_path feed only the reference's commented-out evaluation half (:376-632, dead code there, not built here)
-    p.add_argument('--bert_score_model', default='uitnlp/visobert', type=str,
-                   help="HuggingFace model name or local path for BERTScore (reference: used by its disabled evaluation only)")
+    # declared exactly as the reference declares them (run_pretraining_fcmf.py:53,57,60,66,82).  --bert_score_model, --beam_size and
+    # --eval_batch_size drive the --do_eval generation evaluation (the reference's commented-out half, :376-632, built here in
+    # iaog_eval.py); --resnet_label_path is read nowhere, there or here
+    p.add_argument('--bert_score_model', default=DEFAULT_BERT_SCORE_MODEL, type=str,
+                   help="LOCAL model directory of the BERTScore encoder (--do_eval; a hub name cannot be fetched: download it first). "
+                        "With --synthetic_steps the default is the --pretrained_hf_model directory")
     p.add_argument('--resnet_label_path', default='/kaggle/input/resnet-output')
     p.add_argument("--max_seq_length", default=170, type=int, help="encoder prompt length (the reference's dataset hard-codes 170)")
     p.add_argument("--beam_size", default=2, type=int)
@@ -83,14 +93,29 @@ def build_parser():
     p.add_argument('--resnet_checkpoint', default=None, type=str, help="torchvision resnet152 state dict for the HIP trunk")
     p.add_argument('--synthetic_pixels', type=int, default=0,
                    help="with --synthetic_steps: batches carry SIZE x SIZE pixel crops and the ResNet-152 trunks run inside the step")
+    p.add_argument('--synthetic_eval_samples', type=int, default=0,
+                   help="with --synthetic_steps and --do_eval: dev and test sets of N seeded synthetic samples each")
     return p
+
+
+def scorer_dir(args):
+    """the BERTScore model directory of a --do_eval run, checked before anything is trained"""
+    path = args.bert_score_model
+    if args.synthetic_steps > 0 and path == DEFAULT_BERT_SCORE_MODEL:
+        path = args.pretrained_hf_model
+    if not os.path.isdir(path):
+        raise ValueError(f"--bert_score_model {path!r}: --do_eval needs a local model directory (config.json + weights of a "
+                         f"RoBERTa-family encoder, e.g. a downloaded uitnlp/visobert); nothing is fetched from a hub")
+    return path
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    bert_score_dir = scorer_dir(args) if args.do_eval else None
     rank, _, world, device, master, logger = init_run(args, "iaog", "pretraining_iaog.log", script="run_pretraining_fcmf.py")
 
     tokenizer = None
+    dev_set = test_set = None          # callables -> the batches of one pass (--do_eval)
     if args.synthetic_steps <= 0:
         from transformers import AutoTokenizer
         tokenizer = AutoTokenizer.from_pretrained(args.pretrained_hf_model)
@@ -105,6 +130,9 @@ def main(argv=None):
     # the two ResNet-152 extractors (reference :191-194) whenever pixels enter the step: real data without a feature cache,
     # or --synthetic_pixels
     r_img = r_roi = None
+    if args.do_eval and args.synthetic_steps <= 0 and args.feature_cache_dir:
+        raise ValueError("--do_eval decodes the dev / test reviews from pixels: the feature cache holds the training reviews only, "
+                         "run without --feature_cache_dir")
     if (args.synthetic_steps > 0 and args.synthetic_pixels > 0) or (args.synthetic_steps <= 0 and not args.feature_cache_dir):
         from fcmf_framework.resnet import resnet152
         sd = torch.load(args.resnet_checkpoint, map_location='cpu', weights_only=True) if args.resnet_checkpoint else None
@@ -125,22 +153,44 @@ def main(argv=None):
         cfg = model.encoder.bert.cell.config
         cfgd = dict(vocab_size=cfg.vocab_size, pad_token_id=cfg.pad_token_id)
 
+        def draw(B, batch_seed, dec_seed):
+            b = synth.synth_batch(B, cfgd, S=min(args.max_seq_length, 128, cfg.max_position_embeddings - 2), num_imgs=args.num_imgs, num_roi=args.num_rois,
+                                  num_aspects=1, seed=batch_seed, coord_dtype=torch.float32)
+            g = torch.Generator().manual_seed(dec_seed)
+            dec = torch.randint(3, vocab, (B, args.synthetic_dec_len), generator=g)
+            lab = torch.roll(dec, -1, dims=1)
+            lab[:, -1] = -100                                                           # iaog_dataset.py:93-96
+            if args.synthetic_pixels:             # pixel crops in the IAOG dataset's float32 layout (iaog_dataset.py:148)
+                b["visual_embeds_att"], b["roi_embeds_att"] = synth.synth_pixel_batch(
+                    B, args.num_imgs, args.num_rois, args.synthetic_pixels, dec_seed, torch.float32)
+            return (b["visual_embeds_att"], b["roi_embeds_att"], b["roi_coors"], b["input_ids"][:, 0],
+                    b["token_type_ids"][:, 0], b["attention_mask"][:, 0], b["added_attention_mask"][:, 0], dec, lab)
+
         def batches():
             for i in range(args.synthetic_steps):
-                b = synth.synth_batch(args.train_batch_size, cfgd, S=min(args.max_seq_length, 128, cfg.max_position_embeddings - 2), num_imgs=args.num_imgs, num_roi=args.num_rois,
-                                      num_aspects=1, seed=args.seed + 1000 * rank + i, coord_dtype=torch.float32)
-                g = torch.Generator().manual_seed(args.seed + i)
-                dec = torch.randint(3, vocab, (args.train_batch_size, args.synthetic_dec_len), generator=g)
-                lab = torch.roll(dec, -1, dims=1)
-                lab[:, -1] = -100                                                           # iaog_dataset.py:93-96
-                if args.synthetic_pixels:             # pixel crops in the IAOG dataset's float32 layout (iaog_dataset.py:148)
-                    # (this seed lacks the `1000 * rank` term of the batch seed above: every rank draws the same pixels)
-                    b["visual_embeds_att"], b["roi_embeds_att"] = synth.synth_pixel_batch(
-                        args.train_batch_size, args.num_imgs, args.num_rois, args.synthetic_pixels, args.seed + i, torch.float32)
-                yield (b["visual_embeds_att"], b["roi_embeds_att"], b["roi_coors"], b["input_ids"][:, 0],
-                       b["token_type_ids"][:, 0], b["attention_mask"][:, 0], b["added_attention_mask"][:, 0], dec, lab)
+                # (the decoder / pixel seed lacks the `1000 * rank` term of the batch seed: every rank draws the same pixels)
+                yield draw(args.train_batch_size, args.seed + 1000 * rank + i, args.seed + i)
         steps_per_epoch = args.synthetic_steps
         make_loader = batches
+
+        if args.do_eval and args.synthetic_eval_samples > 0:
+            # dev / test sets drawn like the training batches, in the dataset's 11-tuple; the text path runs through IdTokenizer
+            from fcmf_framework.roberta import RobertaConfig
+            from review_batches import ASPECTS
+            aspects = list(args.list_aspect) or list(ASPECTS)
+            tokenizer = score_tokenizer = synth.IdTokenizer(dict(
+                vocab_size=min(vocab, RobertaConfig.from_pretrained(bert_score_dir).vocab_size), pad_token_id=cfg.pad_token_id))
+
+            def eval_set(seed0):
+                def it():
+                    n = args.synthetic_eval_samples
+                    for s0 in range(0, n, args.eval_batch_size):
+                        B = min(args.eval_batch_size, n - s0)
+                        vis, roi, coors, ids, tt, am, added, dec, lab = draw(B, seed0 + s0, seed0 + s0 + 7)
+                        yield (vis, roi, coors, lab, dec, ids, tt, am, added, [aspects[(s0 + k) % len(aspects)] for k in range(B)],
+                               [f"synthetic review {s0 + k}" for k in range(B)])
+                return it
+            dev_set, test_set = eval_set(args.seed + 500000), eval_set(args.seed + 600000)
     else:
         # real data (reference :130-183): reviews with `iaog_labels`, one sample per (review, aspect); photos through the
         # HIP ResNet-152 trunk inside the step, or a precomputed feature cache.  (The reference also runs underthesea's
@@ -177,6 +227,28 @@ def main(argv=None):
         steps_per_epoch = len(loader)
         make_loader = batches
 
+        if args.do_eval:
+            # dev (reference :133,175,282) and, if its file is there, test (:465-467): same plumbing as the train set, in order
+            from torch.utils.data import SequentialSampler
+            from transformers import AutoTokenizer
+            aspects = list(train_ds.ASPECT)
+            score_tokenizer = AutoTokenizer.from_pretrained(bert_score_dir, local_files_only=True)
+
+            def eval_set(name):
+                path = f'{args.pretrained_data_dir}/{name}_with_iaog.json'
+                if not os.path.exists(path):
+                    return None
+                data = pd.read_json(path)
+                if 'iaog_labels' not in data.columns:
+                    raise ValueError(f"'iaog_labels' column not found in {path}")
+                ds = IAOGDataset(data, tokenizer, args.image_dir, roi_df, dict_image_aspect, dict_roi_aspect, args.num_imgs,
+                                 args.num_rois, args.max_len_decoder, max_seq_length=args.max_seq_length,
+                                 list_aspect=args.list_aspect or None)
+                return lambda: DataLoader(ds, sampler=SequentialSampler(ds), batch_size=args.eval_batch_size)
+            dev_set, test_set = eval_set('dev'), eval_set('test')
+            if dev_set is None:
+                raise ValueError(f"--do_eval: {args.pretrained_data_dir}/dev_with_iaog.json not found")
+
     num_train_steps = int(steps_per_epoch / args.gradient_accumulation_steps * args.num_train_epochs)
     scheduler = get_linear_schedule_with_warmup(optimizer, int(num_train_steps * args.warmup_proportion), num_train_steps)
     # the trunks' gradients are produced LAST in backward (the extractors run first in the step): behind the model's in the arena
@@ -186,12 +258,14 @@ def main(argv=None):
         reducer = GradReducer(arena)
         reducer.broadcast_parameters(0)
     start_epoch = 0
+    best_score = 0.0
     if args.resume_from_checkpoint and os.path.isfile(args.resume_from_checkpoint):
         ck = torch.load(args.resume_from_checkpoint, map_location=device, weights_only=True)
         model.load_state_dict(ck['model_state_dict'])
         optimizer.load_state_dict(ck['optimizer_state_dict'])
         scheduler.load_state_dict(ck['scheduler_state_dict'])
         start_epoch = ck['epoch'] + 1
+        best_score = float(ck.get('best_score') or 0.0)                     # reference :271
         ops.shadows.clear()
         load_resnets(args.resume_from_checkpoint, r_img, r_roi, device, logger if master else None, old="iaog_model")   # reference :244-255
 
@@ -203,6 +277,24 @@ def main(argv=None):
         # model(...) -> logits -> CrossEntropyLoss(ignore_index=-100) (reference :309-324) as one fused call
         return model.forward_loss(enc_X, dec_X, labels, vis, roi, coors, tt, am, added, ignore_index=-100)
 
+    evaluate = None
+    if args.do_eval and master and dev_set is not None:
+        from fcmf_framework.bertscore import BertScorer
+        from iaog_eval import aspect_line, generate, macro_bertscore, write_predictions
+        scorer = BertScorer(bert_score_dir, num_layers=12, device=device)
+        score_fn = lambda cands, refs: scorer.score(cands, refs, score_tokenizer)
+
+        def evaluate(batches):
+            """-> (per_aspect, macro, results) of one pass over a dev / test set"""
+            model.eval()
+            if r_img is not None:
+                r_img.eval(); r_roi.eval()
+            preds, refs, results = generate(model, tokenizer, batches, features, args.beam_size, args.max_len_decoder, aspects)
+            per_aspect, macro = macro_bertscore(preds, refs, aspects, score_fn)
+            return per_aspect, macro, results
+    elif args.do_eval and master:
+        logger.info("--do_eval: no dev set (--synthetic_eval_samples is 0): nothing is evaluated")
+
     if args.do_train:
         for epoch in range(start_epoch, int(args.num_train_epochs)):
             model.train()
@@ -211,11 +303,43 @@ def main(argv=None):
             log = lambda step, loss: logger.info("epoch %d step %d loss %.4f", epoch, step, loss)
             train_epoch(DevicePrefetcher(make_loader(), device), loss_fn, arena=arena, reducer=reducer, optimizer=optimizer,
                         scheduler=scheduler, accum=args.gradient_accumulation_steps, log=log if master else None)
+            if evaluate is not None:                                     # reference :376-452; the other ranks wait at the barrier below
+                logger.info("***** Running evaluation on Dev Set with BEAM SEARCH *****")
+                per_aspect, macro, _ = evaluate(dev_set())
+                logger.info("Computing BERTScore for Dev Set using model: %s ...", bert_score_dir)
+                for a, m in per_aspect.items():
+                    if m is not None:
+                        logger.info("  Aspect: " + aspect_line(a, m))
+                logger.info("Epoch %d [Macro-Avg] F1: %.4f", epoch, macro[2])
+                if macro[2] > best_score:
+                    best_score = macro[2]
+                    logger.info("New Best F1-Score (%.4f)! Saving model...", best_score)
+                    save_model(f'{args.output_dir}/seed_{args.seed}_iaog_model_best.pth', model, optimizer, scheduler, epoch, best_score)
+                    save_extractors(args.output_dir, args.seed, 'best', r_img, r_roi, optimizer, scheduler, epoch, best_score)
             if world > 1:
                 torch.distributed.barrier()
             if master:
-                save_model(f'{args.output_dir}/seed_{args.seed}_iaog_model_last.pth', model, optimizer, scheduler, epoch)
-                save_extractors(args.output_dir, args.seed, 'last', r_img, r_roi, optimizer, scheduler, epoch)   # reference :458-459
+                save_model(f'{args.output_dir}/seed_{args.seed}_iaog_model_last.pth', model, optimizer, scheduler, epoch, best_score)
+                save_extractors(args.output_dir, args.seed, 'last', r_img, r_roi, optimizer, scheduler, epoch, best_score)   # reference :458-459
+    if evaluate is not None and test_set is not None:                    # reference :462-632
+        best = f'{args.output_dir}/seed_{args.seed}_iaog_model_best.pth'
+        if os.path.exists(best):
+            logger.info("Loading Best Checkpoint for Testing: %s", best)
+            model.load_state_dict(torch.load(best, map_location=device, weights_only=True)['model_state_dict'])
+            ops.shadows.clear()
+            load_resnets(best, r_img, r_roi, device, logger, old="iaog_model")
+        logger.info("Computing BERTScore for Test Set using model: %s ...", bert_score_dir)
+        per_aspect, macro, results = evaluate(test_set())
+        log_path = f"{args.output_dir}/iaog_test_predictions_formatted.txt"
+        write_predictions(log_path, bert_score_dir, per_aspect, macro, results)
+        for a, m in per_aspect.items():
+            if m is not None:
+                logger.info(aspect_line(a, m))
+        logger.info("***** TEST RESULTS (Macro Avg) *****")
+        logger.info("Test Precision: %.4f", macro[0])
+        logger.info("Test Recall:    %.4f", macro[1])
+        logger.info("Test F1-Score:  %.4f", macro[2])
+        logger.info("Formatted predictions saved to %s", log_path)
     arena.deactivate()
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -248,3 +248,43 @@ def synth_pixel_batch(B, num_imgs, num_rois, size, seed, roi_dtype):
     vis = synth_crops(B * num_imgs, size, seed=seed).view(B, num_imgs, 3, size, size)
     roi = synth_crops(B * num_imgs * num_rois, size, seed=seed + 7919).view(B, num_imgs, num_rois, 3, size, size)
     return vis, roi.to(roi_dtype)
+
+
+class IdTokenizer:
+    """The tokenizer of synthetic mode (no vocabulary file is reachable offline): a text is its token ids written as
+    space-joined decimals, so ids -> text -> ids is the identity and the drivers' text path (beam-search decode, label decode,
+    BERTScore over strings) runs as it does with a real tokenizer.  Special ids as in the synthetic batches: <s> = 0 (bos and cls),
+    </s> = 2 (sep and eos), pad from the config."""
+
+    def __init__(self, cfg):
+        self.vocab_size = cfg["vocab_size"]
+        self.pad_token_id = cfg["pad_token_id"]
+        self.bos_token_id = self.cls_token_id = cfg.get("bos_token_id", 0)
+        self.sep_token_id = self.eos_token_id = cfg.get("eos_token_id", 2)
+        self.all_special_ids = sorted({self.pad_token_id, self.bos_token_id, self.sep_token_id})
+
+    def __len__(self):
+        return self.vocab_size
+
+    def encode(self, text, add_special_tokens=True, truncation=False, max_length=None, **unused):
+        ids = [int(t) for t in str(text).split()]
+        bad = [i for i in ids if not 0 <= i < self.vocab_size]
+        if bad:
+            raise ValueError(f"IdTokenizer: ids {bad[:4]} outside the vocabulary of {self.vocab_size}")
+        if truncation and max_length is not None:
+            ids = ids[:max(max_length - (2 if add_special_tokens else 0), 0)]
+        return [self.bos_token_id] + ids + [self.sep_token_id] if add_special_tokens else ids
+
+    def decode(self, ids, skip_special_tokens=False, **unused):
+        ids = [int(i) for i in (ids.tolist() if hasattr(ids, "tolist") else ids)]
+        if skip_special_tokens:
+            ids = [i for i in ids if i not in self.all_special_ids]
+        return " ".join(str(i) for i in ids)
+
+    def __call__(self, text, max_length=None, padding=False, truncation=False, add_special_tokens=True, **unused):
+        ids = self.encode(text, add_special_tokens=add_special_tokens, truncation=truncation, max_length=max_length)
+        mask = [1] * len(ids)
+        if padding == 'max_length' and max_length is not None:
+            mask += [0] * (max_length - len(ids))
+            ids = ids + [self.pad_token_id] * (max_length - len(ids))
+        return {"input_ids": ids, "attention_mask": mask}

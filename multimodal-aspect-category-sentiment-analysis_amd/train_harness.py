@@ -79,11 +79,11 @@ def load_resnets(path, resnet_img, resnet_roi, device, logger=None, old="fcmf_mo
     return loaded
 
 
-def save_extractors(output_dir, seed, tag, resnet_img, resnet_roi, optimizer, scheduler, epoch):
+def save_extractors(output_dir, seed, tag, resnet_img, resnet_roi, optimizer, scheduler, epoch, best_score=0.0):
     """the extractors (if any) beside the model checkpoint (run_multimodal_fcmf.py:557-563, run_pretraining_fcmf.py:457-459)"""
     for net, name in ((resnet_img, "resimg"), (resnet_roi, "resroi")):
         if net is not None:
-            save_model(f'{output_dir}/seed_{seed}_{name}_model_{tag}.pth', net, optimizer, scheduler, epoch)
+            save_model(f'{output_dir}/seed_{seed}_{name}_model_{tag}.pth', net, optimizer, scheduler, epoch, best_score)
 
 
 def build_extractors(make_trunk, fine_tune, device):
