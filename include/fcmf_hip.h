@@ -178,6 +178,28 @@ int fcmf_attn_mfma_bwd(const void* q, const void* k, const void* v, const float*
  * mm_modeling.py:182-184 / HF RobertaSelfAttention's three nn.Linear biases) without another pass over dqkv. */
 
 /* ---------------------------------------------------------------------------------------
+ * MFMA attention with any number of keys and a key/value set shared by consecutive query groups: bf16, head dim 64,
+ * Tq <= 256, 1 <= Tk <= 2^20 (FCMF_ERR_UNSUPPORTED beyond).  The cross-attention of the comparison baselines (mRoBERTa,
+ * TomBERT): the text queries of the `kv_share` aspect prompts of a review attend to all of its visual tokens.
+ *   Q [G,Tq,heads*64]; K/V [G/kv_share,Tk,heads*64], group g reads key set g / kv_share (G % kv_share == 0);
+ *   mask [G,Tk] additive float32 or NULL; out [G,Tq,heads*64]; lse [G,heads,Tq].
+ * Semantics, row strides and alignment rules are those of fcmf_attn_mfma_fwd / _bwd: softmax(scale QK^T + mask) with the
+ * mask added in float32 (a finfo.min key gets probability exactly 0; a row whose every key is masked is uniform over all
+ * Tk keys), dropout on the probabilities with the same counter function of (seed, group, head, query, key), then V.
+ * Backward: dq [G,Tq,.]; dk / dv [G/kv_share,Tk,.] are the sums over the sharing groups, accumulated in float32 and rounded
+ * to bf16 once.  kv_share > 1 needs `workspace`: caller-owned device memory of at least
+ * 2 * (G/kv_share) * Tk * heads*64 * 4 bytes, 16-byte aligned (contents need not be initialised; FCMF_ERR_ARG if too small). */
+int fcmf_attn_mfma_long_fwd(const void* q, const void* k, const void* v, const float* mask,
+                            void* out, float* lse, int G, int heads, int Tq, int Tk, int kv_share,
+                            int64_t ldq, int64_t ldk, int64_t ldo, float scale,
+                            float dropout_p, uint64_t seed, void* stream);
+int fcmf_attn_mfma_long_bwd(const void* q, const void* k, const void* v, const float* mask,
+                            const void* out, const void* dout, const float* lse,
+                            void* dq, void* dk, void* dv, int G, int heads, int Tq, int Tk, int kv_share,
+                            int64_t ldq, int64_t ldk, int64_t ldo, float scale,
+                            float dropout_p, uint64_t seed, float* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Attention probabilities on request: P = softmax(score) as float32, BEFORE dropout, recomputed from Q and K with exactly the
  * score definition of fcmf_attn_desc above (the forward kernels never materialise P).  Both entry points find the row maximum
  * and sum themselves (no lse of a forward is needed); a row whose every key carries the finfo(float32).min mask comes out

@@ -1,0 +1,536 @@
+// MFMA attention with any number of keys and a key/value set shared by consecutive query groups: bf16, head dim 64,
+// up to 256 queries per group.  The cross-attention of the comparison baselines: the text queries of the `kv_share`
+// aspect prompts of a review attend to all of the review's visual tokens (371 or 595 keys), which are projected and stored
+// once per review -- group g reads key set g / kv_share.
+//   forward : one workgroup per (group, head, 128-query tile).  The keys go by in 128-key tiles: the next tile's K / V rows
+//             are in flight (in registers) while the current tile is computed from its LDS images, exactly as one tile of
+//             attn_mfma.hip is (S^T accumulators with the key index in the registers, P never leaves them), under a
+//             running row maximum and sum that rescale the O accumulators.  Dropout multiplies the unnormalised
+//             probabilities, the row sum is taken before it, and O is divided by the sum at the end.  32 KiB of LDS.
+//   backward: one workgroup per (key set, head) walks the `kv_share` groups that read the set.  Per group, Q, dO, the
+//             logsumexp and the row dot-products stay resident (Tq <= 256) and the 32-key chunk loop of attn_mfma.hip runs
+//             inside the loop over 128-key tiles: dQ accumulates across tiles in registers, dK / dV of a chunk are
+//             finished when the chunk leaves.  Every dK / dV element belongs to ONE lane for all groups, so their sum over
+//             the groups is a private float32 read-modify-write in a workspace, rounded to bf16 once by the last group:
+//             no atomics, no partial buffers, deterministic.  80 KiB (Tq <= 128) or 112 KiB of LDS.
+// Tiles (forward) and chunks (backward) whose keys all carry the hard mask (<= -1e30, HF's finfo.min) are skipped with
+// bit-identical results unless the group has no live key at all (then softmax is uniform over ALL keys).
+#include "attn_tiles.h"
+
+struct AttnLongParams {
+  AttnMfmaParams a;      // (G = number of query groups; k / v / dk / dv hold G / kv_share key sets)
+  int kv_share;
+  float* ws;             // backward, kv_share > 1: [2][G / kv_share][Tk][heads * 64] f32 running sums of dK | dV
+};
+
+// does the group have any key that is not hard-masked?  (wave-uniform)
+__device__ __forceinline__ bool any_live_key(const float* mrow, int Tk, int lane) {
+  for (int k0 = 0; k0 < Tk; k0 += 64) {
+    const int key = k0 + lane;
+    if (__ballot(key < Tk && mrow[key] > -1e30f)) return true;
+  }
+  return false;
+}
+// ... and among keys k0 .. k0 + n - 1 (n <= 128)?
+__device__ __forceinline__ bool any_live_in(const float* mrow, int Tk, int k0, int n, int lane) {
+  const int a = k0 + lane, b = k0 + 64 + lane;
+  const bool la = lane < n && a < Tk && mrow[a] > -1e30f;
+  const bool lb = 64 + lane < n && b < Tk && mrow[b] > -1e30f;
+  return __ballot(la || lb) != 0;
+}
+
+// =========================================================================================
+__global__ __launch_bounds__(256, 2) void attn_long_fwd_kernel(AttnLongParams L) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const AttnMfmaParams& P = L.a;
+  char* Ks = smem;
+  char* Vs = smem + TILE_B;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int g = blockIdx.x / P.heads, h = blockIdx.x % P.heads;
+  const int q0 = blockIdx.y * AT + w * 32;
+  const int64_t kbase = (int64_t)(g / L.kv_share) * P.Tk;
+  const bf16_t* kp = P.k + kbase * P.ldk + h * AD;
+  const bf16_t* vp = P.v + kbase * P.ldk + h * AD;
+  const float* mrow = P.mask ? P.mask + (int64_t)g * P.Tk : nullptr;
+  const int ntiles = (P.Tk + AT - 1) / AT;
+  const bool skip_dead = mrow && any_live_key(mrow, P.Tk, lane);
+  auto next_live = [&](int t) {      // first tile >= t with a live key (the same in every wave: barriers stay matched)
+    while (skip_dead && t < ntiles && !any_live_in(mrow, P.Tk, t * AT, AT, lane)) ++t;
+    return t;
+  };
+  int t = next_live(0);
+  bf16x8 qf[2][2];
+  {
+    const TileRegs kt = load_tile(kp + (int64_t)t * AT * P.ldk, P.ldk, P.Tk - t * AT, tid);
+    const TileRegs vt = load_tile(vp + (int64_t)t * AT * P.ldk, P.ldk, P.Tk - t * AT, tid);
+    load_q_frags(P, g, h, q0, lane, qf);
+    store_tile<false>(Ks, kt, tid);
+    store_tile<true>(Vs, vt, tid);
+  }
+  __syncthreads();
+  const float inv_keep = P.p > 0.f ? 1.0f / (1.0f - P.p) : 1.0f;
+  const uint64_t drop_base = ((uint64_t)g * P.heads + h) * P.Tq * P.Tk;
+  float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+  f32x4 oc[4][2];
+#pragma unroll
+  for (int df = 0; df < 4; ++df)
+#pragma unroll
+    for (int f = 0; f < 2; ++f) oc[df][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  while (t < ntiles) {
+    const int tn = next_live(t + 1);
+    TileRegs kt, vt;
+    if (tn < ntiles) {                        // next tile's rows: in flight under this tile's arithmetic
+      kt = load_tile(kp + (int64_t)tn * AT * P.ldk, P.ldk, P.Tk - tn * AT, tid);
+      vt = load_tile(vp + (int64_t)tn * AT * P.ldk, P.ldk, P.Tk - tn * AT, tid);
+    }
+    const int k0 = t * AT;
+    const int rows = min(AT, P.Tk - k0);      // keys of this tile; 16-key fragments past them are skipped
+    // S^T[key][q]: 8 key fragments x 2 query fragments
+    f32x4 sc[8][2];
+#pragma unroll
+    for (int kf = 0; kf < 8; ++kf)
+#pragma unroll
+      for (int f = 0; f < 2; ++f) sc[kf][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int kf = 0; kf < 8; ++kf) {
+        if (16 * kf >= rows) continue;
+        const bf16x8 ka = frag_row64(Ks, 16 * kf, s, lane);
+#pragma unroll
+        for (int f = 0; f < 2; ++f) sc[kf][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[f][s], sc[kf][f], 0, 0, 0);
+      }
+    // lane holds, for query q0+16f+(lane&15), keys k0 + 16kf + 4(lane>>4) + r
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      const int q = q0 + 16 * f + (lane & 15);
+      float m = -INFINITY;
+#pragma unroll
+      for (int kf = 0; kf < 8; ++kf) {
+        if (16 * kf >= rows) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int key = k0 + 16 * kf + 4 * (lane >> 4) + r;
+          float s = -INFINITY;
+          if (key < P.Tk) s = sc[kf][f][r] * P.scale + (mrow ? mrow[key] : 0.f);
+          sc[kf][f][r] = s;
+          m = fmaxf(m, s);
+        }
+      }
+      m = fmaxf(m, __shfl_xor(m, 16, 64));
+      m = fmaxf(m, __shfl_xor(m, 32, 64));
+      const float m_new = fmaxf(m_run[f], m);            // (finite: every tile has a key below Tk)
+      const float alpha = __expf(m_run[f] - m_new);      // 0 at the first tile, and after tiles that held only hard-masked keys
+      float sum = 0.f;
+#pragma unroll
+      for (int kf = 0; kf < 8; ++kf) {
+        if (16 * kf >= rows) continue;         // (sc of a skipped fragment stays 0 = its probabilities)
+        float dm[4] = {1.f, 1.f, 1.f, 1.f};
+        if (P.p > 0.f)
+          dropout_mult4(P.seed, drop_base + (__umul24((unsigned)q, (unsigned)P.Tk) + (unsigned)(k0 + 16 * kf + 4 * (lane >> 4))),
+                        P.p, inv_keep, dm);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = __expf(sc[kf][f][r] - m_new);
+          sum += e;
+          sc[kf][f][r] = e * dm[r];
+        }
+      }
+      sum += __shfl_xor(sum, 16, 64);
+      sum += __shfl_xor(sum, 32, 64);
+      l_run[f] = l_run[f] * alpha + sum;
+      m_run[f] = m_new;
+#pragma unroll
+      for (int df = 0; df < 4; ++df) oc[df][f] *= alpha;
+    }
+    // O^T[d][q] += sum_key V[key][d] P[q][key]
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if (32 * s >= rows) continue;
+      bf16x8 pb[2];
+#pragma unroll
+      for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { pb[f][r] = (bf16_t)sc[2 * s][f][r]; pb[f][4 + r] = (bf16_t)sc[2 * s + 1][f][r]; }
+#pragma unroll
+      for (int df = 0; df < 4; ++df) {
+        const bf16x8 va = frag_tr64p(Vs, 16 * df, s, lane);
+#pragma unroll
+        for (int f = 0; f < 2; ++f) oc[df][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pb[f], oc[df][f], 0, 0, 0);
+      }
+    }
+    __syncthreads();                          // every wave is done with the images
+    if (tn < ntiles) {
+      store_tile<false>(Ks, kt, tid);
+      store_tile<true>(Vs, vt, tid);
+    }
+    __syncthreads();
+    t = tn;
+  }
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const int q = q0 + 16 * f + (lane & 15);
+    if (q < P.Tq) {
+      const float inv = 1.0f / l_run[f];
+      if ((lane >> 4) == 0 && P.lse) P.lse[((int64_t)g * P.heads + h) * P.Tq + q] = m_run[f] + __logf(l_run[f]);
+      bf16_t* orow = P.out + ((int64_t)g * P.Tq + q) * P.ldo + h * AD + 4 * (lane >> 4);
+#pragma unroll
+      for (int df = 0; df < 4; ++df) store4(orow + 16 * df, oc[df][f] * inv);
+    }
+  }
+}
+
+// =========================================================================================
+// dK / dV of 32-key chunk `cg` (global chunk index) after group `sm` of the key set: add the running float32 sums of the
+// earlier groups, then either keep the sum (more groups follow) or round it to bf16 (last group).  `contrib` = false: the
+// chunk was skipped for this group (all its keys hard-masked), aV / aK are not read.
+__device__ __forceinline__ void finish_chunk(const AttnLongParams& L, int64_t kbase, int h, int w, int lane, int cg, int sm,
+                                             bool contrib, const f32x4 (&aV)[2], const f32x4 (&aK)[2]) {
+  const AttnMfmaParams& P = L.a;
+  const bool first = sm == 0, last = sm == L.kv_share - 1;
+  if (!contrib && !first && !last) return;       // the running sums stand as they are
+  const int dcol = h * AD + 16 * w + 4 * (lane >> 4);
+  const int64_t HD = (int64_t)P.heads * AD;
+  const int64_t dv_off = (int64_t)(P.G / L.kv_share) * P.Tk * HD;      // the dV half of the workspace
+#pragma unroll
+  for (int kf = 0; kf < 2; ++kf) {
+    const int key = 32 * cg + 16 * kf + (lane & 15);
+    if (key >= P.Tk) continue;
+    f32x4 tv = f32x4{0.f, 0.f, 0.f, 0.f}, tk = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (contrib) { tv = aV[kf]; tk = aK[kf] * P.scale; }
+    float* wk = L.ws + (kbase + key) * HD + dcol;      // (not dereferenced when kv_share == 1: first and last)
+    if (!first) {
+      tk += *reinterpret_cast<const f32x4*>(wk);
+      tv += *reinterpret_cast<const f32x4*>(wk + dv_off);
+    }
+    if (!last) {
+      *reinterpret_cast<f32x4*>(wk) = tk;
+      *reinterpret_cast<f32x4*>(wk + dv_off) = tv;
+    } else {
+      store4(P.dv + (kbase + key) * P.ldk + dcol, tv);
+      store4(P.dk + (kbase + key) * P.ldk + dcol, tk);
+    }
+  }
+}
+
+template <int NQT>
+__device__ __forceinline__ void attn_long_bwd_body(const AttnLongParams& L) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const AttnMfmaParams& P = L.a;
+  char* Qs = smem;                               // NQT tiles
+  char* dOs = Qs + NQT * TILE_B;                 // NQT tiles
+  char* Ks = dOs + NQT * TILE_B;                 // the current 128-key tile
+  char* Vs = Ks + TILE_B;
+  char* PdT = Vs + TILE_B;                       // [32 keys][128 q] bf16 of the current (key chunk, query tile), 8 KiB
+  char* dST = PdT + TILE_B / 2;                  // 8 KiB
+  const int ks = blockIdx.x / P.heads, h = blockIdx.x % P.heads;
+  const int64_t kbase = (int64_t)ks * P.Tk;
+  const bf16_t* kp = P.k + kbase * P.ldk + h * AD;
+  const bf16_t* vp = P.v + kbase * P.ldk + h * AD;
+  const int ntiles = (P.Tk + AT - 1) / AT;
+  const float inv_keep = P.p > 0.f ? 1.0f / (1.0f - P.p) : 1.0f;
+  const uint32_t drop_thr = dropout_threshold(P.p);
+  // One workgroup per CU (NQT = 2) has the registers to hold the next tile while it computes; two per CU (NQT = 1, 256
+  // registers each) overlap each other's loads instead.
+  constexpr bool PREFETCH = NQT == 2;
+  const f32x4 zero4[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+
+#pragma unroll 1
+  for (int sm = 0; sm < L.kv_share; ++sm) {
+    // (the thread index is made opaque per group: otherwise every lane-dependent address and dropout term of the chunk loop is
+    //  hoisted out of THIS loop too and stays live across the prologue, which costs ~100 spilled registers)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, w = tid >> 6, odd = lane & 1;
+    const int g = ks * L.kv_share + sm;
+    const int64_t qbase = (int64_t)g * P.Tq;
+    const float* mrow = P.mask ? P.mask + (int64_t)g * P.Tk : nullptr;
+    float score_scale = P.scale;          // (0 for a group whose every key is hard-masked: see below)
+    const bool live_any = !mrow || any_live_key(mrow, P.Tk, lane);
+    const bool skip_dead = mrow && live_any;
+    auto next_live = [&](int t) {
+      while (skip_dead && t < ntiles && !any_live_in(mrow, P.Tk, t * AT, AT, lane)) ++t;
+      return t;
+    };
+    int t = next_live(0);
+    // ---- prologue of the group: Q and dO tiles, delta[q] = sum_d dO[q][d] O[q][d] and the logsumexp of the rows whose
+    // values this lane's accumulator registers hold, the first live K / V tile
+    float dl4[NQT][2][4], lse4[NQT][2][4];
+    {
+      TileRegs tq[NQT], td[NQT];
+#pragma unroll
+      for (int qt = 0; qt < NQT; ++qt) {
+        tq[qt] = load_tile(P.q + (qbase + qt * AT) * P.ldq + h * AD, P.ldq, P.Tq - qt * AT, tid);
+        td[qt] = load_tile(P.dout + (qbase + qt * AT) * P.ldo + h * AD, P.ldo, P.Tq - qt * AT, tid);
+      }
+      const TileRegs tk = load_tile(kp + (int64_t)t * AT * P.ldk, P.ldk, P.Tk - t * AT, tid);
+      const TileRegs tv = load_tile(vp + (int64_t)t * AT * P.ldk, P.ldk, P.Tk - t * AT, tid);
+#pragma unroll
+      for (int qt = 0; qt < NQT; ++qt) {
+        const int q = qt * AT + 32 * w + (lane >> 1), half = lane & 1;
+        float sd = 0.f;
+        if (q < P.Tq) {
+          const bf16_t* a = P.dout + (qbase + q) * P.ldo + h * AD + 32 * half;
+          const bf16_t* b = P.o + (qbase + q) * P.ldo + h * AD + 32 * half;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const bf16x8 x = *reinterpret_cast<const bf16x8*>(a + 8 * i);
+            const bf16x8 y = *reinterpret_cast<const bf16x8*>(b + 8 * i);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sd += (float)x[j] * (float)y[j];
+          }
+        }
+        sd += __shfl_xor(sd, 1, 64);
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int ql = 16 * f + 4 * (lane >> 4) + r;          // row inside the wave's 32
+            dl4[qt][f][r] = __shfl(sd, 2 * ql, 64);
+            const int q2 = qt * AT + 32 * w + ql;
+            lse4[qt][f][r] = q2 < P.Tq ? P.lse[((int64_t)g * P.heads + h) * P.Tq + q2] : 0.f;
+          }
+      }
+      __syncthreads();                     // the previous group is done with every image
+#pragma unroll
+      for (int qt = 0; qt < NQT; ++qt) {
+        store_tile<false>(Qs + qt * TILE_B, tq[qt], tid);
+        store_tile<false>(dOs + qt * TILE_B, td[qt], tid);
+      }
+      store_tile<false>(Ks, tk, tid);
+      store_tile<false>(Vs, tv, tid);
+    }
+    __syncthreads();
+    if (!live_any) {
+      // no live key: softmax is uniform over ALL keys, and the forward's logsumexp is finfo.min itself (log Tk is absorbed),
+      // from which exp(s + mask - lse) would give 1 instead of 1 / Tk: drop the mask and the scores and take lse = log Tk
+      mrow = nullptr;
+      score_scale = 0.f;
+      const float ltk = __logf((float)P.Tk);
+#pragma unroll
+      for (int qt = 0; qt < NQT; ++qt)
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) lse4[qt][f][r] = ltk;
+    }
+    // operands that stay in registers, per query tile: the wave's 32 query rows of Q and dO (phase 1) and the transposed
+    // 16-column slices dO^T / Q^T [d = 16w ..][q] that dV / dK of every key chunk multiply (phase 2)
+    bf16x8 qa[NQT][2][2], da[NQT][2][2], oT[NQT][4], qT[NQT][4];
+    f32x4 aQ[NQT][4][2];
+#pragma unroll
+    for (int qt = 0; qt < NQT; ++qt) {
+#pragma unroll
+      for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          qa[qt][f][s] = frag_row64(Qs + qt * TILE_B, 32 * w + 16 * f, s, lane);
+          da[qt][f][s] = frag_row64(dOs + qt * TILE_B, 32 * w + 16 * f, s, lane);
+        }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        oT[qt][s] = frag_tr64(dOs + qt * TILE_B, 16 * w, s, lane);     // A[row = d][k = q]
+        qT[qt][s] = frag_tr64(Qs + qt * TILE_B, 16 * w, s, lane);
+      }
+#pragma unroll
+      for (int df = 0; df < 4; ++df)
+#pragma unroll
+        for (int f = 0; f < 2; ++f) aQ[qt][df][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // dropout mask shared between neighbouring lanes (see attn_mfma.hip): one hash decides the element pair (q, key & ~1),
+    // (q, key | 1).  Needs an even Tk and a 32-bit pair index that does not wrap inside this (group, head).
+    const uint64_t drop_base = ((uint64_t)g * P.heads + h) * P.Tq * P.Tk;      // dropout counter of (query 0, key 0)
+    const uint64_t pair_base = drop_base >> 1;
+    const uint32_t pb_lo = (uint32_t)pair_base, pb_hi = (uint32_t)(pair_base >> 32);
+    const bool share_hash = P.p > 0.f && (P.Tk & 1) == 0 &&
+                            (uint64_t)pb_lo + (uint64_t)(2 * AT + 2) * (uint64_t)(P.Tk >> 1) + (uint64_t)P.Tk < 0xFFFFFFFFull;
+    const uint32_t hash_k0 = (uint32_t)P.seed ^ ((pb_hi << 7) | (pb_hi >> 25)), hash_s1 = (uint32_t)(P.seed >> 32);
+
+    // dead tiles before the first live one
+#pragma unroll 1
+    for (int cg = 0; cg < 4 * min(t, ntiles); ++cg) finish_chunk(L, kbase, h, w, lane, cg, sm, false, zero4, zero4);
+#pragma unroll 1
+    while (t < ntiles) {
+      const int tn = next_live(t + 1);
+      TileRegs nk, nv;
+      if (PREFETCH && tn < ntiles) {          // next live tile's rows: in flight under this tile's arithmetic
+        nk = load_tile(kp + (int64_t)tn * AT * P.ldk, P.ldk, P.Tk - tn * AT, tid);
+        nv = load_tile(vp + (int64_t)tn * AT * P.ldk, P.ldk, P.Tk - tn * AT, tid);
+      }
+      const int rows = min(AT, P.Tk - t * AT);
+#pragma unroll 1
+      for (int c = 0; 32 * c < rows; ++c) {
+        const int cg = 4 * t + c;               // global chunk index
+        if (skip_dead && !any_live_in(mrow, P.Tk, 32 * cg, 32, lane)) {      // probabilities exactly 0: nothing for dQ, dK = dV = 0
+          finish_chunk(L, kbase, h, w, lane, cg, sm, false, zero4, zero4);
+          continue;
+        }
+        f32x4 aV[2], aK[2];
+#pragma unroll
+        for (int kf = 0; kf < 2; ++kf) { aV[kf] = f32x4{0.f, 0.f, 0.f, 0.f}; aK[kf] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+#pragma unroll
+        for (int qt = 0; qt < NQT; ++qt) {
+          // ---- phase 1 (wave = 32 query rows): Pdrop^T and dS^T [key][q] of (chunk, query tile) into LDS
+          f32x4 sS[2][2], sP[2][2];
+#pragma unroll
+          for (int k4 = 0; k4 < 2; ++k4)
+#pragma unroll
+            for (int f = 0; f < 2; ++f) { sS[k4][f] = f32x4{0.f, 0.f, 0.f, 0.f}; sP[k4][f] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+#pragma unroll
+          for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int k4 = 0; k4 < 2; ++k4) {
+              const bf16x8 kb = frag_row64(Ks, 32 * c + 16 * k4, s, lane);
+              const bf16x8 vb = frag_row64(Vs, 32 * c + 16 * k4, s, lane);
+#pragma unroll
+              for (int f = 0; f < 2; ++f) {
+                sS[k4][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[qt][f][s], kb, sS[k4][f], 0, 0, 0);   // D[q][key]
+                sP[k4][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da[qt][f][s], vb, sP[k4][f], 0, 0, 0);
+              }
+            }
+#pragma unroll
+          for (int k4 = 0; k4 < 2; ++k4) {
+            const int kl = 16 * k4 + (lane & 15), key = 32 * cg + kl;
+            const float mk = (mrow && key < P.Tk) ? mrow[key] : 0.f;
+#pragma unroll
+            for (int f = 0; f < 2; ++f) {
+              f32x4 pdv, dsv;
+              float mult4[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+              if (share_hash) {
+                const unsigned q0 = qt * AT + 32 * w + 16 * f + 4 * (lane >> 4);
+                const uint32_t o0 = pb_lo + __umul24(q0 + 2 * odd, (unsigned)P.Tk >> 1) + ((unsigned)key >> 1);
+                const uint32_t hA = fcmf_hash32_rounds(o0 ^ hash_k0, hash_s1);
+                const uint32_t hB = fcmf_hash32_rounds((o0 + ((unsigned)P.Tk >> 1)) ^ hash_k0, hash_s1);
+                const uint32_t nA = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hA, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]: lane ^ 1
+                const uint32_t nB = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hB, 0xB1, 0xf, 0xf, true);
+                const uint32_t hr[4] = {odd ? nA : hA, odd ? nB : hB, odd ? hA : nA, odd ? hB : nB};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mult4[r] = ((hr[r] >> (16 * odd)) & 0xFFFFu) >= drop_thr ? inv_keep : 0.f;   // (key & 1 == lane & 1)
+              }
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int q = qt * AT + 32 * w + 16 * f + 4 * (lane >> 4) + r;
+                float pr = 0.f, mult = mult4[r];
+                if (key < P.Tk && q < P.Tq) pr = __expf(sS[k4][f][r] * score_scale + mk - lse4[qt][f][r]);
+                if (P.p > 0.f && !share_hash) mult = dropout_mult(P.seed, drop_base + (__umul24((unsigned)q, (unsigned)P.Tk) + (unsigned)key), P.p, inv_keep);
+                pdv[r] = pr * mult;
+                dsv[r] = pr * (sP[k4][f][r] * mult - dl4[qt][f][r]);
+              }
+              const int ch = 4 * w + 2 * f + (lane >> 5);
+              const int o = off128(kl, ch) + ((lane >> 4) & 1) * 8;
+              store4(reinterpret_cast<bf16_t*>(PdT + o), pdv);
+              store4(reinterpret_cast<bf16_t*>(dST + o), dsv);
+            }
+          }
+          __syncthreads();
+          // ---- phase 2: dQ^T[d][q] += K^T[d][keys of the chunk] dS^T[keys][q]  (wave = 32 queries)
+          {
+            bf16x8 tb[2];
+#pragma unroll
+            for (int f = 0; f < 2; ++f) tb[f] = frag_tr128(dST, 32 * w + 16 * f, 0, lane);    // B[k = key][col = q]
+#pragma unroll
+            for (int df = 0; df < 4; ++df) {
+              const bf16x8 ka2 = frag_tr64(Ks, 16 * df, c, lane);                              // A[row = d][k = key]
+#pragma unroll
+              for (int f = 0; f < 2; ++f) aQ[qt][df][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka2, tb[f], aQ[qt][df][f], 0, 0, 0);
+            }
+          }
+          // dV^T / dK^T [d = 16w..][key of the chunk] += dO^T / Q^T [d][q of this tile] x Pdrop / dS [q][key]
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int kf = 0; kf < 2; ++kf) {
+              const bf16x8 pb = frag_row128(PdT, 16 * kf, s, lane);   // B[k = q][col = key]
+              const bf16x8 sb = frag_row128(dST, 16 * kf, s, lane);
+              aV[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oT[qt][s], pb, aV[kf], 0, 0, 0);
+              aK[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qT[qt][s], sb, aK[kf], 0, 0, 0);
+            }
+          __syncthreads();   // the chunk images are rewritten by the next query tile / chunk
+        }
+        finish_chunk(L, kbase, h, w, lane, cg, sm, true, aV, aK);
+      }
+      // dead tiles between this one and the next live one
+#pragma unroll 1
+      for (int cg = 4 * (t + 1); cg < 4 * min(tn, ntiles); ++cg) finish_chunk(L, kbase, h, w, lane, cg, sm, false, zero4, zero4);
+      if (tn < ntiles) {                      // (every wave passed the barrier that ends the tile's last chunk)
+        if (!PREFETCH) {
+          nk = load_tile(kp + (int64_t)tn * AT * P.ldk, P.ldk, P.Tk - tn * AT, tid);
+          nv = load_tile(vp + (int64_t)tn * AT * P.ldk, P.ldk, P.Tk - tn * AT, tid);
+        }
+        store_tile<false>(Ks, nk, tid);
+        store_tile<false>(Vs, nv, tid);
+      }
+      __syncthreads();
+      t = tn;
+    }
+#pragma unroll
+    for (int qt = 0; qt < NQT; ++qt)
+#pragma unroll
+      for (int f = 0; f < 2; ++f) {
+        const int x = qt * AT + 32 * w + 16 * f + (lane & 15);
+        if (x < P.Tq) {
+          const int dcol = h * AD + 4 * (lane >> 4);
+#pragma unroll
+          for (int df = 0; df < 4; ++df) store4(P.dq + (qbase + x) * P.ldq + dcol + 16 * df, aQ[qt][df][f] * P.scale);
+        }
+      }
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void attn_long_bwd_kernel(AttnLongParams L) { attn_long_bwd_body<1>(L); }
+__global__ __launch_bounds__(256, 1) void attn_long_bwd256_kernel(AttnLongParams L) { attn_long_bwd_body<2>(L); }
+
+// =========================================================================================
+static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+constexpr int LONG_MAX_TK = 1 << 20;      // (q * Tk of the dropout counter is a 24-bit multiply; far above any visual token count)
+
+extern "C" int fcmf_attn_mfma_long_fwd(const void* q, const void* k, const void* v, const float* mask, void* out, float* lse,
+                                       int G, int heads, int Tq, int Tk, int kv_share, int64_t ldq, int64_t ldk, int64_t ldo,
+                                       float scale, float dropout_p, uint64_t seed, void* stream) {
+  if (!q || !k || !v || !out || G <= 0 || heads <= 0 || Tq <= 0 || Tk <= 0 || kv_share <= 0 || G % kv_share) return FCMF_ERR_ARG;
+  if (Tq > 2 * AT || Tk > LONG_MAX_TK || ldq % 8 || ldk % 8 || ldo % 4 || !al16(q) || !al16(k) || !al16(v) || !al16(out))
+    return FCMF_ERR_UNSUPPORTED;
+  AttnLongParams L{};
+  AttnMfmaParams& P = L.a;
+  P.q = (const bf16_t*)q; P.k = (const bf16_t*)k; P.v = (const bf16_t*)v; P.mask = mask; P.out = (bf16_t*)out; P.lse = lse;
+  P.G = G; P.heads = heads; P.Tq = Tq; P.Tk = Tk; P.ldq = ldq; P.ldk = ldk; P.ldo = ldo;
+  P.scale = scale; P.p = dropout_p; P.seed = seed;
+  L.kv_share = kv_share;
+  const dim3 grid(G * heads, (Tq + AT - 1) / AT);
+  static bool attr = false;      // (this kernel's dynamic LDS is one constant: its limit is raised once)
+  return fcmf_launch_flagged(&attr, attn_long_fwd_kernel, grid, dim3(256), 2 * TILE_B, reinterpret_cast<hipStream_t>(stream), L);
+}
+
+// bytes of the backward's float32 workspace: running sums of dK | dV, one row per key of every key set
+static int64_t long_bwd_workspace(int G, int heads, int Tk, int kv_share) {
+  return kv_share > 1 ? 2 * (int64_t)(G / kv_share) * Tk * heads * AD * (int64_t)sizeof(float) : 0;
+}
+
+extern "C" int fcmf_attn_mfma_long_bwd(const void* q, const void* k, const void* v, const float* mask, const void* out,
+                                       const void* dout, const float* lse, void* dq, void* dk, void* dv, int G, int heads,
+                                       int Tq, int Tk, int kv_share, int64_t ldq, int64_t ldk, int64_t ldo, float scale,
+                                       float dropout_p, uint64_t seed, float* workspace, int64_t workspace_bytes, void* stream) {
+  if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || G <= 0 || heads <= 0 || Tq <= 0 || Tk <= 0 ||
+      kv_share <= 0 || G % kv_share)
+    return FCMF_ERR_ARG;
+  if (kv_share > 1 && (!workspace || workspace_bytes < long_bwd_workspace(G, heads, Tk, kv_share))) return FCMF_ERR_ARG;
+  if (Tq > 2 * AT || Tk > LONG_MAX_TK || ldq % 8 || ldk % 8 || ldo % 8 || !al16(q) || !al16(k) || !al16(v) || !al16(out) ||
+      !al16(dout) || !al16(dq) || !al16(dk) || !al16(dv) || !al16(workspace))
+    return FCMF_ERR_UNSUPPORTED;
+  AttnLongParams L{};
+  AttnMfmaParams& P = L.a;
+  P.q = (const bf16_t*)q; P.k = (const bf16_t*)k; P.v = (const bf16_t*)v; P.mask = mask; P.o = (const bf16_t*)out;
+  P.dout = (const bf16_t*)dout; P.lse = const_cast<float*>(lse); P.dq = (bf16_t*)dq; P.dk = (bf16_t*)dk; P.dv = (bf16_t*)dv;
+  P.G = G; P.heads = heads; P.Tq = Tq; P.Tk = Tk; P.ldq = ldq; P.ldk = ldk; P.ldo = ldo;
+  P.scale = scale; P.p = dropout_p; P.seed = seed;
+  L.kv_share = kv_share; L.ws = workspace;
+  const dim3 grid((G / kv_share) * heads);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (Tq > AT) {
+    static bool attr2 = false;      // (this kernel's dynamic LDS is one constant: its limit is raised once)
+    return fcmf_launch_flagged(&attr2, attn_long_bwd256_kernel, grid, dim3(256), 7 * TILE_B, st, L);      // 112 KiB: one workgroup per CU
+  }
+  static bool attr = false;
+  return fcmf_launch_flagged(&attr, attn_long_bwd_kernel, grid, dim3(256), 5 * TILE_B, st, L);          // 80 KiB: two per CU
+}

@@ -1342,6 +1342,136 @@ def attention(q, k1=None, v1=None, k2=None, v2=None, mask=None, bias=None, heads
                              next_seed() if p > 0 else 0, causal)
 
 
+class SharedKVAttentionFn(torch.autograd.Function):
+    """MFMA attention over any number of keys, one key/value set per `kv_share` consecutive query groups
+    (fcmf_attn_mfma_long_fwd / _bwd): q [G,Tq,heads*64], k / v [G/kv_share,Tk,heads*64], mask [G,Tk] additive float32."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, heads, kv_share, scale, p, seed):
+        H.require_cuda(q, k, v)
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        mask = None if mask is None else mask.contiguous().float()
+        G, Tq, HD = q.shape
+        Tk = k.shape[1]
+        out = torch.empty_like(q)
+        lse = torch.empty((G, heads, Tq), dtype=torch.float32, device=q.device)
+        H.check(H.lib().fcmf_attn_mfma_long_fwd(H.ptr(q), H.ptr(k), H.ptr(v), H.ptr(mask), H.ptr(out), H.ptr(lse), G, heads, Tq, Tk,
+                                                kv_share, HD, HD, HD, scale, p, seed, H.stream()), "fcmf_attn_mfma_long_fwd")
+        ctx.save_for_backward(q, k, v, mask, out, lse)
+        ctx.cfg = (heads, kv_share, scale, p, seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, mask, out, lse = ctx.saved_tensors
+        heads, kv_share, scale, p, seed = ctx.cfg
+        G, Tq, HD = q.shape
+        Tk = k.shape[1]
+        dout = dout.contiguous()
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        # running float32 sums of dk | dv over the sharing groups (written before they are read: no fill)
+        ws = torch.empty(2 * k.numel(), dtype=torch.float32, device=q.device) if kv_share > 1 else None
+        H.check(H.lib().fcmf_attn_mfma_long_bwd(H.ptr(q), H.ptr(k), H.ptr(v), H.ptr(mask), H.ptr(out), H.ptr(dout), H.ptr(lse),
+                                                H.ptr(dq), H.ptr(dk), H.ptr(dv), G, heads, Tq, Tk, kv_share, HD, HD, HD, scale, p,
+                                                seed, H.ptr(ws), 0 if ws is None else ws.numel() * 4, H.stream()),
+                "fcmf_attn_mfma_long_bwd")
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+class ChunkedF32AttentionFn(torch.autograd.Function):
+    """float32 parity mode of shared_kv_attention for more shared keys than the VALU kernels hold in LDS: the keys go through
+    fcmf_attn_small_fwd in chunks, each with its own logsumexp, and the chunk outputs are merged with the weights
+    exp(lse_chunk - lse) (a few element-wise torch operations on [chunks, G, heads, Tq]: this mode exists to be compared with,
+    not to be fast).  The backward runs fcmf_attn_small_bwd per chunk with the MERGED output and logsumexp, from which the
+    kernel recomputes exactly the global probabilities of the chunk's keys.  q may be a strided view (one sharing member).
+    Not covered: a group without any live key (its chunks would be weighted equally, not by their sizes)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, heads, scale, p, seed, chunk):
+        H.require_cuda(q, k, v)
+        q = q if q.stride(2) == 1 and q.stride(1) >= q.shape[2] else q.contiguous()
+        k, v = k.contiguous(), v.contiguous()
+        G, R, HD = q.shape
+        T = k.shape[1]
+        bounds = [(c, min(c + chunk, T)) for c in range(0, T, chunk)]
+        masks = [None if mask is None else mask[:, a:b].contiguous().float() for a, b in bounds]
+        outs = torch.empty((len(bounds), G, R, HD), dtype=q.dtype, device=q.device)
+        lses = torch.empty((len(bounds), G, heads, R), dtype=torch.float32, device=q.device)
+        for i, (a, b) in enumerate(bounds):
+            d = _desc(q, k[:, a:b], v[:, a:b], None, None, masks[i], None, heads, 1, scale, p, (seed + i) & 0xFFFFFFFFFFFFFFFF, False, 0)
+            H.check(H.lib().fcmf_attn_small_fwd(d, H.ptr(outs[i]), H.ptr(lses[i]), H.stream()), "fcmf_attn_small_fwd")
+        lse = torch.logsumexp(lses, 0)
+        w = torch.exp(lses - lse).transpose(2, 3).unsqueeze(-1)                       # [chunks, G, R, heads, 1]
+        out = (outs.view(len(bounds), G, R, heads, HD // heads) * w).sum(0).view(G, R, HD)
+        ctx.save_for_backward(q, k, v, out, lse, *[m for m in masks if m is not None])
+        ctx.cfg = (heads, scale, p, seed, bounds, mask is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, *masks = ctx.saved_tensors
+        heads, scale, p, seed, bounds, has_mask = ctx.cfg
+        G, R, HD = q.shape
+        dout = dout.contiguous()
+        dq = torch.zeros((G, R, HD), dtype=q.dtype, device=q.device)
+        dk, dv = torch.empty_like(k), torch.empty_like(v)
+        for i, (a, b) in enumerate(bounds):
+            d = _desc(q, k[:, a:b], v[:, a:b], None, None, masks[i] if has_mask else None, None, heads, 1, scale, p,
+                      (seed + i) & 0xFFFFFFFFFFFFFFFF, False, 0)
+            dqc = torch.empty(((b - a + 127) // 128, G, R, HD), dtype=q.dtype, device=q.device)
+            dkc = torch.empty((G, b - a, HD), dtype=q.dtype, device=q.device)
+            dvc = torch.empty((G, b - a, HD), dtype=q.dtype, device=q.device)
+            H.check(H.lib().fcmf_attn_small_bwd(d, H.ptr(out), H.ptr(dout), H.ptr(lse), H.ptr(dqc), H.ptr(dkc), H.ptr(dvc), None, None,
+                                                None, H.stream()), "fcmf_attn_small_bwd")
+            dq += _sum_leading(dqc)
+            dk[:, a:b], dv[:, a:b] = dkc, dvc
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def shared_kv_attention(q, k, v, mask=None, heads=12, kv_share=1, scale=None, p=0.0, training=False):
+    """softmax(scale q k^T + mask) v where group g of q [G,Tq,HD] reads key set g // kv_share of k / v [G/kv_share,Tk,HD]
+    (the aspect prompts of a review share its visual tokens); mask [G,Tk] additive.  bf16 with head dim 64: the long-key
+    MFMA kernel, any Tk.  float32 (the parity mode): the VALU kernels, one `attention` call per sharing member on a
+    strided view of q; autograd sums the members' key gradients in float32.  Up to valu_float32_key_limit(d) keys (285 at
+    head dim 64: the float32 K / V images of a head must fit in LDS) the keys go in one piece, beyond that in chunks of 256
+    merged by their logsumexps (ChunkedF32AttentionFn)."""
+    G, Tq, HD = q.shape
+    d = HD // heads
+    scale = 1.0 / math.sqrt(d) if scale is None else scale
+    p = float(p) if training else 0.0
+    if (kv_share < 1 or G % kv_share or k.shape != v.shape or k.shape[0] * kv_share != G or k.shape[2] != HD
+            or k.dtype != q.dtype or v.dtype != q.dtype or (mask is not None and tuple(mask.shape) != (G, k.shape[1]))):
+        raise H.HipLibraryError(f"shared_kv_attention: q {tuple(q.shape)} / k {tuple(k.shape)} / v {tuple(v.shape)} do not "
+                                f"form {kv_share} query groups per key set")
+    if q.dtype == torch.bfloat16 and d * heads == HD and d == 64:
+        return SharedKVAttentionFn.apply(q, k, v, mask, heads, kv_share, float(scale), p, next_seed() if p > 0 else 0)
+    if q.dtype == torch.float32 and d <= 128:
+        # one call per sharing member on a strided view of q; the keys in one piece while the VALU kernels hold them in LDS,
+        # else in chunks of 256 merged by their logsumexps
+        seeds = [next_seed() if p > 0 else 0 for _ in range(kv_share)]
+        view = lambda m: (q[m::kv_share], k, v, None if mask is None else mask[m::kv_share])
+        if k.shape[1] <= valu_float32_key_limit(d):
+            outs = [AttentionFn.apply(*view(m)[:3], None, None, view(m)[3], None, heads, 1, float(scale), p, seeds[m], False)
+                    for m in range(kv_share)]
+        else:
+            outs = [ChunkedF32AttentionFn.apply(*view(m), heads, float(scale), p, seeds[m], min(256, valu_float32_key_limit(d)))
+                    for m in range(kv_share)]
+        return torch.stack(outs, 1).reshape(G, Tq, HD)
+    raise H.HipLibraryError(f"shared_kv_attention: unsupported configuration ({q.dtype}, head dim {d}): bf16 with head dim 64, "
+                            "or float32 with head dim <= 128")
+
+
+def valu_float32_key_limit(d):
+    """most shared keys the float32 VALU attention takes at head dim d: its K and V images (rows of d + 4 floats), the waves'
+    score rows and one query row must fit the 160 KiB of LDS (fcmf_attn_small_fwd), and never more than its 512-key limit"""
+    def fits(T):
+        return 4 * (2 * T * (d + 4) + 4 * 64 * (4 if T <= 256 else 8) + d) <= 160 * 1024
+    T = 512
+    while T > 0 and not fits(T):
+        T -= 1
+    return T
+
+
 def attention_probs(q, k1=None, k2=None, mask=None, bias=None, heads=12, group_div=1, scale=None, causal=False,
                     head_quirk=False, slot_major=False, out=None):
     """softmax(score) of `attention` / fcmf_attn_desc as float32, before dropout, recomputed from q and the keys (no values, no

@@ -111,3 +111,57 @@ class ReviewProducer:
         if self.cache is not None:
             return self.cache[index]
         return self.pixels(photos)
+
+
+# ---- text layouts of the comparison baselines (mRoBERTa, TomBERT, EF-CapTrRoBERTa) ---------------------------------------
+TARGET_LEN = 16
+NO_CAPTION = "hình ảnh bình thường"      # the caption EF-CapTr uses for a review without captioned photos
+
+
+def _ids_mask(tok):
+    as_t = lambda k: torch.as_tensor(tok[k]).reshape(-1)
+    return as_t('input_ids'), as_t('attention_mask')
+
+
+def sentence_prompt(tokenizer, aspect, text, max_len=SEQ_LEN):
+    """TomBERT's sentence and mRoBERTa's only input: "<aspect> </s></s> <review>", lower-cased, '_' -> ' ', `max_len` positions
+    (train_tomroberta_vimacsa_full.py:145-146; mRoBERTa's tokenizer pair call, train_mroberta_vimacsa_full.py:146-153, puts the
+    same separators between the same two texts) -> (input_ids, attention_mask)"""
+    sentence = f"{display_name(aspect)} </s></s> {text}".lower().replace('_', ' ')
+    return _ids_mask(tokenizer(sentence, max_length=max_len, padding='max_length', truncation=True))
+
+
+def target_prompt(tokenizer, aspect, max_len=TARGET_LEN):
+    """TomBERT's target: the aspect name alone, 16 positions (train_tomroberta_vimacsa_full.py:141-142)"""
+    return _ids_mask(tokenizer(display_name(aspect).lower(), max_length=max_len, padding='max_length', truncation=True))
+
+
+def caption_string(photos, caption_dict, num_img):
+    """captions of the first num_img photos, looked up by name and then by base name, joined with ". "
+    (train_ef_captr_roberta.py:69-79)"""
+    caps = []
+    for name in list(photos or [])[:num_img]:
+        cap = caption_dict.get(name) or caption_dict.get(os.path.basename(name))
+        if cap:
+            caps.append(cap)
+    return ". ".join(caps) if caps else NO_CAPTION
+
+
+def caption_pair(tokenizer, aspect, text, captions, max_len):
+    """EF-CapTr's pair (review, "<aspect> . <captions>") at `max_len` positions (train_ef_captr_roberta.py:95-106)"""
+    second = f"{aspect.replace('_', ' ')} . {captions}"
+    return _ids_mask(tokenizer(text, second, max_length=max_len, padding='max_length', truncation=True))
+
+
+def polarity_labels(annotations, aspects=ASPECTS, first_wins=True):
+    """"Aspect#Polarity" annotations -> one label per aspect in the fixed order, None (0) where absent.  mRoBERTa / TomBERT
+    keep the FIRST mention of an aspect (list.index, train_mroberta_vimacsa_full.py:121-141), EF-CapTr the LAST (a dict that
+    is overwritten, train_ef_captr_roberta.py:83-86)."""
+    polarity = {}
+    for item in annotations:
+        asp, pol = item.split("#")
+        if first_wins:
+            polarity.setdefault(display_name(asp), pol)
+        else:
+            polarity[display_name(asp)] = pol
+    return torch.tensor([POLARITY[polarity.get(display_name(a), "None")] for a in aspects])
