@@ -243,6 +243,24 @@ int fcmf_bertscore(const void* cand, const void* ref, const int* cand_len, const
                    int64_t ldr, int64_t sr, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * log-softmax + top-k of the rows of a logits matrix, one launch: the tail of an IAOG decode step (the reference's
+ * `log_softmax(logits)` + `topk(beam_size)`, fcmf_pretraining.py:476-480), for `rows` independent rows at once.
+ *   logits [rows, ld] in `dtype` (FCMF_F32 / FCMF_BF16), row r at logits + r*ld (elements); only columns 0 .. V-1 are ever
+ *   loaded (ld >= V: the column padding 64001 -> 64032 of the bf16 vocabulary projection may hold anything, NaN included);
+ *   lse[r] = log sum_{j<V} exp(x[r,j]), float32, the row maximum subtracted;
+ *   ids  int32   [rows, k]: the columns of the k largest entries of the row, by stored value descending, the LOWER column first
+ *                among equal values (= a stable descending sort of the row).  The selection compares stored values, so it
+ *                carries no rounding;
+ *   logp float32 [rows, k]: x[r, ids] - lse[r].  An entry -inf has log-probability -inf and sorts last.
+ * A row of only -inf, or one holding NaN, is undefined (as for torch).  Fixed-order reductions, no atomics: two launches give
+ * the same bits.  Rows that are 16-byte aligned (logits and ld * element size multiples of 16) are read 16 bytes per lane,
+ * any other layout one element per lane.
+ * Limits: 1 <= k <= 16, k <= V, dtype FCMF_F32 / FCMF_BF16 -- FCMF_ERR_UNSUPPORTED otherwise; NULL pointers, rows < 0 or ld < V
+ * are FCMF_ERR_ARG; rows == 0 succeeds without a launch. */
+int fcmf_logsoftmax_topk(const void* logits, int64_t ld, int rows, int V, int k, float* logp, int32_t* ids, int dtype,
+                         void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * y = LayerNorm(dropout(x) + res) * gamma + beta   (eps inside the sqrt, biased variance)
  * Replaces BertSelfOutput/BertOutput/AddNorm + FCMFLayerNorm (mm_modeling.py:158-171,
  * 276-280,324-328,566-573) and HF nn.LayerNorm(eps=1e-5).

@@ -14,11 +14,18 @@ What the reference's loop does, and what this module does with it on the GPU:
   * scores are Python floats summed in the reference's order; candidates are sorted by score, descending and stable (:493).
 Batch size 1 per decoder call, as in the reference: the decoder `Attention`'s slot -> head pairing depends on the batch
 size (mm_modeling.py:79-85), so stacking beams into one call would change the arithmetic.
+
+`beam_search_batch` / `beam_search_ids_batch` advance a whole eval batch one beam round per decoder call instead.  At batch size
+1 the pairing is the plain one (slot s reads head s), so the (sample, last token) rows of every sample's live beams that the memo
+does not hold yet go through ONE `IAOGDecoder.decode_step` with the plain pairing per row -- the batch-1 result of each row, one
+vocabulary GEMM with M = rows, log-softmax + top-k in one HIP kernel (csrc/topk.hip: no eager log_softmax / topk), one host read per
+round.  The beam rules per sample are `beam_search_ids`'s, unchanged: `beam_rounds` is that loop over many samples with the
+device step behind a callable.
 """
 import torch
 import torch.nn.functional as F
 
-__all__ = ["beam_search", "beam_search_ids"]
+__all__ = ["beam_search", "beam_search_ids", "beam_search_batch", "beam_search_ids_batch", "beam_rounds"]
 
 
 @torch.no_grad()
@@ -76,3 +83,82 @@ def beam_search(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_emb
     ids, _, _ = beam_search_ids(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds,
                                 roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len)
     return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip()]
+
+
+def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=20):
+    """the loop of `beam_search_ids` for `num_samples` samples side by side, on the host alone.  Per round: the (sample, last token)
+    pairs of every live beam of every unfinished sample that the memo does not hold are collected (each once, in order of first
+    appearance) and handed to ONE call step_many(pairs) -> {pair: (top log-probabilities, top ids)} (Python lists of at least
+    beam_size entries); then every sample advances by exactly `beam_search_ids`'s rules: the same candidate order, the same stable
+    sort, the same finishing rules, Python-float sums in the same order.  A sample whose beams are finished drops out.
+    -> [(ids of the best sequence incl. the start token, its score, the finished list [(score, ids)])], one entry per sample"""
+    memo = {}
+    beams = [[(0.0, [int(start_id)])] for _ in range(num_samples)]
+    final = [[] for _ in range(num_samples)]
+    live = list(range(num_samples))
+    for _ in range(max_len):
+        if not live:
+            break
+        need = []
+        for b in live:
+            for _, seq in beams[b]:
+                pair = (b, seq[-1])
+                if seq[-1] != sep_id and pair not in memo and pair not in need:
+                    need.append(pair)
+        if need:
+            memo.update(step_many(need))
+        still = []
+        for b in live:
+            cands = []
+            for score, seq in beams[b]:
+                if seq[-1] == sep_id:                         # finished beams leave the search (:444-447)
+                    final[b].append((score, seq))
+                    continue
+                top_s, top_i = memo[(b, seq[-1])]
+                for k in range(beam_size):
+                    cands.append((score + top_s[k], seq + [top_i[k]]))
+            if not cands:
+                continue
+            beams[b] = sorted(cands, key=lambda c: c[0], reverse=True)[:beam_size]
+            if all(seq[-1] == sep_id for _, seq in beams[b]):  # (:500-502)
+                final[b].extend(beams[b])
+                continue
+            still.append(b)
+        live = still
+    out = []
+    for b in range(num_samples):
+        fin = final[b] if final[b] else list(beams[b])        # nothing finished within max_len (:505-506)
+        best_score, best_seq = sorted(fin, key=lambda c: c[0], reverse=True)[0]
+        out.append((best_seq, best_score, fin))
+    return out
+
+
+@torch.no_grad()
+def beam_search_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
+                          beam_size=3, max_len=20):
+    """`beam_search_ids` of every sample of a batch ([B, ...] tensors), one decoder call per beam round for all of them: the encoder
+    and `project_encoder` run once for the batch.  -> [(ids, score, final)], one entry per sample"""
+    model.eval()
+    enc = model.encoder(enc_ids, vis_embeds, roi_embeds, roi_coors, enc_type, enc_mask, add_mask)
+    enc = enc[0] if isinstance(enc, tuple) else enc
+    dec = model.decoder
+    keys = dec.project_encoder(enc)
+    device = enc.device
+
+    def step_many(pairs):
+        idx = torch.tensor(pairs, device=device, dtype=torch.long)          # [n, 2]: (sample, token)
+        logp, ids = dec.decode_step(idx[:, 1].contiguous(), idx[:, 0].contiguous(), enc, keys, beam_size)
+        both = torch.cat((logp, ids.view(torch.float32)), dim=1).cpu()      # ONE host read: the ids ride along as their bits
+        top_s, top_i = both[:, :beam_size].tolist(), both[:, beam_size:].contiguous().view(torch.int32).tolist()
+        return {p: (s, i) for p, s, i in zip(pairs, top_s, top_i)}
+
+    return beam_rounds(step_many, enc_ids.shape[0], start_id, sep_id, beam_size, max_len)
+
+
+def beam_search_batch(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
+                      beam_size=3, max_len=20):
+    """-> [decoded text of the best sequence], one per sample of the batch (what `beam_search` returns per sample, [0])"""
+    start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
+    res = beam_search_ids_batch(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds,
+                                roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len)
+    return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip() for ids, _, _ in res]

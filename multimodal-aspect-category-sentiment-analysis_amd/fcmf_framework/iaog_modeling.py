@@ -19,12 +19,13 @@ from . import _hip as H
 from . import layers, ops
 
 
-def _quirk_attn_fwd(qx, kx, heads, causal):
-    """qx [G, R, heads*d], kx [G, T, heads*d] (row strides arbitrary, unit inner stride) -> out [G, R, heads*d] dense, lse"""
+def _quirk_attn_fwd(qx, kx, heads, causal, head_quirk=1):
+    """qx [G, R, heads*d], kx [G, T, heads*d] (row strides arbitrary, unit inner stride) -> out [G, R, heads*d] dense, lse.
+    head_quirk 0: the plain pairing, slot s reads head s -- what the reference's pairing is at batch size 1 (decode_step)"""
     G, R, HD = qx.shape
     out = torch.empty((G, R, HD), dtype=qx.dtype, device=qx.device)
     lse = torch.empty((G, heads, R), dtype=torch.float32, device=qx.device)
-    a = ops._desc(qx, kx, kx, None, None, None, None, heads, 1, 1.0 / math.sqrt(HD // heads), 0.0, 0, causal, 1)
+    a = ops._desc(qx, kx, kx, None, None, None, None, heads, 1, 1.0 / math.sqrt(HD // heads), 0.0, 0, causal, head_quirk)
     H.check(H.lib().fcmf_attn_small_fwd(a, H.ptr(out), H.ptr(lse), H.stream()), "fcmf_attn_small_fwd")
     return out, lse
 
@@ -327,6 +328,39 @@ class IAOGDecoder(nn.Module):
         the vocabulary projection and the loss fused: the [B, Ld, V] logits are never handed out"""
         X = self.hidden_states(X, state, enc_attention_mask, True)
         return ops.vocab_cross_entropy(X, self.dense.weight, self.dense.bias, labels, ignore_index)
+
+    @torch.no_grad()
+    def decode_step(self, tokens, sample_idx, enc, keys, k):
+        """the is_train=False step of n INDEPENDENT rows in one pass: row i is what forward(tensor([[tokens[i]]]),
+        init_state(enc[s:s+1], None), is_train=False, hoisted = keys of sample s) computes for s = sample_idx[i] -- position 0, no
+        mask on either attention -- followed by log_softmax + topk(k).  At batch size 1 the reference's slot -> head pairing is the
+        plain one (slot s reads head (s*1 + 0) % n_head = s), so the n rows share every GEMM and the cross attention runs with
+        head_quirk 0 (the one-key self attention needs no launch); stacking them into an ordinary batch would pair slots with other heads (mm_modeling.py:79-85).
+        tokens, sample_idx: int64 [n] on the device; enc [Bs, T, H]; keys = project_encoder(enc), formed here when None.
+        -> (log-probabilities float32 [n, k], token ids int32 [n, k]) (ops.vocab_topk); no attention weights are kept.  Dropout is
+        off whatever the module's mode: this is the evaluation step."""
+        n = tokens.shape[0]
+        if keys is None:
+            keys = self.project_encoder(enc)
+        X = _ScaledEmbedding.apply(tokens.view(n, 1), self.embedding.weight, self.pos_encoding.P, math.sqrt(self.num_hiddens),
+                                   ops.compute_dtype())                              # [n, 1, H]: every row at position 0
+        def add_norm(an, x, y):                                                      # AddNorm in eval mode, whatever self.training says
+            return ops.add_layer_norm(y, x, an.ln.weight, an.ln.bias, an.ln.variance_epsilon, 0.0, False)
+
+        for blk, kx in zip(self.blks, keys):
+            a1, a2 = blk.attention1, blk.attention2
+            nh = a1.n_head
+            # self attention of a one-token row: ONE key, so its softmax is 1 and, values being the keys (mm_modeling.py:129) and the
+            # pairing plain, the output IS the token's kx -- bit for bit what the kernel would return (1 * kx).  No w_qx product and
+            # no attention launch for it.
+            o = ops.head_project(ops._rows(X), [a1.w_kx]).view(n, 1, -1)
+            HD = o.shape[2]
+            Y = add_norm(blk.addnorm1, X, ops.linear(o, a1.proj.weight, a1.proj.bias))
+            qx = ops.head_project(ops._rows(Y), [a2.w_qx]).view(n, 1, HD)
+            o, _ = _quirk_attn_fwd(qx, kx.index_select(0, sample_idx), nh, False, head_quirk=0)      # [n, T, HD] gather: T = 1 + 2*num_imgs rows each
+            Z = add_norm(blk.addnorm2, Y, ops.linear(o, a2.proj.weight, a2.proj.bias))
+            X = add_norm(blk.add_norm3, Z, blk.ffn(Z))
+        return ops.vocab_topk(X.view(n, -1), self.dense.weight, self.dense.bias, k)
 
     @property
     def attention_weights(self):

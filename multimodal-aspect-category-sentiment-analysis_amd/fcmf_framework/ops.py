@@ -83,6 +83,7 @@ def next_seed():
 
 
 VOCAB_PAD = 32   # row padding of ragged 2-D weights (one MFMA k-tile)
+TOPK_MAX = 16    # fcmf_logsoftmax_topk's limit on k (include/fcmf_hip.h)
 
 
 class _Shadows:
@@ -1009,6 +1010,50 @@ class VocabCrossEntropyFn(torch.autograd.Function):
 def vocab_cross_entropy(x, weight, bias, labels, ignore_index=-100):
     """mean CE of the vocabulary projection of x over the non-ignored positions (torch CrossEntropyLoss semantics)"""
     return VocabCrossEntropyFn.apply(x, weight, bias, labels, int(ignore_index))
+
+
+def logsoftmax_topk(logits, V, k):
+    """logits [n, >= V] (unit inner stride, any row stride; columns >= V are never read) -> (log-probabilities float32 [n, k], column
+    indices int32 [n, k]) of the k largest entries of every row's first V columns, by value descending, the lower column first
+    among equals: log_softmax + topk in one launch (fcmf_logsoftmax_topk, include/fcmf_hip.h)"""
+    H.require_cuda(logits)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] < V:
+        raise H.HipLibraryError(f"logsoftmax_topk: want [n, >= {V}] rows with unit inner stride, got {tuple(logits.shape)} / {logits.stride()}")
+    n = logits.shape[0]
+    ld = logits.stride(0) if n > 1 else max(logits.stride(0), V)      # (one row: its stride means nothing)
+    if ld < V:
+        raise H.HipLibraryError(f"logsoftmax_topk: rows overlap (row stride {ld} < {V} columns)")
+    logp = torch.empty((n, k), dtype=torch.float32, device=logits.device)
+    ids = torch.empty((n, k), dtype=torch.int32, device=logits.device)
+    if n == 0:
+        return logp, ids
+    H.check(H.lib().fcmf_logsoftmax_topk(H.ptr(logits), ld, n, V, k, H.ptr(logp), H.ptr(ids), H.dt(logits),
+                                         H.stream()), "fcmf_logsoftmax_topk")
+    return logp, ids
+
+
+@torch.no_grad()
+def vocab_topk(x, weight, bias, k):
+    """the k most probable tokens of every row of x [n, K] under softmax(x W^T + b), weight [V, K] -> (log-probabilities float32
+    [n, k], token ids int32 [n, k]).  No autograd: the decode step.  The projection is VocabCrossEntropyFn.forward's (bf16 and a ragged
+    vocabulary: the row-padded weight shadow into a column-padded [n, Vp] buffer; else the plain weight), and the kernel reads that
+    buffer with its row stride -- no compaction copy to [n, V], no log-softmax round trip."""
+    x2 = _rows(x)
+    V, K = weight.shape
+    M = x2.shape[0]
+    if x2.dtype == torch.bfloat16 and V % VOCAB_PAD != 0:
+        w = shadows.padded(weight)                     # [Vp, K] bf16, rows >= V zero
+    else:
+        w = as_compute(weight, x2.dtype)
+    Vp = w.shape[0]
+    bp = None
+    if bias is not None:
+        bp = bias.detach()
+        if Vp != V:      # zero-padded once per parameter version, not per decode step (the parameter persists: shadows.derived)
+            bp = shadows.derived(bias, ("vocab_pad", Vp), lambda b: torch.cat((b.float(), b.new_zeros(Vp - V, dtype=torch.float32))))
+    logits = torch.empty((M, Vp), dtype=x2.dtype, device=x2.device)
+    gemm(x2, w, logits, M, Vp, K, _ld(x2), K, Vp, 0, 0, bias=bp)
+    return logsoftmax_topk(logits, V, k)
 
 
 class FFNFn(torch.autograd.Function):

@@ -72,6 +72,8 @@ def build_parser():
     p.add_argument("--do_eval", action='store_true')
     p.add_argument("--train_batch_size", default=16, type=int)
     p.add_argument("--eval_batch_size", default=16, type=int)
+    p.add_argument("--batched_decode", action='store_true',
+                   help="--do_eval: decode a whole eval batch per decoder call (decoding.beam_search_batch) instead of sample by sample")
     p.add_argument("--learning_rate", default=3e-5, type=float)
     p.add_argument("--adam_epsilon", default=1e-8, type=float)
     p.add_argument("--num_train_epochs", default=8.0, type=float)
@@ -112,6 +114,9 @@ def scorer_dir(args):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     bert_score_dir = scorer_dir(args) if args.do_eval else None
+    if args.do_eval and args.batched_decode and not 1 <= args.beam_size <= ops.TOPK_MAX:      # before anything is trained
+        raise ValueError(f"--batched_decode: --beam_size {args.beam_size} is outside the top-k kernel's 1 .. {ops.TOPK_MAX}; "
+                         f"decode without --batched_decode")
     rank, _, world, device, master, logger = init_run(args, "iaog", "pretraining_iaog.log", script="run_pretraining_fcmf.py")
 
     tokenizer = None
@@ -289,7 +294,8 @@ def main(argv=None):
             model.eval()
             if r_img is not None:
                 r_img.eval(); r_roi.eval()
-            preds, refs, results = generate(model, tokenizer, batches, features, args.beam_size, args.max_len_decoder, aspects)
+            preds, refs, results = generate(model, tokenizer, batches, features, args.beam_size, args.max_len_decoder, aspects,
+                                               batched=args.batched_decode)
             per_aspect, macro = macro_bertscore(preds, refs, aspects, score_fn)
             return per_aspect, macro, results
     elif args.do_eval and master:

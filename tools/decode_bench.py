@@ -1,0 +1,138 @@
+"""Benchmark of the IAOG beam-search decode: the per-sample path (decoding.beam_search_ids, one batch-1 decoder call per new
+(sample, last token)) next to the batched path (decoding.beam_search_ids_batch, one IAOGDecoder.decode_step per beam round for the
+whole eval batch), on a synthetic FCMFSeq2Seq at the real geometry: H 768, 12 heads, 12 blocks, V 64001, 7 images, bf16,
+--beam_size 2, --max_len_decoder 20, at 16 and 64 samples per batch.  Also the kernel alone: fcmf_logsoftmax_topk next to eager
+log_softmax + topk on the same [n, 64032] bf16 buffer (V = 64001 columns valid).
+Usage (GPU box, repo root):  python tools/decode_bench.py [--samples 16 64] [--beam_size 2] [--max_len_decoder 20]
+Prints one JSON line.  Decode: wall time per eval batch between device synchronisations, median of 5 (min, max beside it), both
+paths warmed up once per batch size and alternating, the number of decoder calls of each path, and whether the two paths decoded
+the same token sequences.  Kernel: median microseconds of 9 windows of 50 calls between device events, alternating."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.join(os.getcwd(), "multimodal-aspect-category-sentiment-analysis_amd"))
+import torch
+import torch.nn.functional as F
+
+import synthetic_data as synth
+from fcmf_framework import decoding, ops
+from fcmf_framework.fcmf_pretraining import FCMFSeq2Seq
+from fcmf_framework.roberta import RobertaConfig, RobertaModel
+
+p = argparse.ArgumentParser()
+p.add_argument("--samples", type=int, nargs="+", default=[16, 64])
+p.add_argument("--beam_size", type=int, default=2)
+p.add_argument("--max_len_decoder", type=int, default=20)
+p.add_argument("--seq_len", type=int, default=64)
+p.add_argument("--num_rois", type=int, default=4)
+args = p.parse_args()
+
+assert torch.cuda.is_available(), "decode_bench.py measures on the MI355X: no GPU, no number"
+dev = torch.device("cuda:0")
+cfg = synth.BASE_CFG
+V, NI, SEP = cfg["vocab_size"], 7, 2
+torch.manual_seed(0)
+hf = tempfile.mkdtemp(prefix="hf_")
+RobertaModel(RobertaConfig(**cfg)).save_pretrained(hf)
+model = FCMFSeq2Seq(V, args.max_len_decoder, hf, NI, args.num_rois, 1.0).to(dev).eval()
+ops.set_compute_dtype(torch.bfloat16)
+dec = model.decoder
+
+calls = {"forward": 0, "decode_step": 0}
+_fwd, _step = dec.forward, dec.decode_step
+
+
+def counted(name, fn):
+    def run(*a, **k):
+        calls[name] += 1
+        return fn(*a, **k)
+    return run
+
+
+dec.forward, dec.decode_step = counted("forward", _fwd), counted("decode_step", _step)
+
+
+def batch_args(B):
+    b = synth.synth_batch(B, cfg, S=args.seq_len, num_imgs=NI, num_roi=args.num_rois, num_aspects=1, seed=B, coord_dtype=torch.float32)
+    b = {k: v.to(dev) for k, v in b.items()}
+    return (b["input_ids"][:, 0], b["attention_mask"][:, 0], b["token_type_ids"][:, 0], b["added_attention_mask"][:, 0],
+            b["visual_embeds_att"], b["roi_embeds_att"], b["roi_coors"])
+
+
+def per_sample(a):
+    return [decoding.beam_search_ids(model, 0, SEP, *(t[i] for t in a), beam_size=args.beam_size, max_len=args.max_len_decoder)[0]
+            for i in range(a[0].shape[0])]
+
+
+def batched(a):
+    return [r[0] for r in decoding.beam_search_ids_batch(model, 0, SEP, *a, beam_size=args.beam_size, max_len=args.max_len_decoder)]
+
+
+def timed(fn, a):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn(a)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def stats(ts):
+    return dict(median_ms=round(statistics.median(ts) * 1e3, 1), min_ms=round(min(ts) * 1e3, 1), max_ms=round(max(ts) * 1e3, 1))
+
+
+res = {"geometry": dict(H=cfg["hidden_size"], heads=cfg["num_attention_heads"], blocks=cfg["num_hidden_layers"], V=V, num_imgs=NI,
+                        dtype="bf16", beam_size=args.beam_size, max_len=args.max_len_decoder), "decode": [], "kernel": []}
+for B in args.samples:
+    a = batch_args(B)
+    ids_one, ids_many = per_sample(a), batched(a)                         # warm-up of every shape of both paths
+    times = {"per_sample": [], "batched": []}
+    for _ in range(5):
+        for k in calls:
+            calls[k] = 0
+        times["per_sample"].append(timed(per_sample, a)[0])
+        n_one = dict(calls)
+        for k in calls:
+            calls[k] = 0
+        times["batched"].append(timed(batched, a)[0])
+        n_many = dict(calls)
+    res["decode"].append({"samples_per_batch": B, "per_sample": stats(times["per_sample"]), "batched": stats(times["batched"]),
+                          "decoder_calls": {"per_sample": n_one["forward"], "batched": n_many["decode_step"]},
+                          "same_sequences": sum(x == y for x, y in zip(ids_one, ids_many)), "mean_len": sum(map(len, ids_many)) / B})
+
+# ---- the kernel alone
+Vp = (V + ops.VOCAB_PAD - 1) // ops.VOCAB_PAD * ops.VOCAB_PAD
+
+
+def window(fn, reps=50):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(reps):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / reps * 1e3
+
+
+for n in sorted({B * args.beam_size for B in args.samples}):
+    x = (torch.randn(n, Vp, generator=torch.Generator().manual_seed(n)) * 3).to(dev).bfloat16()
+    kernel = lambda: ops.logsoftmax_topk(x, V, args.beam_size)
+    eager = lambda: torch.topk(F.log_softmax(x[:, :V].float(), dim=-1), args.beam_size)
+    for fn in (kernel, eager):
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    t = {"kernel": [], "eager": []}
+    for _ in range(9):
+        t["kernel"].append(window(kernel))
+        t["eager"].append(window(eager))
+    (kl, ki), (el, ei) = kernel(), eager()
+    res["kernel"].append({"rows": n, "ld": Vp, "k": args.beam_size,
+                          "kernel_us": round(statistics.median(t["kernel"]), 1), "kernel_us_min_max": [round(min(t["kernel"]), 1), round(max(t["kernel"]), 1)],
+                          "eager_us": round(statistics.median(t["eager"]), 1), "eager_us_min_max": [round(min(t["eager"]), 1), round(max(t["eager"]), 1)],
+                          "same_ids": bool(torch.equal(ki.long(), ei)), "max_abs_diff": float((kl - el).abs().max())})
+print(json.dumps(res))
