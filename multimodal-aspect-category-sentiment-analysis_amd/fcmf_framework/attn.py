@@ -1,0 +1,106 @@
+"""The one way from attention operands to a launch: a descriptor (fcmf_attn_desc, include/fcmf_hip.h), the MFMA / VALU choice
+made from the descriptor's own fields, and one function per kernel pair.  ops, fused and iaog_modeling normalise their
+operands, build a descriptor here and call these; nothing else in the package launches an fcmf_attn_small / _mfma / _probs
+kernel or fills an AttnDesc."""
+import torch
+
+from . import _hip as H
+
+USE_MFMA_ATTENTION = True   # the single switch: tests and tools turn it off to compare the MFMA kernels with the VALU kernels
+
+
+def desc(q, k1, v1, k2, v2, mask, bias, heads, group_div, scale, p, seed, causal, head_quirk):
+    """q [G,R,heads*d]; k1 / v1 [G,T1,heads*d] shared by the R rows of a group; k2 / v2 [G/group_div,R,T2,heads*d] private per
+    row (V is read with K's strides); mask, bias contiguous float32.  Shapes, strides and addresses only: nothing is launched."""
+    G, R, HD = q.shape
+    d = HD // heads
+    T1 = 0 if k1 is None else k1.shape[1]
+    T2 = 0 if k2 is None else k2.shape[2]
+    a = H.AttnDesc()
+    a.dtype, a.G, a.heads, a.d, a.R, a.T1, a.T2, a.group_div = H.dt(q), G, heads, d, R, T1, T2, group_div
+    a.q_sg, a.q_sr = q.stride(0), q.stride(1)
+    if k1 is not None:
+        a.k1_sg, a.k1_st = k1.stride(0), k1.stride(1)
+    if k2 is not None:
+        a.k2_sg, a.k2_sr, a.k2_st = k2.stride(0), k2.stride(1), k2.stride(2)
+    a.o_sg, a.o_sr = R * HD, HD
+    a.q, a.k1, a.v1, a.k2, a.v2, a.mask, a.bias = H.ptr(q), H.ptr(k1), H.ptr(v1), H.ptr(k2), H.ptr(v2), H.ptr(mask), H.ptr(bias)
+    a.scale, a.dropout_p, a.seed, a.causal, a.head_quirk = scale, p, seed, int(causal), int(head_quirk)
+    return a
+
+
+def mfma_eligible(a):
+    """the text-encoder shape (bf16, head dim 64, <= 256 queries and shared keys, plain mask) goes to the MFMA kernels.  They
+    address row t of group g at (g*T + t)*ld: callers whose operands are not column blocks of [G*T, ld] buffers demand dense ones."""
+    return (USE_MFMA_ATTENTION and a.dtype == H.BF16 and a.d == 64 and a.T2 == 0 and a.k1 is not None and a.bias is None
+            and not a.causal and not a.head_quirk and a.T1 <= 256 and a.R <= 256)
+
+
+def _ld(a):
+    """-> ldq, ldk of the MFMA kernels: the row strides; a group of ONE row has none of its own ((g*1 + 0)*ld: its group stride)"""
+    return (a.q_sr if a.R > 1 else a.q_sg), (a.k1_st if a.T1 > 1 else a.k1_sg)
+
+
+def forward(a, out, lse, mfma):
+    if mfma:
+        H.check(H.lib().fcmf_attn_mfma_fwd(a.q, a.k1, a.v1, a.mask, H.ptr(out), H.ptr(lse), a.G, a.heads, a.R, a.T1, *_ld(a),
+                                           a.o_sr, a.scale, a.dropout_p, a.seed, H.stream()), "fcmf_attn_mfma_fwd")
+    else:
+        H.check(H.lib().fcmf_attn_small_fwd(a, H.ptr(out), H.ptr(lse), H.stream()), "fcmf_attn_small_fwd")
+
+
+def probs(a, out, p_sg, p_sh, mfma):
+    """the pre-dropout softmax as float32: element (g, slot h, r, t) at out + g*p_sg + h*p_sh + r*(T1+T2) + t"""
+    if mfma:
+        H.check(H.lib().fcmf_attn_mfma_probs(a.q, a.k1, a.mask, H.ptr(out), a.G, a.heads, a.R, a.T1, *_ld(a), p_sg, p_sh,
+                                             a.scale, H.stream()), "fcmf_attn_mfma_probs")
+    else:
+        H.check(H.lib().fcmf_attn_probs(a, H.ptr(out), p_sg, p_sh, H.stream()), "fcmf_attn_probs")
+
+
+def small_backward(a, out, dout, lse, like_q, dk1, dv1, dk2=None, dv2=None, dbias=None, scratch=None):
+    """the VALU backward -> dq (shaped like like_q, a [G,R,heads*d] tensor).  The kernel writes one dq partial per 128 SHARED
+    keys, summed here.  scratch (float32, 2*G*heads*R*T2): the grouped backward, dk2 / dv2 already summed over group_div."""
+    nch = max(1, (a.T1 + 127) // 128)
+    dq = torch.empty((nch,) + tuple(like_q.shape), dtype=like_q.dtype, device=like_q.device)
+    if scratch is not None:
+        H.check(H.lib().fcmf_attn_small_bwd_grouped(a, H.ptr(out), H.ptr(dout), H.ptr(lse), H.ptr(dq), H.ptr(dk1), H.ptr(dv1),
+                                                    H.ptr(dk2), H.ptr(dv2), H.ptr(dbias), H.ptr(scratch), scratch.numel() * 4,
+                                                    H.stream()), "fcmf_attn_small_bwd_grouped")
+    else:
+        H.check(H.lib().fcmf_attn_small_bwd(a, H.ptr(out), H.ptr(dout), H.ptr(lse), H.ptr(dq), H.ptr(dk1), H.ptr(dv1),
+                                            H.ptr(dk2), H.ptr(dv2), H.ptr(dbias), H.stream()), "fcmf_attn_small_bwd")
+    return sum_leading(dq)
+
+
+def mfma_backward(a, out, dout, lse, dq, dk, dv, colsum_part=None):
+    """dq / dk / dv: ADDRESSES, written with the row strides of q / k1 (columns of one dqkv buffer, or tensors laid out like
+    q / k1 / v1).  colsum_part (float32 [G, 3*heads*64]): also receives each sequence's column sums of dq | dk | dv."""
+    H.check(H.lib().fcmf_attn_mfma_bwd(a.q, a.k1, a.v1, a.mask, H.ptr(out), H.ptr(dout), H.ptr(lse), dq, dk, dv, a.G, a.heads,
+                                       a.R, a.T1, *_ld(a), a.o_sr, a.scale, a.dropout_p, a.seed, H.ptr(colsum_part), H.stream()),
+            "fcmf_attn_mfma_bwd")
+
+
+def sum_leading(x):
+    """[n, ...] -> [...] summing the leading axis (attention dq chunk partials)"""
+    return x[0] if x.shape[0] == 1 else sum_groups(x, x.shape[0])[0]
+
+
+def sum_groups(x, reps):
+    """[G, ...] -> [G/reps, ...] summing consecutive groups"""
+    G = x.shape[0]
+    inner = x[0].numel()
+    out = torch.empty((G // reps,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    H.check(H.lib().fcmf_sum_axis(H.ptr(x), H.ptr(out), G // reps, reps, inner, H.dt(x), H.stream()), "fcmf_sum_axis")
+    return out
+
+
+def valu_float32_key_limit(d):
+    """most shared keys the float32 VALU attention takes at head dim d: its K and V images (rows of d + 4 floats), the waves'
+    score rows and one query row must fit the 160 KiB of LDS (fcmf_attn_small_fwd), and never more than its 512-key limit"""
+    def fits(T):
+        return 4 * (2 * T * (d + 4) + 4 * 64 * (4 if T <= 256 else 8) + d) <= 160 * 1024
+    T = 512
+    while T > 0 and not fits(T):
+        T -= 1
+    return T

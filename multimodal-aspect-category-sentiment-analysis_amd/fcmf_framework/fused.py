@@ -14,7 +14,7 @@ import os
 import torch
 
 from . import _hip as H
-from . import ops
+from . import attn, ops
 
 
 # --------------------------------------------------------------------------------------
@@ -116,76 +116,46 @@ class _SideGemms:
 # --------------------------------------------------------------------------------------
 # self-attention over a fused [G,T,3H] q|k|v buffer
 # --------------------------------------------------------------------------------------
-def _use_mfma(dtype, Hd, heads, T):
-    return dtype == torch.bfloat16 and Hd // heads == 64 and T <= 256 and ops.USE_MFMA_ATTENTION
-
-
-def _qkv_desc(qkv, G, T, Hd, heads, mask, scale, p, seed):
-    es = qkv.element_size()
-    a = H.AttnDesc()
-    a.dtype, a.G, a.heads, a.d, a.R, a.T1, a.T2, a.group_div = H.dt(qkv), G, heads, Hd // heads, T, T, 0, 1
-    a.q_sg, a.q_sr, a.k1_sg, a.k1_st = T * 3 * Hd, 3 * Hd, T * 3 * Hd, 3 * Hd
-    a.o_sg, a.o_sr = T * Hd, Hd
-    base = qkv.data_ptr()
-    a.q, a.k1, a.v1 = base, base + Hd * es, base + 2 * Hd * es
-    a.mask, a.scale, a.dropout_p, a.seed = H.ptr(mask), scale, p, seed
-    return a
+def _self_desc(qkv, mask, G, T, Hd, heads, p, seed):
+    """attn.desc over the three column blocks of the [G*T, 3H] buffer, read in place (row stride 3H)"""
+    q, k, v = qkv.view(G, T, 3, Hd).unbind(2)
+    return attn.desc(q, k, v, None, None, mask, None, heads, 1, 1.0 / math.sqrt(Hd // heads), p, seed, False, 0)
 
 
 def self_attention_fwd(qkv, mask, G, T, Hd, heads, p, seed):
-    scale = 1.0 / math.sqrt(Hd // heads)
     out = torch.empty((G * T, Hd), dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty((G, heads, T), dtype=torch.float32, device=qkv.device)
-    es, base, L = qkv.element_size(), qkv.data_ptr(), H.lib()
-    if _use_mfma(qkv.dtype, Hd, heads, T):
-        H.check(L.fcmf_attn_mfma_fwd(base, base + Hd * es, base + 2 * Hd * es, H.ptr(mask), H.ptr(out), H.ptr(lse), G, heads,
-                                     T, T, 3 * Hd, 3 * Hd, Hd, scale, p, seed, H.stream()), "fcmf_attn_mfma_fwd")
-    else:
-        a = _qkv_desc(qkv, G, T, Hd, heads, mask, scale, p, seed)
-        H.check(L.fcmf_attn_small_fwd(a, H.ptr(out), H.ptr(lse), H.stream()), "fcmf_attn_small_fwd")
+    a = _self_desc(qkv, mask, G, T, Hd, heads, p, seed)
+    attn.forward(a, out, lse, attn.mfma_eligible(a))
     return out, lse
 
 
 def self_attention_probs(qkv, mask, G, T, Hd, heads, probs):
     """fill probs (float32 [G, heads, T, T], contiguous) with the pre-dropout softmax of self_attention_fwd, read from the same
     [G*T, 3H] q|k|v buffer in place, on the kernel family the forward chose"""
-    scale = 1.0 / math.sqrt(Hd // heads)
     if tuple(probs.shape) != (G, heads, T, T) or probs.dtype != torch.float32 or not probs.is_contiguous():
         raise H.HipLibraryError(f"attention probabilities: need a contiguous float32 {(G, heads, T, T)} tensor")
-    es, base, L = qkv.element_size(), qkv.data_ptr(), H.lib()
-    if _use_mfma(qkv.dtype, Hd, heads, T):
-        H.check(L.fcmf_attn_mfma_probs(base, base + Hd * es, H.ptr(mask), H.ptr(probs), G, heads, T, T, 3 * Hd, 3 * Hd,
-                                       heads * T * T, T * T, scale, H.stream()), "fcmf_attn_mfma_probs")
-    else:
-        a = _qkv_desc(qkv, G, T, Hd, heads, mask, scale, 0.0, 0)
-        H.check(L.fcmf_attn_probs(a, H.ptr(probs), heads * T * T, T * T, H.stream()), "fcmf_attn_probs")
+    a = _self_desc(qkv, mask, G, T, Hd, heads, 0.0, 0)
+    attn.probs(a, probs, heads * T * T, T * T, attn.mfma_eligible(a))
 
 
 def self_attention_bwd(qkv, mask, out, lse, dout, G, T, Hd, heads, p, seed, bias_grad=None):
     """-> dqkv [G*T, 3H].  bias_grad (float32 [3H], accumulated into): the column sums of dqkv = the gradient of the fused
     q|k|v bias; the MFMA kernel produces them per sequence from its f32 accumulators (no extra pass over dqkv)."""
-    scale = 1.0 / math.sqrt(Hd // heads)
-    es, base, L = qkv.element_size(), qkv.data_ptr(), H.lib()
-    if _use_mfma(qkv.dtype, Hd, heads, T):
+    a = _self_desc(qkv, mask, G, T, Hd, heads, p, seed)
+    if attn.mfma_eligible(a):
         dqkv = torch.empty_like(qkv)
-        db = dqkv.data_ptr()
+        db, col = dqkv.data_ptr(), Hd * qkv.element_size()
         part = None if bias_grad is None else torch.empty((G, 3 * Hd), dtype=torch.float32, device=qkv.device)
-        H.check(L.fcmf_attn_mfma_bwd(base, base + Hd * es, base + 2 * Hd * es, H.ptr(mask), H.ptr(out), H.ptr(dout), H.ptr(lse),
-                                     db, db + Hd * es, db + 2 * Hd * es, G, heads, T, T, 3 * Hd, 3 * Hd, Hd, scale, p, seed,
-                                     H.ptr(part), H.stream()), "fcmf_attn_mfma_bwd")
-        if part is not None:
-            H.check(L.fcmf_colsum(H.ptr(part), H.ptr(bias_grad), G, 3 * Hd, 3 * Hd, H.dt(part), 1, H.stream()), "fcmf_colsum")
-        return dqkv
-    a = _qkv_desc(qkv, G, T, Hd, heads, mask, scale, p, seed)
-    nch = max(1, (T + 127) // 128)
-    dq = torch.empty((nch, G, T, Hd), dtype=qkv.dtype, device=qkv.device)
-    dk = torch.empty((G, T, Hd), dtype=qkv.dtype, device=qkv.device)
-    dv = torch.empty((G, T, Hd), dtype=qkv.dtype, device=qkv.device)
-    H.check(L.fcmf_attn_small_bwd(a, H.ptr(out), H.ptr(dout), H.ptr(lse), H.ptr(dq), H.ptr(dk), H.ptr(dv), 0, 0, 0, H.stream()),
-            "fcmf_attn_small_bwd")
-    dqkv = torch.cat((ops._sum_leading(dq), dk, dv), dim=-1).view(G * T, 3 * Hd)
+        attn.mfma_backward(a, out, dout, lse, db, db + col, db + 2 * col, part)
+        rows = part
+    else:
+        dk, dv = (torch.empty((G, T, Hd), dtype=qkv.dtype, device=qkv.device) for _ in range(2))
+        dq = attn.small_backward(a, out, dout, lse, dk, dk, dv)                  # (like_q = dk: dq has the shape and dtype of dk)
+        rows = dqkv = torch.cat((dq, dk, dv), dim=-1).view(G * T, 3 * Hd)
     if bias_grad is not None:
-        H.check(L.fcmf_colsum(H.ptr(dqkv), H.ptr(bias_grad), G * T, 3 * Hd, 3 * Hd, H.dt(dqkv), 1, H.stream()), "fcmf_colsum")
+        H.check(H.lib().fcmf_colsum(H.ptr(rows), H.ptr(bias_grad), rows.shape[0], 3 * Hd, 3 * Hd, H.dt(rows), 1, H.stream()),
+                "fcmf_colsum")
     return dqkv
 
 

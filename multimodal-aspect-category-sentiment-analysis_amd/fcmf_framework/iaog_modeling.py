@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip as H
-from . import layers, ops
+from . import attn, layers, ops
 
 
 def _quirk_attn_fwd(qx, kx, heads, causal, head_quirk=1):
@@ -25,8 +25,8 @@ def _quirk_attn_fwd(qx, kx, heads, causal, head_quirk=1):
     G, R, HD = qx.shape
     out = torch.empty((G, R, HD), dtype=qx.dtype, device=qx.device)
     lse = torch.empty((G, heads, R), dtype=torch.float32, device=qx.device)
-    a = ops._desc(qx, kx, kx, None, None, None, None, heads, 1, 1.0 / math.sqrt(HD // heads), 0.0, 0, causal, head_quirk)
-    H.check(H.lib().fcmf_attn_small_fwd(a, H.ptr(out), H.ptr(lse), H.stream()), "fcmf_attn_small_fwd")
+    a = attn.desc(qx, kx, kx, None, None, None, None, heads, 1, 1.0 / math.sqrt(HD // heads), 0.0, 0, causal, head_quirk)
+    attn.forward(a, out, lse, False)
     return out, lse
 
 
@@ -41,13 +41,9 @@ def _quirk_attn_bwd(qx, kx, out, lse, dout, heads, causal, dq_out, dk_out):
     (slot s of group g reads head (s*G + g) % heads, mm_modeling.py:79-85)"""
     G, R, HD = qx.shape
     T, d = kx.shape[1], HD // heads
-    nch = max(1, (T + 127) // 128)
-    dq_slot = torch.empty((nch, G, R, HD), dtype=qx.dtype, device=qx.device)
     dk_slot = torch.empty((G, T, HD), dtype=qx.dtype, device=qx.device)
-    a = ops._desc(qx, kx, kx, None, None, None, None, heads, 1, 1.0 / math.sqrt(d), 0.0, 0, causal, 1)
-    H.check(H.lib().fcmf_attn_small_bwd(a, H.ptr(out), H.ptr(dout.contiguous()), H.ptr(lse), H.ptr(dq_slot),
-                                        H.ptr(dk_slot), 0, 0, 0, 0, H.stream()), "fcmf_attn_small_bwd")
-    dq_slot = ops._sum_leading(dq_slot)
+    a = attn.desc(qx, kx, kx, None, None, None, None, heads, 1, 1.0 / math.sqrt(d), 0.0, 0, causal, 1)
+    dq_slot = attn.small_backward(a, out, dout.contiguous(), lse, out, dk_slot, None)     # values ARE the keys: dk_slot gets both terms
     L, st = H.lib(), H.stream()
     H.check(L.fcmf_head_gather(H.ptr(dq_slot), H.ptr(dq_out), dq_out.stride(1), G, R, heads, d, H.dt(qx), st), "fcmf_head_gather")
     H.check(L.fcmf_head_gather(H.ptr(dk_slot), H.ptr(dk_out), dk_out.stride(1), G, T, heads, d, H.dt(qx), st), "fcmf_head_gather")

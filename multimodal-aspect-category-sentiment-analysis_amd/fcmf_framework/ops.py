@@ -13,7 +13,8 @@ import weakref
 
 import torch
 
-from . import _hip as H
+from . import _hip as H, attn
+from .attn import valu_float32_key_limit      # noqa: F401  (part of this module's surface: DESIGN.md, shared_kv_attention)
 
 # --------------------------------------------------------------------------------------
 # global state: dropout seeds and bf16 weight shadows
@@ -252,13 +253,15 @@ class _Shadows:
     def derived(self, w, tag, build):
         """a tensor derived from the PARAMETER `w` (a re-layout and / or cast), cached per (storage, shape, tag) and
         rebuilt by `build(w.detach())` when the parameter has changed.  Only ever key this on persistent leaf
-        parameters: a temporary's address is recycled by the caching allocator (and its version is always 0)."""
+        parameters: a temporary's address is recycled by the caching allocator (and its version is always 0).  The entry holds
+        a weak reference to `w` and serves no other tensor: a freed model's parameter addresses are recycled too, for the next
+        model's parameters of the same shape and version (its w_qx where w_kx was)."""
         key = (w.data_ptr(), tuple(w.shape), tag)
         ent = self.mapD.get(key)
-        if ent is not None and ent[1] == w._version and not ent[2]:
+        if ent is not None and ent[1] == w._version and not ent[2] and ent[3]() is w:
             return ent[0]
         t = build(w.detach())
-        self.mapD[key] = [t, w._version, False]
+        self.mapD[key] = [t, w._version, False, weakref.ref(w)]
         return t
 
     def peek(self, w):
@@ -1246,31 +1249,28 @@ def embed_layer_norm(ids, pos, tt, word, ptab, ttab, gamma, beta, eps, p, traini
 # --------------------------------------------------------------------------------------
 # attention
 # --------------------------------------------------------------------------------------
-def _desc(q, k1, v1, k2, v2, mask, bias, heads, group_div, scale, p, seed, causal, head_quirk):
-    G, R, HD = q.shape
-    d = HD // heads
-    T1 = 0 if k1 is None else k1.shape[1]
-    T2 = 0 if k2 is None else k2.shape[2]
-    a = H.AttnDesc()
-    a.dtype, a.G, a.heads, a.d, a.R, a.T1, a.T2, a.group_div = H.dt(q), G, heads, d, R, T1, T2, group_div
-    a.q_sg, a.q_sr = q.stride(0), q.stride(1)
-    if k1 is not None:
-        a.k1_sg, a.k1_st = k1.stride(0), k1.stride(1)
-    if k2 is not None:
-        a.k2_sg, a.k2_sr, a.k2_st = k2.stride(0), k2.stride(1), k2.stride(2)
-    a.o_sg, a.o_sr = R * HD, HD
-    a.q, a.k1, a.v1, a.k2, a.v2 = H.ptr(q), H.ptr(k1), H.ptr(v1), H.ptr(k2), H.ptr(v2)
-    a.mask, a.bias = H.ptr(mask), H.ptr(bias)
-    a.scale, a.dropout_p, a.seed, a.causal, a.head_quirk = scale, p, seed, int(causal), int(head_quirk)
-    return a
+def _query_rows(q, row0):
+    """q [G,R,HD] as the kernels read it in place: unit inner stride, rows that do not overlap.  row0: or ONE row expanded over the
+    R rows, row stride 0 (the [CLS] query against every image's keys)"""
+    ok = q.stride(2) == 1 and (q.stride(1) >= q.shape[2] or (row0 and q.stride(1) == 0))
+    return q if ok else q.contiguous()
 
 
-def _chk_same_layout(a, b):
-    if a is not None and (a.stride() != b.stride() or a.shape != b.shape):
-        raise H.HipLibraryError("attention: K and V of a segment must share shape and strides")
+def _kv_pair(k, v):
+    """K and V of a segment with a unit inner stride and the SAME strides (the descriptor carries K's only)"""
+    if k is None:
+        return None, None
+    k = k if k.stride(-1) == 1 else k.contiguous()
+    v = v if v.stride() == k.stride() else v.contiguous()
+    if v.stride() != k.stride():
+        k = k.contiguous()
+    return k, v
 
 
-USE_MFMA_ATTENTION = True   # tests flip this to compare the MFMA kernel with the VALU kernel
+def _mfma_dense(a, *operands):
+    """attn.mfma_eligible for operands that are tensors of their own: the MFMA kernels take one row stride per operand, so q / k1
+    / v1 must be dense -- which keeps a stride-0 expanded query row, and any row-strided view, on the VALU kernel"""
+    return attn.mfma_eligible(a) and all(t.is_contiguous() for t in operands)
 
 
 class AttentionFn(torch.autograd.Function):
@@ -1282,34 +1282,19 @@ class AttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k1, v1, k2, v2, mask, bias, heads, group_div, scale, p, seed, causal):
         H.require_cuda(q)
-        # (row stride 0 = one query row expanded over R rows -- the [CLS] query against every image's keys: read in place)
-        q = q if q.stride(2) == 1 and (q.stride(1) >= q.shape[2] or q.stride(1) == 0) else q.contiguous()
-        k1 = None if k1 is None else (k1 if k1.stride(2) == 1 else k1.contiguous())
-        v1 = None if v1 is None else (v1 if v1.stride() == k1.stride() else v1.contiguous())
-        if k1 is not None and v1.stride() != k1.stride():
-            k1 = k1.contiguous()
-        k2 = None if k2 is None else (k2 if k2.stride(3) == 1 else k2.contiguous())
-        v2 = None if v2 is None else (v2 if v2.stride() == k2.stride() else v2.contiguous())
-        if k2 is not None and v2.stride() != k2.stride():
-            k2 = k2.contiguous()
+        q = _query_rows(q, True)
+        k1, v1 = _kv_pair(k1, v1)
+        k2, v2 = _kv_pair(k2, v2)
         mask = None if mask is None else mask.contiguous().float()
         bias = None if bias is None else bias.contiguous()
         G, R, HD = q.shape
         out = torch.empty((G, R, HD), dtype=q.dtype, device=q.device)
         lse = torch.empty((G, heads, R), dtype=torch.float32, device=q.device)
-        # text-encoder shape (bf16, head dim 64, <=256 queries / keys, plain mask): MFMA kernel
-        mfma = (q.dtype == torch.bfloat16 and HD // heads == 64 and k2 is None and bias is None and not causal
-                and k1 is not None and k1.shape[1] <= 256 and R <= 256 and q.is_contiguous() and k1.is_contiguous()
-                and v1.is_contiguous() and USE_MFMA_ATTENTION)
-        if mfma:
-            H.check(H.lib().fcmf_attn_mfma_fwd(H.ptr(q), H.ptr(k1), H.ptr(v1), H.ptr(mask), H.ptr(out), H.ptr(lse), G, heads,
-                                               R, k1.shape[1], HD, HD, HD, scale, p, seed, H.stream()), "fcmf_attn_mfma_fwd")
-        else:
-            a = _desc(q, k1, v1, k2, v2, mask, bias, heads, group_div, scale, p, seed, causal, 0)
-            H.check(H.lib().fcmf_attn_small_fwd(a, H.ptr(out), H.ptr(lse), H.stream()), "fcmf_attn_small_fwd")
+        a = attn.desc(q, k1, v1, k2, v2, mask, bias, heads, group_div, scale, p, seed, causal, 0)
+        ctx.mfma = _mfma_dense(a, q, k1, v1)
+        attn.forward(a, out, lse, ctx.mfma)
         ctx.save_for_backward(q, k1, v1, k2, v2, mask, bias, out, lse)
         ctx.cfg = (heads, group_div, scale, p, seed, causal)
-        ctx.mfma = mfma
         return out
 
     @staticmethod
@@ -1318,64 +1303,31 @@ class AttentionFn(torch.autograd.Function):
         heads, group_div, scale, p, seed, causal = ctx.cfg
         G, R, HD = q.shape
         dout = dout.contiguous()
+        a = attn.desc(q, k1, v1, k2, v2, mask, bias, heads, group_div, scale, p, seed, causal, 0)
         if ctx.mfma:
             dq, dk, dv = torch.empty_like(q), torch.empty_like(k1), torch.empty_like(v1)
-            H.check(H.lib().fcmf_attn_mfma_bwd(H.ptr(q), H.ptr(k1), H.ptr(v1), H.ptr(mask), H.ptr(out), H.ptr(dout),
-                                               H.ptr(lse), H.ptr(dq), H.ptr(dk), H.ptr(dv), G, heads, R, k1.shape[1], HD, HD,
-                                               HD, scale, p, seed, None, H.stream()), "fcmf_attn_mfma_bwd")
+            attn.mfma_backward(a, out, dout, lse, H.ptr(dq), H.ptr(dk), H.ptr(dv))
             return dq, dk, dv, None, None, None, None, None, None, None, None, None, None
-        T1 = 0 if k1 is None else k1.shape[1]
-        nch = max(1, (T1 + 127) // 128)
-        dq = torch.empty((nch, G, R, HD), dtype=q.dtype, device=q.device)   # one partial per 128-key chunk
-        dk1 = dv1 = dk2 = dv2 = dbias = None
+        new = lambda like, *shape: torch.empty(shape, dtype=like.dtype, device=q.device)
+        dk1 = dv1 = dk2 = dv2 = dbias = scratch = None
         if k1 is not None:
-            dk1 = torch.empty((G, T1, HD), dtype=k1.dtype, device=q.device)
-            dv1 = torch.empty((G, T1, HD), dtype=k1.dtype, device=q.device)
-        T2 = 0 if k2 is None else k2.shape[2]
+            dk1, dv1 = new(k1, G, a.T1, HD), new(k1, G, a.T1, HD)
         # private keys shared by `group_div` groups: the library sums their gradients over the group (no per-group rows)
         grouped = k2 is not None and group_div <= 8 and G % group_div == 0
         if k2 is not None:
             G2 = G // group_div if grouped else G
-            dk2 = torch.empty((G2, R, T2, HD), dtype=q.dtype, device=q.device)
-            dv2 = torch.empty((G2, R, T2, HD), dtype=q.dtype, device=q.device)
+            dk2, dv2 = new(q, G2, R, a.T2, HD), new(q, G2, R, a.T2, HD)
         if bias is not None and ctx.needs_input_grad[6]:
-            T = (0 if k1 is None else k1.shape[1]) + T2
-            dbias = torch.empty((G, heads, R, T), dtype=torch.float32, device=q.device)
-        a = _desc(q, k1, v1, k2, v2, mask, bias, heads, group_div, scale, p, seed, causal, 0)
+            dbias = torch.empty((G, heads, R, a.T1 + a.T2), dtype=torch.float32, device=q.device)
         if grouped:
-            scratch = torch.empty(2 * G * heads * R * T2, dtype=torch.float32, device=q.device)
-            H.check(H.lib().fcmf_attn_small_bwd_grouped(a, H.ptr(out), H.ptr(dout), H.ptr(lse), H.ptr(dq), H.ptr(dk1), H.ptr(dv1),
-                                                        H.ptr(dk2), H.ptr(dv2), H.ptr(dbias), H.ptr(scratch), scratch.numel() * 4,
-                                                        H.stream()), "fcmf_attn_small_bwd_grouped")
-        else:
-            H.check(H.lib().fcmf_attn_small_bwd(a, H.ptr(out), H.ptr(dout), H.ptr(lse), H.ptr(dq), H.ptr(dk1), H.ptr(dv1),
-                                                H.ptr(dk2), H.ptr(dv2), H.ptr(dbias), H.stream()), "fcmf_attn_small_bwd")
-        dq = _sum_leading(dq)
+            scratch = torch.empty(2 * G * heads * R * a.T2, dtype=torch.float32, device=q.device)
+        dq = attn.small_backward(a, out, dout, lse, q, dk1, dv1, dk2, dv2, dbias, scratch)
         if group_div > 1:
             if dk2 is not None and not grouped:
-                dk2, dv2 = _sum_groups(dk2, group_div), _sum_groups(dv2, group_div)
+                dk2, dv2 = attn.sum_groups(dk2, group_div), attn.sum_groups(dv2, group_div)
             if dbias is not None:
-                dbias = _sum_groups(dbias, group_div)
+                dbias = attn.sum_groups(dbias, group_div)
         return dq, dk1, dv1, dk2, dv2, None, dbias, None, None, None, None, None, None
-
-
-def _sum_leading(x):
-    """[n, ...] -> [...] summing the leading axis (attention dq chunk partials)"""
-    if x.shape[0] == 1:
-        return x[0]
-    inner = x[0].numel()
-    out = torch.empty(x.shape[1:], dtype=x.dtype, device=x.device)
-    H.check(H.lib().fcmf_sum_axis(H.ptr(x), H.ptr(out), 1, x.shape[0], inner, H.dt(x), H.stream()), "fcmf_sum_axis")
-    return out
-
-
-def _sum_groups(x, reps):
-    """[G, ...] -> [G/reps, ...] summing consecutive groups"""
-    G = x.shape[0]
-    inner = x[0].numel()
-    out = torch.empty((G // reps,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
-    H.check(H.lib().fcmf_sum_axis(H.ptr(x), H.ptr(out), G // reps, reps, inner, H.dt(x), H.stream()), "fcmf_sum_axis")
-    return out
 
 
 def attention(q, k1=None, v1=None, k2=None, v2=None, mask=None, bias=None, heads=12, group_div=1, scale=None,
@@ -1434,7 +1386,7 @@ class ChunkedF32AttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, mask, heads, scale, p, seed, chunk):
         H.require_cuda(q, k, v)
-        q = q if q.stride(2) == 1 and q.stride(1) >= q.shape[2] else q.contiguous()
+        q = _query_rows(q, False)
         k, v = k.contiguous(), v.contiguous()
         G, R, HD = q.shape
         T = k.shape[1]
@@ -1443,8 +1395,8 @@ class ChunkedF32AttentionFn(torch.autograd.Function):
         outs = torch.empty((len(bounds), G, R, HD), dtype=q.dtype, device=q.device)
         lses = torch.empty((len(bounds), G, heads, R), dtype=torch.float32, device=q.device)
         for i, (a, b) in enumerate(bounds):
-            d = _desc(q, k[:, a:b], v[:, a:b], None, None, masks[i], None, heads, 1, scale, p, (seed + i) & 0xFFFFFFFFFFFFFFFF, False, 0)
-            H.check(H.lib().fcmf_attn_small_fwd(d, H.ptr(outs[i]), H.ptr(lses[i]), H.stream()), "fcmf_attn_small_fwd")
+            d = attn.desc(q, k[:, a:b], v[:, a:b], None, None, masks[i], None, heads, 1, scale, p, (seed + i) & 0xFFFFFFFFFFFFFFFF, False, 0)
+            attn.forward(d, outs[i], lses[i], False)
         lse = torch.logsumexp(lses, 0)
         w = torch.exp(lses - lse).transpose(2, 3).unsqueeze(-1)                       # [chunks, G, R, heads, 1]
         out = (outs.view(len(bounds), G, R, heads, HD // heads) * w).sum(0).view(G, R, HD)
@@ -1461,14 +1413,10 @@ class ChunkedF32AttentionFn(torch.autograd.Function):
         dq = torch.zeros((G, R, HD), dtype=q.dtype, device=q.device)
         dk, dv = torch.empty_like(k), torch.empty_like(v)
         for i, (a, b) in enumerate(bounds):
-            d = _desc(q, k[:, a:b], v[:, a:b], None, None, masks[i] if has_mask else None, None, heads, 1, scale, p,
-                      (seed + i) & 0xFFFFFFFFFFFFFFFF, False, 0)
-            dqc = torch.empty(((b - a + 127) // 128, G, R, HD), dtype=q.dtype, device=q.device)
-            dkc = torch.empty((G, b - a, HD), dtype=q.dtype, device=q.device)
-            dvc = torch.empty((G, b - a, HD), dtype=q.dtype, device=q.device)
-            H.check(H.lib().fcmf_attn_small_bwd(d, H.ptr(out), H.ptr(dout), H.ptr(lse), H.ptr(dqc), H.ptr(dkc), H.ptr(dvc), None, None,
-                                                None, H.stream()), "fcmf_attn_small_bwd")
-            dq += _sum_leading(dqc)
+            d = attn.desc(q, k[:, a:b], v[:, a:b], None, None, masks[i] if has_mask else None, None, heads, 1, scale, p,
+                          (seed + i) & 0xFFFFFFFFFFFFFFFF, False, 0)
+            dkc, dvc = (torch.empty((G, b - a, HD), dtype=q.dtype, device=q.device) for _ in range(2))
+            dq += attn.small_backward(d, out, dout, lse, q, dkc, dvc)
             dk[:, a:b], dv[:, a:b] = dkc, dvc
         return dq, dk, dv, None, None, None, None, None, None
 
@@ -1506,50 +1454,30 @@ def shared_kv_attention(q, k, v, mask=None, heads=12, kv_share=1, scale=None, p=
                             "or float32 with head dim <= 128")
 
 
-def valu_float32_key_limit(d):
-    """most shared keys the float32 VALU attention takes at head dim d: its K and V images (rows of d + 4 floats), the waves'
-    score rows and one query row must fit the 160 KiB of LDS (fcmf_attn_small_fwd), and never more than its 512-key limit"""
-    def fits(T):
-        return 4 * (2 * T * (d + 4) + 4 * 64 * (4 if T <= 256 else 8) + d) <= 160 * 1024
-    T = 512
-    while T > 0 and not fits(T):
-        T -= 1
-    return T
-
-
 def attention_probs(q, k1=None, k2=None, mask=None, bias=None, heads=12, group_div=1, scale=None, causal=False,
                     head_quirk=False, slot_major=False, out=None):
     """softmax(score) of `attention` / fcmf_attn_desc as float32, before dropout, recomputed from q and the keys (no values, no
     logsumexp of a forward): [G, heads, R, T1+T2], or with slot_major [heads*G, R, T1+T2] where index h*G + g is output slot h of
     group g (with head_quirk, the order of the reference Attention's `score`, mm_modeling.py:126-132).  Same operand layouts, stride
-    normalisation and MFMA / VALU choice as AttentionFn.forward.  Detached; there is no backward.  out: a float32 tensor of that
-    shape to fill instead of a new one."""
+    normalisation and MFMA / VALU choice as AttentionFn.forward (_query_rows, _mfma_dense over attn.mfma_eligible).  Detached;
+    there is no backward.  out: a float32 tensor of that shape to fill instead of a new one."""
     H.require_cuda(q)
-    q = q.detach()
-    q = q if q.stride(2) == 1 and (q.stride(1) >= q.shape[2] or q.stride(1) == 0) else q.contiguous()
+    q = _query_rows(q.detach(), True)
     k1 = None if k1 is None else (k1.detach() if k1.stride(2) == 1 else k1.detach().contiguous())
     k2 = None if k2 is None else (k2.detach() if k2.stride(3) == 1 else k2.detach().contiguous())
     mask = None if mask is None else mask.detach().contiguous().float()
     bias = None if bias is None else bias.detach().contiguous()
     G, R, HD = q.shape
-    d = HD // heads
     T = (0 if k1 is None else k1.shape[1]) + (0 if k2 is None else k2.shape[2])
-    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    scale = 1.0 / math.sqrt(HD // heads) if scale is None else float(scale)
     shape = (heads * G, R, T) if slot_major else (G, heads, R, T)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=q.device)
     elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != q.device:
         raise H.HipLibraryError(f"attention_probs: out must be a contiguous float32 {shape} tensor on {q.device}")
     p_sg, p_sh = (R * T, G * R * T) if slot_major else (heads * R * T, R * T)
-    mfma = (q.dtype == torch.bfloat16 and d == 64 and k2 is None and bias is None and not causal and not head_quirk
-            and k1 is not None and k1.shape[1] <= 256 and R <= 256 and q.is_contiguous() and k1.is_contiguous()
-            and USE_MFMA_ATTENTION)
-    if mfma:
-        H.check(H.lib().fcmf_attn_mfma_probs(H.ptr(q), H.ptr(k1), H.ptr(mask), H.ptr(out), G, heads, R, T, HD, HD, p_sg, p_sh,
-                                             scale, H.stream()), "fcmf_attn_mfma_probs")
-    else:
-        a = _desc(q, k1, None, k2, None, mask, bias, heads, group_div, scale, 0.0, 0, causal, head_quirk)
-        H.check(H.lib().fcmf_attn_probs(a, H.ptr(out), p_sg, p_sh, H.stream()), "fcmf_attn_probs")
+    a = attn.desc(q, k1, None, k2, None, mask, bias, heads, group_div, scale, 0.0, 0, causal, head_quirk)
+    attn.probs(a, out, p_sg, p_sh, _mfma_dense(a, q, k1))
     return out
 
 

@@ -1,6 +1,10 @@
 """shared test helpers (tests may use oracle/, the product may not)"""
+import contextlib
+import ctypes
+import hashlib
 import tempfile
 
+import pytest
 import torch
 
 import synthetic_data as synth
@@ -33,3 +37,75 @@ def rel_err(a, b):
 
 def max_err(a, b):
     return (a.detach().float().cpu() - b.detach().float().cpu()).abs().max().item()
+
+
+class _CallRecorder:
+    """stands in for _hip._lib: every entry point of _hip.SIGNATURES appends (name, its scalar arguments, its return code) to
+    `calls` and forwards the call.  Scalar = declared as anything but c_void_p / a POINTER: addresses are left out.
+    desc: the record is what the C ABI receives -- a scalar declared `float` is recorded as the float32 it is converted to, and
+    a fourth element holds, for every fcmf_attn_desc argument, (its non-pointer fields, which pointer fields are non-null,
+    whether v1 == k1)."""
+
+    def __init__(self, real, signatures, desc=False):
+        from fcmf_framework._hip import AttnDesc
+        self._AttnDesc = AttnDesc
+        self._real, self.calls, self._desc = real, [], desc
+        self._scalars = {n: [i for i, t in enumerate(sig) if t is not ctypes.c_void_p and not issubclass(t, ctypes._Pointer)]
+                         for n, sig in signatures.items()}
+        self._floats = {n: {i for i, t in enumerate(sig) if t is ctypes.c_float} for n, sig in signatures.items()}
+
+    def __getattr__(self, name):
+        fn, keep = getattr(self._real, name), self._scalars.get(name)
+        if keep is None:
+            return fn
+        floats = self._floats[name]
+
+        def call(*args):
+            rc = fn(*args)
+            if self._desc:
+                scalars = tuple(ctypes.c_float(args[i]).value if i in floats else args[i] for i in keep)
+                self.calls.append((name, scalars, rc, tuple(_desc_record(a) for a in args if isinstance(a, self._AttnDesc))))
+            else:
+                self.calls.append((name, tuple(args[i] for i in keep), rc))
+            return rc
+        return call
+
+
+def desc_fields(a):
+    """-> (names of the non-pointer fields, names of the pointer fields) of a ctypes descriptor, in declaration order"""
+    names = [n for n, _ in a._fields_]
+    ptrs = [n for n, t in a._fields_ if t is ctypes.c_void_p]
+    return [n for n in names if n not in ptrs], ptrs
+
+
+def _desc_record(a):
+    plain, ptrs = desc_fields(a)
+    return (tuple(getattr(a, n) for n in plain), tuple(getattr(a, n) is not None for n in ptrs),
+            a.v1 == a.k1)
+
+
+def _calls_digest(calls):
+    return hashlib.sha256(repr(calls).encode()).hexdigest()
+
+
+def _recorded(fn, desc=False):
+    """fn() with the recorder in place of the library -> its calls"""
+    from fcmf_framework import _hip as H
+    H.gemm_ctx(workspace=True)                   # (the first use of a stream creates its context and workspace: not part of the pass)
+    real = H.lib()
+    H._lib = rec = _CallRecorder(real, H.SIGNATURES, desc)
+    try:
+        fn()
+        torch.cuda.synchronize()
+    finally:
+        H._lib = real
+    return rec.calls
+
+
+@contextlib.contextmanager
+def mfma_attention(on):
+    """the MFMA / VALU switch of the attention call path set to `on` inside the block (monkeypatch: raises if there is no such switch)"""
+    from fcmf_framework import attn
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(attn, "USE_MFMA_ATTENTION", on)
+        yield

@@ -9,7 +9,7 @@ import math
 import pytest
 import torch
 
-from helpers import rel_err
+from helpers import mfma_attention, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -133,14 +133,11 @@ def test_long_attention_dropout_equals_valu_kernel(dev, G, Tq, Tk):
     q0, k0, v0, w = _operands(G, 1, Tq, Tk, dev)
     mask = _mask(G, Tk, ["random"] * G).to(dev)
     got = _run(ops, q0, k0, v0, w, mask, 1, p=0.2)
-    ops.USE_MFMA_ATTENTION = False
-    try:
+    with mfma_attention(False):
         q, k, v = (t.clone().requires_grad_(True) for t in (q0, k0, v0))
         ops.manual_seed(5)
         out = ops.attention(q, k, v, mask=mask, heads=HEADS, p=0.2, training=True)
         (out.float() * w.float()).sum().backward()
-    finally:
-        ops.USE_MFMA_ATTENTION = True
     for a, b, n in zip(got, (out, q.grad, k.grad, v.grad), ("out", "dq", "dk", "dv")):
         e = rel_err(a, b)
         print(G, Tq, Tk, n, e)

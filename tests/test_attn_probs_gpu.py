@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from conftest import GOLD
-from helpers import rel_err
+from helpers import mfma_attention, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -99,11 +99,8 @@ def test_desc_kernel_matches_float64(dev, dtype, case):
     from fcmf_framework import ops
     G, R, heads, d, T1, T2, gd, _, _, causal = case
     q, k1, k2, mask, bias = _inputs(case, dev, dtype)
-    ops.USE_MFMA_ATTENTION = False            # (1, 150, 2, 64, ...) has private keys, so no case is MFMA-eligible anyway
-    try:
+    with mfma_attention(False):            # (1, 150, 2, 64, ...) has private keys, so no case is MFMA-eligible anyway
         got = ops.attention_probs(q, k1=k1, k2=k2, mask=mask, bias=bias, heads=heads, group_div=gd, causal=causal)
-    finally:
-        ops.USE_MFMA_ATTENTION = True
     assert not got.requires_grad
     _check(f"desc {case} {dtype}", got.cpu(), _probs_ref(q, k1, k2, mask, bias, heads, gd, None, causal))
 
@@ -204,11 +201,8 @@ def test_mfma_kernel_matches_float64_and_desc_kernel(dev, Tq, Tk):
     for g_ in range(G):
         assert not got[g_, :, :, int(lens[g_]):].any(), "a finfo.min-masked key has a non-zero probability"
     # the descriptor kernel on the same inputs
-    ops.USE_MFMA_ATTENTION = False
-    try:
+    with mfma_attention(False):
         valu = ops.attention_probs(q, k1=k, mask=mask, heads=heads)
-    finally:
-        ops.USE_MFMA_ATTENTION = True
     _check(f"valu dense {Tq}x{Tk}", valu.cpu(), ref)
     err = rel_err(got, valu)
     print(f"mfma vs valu {Tq}x{Tk}: rel_err {err:.3e}")
@@ -251,11 +245,8 @@ def test_fully_masked_sequence_is_uniform(dev, T, use_mfma):
     m01[1] = 0
     m01[2, T // 2:] = 0
     mask = ((1 - m01) * FMIN).to(dev)
-    ops.USE_MFMA_ATTENTION = use_mfma
-    try:
+    with mfma_attention(use_mfma):
         got = ops.attention_probs(q, k1=k, mask=mask, heads=heads).cpu()
-    finally:
-        ops.USE_MFMA_ATTENTION = True
     _check(f"fully masked T={T} mfma={use_mfma}", got, _probs_ref(q, k, mask=mask, heads=heads))
     dev_u = (got[1] - 1.0 / T).abs().max().item()
     print(f"  uniform row: max |p - 1/T| {dev_u:.3e}")

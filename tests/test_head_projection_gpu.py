@@ -1,11 +1,9 @@
 """The IAOG decoder's per-head projections (ops.head_linear: HeadLinearFn over ops.head_project / ops.head_project_bwd) on their
 own against float64 autograd, and the library calls a whole decoder step makes."""
-import hashlib
-
 import pytest
 import torch
 
-from helpers import rel_err
+from helpers import _calls_digest, _recorded, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -21,46 +19,6 @@ def _set(dtype):
     from fcmf_framework import ops
     ops.set_compute_dtype(dtype)
     ops.shadows.clear()
-
-
-class _CallRecorder:
-    """stands in for _hip._lib: every entry point of _hip.SIGNATURES appends (name, its scalar arguments, its return code) to
-    `calls` and forwards the call.  Scalar = declared as anything but c_void_p / a POINTER: addresses are left out."""
-
-    def __init__(self, real, signatures):
-        import ctypes
-        self._real, self.calls = real, []
-        self._scalars = {n: [i for i, t in enumerate(sig) if t is not ctypes.c_void_p and not issubclass(t, ctypes._Pointer)]
-                         for n, sig in signatures.items()}
-
-    def __getattr__(self, name):
-        fn, keep = getattr(self._real, name), self._scalars.get(name)
-        if keep is None:
-            return fn
-
-        def call(*args):
-            rc = fn(*args)
-            self.calls.append((name, tuple(args[i] for i in keep), rc))
-            return rc
-        return call
-
-
-def _calls_digest(calls):
-    return hashlib.sha256(repr(calls).encode()).hexdigest()
-
-
-def _recorded(fn):
-    """fn() with the recorder in place of the library -> its calls"""
-    from fcmf_framework import _hip as H
-    H.gemm_ctx(workspace=True)                   # (the first use of a stream creates its context and workspace: not part of the pass)
-    real = H.lib()
-    H._lib = rec = _CallRecorder(real, H.SIGNATURES)
-    try:
-        fn()
-        torch.cuda.synchronize()
-    finally:
-        H._lib = real
-    return rec.calls
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -173,10 +131,10 @@ def test_head_projection_weight_gradients_in_the_arena(dev, nw, tokens):
 # ------------------------------------------------------------------------------------------------------------------------
 # the decoder's library calls, in order
 # ------------------------------------------------------------------------------------------------------------------------
-def _decoder_calls(dev, case):
+def _decoder_calls(dev, case, desc=False):
     """[(entry point, scalar arguments, return code)] of one pass of a 2-block, 4-head, 256-wide IAOGDecoder over B = 3 sequences
     of 8 tokens and a [3, 16, 256] encoder output that requires grad.  case: "fp32" / "bf16" / "bf16-arena" (loss + backward, the
-    last under GradArena.for_model) or "bf16-project" (project_encoder under no_grad)"""
+    last under GradArena.for_model) or "bf16-project" (project_encoder under no_grad).  desc: helpers._recorded's option"""
     from fcmf_framework import dp, ops
     from fcmf_framework.iaog_modeling import IAOGDecoder
     _set(torch.float32 if case == "fp32" else torch.bfloat16)
@@ -197,7 +155,7 @@ def _decoder_calls(dev, case):
     try:
         if arena is not None:
             arena.zero()
-        return _recorded(run)
+        return _recorded(run, desc=desc)
     finally:
         if arena is not None:
             arena.deactivate()

@@ -8,7 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import max_err, rel_err
+from helpers import max_err, mfma_attention, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -1036,15 +1036,12 @@ def test_attention_mfma_padded_sequences_skip_is_exact(dev, T, p):
     w = mk((G, T, HD), 9)
     res = {}
     for use in (True, False):
-        ops.USE_MFMA_ATTENTION = use
-        try:
+        with mfma_attention(use):
             q, k, v = (t.clone().requires_grad_(True) for t in (q0, k0, v0))
             ops.manual_seed(5)
             out = ops.attention(q, k, v, mask=mask, heads=heads, p=p, training=p > 0)
             (out.float() * w.float()).sum().backward()
             res[use] = (out.detach(), q.grad, k.grad, v.grad)
-        finally:
-            ops.USE_MFMA_ATTENTION = True
     for a, b, name in zip(res[True], res[False], ("out", "dq", "dk", "dv")):
         assert rel_err(a, b) < 3e-2, name
     for g, l in enumerate(lens):           # padded keys receive exactly zero gradient
@@ -1074,13 +1071,10 @@ def test_attention_mfma_fully_masked_sequence_is_uniform(dev, T):
     ref = (torch.softmax(sc, -1) @ sp(vr)).transpose(1, 2).reshape(3, T, HD)
     (ref * w.float()).sum().backward()
     for use in (True, False):
-        ops.USE_MFMA_ATTENTION = use
-        try:
+        with mfma_attention(use):
             q, k, v = (t.clone().requires_grad_(True) for t in (q0, k0, v0))
             out = ops.attention(q, k, v, mask=mask, heads=heads, p=0.0, training=False)
             (out.float() * w.float()).sum().backward()
-        finally:
-            ops.USE_MFMA_ATTENTION = True
         assert rel_err(out, ref) < 2e-2, use
         assert rel_err(v.grad, vr.grad) < 3e-2, use
         # (autograd semantics: the gradient flows through `scores + mask` with derivative 1 although finfo.min absorbs the
@@ -1104,15 +1098,12 @@ def test_attention_mfma_matches_reference_and_valu_kernel(dev, Tq, Tk, p):
     w = mk((G, Tq, HD), 9)
     res = {}
     for use in (True, False):
-        ops.USE_MFMA_ATTENTION = use
-        try:
+        with mfma_attention(use):
             q, k, v = (t.clone().requires_grad_(True) for t in (q0, k0, v0))
             ops.manual_seed(5)
             out = ops.attention(q, k, v, mask=mask, heads=heads, p=p, training=p > 0)
             (out.float() * w.float()).sum().backward()
             res[use] = (out.detach(), q.grad, k.grad, v.grad)
-        finally:
-            ops.USE_MFMA_ATTENTION = True
     for a, b, name in zip(res[True], res[False], ("out", "dq", "dk", "dv")):
         assert rel_err(a, b) < 3e-2, name
     if p == 0.0:

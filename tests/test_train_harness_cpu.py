@@ -118,6 +118,25 @@ def test_extractor_checkpoints_beside_the_model(tmp_path):
     assert sorted(os.listdir(tmp_path)) == ["runs"]
 
 
+def test_derived_shadow_is_not_served_to_another_parameter_at_the_same_address():
+    """a freed model's parameter addresses are recycled for the next model's parameters of the same shape and version: the
+    re-layout cached for the first must not come back for the second (two Parameters over one storage stand in for that)"""
+    from fcmf_framework import ops
+    a = torch.nn.Parameter(torch.arange(6.0).view(2, 3))
+    b = torch.nn.Parameter(a.data)
+    assert a.data_ptr() == b.data_ptr() and a._version == b._version and a is not b
+    built = []
+    build = lambda owner: lambda src: built.append(owner) or src.t().contiguous()
+    try:
+        ta = ops.shadows.derived(a, "t", build("a"))
+        assert ops.shadows.derived(a, "t", build("a")) is ta and built == ["a"]
+        tb = ops.shadows.derived(b, "t", build("b"))
+        assert tb is not ta and built == ["a", "b"]
+        assert ops.shadows.derived(b, "t", build("b")) is tb and built == ["a", "b"]
+    finally:
+        ops.shadows.clear()
+
+
 def test_synth_pixel_batch_is_the_two_seeded_crop_draws():
     seed = 11
     vis, roi = synth.synth_pixel_batch(2, 2, 3, 16, seed, torch.float64)

@@ -16,7 +16,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.getcwd(), "multimodal-aspect-category-sentiment-analysis_amd"))
 import torch
-from fcmf_framework import ops
+from fcmf_framework import attn, ops
 
 dev = torch.device("cuda:0")
 B, A, heads, Tq, HD, p = 64, 6, 12, 170, 768, 0.1
@@ -70,11 +70,11 @@ for Tk, per_photo in ((371, 53), (595, 85)):
         ve = v.detach().repeat_interleave(A, 0).requires_grad_(True)
 
         def valu(q, k, v):
-            ops.USE_MFMA_ATTENTION = False
+            attn.USE_MFMA_ATTENTION = False
             try:
                 return ops.attention(q, k, v, mask=mask, heads=heads, p=p, training=True)
             finally:
-                ops.USE_MFMA_ATTENTION = True
+                attn.USE_MFMA_ATTENTION = True
         routes["valu_expanded"] = (valu, q, ke, ve, w)
     t = measure(routes)
     res[f"Tk{Tk}"] = {f"{n}_fwd_bwd_us": round(us, 1) for n, us in t.items()}
