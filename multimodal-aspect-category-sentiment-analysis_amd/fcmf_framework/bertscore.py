@@ -25,7 +25,6 @@ class BertScorer:
         if not isinstance(model, RobertaModel):
             model = RobertaModel.from_pretrained(model)
             model = model.to(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
-            ops.shadows.clear()      # (keyed by storage address: the new weights may sit where a freed model's were)
         elif device is not None:
             model = model.to(device)
         self.model = model.eval()

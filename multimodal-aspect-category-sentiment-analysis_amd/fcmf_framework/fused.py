@@ -63,9 +63,9 @@ def _fused_weight(ws, dtype):
             torch.as_strided(w0.detach(), (len(ws) * w0.shape[0],), (1,))
         if dtype == torch.float32:
             return flat
-        # the shadow cache keys on (ptr, shape); `flat` shares w0's version counter, and FusedAdamW marks
-        # every shadow it did not refresh itself as stale
-        return ops.shadows.get(flat)
+        # `flat` is a temporary: the shadow belongs to w0 (or to the packed parameter w0 is a view of), whose version
+        # counter it shares; FusedAdamW marks every shadow it did not refresh itself as stale
+        return ops.shadows.get(flat, owner=w0)
     cat = torch.cat([w.detach() for w in ws], 0)
     return cat if dtype == torch.float32 else ops.cast(cat, dtype)
 

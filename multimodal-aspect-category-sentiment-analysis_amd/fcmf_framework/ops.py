@@ -9,15 +9,15 @@ refreshed when the parameter changes.
 import ctypes
 import math
 import os
-import weakref
 
 import torch
 
 from . import _hip as H, attn
 from .attn import valu_float32_key_limit      # noqa: F401  (part of this module's surface: DESIGN.md, shared_kv_attention)
+from .shadows import VOCAB_PAD, shadows      # noqa: F401  (the weight-shadow cache: `ops.shadows` is the one instance)
 
 # --------------------------------------------------------------------------------------
-# global state: dropout seeds and bf16 weight shadows
+# global state: compute dtype, fp8 switch, dropout seeds
 # --------------------------------------------------------------------------------------
 _compute_dtype = torch.float32
 
@@ -83,222 +83,7 @@ def next_seed():
     return (x * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
 
 
-VOCAB_PAD = 32   # row padding of ragged 2-D weights (one MFMA k-tile)
 TOPK_MAX = 16    # fcmf_logsoftmax_topk's limit on k (include/fcmf_hip.h)
-
-
-class _Shadows:
-    """bf16 copies of float32 master parameters, keyed by storage address."""
-
-    def __init__(self):
-        self.map = {}
-        self.pad = {}
-        self.mapT = {}
-        self.mapD = {}
-        self.mapQ = {}
-        self.mapQT = {}
-        self.mapH = {}
-        self._mt_tables = None
-
-    def get_t(self, w, owner=None):
-        """bf16 TRANSPOSE [K, N] of a float32 [N, K] weight: dX = dY W then reads W^T as a K-contiguous operand
-        (ds_read_b128 instead of transposed LDS reads: the NT kernels run 10-25 % faster than the NN ones).
-        Rebuilt lazily after every optimizer step (one small kernel per weight).
-        owner: the Parameter whose storage `w` is (a view of); defaults to `w`.  The entry only holds a WEAK reference to
-        it: `refresh_transposed` re-reads the source by raw address, which is only legal while that tensor is alive."""
-        key = (w.data_ptr(), tuple(w.shape))
-        ent = self.mapT.get(key)
-        owner = w if owner is None else owner
-        if ent is not None and ent[1] == w._version and not ent[2] and ent[4]() is owner:
-            return ent[0]
-        sh = ent[0] if ent is not None else torch.empty((w.shape[1], w.shape[0]), dtype=torch.bfloat16, device=w.device)
-        src = w.detach()
-        if not src.is_contiguous():
-            src = src.contiguous()
-        H.check(H.lib().fcmf_cast_transpose(H.ptr(src), H.ptr(sh), w.shape[0], w.shape[1], H.stream()), "fcmf_cast_transpose")
-        self.mapT[key] = [sh, w._version, False, w.is_contiguous(), weakref.ref(owner), w.data_ptr() - owner.data_ptr()]
-        return sh
-
-    def _prune_transposed(self):
-        """drop the transposed copies whose source tensor is gone (a freed model: its storage may have been returned to the
-        driver, or recycled for something else) or has moved (`.to()`, re-fused q|k|v storage)"""
-        dead = []
-        for k, ent in self.mapT.items():
-            o = ent[4]()
-            if o is None or o.data_ptr() + ent[5] != k[0]:
-                dead.append(k)
-        for k in dead:
-            del self.mapT[k]
-        if dead:
-            self._mt_tables = None
-
-    def refresh_transposed(self):
-        """rebuild EVERY cached transposed copy of a LIVE weight in one launch (called by the fused optimizers right after
-        their update: all of them are stale at that point, and rebuilding them lazily costs one small launch per weight)"""
-        if not self.mapT:
-            return
-        self._prune_transposed()
-        items = [(k, ent) for k, ent in self.mapT.items() if ent[3]]      # (sources read in place must be dense [R, C])
-        if not items:
-            return
-        sig = tuple((k[0], ent[0].data_ptr()) for k, ent in items)
-        if self._mt_tables is None or self._mt_tables[0] != sig:
-            dev = items[0][1][0].device
-            desc = []
-            for t, (k, ent) in enumerate(items):
-                R, C = k[1]
-                desc += [(t, r, c) for r in range((R + 63) // 64) for c in range((C + 63) // 64)]
-            self._mt_tables = (sig,
-                               torch.tensor([k[0] for k, _ in items], dtype=torch.int64, device=dev),
-                               torch.tensor([ent[0].data_ptr() for _, ent in items], dtype=torch.int64, device=dev),
-                               torch.tensor([list(k[1]) for k, _ in items], dtype=torch.int32, device=dev),
-                               torch.tensor(desc, dtype=torch.int32, device=dev), len(desc))
-        _, src, dst, dims, desc, n = self._mt_tables
-        H.check(H.lib().fcmf_multi_cast_transpose(H.ptr(src), H.ptr(dst), H.ptr(dims), H.ptr(desc), n, H.stream()),
-                "fcmf_multi_cast_transpose")
-        for _, ent in items:
-            ent[2] = False
-            ent[1] = ent[4]()._version       # fresh as of the owner's current version
-
-    def head_nk(self, ws):
-        """bf16 [len(ws) * n_head * d, E] re-layout ("nn.Linear layout", natural head order) of the per-head weights `ws` (float32
-        Parameters [n_head, E, d] of the IAOG decoder's Attention): row (i * n_head + h) * d + j = ws[i][h, :, j].  Every [d, E]
-        row block is the transpose of the dense [E, d] slice ws[i][h] and is REGISTERED as one of the transposed copies, so
-        `refresh_transposed` rebuilds all of them -- every block of the decoder -- in the optimizer's one launch (the round-2 form
-        rebuilt each layout with permute + reshape copies, a cat and a cast per step and block: 130 launches).  With another
-        optimizer the first use after an update refreshes everything, also in one launch."""
-        key = tuple(w.data_ptr() for w in ws) + (tuple(ws[0].shape),)
-        ent = self.mapH.get(key)
-        if ent is None or any(r() is None for r in ent[2]):
-            nh, E, d = ws[0].shape
-            buf = torch.empty((len(ws) * nh * d, E), dtype=torch.bfloat16, device=ws[0].device)
-            pieces = []
-            for i, w in enumerate(ws):
-                if w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape) != (nh, E, d):
-                    raise H.HipLibraryError("head_nk: dense float32 [n_head, E, d] parameters expected")
-                for h in range(nh):
-                    src, dst = w.detach()[h], buf[(i * nh + h) * d:(i * nh + h + 1) * d]
-                    # (the GROUP is part of the key: the same parameter may sit in two groupings -- [w_kx] alone and [w_kx, w_qx] --
-                    #  and each grouping's buffer must keep its own registered pieces, or the loser would serve stale weights)
-                    k2 = (src.data_ptr(), (E, d), key)
-                    self.mapT[k2] = [dst, -1, True, True, weakref.ref(w), src.data_ptr() - w.data_ptr()]
-                    pieces.append(k2)
-            self._mt_tables = None
-            ent = self.mapH[key] = (buf, pieces, [weakref.ref(w) for w in ws])
-        buf, pieces, owners = ent
-        for k2 in pieces:
-            e = self.mapT.get(k2)
-            if e is None or e[2] or e[1] != e[4]()._version:
-                if e is None:              # (pruned: the parameter moved) -- start over
-                    del self.mapH[key]
-                    return self.head_nk(ws)
-                self.refresh_transposed()
-                break
-        return buf
-
-    def get_fp8(self, w, owner=None):
-        """(q [N, K] e4m3 bytes, scale [N] float32) of a float32 [N, K] weight, quantised per output row; rebuilt lazily
-        after the parameter changed (FusedAdamW marks every shadow stale)"""
-        key = (w.data_ptr(), tuple(w.shape))
-        ent = self.mapQ.get(key)
-        owner = w if owner is None else owner
-        if ent is not None and ent[1] == w._version and not ent[2] and ent[3]() is owner:
-            return ent[0]
-        src = self.get(w) if w.is_contiguous() else w.detach().contiguous()       # the bf16 shadow: half the bytes to read
-        q, sc = quant_fp8_rows(src, w.shape[0], w.shape[1], w.shape[1], out=None if ent is None else ent[0])
-        self.mapQ[key] = [(q, sc), w._version, False, weakref.ref(owner)]
-        return q, sc
-
-    def get_fp8_t(self, w, owner=None):
-        """(q [K, N] e4m3, scale [K]) of the TRANSPOSE of a float32 [N, K] weight, quantised per input row: the B operand
-        of dX = dY W on the fp8 kernel (contraction over N)"""
-        key = (w.data_ptr(), tuple(w.shape))
-        ent = self.mapQT.get(key)
-        owner = w if owner is None else owner
-        if ent is not None and ent[1] == w._version and not ent[2] and ent[3]() is owner:
-            return ent[0]
-        wt = self.get_t(w, owner)                                                   # [K, N] bf16, fresh
-        q, sc = quant_fp8_rows(wt, wt.shape[0], wt.shape[1], wt.shape[1], out=None if ent is None else ent[0])
-        self.mapQT[key] = [(q, sc), w._version, False, weakref.ref(owner)]
-        return q, sc
-
-    def padded(self, w):
-        """the fresh bf16 copy of a 2-D weight including its zero rows up to a multiple of 32"""
-        sh = self.get(w)
-        return self.pad.get((w.data_ptr(), tuple(w.shape)), sh)
-
-    def get(self, w):
-        key = (w.data_ptr(), tuple(w.shape))
-        ent = self.map.get(key)
-        if ent is not None and ent[1] == w._version and not ent[2]:
-            return ent[0]
-        if ent is not None:
-            sh = ent[0]
-        elif w.dim() == 2 and w.shape[0] % VOCAB_PAD != 0:
-            # 2-D weights with a ragged row count (the 64001-row tied vocabulary matrix) get ZERO rows up to the next
-            # multiple of 32 behind the copy: `padded(w)` hands the MFMA kernels a regular [rows32, K] operand
-            rows = (w.shape[0] + VOCAB_PAD - 1) // VOCAB_PAD * VOCAB_PAD
-            full = torch.zeros((rows, w.shape[1]), dtype=torch.bfloat16, device=w.device)
-            sh = full[:w.shape[0]]
-            self.pad[key] = full
-        else:
-            sh = torch.empty(w.shape, dtype=torch.bfloat16, device=w.device)
-        src = w.detach()
-        if not src.is_contiguous():
-            src = src.contiguous()
-        H.check(H.lib().fcmf_cast(H.ptr(src), H.ptr(sh), src.numel(), H.F32, H.BF16, H.stream()), "fcmf_cast")
-        self.map[key] = [sh, w._version, False]
-        return sh
-
-    def derived(self, w, tag, build):
-        """a tensor derived from the PARAMETER `w` (a re-layout and / or cast), cached per (storage, shape, tag) and
-        rebuilt by `build(w.detach())` when the parameter has changed.  Only ever key this on persistent leaf
-        parameters: a temporary's address is recycled by the caching allocator (and its version is always 0).  The entry holds
-        a weak reference to `w` and serves no other tensor: a freed model's parameter addresses are recycled too, for the next
-        model's parameters of the same shape and version (its w_qx where w_kx was)."""
-        key = (w.data_ptr(), tuple(w.shape), tag)
-        ent = self.mapD.get(key)
-        if ent is not None and ent[1] == w._version and not ent[2] and ent[3]() is w:
-            return ent[0]
-        t = build(w.detach())
-        self.mapD[key] = [t, w._version, False, weakref.ref(w)]
-        return t
-
-    def peek(self, w):
-        ent = self.map.get((w.data_ptr(), tuple(w.shape)))
-        return None if ent is None else ent[0]
-
-    def mark_fresh(self, w):
-        ent = self.map.get((w.data_ptr(), tuple(w.shape)))
-        if ent is not None:
-            ent[1] = w._version
-            ent[2] = False
-
-    def mark_all_stale(self):
-        for ent in self.map.values():
-            ent[2] = True
-        for ent in self.mapT.values():
-            ent[2] = True
-        for ent in self.mapD.values():
-            ent[2] = True
-        for m in (self.mapQ, self.mapQT):
-            for k in [k for k, ent in m.items() if ent[3]() is None]:      # quantised copies of freed weights
-                del m[k]
-            for ent in m.values():
-                ent[2] = True
-
-    def clear(self):
-        self.map.clear()
-        self.pad.clear()
-        self.mapT.clear()
-        self.mapD.clear()
-        self.mapQ.clear()
-        self.mapQT.clear()
-        self.mapH.clear()
-        self._mt_tables = None
-
-
-shadows = _Shadows()
 
 # --------------------------------------------------------------------------------------
 # flat gradient arena (dp.GradArena): weight-gradient buffers come out of the parameter's slice of ONE zeroed

@@ -229,7 +229,6 @@ def main(argv=None):
             resnet_img, resnet_roi = build_extractors(lambda: resnet152(weights=weights) if weights is not None else resnet152(),
                                                       args.fine_tune_cnn, device)
     model = model.to(device)
-    ops.shadows.clear()
     optimizer = FusedAdamW(param_groups(model), lr=args.learning_rate)
     steps_per_epoch = len(train_loader) if train_loader is not None else 0
     num_train_steps = int(steps_per_epoch / args.gradient_accumulation_steps * args.num_train_epochs)

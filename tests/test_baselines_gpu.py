@@ -96,7 +96,6 @@ def test_mroberta_matches_torch_modules(dev, hf_dir, geom):
     _seed_params(model)
     ref = _load_ref(RefM(), model)
     model = model.to(dev).eval()
-    ops.shadows.clear()          # (bf16 weight copies are cached by address: an earlier test's model lived where this one does)
     ids, mask, _, _, vis, roi = _batch(NI, NR)
     ids, mask = ids[:, 0], mask[:, 0]
     w = torch.randn(B, 4, generator=torch.Generator().manual_seed(9))
@@ -124,7 +123,6 @@ def test_tombert_matches_torch_modules(dev, hf_dir, geom):
     _seed_params(model)
     ref = _load_ref(RefT(), model)
     model = model.to(dev).eval()
-    ops.shadows.clear()          # (bf16 weight copies are cached by address: an earlier test's model lived where this one does)
     ids, mask, tids, tmask, vis, roi = _batch(NI, NR)
     ids, mask, tids, tmask = ids[:, 0], mask[:, 0], tids[:, 0], tmask[:, 0]
     w = torch.randn(B, 4, generator=torch.Generator().manual_seed(9))
@@ -155,7 +153,6 @@ def test_forward_aspects_equals_stacked_forward(dev, hf_dir, name, geom):
     model = getattr(baselines, name)(hf_dir)
     _seed_params(model)
     model = model.to(dev).eval()
-    ops.shadows.clear()          # (bf16 weight copies are cached by address: an earlier test's model lived where this one does)
     ids, mask, tids, tmask, vis, roi = (t.to(dev) for t in _batch(NI, NR))
     labels = torch.randint(0, 4, (B, A), generator=torch.Generator().manual_seed(3)).to(dev)
     if name == "mRoBERTa":

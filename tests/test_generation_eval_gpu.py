@@ -19,14 +19,11 @@ DTYPES = [torch.float32, torch.bfloat16]
 
 
 def tiny_roberta(dev, layers=2):
-    from fcmf_framework import ops
     from fcmf_framework.roberta import RobertaConfig, RobertaModel
     cfg = dict(synth.TINY_CFG, num_hidden_layers=layers)
     m = RobertaModel(RobertaConfig(**cfg))
     m.load_state_dict(synth.synth_params(synth.roberta_param_shapes(cfg)))
-    m = m.to(dev).eval()
-    ops.shadows.clear()      # (bf16 weight copies are keyed by storage address: a freed model's may be recycled)
-    return m
+    return m.to(dev).eval()
 
 
 def sentences(lengths, seed):

@@ -943,10 +943,10 @@ def test_transposed_weight_copies_refreshed_in_one_launch(dev):
     before = [w.detach().clone() for w in ws]
     opt.step()
     for w, b in zip(ws, before):
-        ent = ops.shadows.mapT[(w.data_ptr(), tuple(w.shape))]
-        assert ent[2] is False                                   # fresh: nothing left to rebuild lazily
+        ent = ops.shadows.lookup("t", w)
+        assert ent.stale is False and ent.version == w._version  # fresh: nothing left to rebuild lazily
         assert not torch.equal(w.detach(), b)
-        assert torch.equal(ent[0], w.detach().t().contiguous().bfloat16())
+        assert torch.equal(ent.payload, w.detach().t().contiguous().bfloat16())
     ops.shadows.clear()
 
 
@@ -963,15 +963,14 @@ def test_transposed_copies_of_freed_weights_are_dropped(dev):
     view_owner = torch.nn.Parameter(_rand((96, 64), dev, seed=3))
     ops.shadows.get_t(keep); ops.shadows.get_t(gone)
     ops.shadows.get_t(view_owner.detach()[:64], owner=view_owner)      # a temporary view keyed on its Parameter
-    assert len(ops.shadows.mapT) == 3
-    gone_key = (gone.data_ptr(), tuple(gone.shape))
+    assert len(ops.shadows) == 3 and ops.shadows.lookup("t", gone) is not None
     del gone
     gc.collect()
     opt = FusedAdamW([keep], lr=1e-2)
     keep.grad = _rand(keep.shape, dev, seed=4)
     opt.step()                                                         # -> refresh_transposed()
-    assert gone_key not in ops.shadows.mapT and len(ops.shadows.mapT) == 2
-    assert torch.equal(ops.shadows.mapT[(keep.data_ptr(), tuple(keep.shape))][0], keep.detach().t().contiguous().bfloat16())
+    assert len(ops.shadows) == 2 and ops.shadows.lookup("t", view_owner.detach()[:64], owner=view_owner) is not None   # (gone's is the one dropped)
+    assert torch.equal(ops.shadows.lookup("t", keep).payload, keep.detach().t().contiguous().bfloat16())
     # a NEW weight that lands on the recycled address is never served the dead weight's copy
     fresh = torch.nn.Parameter(_rand((256, 64), dev, seed=5))
     assert torch.equal(ops.shadows.get_t(fresh), fresh.detach().t().contiguous().bfloat16())

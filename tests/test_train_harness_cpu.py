@@ -97,44 +97,25 @@ def test_extractor_checkpoints_beside_the_model(tmp_path):
                      ("seed_1_iaog_model_last.pth", dict(old="iaog_model")), ("seed_1_fcmf_model_last.pth", {})):
         img2, roi2 = _extractors(1)
         assert not torch.equal(img2.weight, img.weight)
-        ops.shadows.map["stale"] = None
+        ops.shadows.derived(img2.weight, "stale", torch.clone)
         got = H.load_resnets(str(d / name), img2, roi2, "cpu", **kw)
         assert got == want, (name, kw, got)                  # image first; the directory `runs/fcmf` keeps its name
         assert torch.equal(img2.weight, img.weight) and torch.equal(roi2.bias, roi.bias)
-        assert not ops.shadows.map                           # cached copies of the old weights are dropped
+        assert len(ops.shadows) == 0                         # cached copies of the old weights are dropped
     # nothing to load: an extractor that is None, or no file beside the checkpoint
     img2, roi2 = _extractors(1)
     before = img2.weight.detach().clone()
-    ops.shadows.map["kept"] = None
+    kept = ops.shadows.derived(img2.weight, "kept", torch.clone)
     try:
         assert H.load_resnets(str(d / "seed_1_fcmf_model_last.pth"), None, None, "cpu") == []
         assert H.load_resnets(str(d / "seed_2_fcmf_model_last.pth"), img2, roi2, "cpu") == []
         assert H.load_resnets(str(tmp_path / "runs" / "seed_1_fcmf_model_last.pth"), img2, roi2, "cpu") == []
-        assert torch.equal(img2.weight, before) and "kept" in ops.shadows.map
+        assert torch.equal(img2.weight, before) and len(ops.shadows) == 1 and ops.shadows.lookup("derived", img2.weight, "kept").payload is kept
         assert H.load_resnets(str(d / "seed_1_fcmf_model_last.pth"), None, roi2, "cpu") == want[1:]
     finally:
         ops.shadows.clear()
     H.save_extractors(str(tmp_path), 1, "best", None, None, opt, sched, 0)
     assert sorted(os.listdir(tmp_path)) == ["runs"]
-
-
-def test_derived_shadow_is_not_served_to_another_parameter_at_the_same_address():
-    """a freed model's parameter addresses are recycled for the next model's parameters of the same shape and version: the
-    re-layout cached for the first must not come back for the second (two Parameters over one storage stand in for that)"""
-    from fcmf_framework import ops
-    a = torch.nn.Parameter(torch.arange(6.0).view(2, 3))
-    b = torch.nn.Parameter(a.data)
-    assert a.data_ptr() == b.data_ptr() and a._version == b._version and a is not b
-    built = []
-    build = lambda owner: lambda src: built.append(owner) or src.t().contiguous()
-    try:
-        ta = ops.shadows.derived(a, "t", build("a"))
-        assert ops.shadows.derived(a, "t", build("a")) is ta and built == ["a"]
-        tb = ops.shadows.derived(b, "t", build("b"))
-        assert tb is not ta and built == ["a", "b"]
-        assert ops.shadows.derived(b, "t", build("b")) is tb and built == ["a", "b"]
-    finally:
-        ops.shadows.clear()
 
 
 def test_synth_pixel_batch_is_the_two_seeded_crop_draws():
