@@ -501,12 +501,27 @@ int fcmf_gemm_colblocks(fcmf_gemm_ctx* ctx, const void* A, const void* B, float*
                         int64_t ldb, int64_t ldc, int trans_a, int trans_b, int col_block, int64_t col_block_stride,
                         int accumulate, void* stream);
 
-/* `count` same-shape weight gradients in one launch: C_i [M, N] float32 (+)= A_i^T B_i with A_i = dY_i [K, M], B_i = X_i [K, N]
- * (bf16, K = tokens) -- nn.Linear's weight gradient (loss.backward(), run_multimodal_fcmf.py:466) for the layers of an encoder,
- * which the host queues during the backward pass and multiplies together: the tiles of all matrices form ONE work list for the
- * persistent 256 x 256 kernel (a 768 x 768 gradient alone is 9 tiles; alone it fills the chip only through a 28-way split of K
- * and a 64 MB partial-tile round trip).  A / B / C: host arrays of `count` device pointers.  accumulate as fcmf_gemm.  Shapes the
- * persistent kernel does not take (M or N < 256, unaligned) and count == 1 run as `count` fcmf_gemm calls: same results. */
+/* The weight gradients of a whole backward pass in one launch: C_i [M_i, N_i] float32 (+)= A_i^T B_i for `count` problems of ANY
+ * shapes, A_i = dY_i [K_i, M_i], B_i = X_i [K_i, N_i] (bf16, K_i = tokens) -- nn.Linear's weight gradient (loss.backward(),
+ * run_multimodal_fcmf.py:466), which the host queues during the backward pass.  The 256 x 256 tiles of all matrices form ONE work
+ * list for the persistent kernel: whole rounds of equal-depth tiles run unsplit and write C themselves, the rest is cut into
+ * near-equal pieces of K whose partial tiles one reduce launch sums in a fixed order (bit-identical from run to run).  Several
+ * problems may name the SAME C (a weight applied more than once): C (+)= the sum of all of them.  A / B / C: host arrays of `count`
+ * device pointers; M / N / K / lda / ldb / ldc: host arrays of `count`.  accumulate as fcmf_gemm.  The tables travel through the
+ * head of the context's workspace.  Problems the tile kernel does not take (M or N < 256, unaligned), a list of fewer than two
+ * that it takes, and every problem when there is no workspace run as fcmf_gemm calls inside: same results. */
+int fcmf_gemm_dw_list(fcmf_gemm_ctx* ctx, int count, const void* const* A, const void* const* B, void* const* C, const int* M,
+                      const int* N, const int* K, const int64_t* lda, const int64_t* ldb, const int64_t* ldc, int accumulate,
+                      void* stream);
+/* The work list fcmf_gemm_dw_list builds, without a device: from the shapes, dest[i] (index of the first problem that shares problem
+ * i's C; i itself otherwise), the workgroup count and the workspace size.  items [max_items][6] = problem, tile row, tile column,
+ * first k-tile (32 deep), k-tiles, workspace slot (-1: the item writes C) in launch order (item i runs on workgroup i % num_cus);
+ * reduce [max_reduce][5] = first slot, slots, problem, tile row, tile column; either may be NULL.  info[6] = items, reduce entries,
+ * slots, bytes of tables at the head of the workspace, workspace bytes needed in all, planned efficiency (mean / max k-tiles per
+ * workgroup) in millionths.  FCMF_ERR_UNSUPPORTED: the workspace is too small for the partial tiles of the shared destinations. */
+int fcmf_gemm_dw_list_plan(int count, const int* M, const int* N, const int* K, const int* dest, int num_cus, int64_t ws_bytes,
+                           int* items, int max_items, int* reduce, int max_reduce, int64_t* info);
+/* `count` same-shape problems: fcmf_gemm_dw_list with one shape. */
 int fcmf_gemm_dw_batched(fcmf_gemm_ctx* ctx, int count, const void* const* A, const void* const* B, void* const* C, int M, int N, int K,
                          int64_t lda, int64_t ldb, int64_t ldc, int accumulate, void* stream);
 /* Implicit-GEMM convolution for inputs with few channels -- the trunk's stem, conv1 = 7x7 / stride 2 / pad 3 on RGB crops

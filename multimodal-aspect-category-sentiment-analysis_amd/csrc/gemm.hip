@@ -8,10 +8,16 @@
 //   gemm_generic_kernel: any dtype / any stride, exact-f32 v_mfma_f32_16x16x4_f32.  Parity path (fp32 mode) and odd
 //                        shapes (classifier N=4, box WG 64->8 ...);
 //   gemm_bf16_small_kernel: 64x64 tiles where 128x128 tiles would leave most CUs empty; gemm_fp8_tile192_kernel: e4m3 operands;
-//   gemm_bf16_dw_batched_kernel: up to 32 same-shape weight gradients as one work list; splitk_reduce_*: the reduce passes.
+//   gemm_bf16_dw_batched_kernel: the weight gradients of a whole backward pass, of any shapes, as one work list (plan_dw_list);
+//   splitk_reduce_*: the reduce passes.
 // Host half (end of the file): entry point -> GemmArgs -> plan_gemm (pure) -> GemmPlan -> run_plan (the only launcher).
 #include "common.h"
+#include <algorithm>
 #include <cstdio>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <vector>
 
 struct GemmParams {
   const void* A; const void* B; void* C; const float* bias; void* aux;
@@ -34,12 +40,24 @@ struct GemmParams {
   // log2 of the element distance between neighbouring pixels of the convolution's input (= cv_logC for an NHWC activation
   // whose k-tiles walk the channels of one tap; smaller for fcmf_conv_gemm_runs, whose "tap" is a run of several whole pixels)
   int cv_logP;
-  // batched weight gradients (gemm_bf16_dw_batched_kernel): the `tiles` output tiles cover `tiles / tiles_per_mat` same-shape
-  // matrices, tile t belongs to matrix t / tiles_per_mat whose operand / output pointers come from the BatchPtrs argument
-  int tiles_per_mat;
 };
-constexpr int BATCH_MAX = 32;      // matrices per launch (the three pointer tables travel as a kernel argument: 768 bytes)
-struct BatchPtrs { const void* A[BATCH_MAX]; const void* B[BATCH_MAX]; void* C[BATCH_MAX]; };
+// Weight-gradient work list (gemm_bf16_dw_batched_kernel): `total_items` (tile, k-range) items over matrices of ANY shapes.  The
+// three tables live in device memory (uploaded per launch: fcmf_gemm_dw_list); everything an item needs beyond the main loop's
+// constants is read from them per item and made wave-uniform.
+struct DwMat {                     // one problem C [M, N] (+)= A^T B: 64 bytes
+  const void* A; const void* B; float* C;
+  int M, N, lda, ldb;              // (K * ld < 2^30: the leading dimensions fit an int)
+  int64_t ldc;
+  unsigned a_bytes, b_bytes;       // operand extents for the buffer range check
+  int pad[2];
+};
+struct DwItem {                    // 16 bytes
+  int mt;                          // matrix | tile row << 16 | tile column << 24 (tile rows / columns < 256)
+  int kt_begin, nkt;               // k-tiles [kt_begin, kt_begin + nkt) of the matrix's contraction
+  int slot;                        // < 0: the item covers the whole contraction and writes C itself (row epilogue); else the
+};                                 // index of its fragment-layout partial tile in the workspace
+struct DwRed { int slot0, count, mat, tile; };   // C tile `tile` (row | column << 16) of matrix `mat` (+)= partials slot0 .. slot0 + count - 1
+struct DwList { const DwMat* mats; const DwItem* items; };
 
 // element offset of the receptive-field origin of output row `row` in the (padded) input
 __device__ __forceinline__ int64_t conv_row_base(const GemmParams& p, int row) {
@@ -459,6 +477,20 @@ __device__ __forceinline__ void store8f(float* q, const f32x2 (&v)[4]) {
   *reinterpret_cast<f32x4*>(q + 4) = f32x4{v[2][0], v[2][1], v[3][0], v[3][1]};
 }
 
+// the same through a pointer the kernel assembled from table words: `generic` to the compiler (flat loads / stores, which also
+// count as LDS traffic) unless told that it is global memory
+typedef __attribute__((address_space(1))) f32x4 global_f32x4;
+__device__ __forceinline__ void load8f_global(const float* q, f32x2 (&v)[4]) {
+  const global_f32x4* g = (const global_f32x4*)q;
+  const f32x4 a = g[0], b = g[1];
+  v[0] = f32x2{a[0], a[1]}; v[1] = f32x2{a[2], a[3]}; v[2] = f32x2{b[0], b[1]}; v[3] = f32x2{b[2], b[3]};
+}
+__device__ __forceinline__ void store8f_global(float* q, const f32x2 (&v)[4]) {
+  global_f32x4* g = (global_f32x4*)q;
+  g[0] = f32x4{v[0][0], v[0][1], v[1][0], v[1][1]};
+  g[1] = f32x4{v[2][0], v[2][1], v[3][0], v[3][1]};
+}
+
 // MI = 16-row fragments per wave along M: 8 -> 256x256 block tile, 6 -> 192x256 (row-major A only).  The
 // 192-row variant exists for tile-count quantisation: M = 49152, N = 768 gives 576 tiles of 256 rows (2.25
 // rounds on 256 CUs, the last one a quarter full) but 768 tiles of 192 rows = exactly 3 rounds of 3/4 the work.
@@ -483,7 +515,7 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 // zero-filled columns a 256-column tile would carry (those layers ran on the 128 x 128 kernel at ~370 TFLOP/s, half of it on
 // zeros for N = 64).  K-contiguous operands, 64-deep k-tiles, bf16 output, no epilogue operand.
 template <bool A_TR, bool B_TR, typename TC, int EPI, int MI, int KB, bool FP8 = false, bool BATCH = false, int WNW = 4>
-__device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, const BatchPtrs* bp = nullptr) {
+__device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, const DwList* dw = nullptr) {
   static_assert(!BATCH || (A_TR && B_TR && sizeof(TC) == 4 && MI == 8 && KB == 32), "batched: the weight-gradient kernel");
   static_assert(WNW == 4 ? (MI == 8 || (MI == 6 && !A_TR && sizeof(TC) == 2))
                          : ((WNW == 2 && MI == 4) || (WNW == 1 && MI == 2)) && !A_TR && !B_TR && sizeof(TC) == 2 && KB == 64 && !FP8 &&
@@ -517,6 +549,16 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
   // XCD-aware order inside a round: the workgroups of one XCD (blockIdx % 8) take consecutive logical
   // items, and consecutive items share the A row-panel (all N tiles of one M tile) -> L2 hits.
   const int tiles_n = (p.N + GB - 1) / GB;
+  // BATCH: the problem of the current work item is that of the item's matrix, re-read per item (decode); else the launch's own
+  [[maybe_unused]] int cM = 0, cN = 0, cslot = -1, clda = 0, cldb = 0;
+  [[maybe_unused]] int64_t cldc = 0;
+  [[maybe_unused]] float* cC = nullptr;
+  [[maybe_unused]] unsigned ca_step = 0, cb_step = 0;
+  auto dim_m = [&]() { if constexpr (BATCH) return cM; else return p.M; };
+  auto dim_n = [&]() { if constexpr (BATCH) return cN; else return p.N; };
+  auto ld_a = [&]() -> int64_t { if constexpr (BATCH) return clda; else return p.lda; };
+  auto ld_b = [&]() -> int64_t { if constexpr (BATCH) return cldb; else return p.ldb; };
+  auto ld_c = [&]() -> int64_t { if constexpr (BATCH) return cldc; else return p.ldc; };
   const int nblk = gridDim.x;
   int slot = blockIdx.x;
   {
@@ -528,7 +570,7 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
   const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.B), 0, p.b_bytes, 0x00020000);
   constexpr bool ASM_DMA = A_TR || B_TR;    // (see dma16_asm: transposed fragment reads must not see a compiler-visible LDS-DMA)
   [[maybe_unused]] u32x4 wA = rsrc_words(p.A, p.a_bytes), wB = rsrc_words(p.B, p.b_bytes);   // (BATCH: re-pointed per work item)
-  const unsigned a_step = A_TR ? (unsigned)(KB * p.lda * 2) : (unsigned)(KB * 2);
+  const unsigned a_step = A_TR ? (unsigned)(KB * p.lda * 2) : (unsigned)(KB * 2);           // (BATCH: ca_step / cb_step, per work item)
   const unsigned b_step = B_TR ? (unsigned)(KB * p.ldb * 2) : (unsigned)(KB * 2);
   // Per-lane LDS offsets are computed ONCE; fragment f of a K-contiguous operand is a constant 1 KiB
   // step away (row bit 3, which drives the swizzle, does not depend on f).
@@ -564,9 +606,25 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
 
   struct Item { int i0, j0, kt_begin, nkt, zsplit, batch; };
   auto decode = [&](int item) -> Item {
+    if constexpr (BATCH) {
+      // the item and its matrix from the tables (vector loads of a wave-uniform address; every word is made scalar, so neither
+      // the descriptors nor the dimensions cost a VGPR in the main loop)
+      auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+      const int4 it = *reinterpret_cast<const int4*>(dw->items + item);
+      const int mt = uni(it.x), mat = mt & 0xFFFF;
+      const int4* mq = reinterpret_cast<const int4*>(dw->mats + mat);
+      const int4 m0 = mq[0], m1 = mq[1], m2 = mq[2], m3 = mq[3];
+      wA = u32x4{(unsigned)uni(m0.x), (unsigned)uni(m0.y) & 0xFFFFu, (unsigned)uni(m3.x), 0x00020000u};
+      wB = u32x4{(unsigned)uni(m0.z), (unsigned)uni(m0.w) & 0xFFFFu, (unsigned)uni(m3.y), 0x00020000u};
+      cC = reinterpret_cast<float*>(((unsigned long long)(unsigned)uni(m1.y) << 32) | (unsigned)uni(m1.x));
+      cM = uni(m1.z); cN = uni(m1.w); clda = uni(m2.x); cldb = uni(m2.y);
+      cldc = (int64_t)(((unsigned long long)(unsigned)uni(m2.w) << 32) | (unsigned)uni(m2.z));
+      ca_step = (unsigned)(KB * 2) * (unsigned)clda; cb_step = (unsigned)(KB * 2) * (unsigned)cldb;
+      cslot = uni(it.w);
+      return Item{((mt >> 16) & 0xFF) * TM, ((mt >> 24) & 0xFF) * GB, uni(it.y), uni(it.z), 0, mat};
+    }
     const int zsplit = item / p.tiles, tile = item - zsplit * p.tiles;
     int local = tile, batch = 0;
-    if constexpr (BATCH) { batch = tile / p.tiles_per_mat; local = tile - batch * p.tiles_per_mat; }
     const int tile_m = local / tiles_n, tile_n = local % tiles_n;
     const int kb = zsplit * p.ktiles_per_split;
     return Item{tile_m * TM, tile_n * GB, kb, min(nk_total, kb + p.ktiles_per_split) - kb, zsplit, batch};
@@ -592,15 +650,15 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
   auto sources = [&](const Item& w) -> Src {
     Src r;
 #pragma unroll
-    for (int j = 0; j < A_PIECES; ++j) r.a[j] = dma_voffset_t<A_TR, KB, FP8, PAD_TR>(a_piece0 + j, lane, p.lda, w.i0, p.M, p.cv_C ? &p : nullptr);
+    for (int j = 0; j < A_PIECES; ++j) r.a[j] = dma_voffset_t<A_TR, KB, FP8, PAD_TR>(a_piece0 + j, lane, ld_a(), w.i0, dim_m(), p.cv_C ? &p : nullptr);
 #pragma unroll
-    for (int j = 0; j < B_PIECES; ++j) r.b[j] = dma_voffset_t<B_TR, KB, FP8, PAD_TR>(wave * B_PIECES + j, lane, p.ldb, w.j0, p.N);
+    for (int j = 0; j < B_PIECES; ++j) r.b[j] = dma_voffset_t<B_TR, KB, FP8, PAD_TR>(wave * B_PIECES + j, lane, ld_b(), w.j0, dim_n());
     return r;
   };
   // DMA of k-tile t of item w: A tile to sa and / or B tile to sb (nullptr = skip)
   auto issue_ab = [&](const Item& w, const Src& src, int t, char* sa, char* sb) {
-    const unsigned ka = (!A_TR && !FP8 && p.cv_C) ? conv_k_offset(p, (w.kt_begin + t) * KB) : (unsigned)(w.kt_begin + t) * a_step;
-    const unsigned kb = (unsigned)(w.kt_begin + t) * b_step;
+    const unsigned ka = (!A_TR && !FP8 && p.cv_C) ? conv_k_offset(p, (w.kt_begin + t) * KB) : (unsigned)(w.kt_begin + t) * (BATCH ? ca_step : a_step);
+    const unsigned kb = (unsigned)(w.kt_begin + t) * (BATCH ? cb_step : b_step);
     if (sa) {
 #pragma unroll
       for (int j = 0; j < A_PIECES; ++j) {
@@ -646,8 +704,7 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
     // compiler can see, here, where nothing of this item is in flight yet, empties its scoreboard for the whole main loop.
     __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0), expcnt / lgkmcnt untouched
   }
-  const Item w = decode(item);
-  if constexpr (BATCH) { wA = rsrc_words(bp->A[w.batch], p.a_bytes); wB = rsrc_words(bp->B[w.batch], p.b_bytes); }
+  const Item w = decode(item);      // (BATCH: re-points wA / wB / cC and the dimensions at the item's matrix)
   Src src = sources(w);
 #pragma unroll
   for (int j = 0; j < A_PIECES; ++j) asm volatile("" : "+v"(src.a[j]), "+v"(src.b[j]));   // materialised here, not re-derived per k-tile
@@ -830,7 +887,7 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
     for (int rnd = EARLY_AUX ? 2 : 0; rnd < (EARLY_AUX ? NRND : 2); ++rnd) load_aux(rnd);
   }
 
-  TC* C = reinterpret_cast<TC*>(BATCH ? bp->C[w.batch] : p.C);
+  TC* C = reinterpret_cast<TC*>(BATCH ? (void*)cC : p.C);
   if constexpr (sizeof(TC) == 2) {
     // ---- wave-local bf16 epilogue ------------------------------------------------------------------
     // Every wave of the workgroup has passed barrier nkt-1, so every stage except that of tile nkt-1
@@ -1068,8 +1125,9 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
     // accumulators -> LDS (f32, one 128-row half at a time, the whole ring) -> row-wise output with
     // whole-row stores or 256-byte float atomics for split-K
     constexpr int LPR = GB / 8, RPI = 64 / LPR, RPW = 128 / NW;
-    const bool to_ws = p.ws != nullptr && p.ksplit > 1;     // k-split partials go to the workspace with plain stores
-    if (to_ws && !p.bias && !p.colsum) {
+    // k-split partials go to the workspace with plain stores (BATCH: the items the planner gave a partial-tile slot)
+    const bool to_ws = BATCH ? cslot >= 0 : p.ws != nullptr && p.ksplit > 1;
+    if (to_ws && (BATCH || (!p.bias && !p.colsum))) {
       // The workspace layout is ours to choose: the partial tile goes out in the FRAGMENT layout, straight from the accumulator
       // registers -- every store instruction is one contiguous KiB (64 lanes x 16 B), no LDS staging, no barrier.  The reduce pass
       // (splitk_reduce_frag_kernel) reads the partials back in the same order and only there maps (fragment, lane) to (row, column).
@@ -1078,7 +1136,7 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
       int lane_w = lane;
       asm volatile("" : "+v"(lane_w));            // (laundered: not hoisted above the main loop, where every VGPR is spoken for)
       const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(p.ws, 0, 0x7FFFFFFF, 0x00020000);
-      const unsigned wbase = (unsigned)item * (unsigned)(GB * GB * 4) + (unsigned)wave * (32u * 1024u);
+      const unsigned wbase = (unsigned)(BATCH ? cslot : item) * (unsigned)(GB * GB * 4) + (unsigned)wave * (32u * 1024u);
 #pragma unroll
       for (int fj = 0; fj < 4; ++fj)
 #pragma unroll
@@ -1089,10 +1147,10 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
       continue;                                   // (barrier-free, like the bf16 epilogue: the next item's tiles 0-2 go to the three
                                                   //  stages every wave has finished reading; the fourth waits for ITS barrier 0)
     }
-    const bool atomic = (p.ksplit > 1) && !to_ws;
+    const bool atomic = !BATCH && (p.ksplit > 1) && !to_ws;      // (BATCH: an item without a slot is its tile's only producer)
     const bool lead = (w.zsplit == 0);
     float* Cout = to_ws ? p.ws + (int64_t)w.zsplit * p.M * p.N : reinterpret_cast<float*>(C);
-    const int64_t ldo = to_ws ? (int64_t)p.N : p.ldc;
+    const int64_t ldo = to_ws ? (int64_t)p.N : ld_c();
     const bool rmw = p.accumulate && !to_ws;                // (the reduce pass adds the old C once)
     float* Ct = reinterpret_cast<float*>(smem);   // [128][256] f32; 16-B chunk index XOR (row & 7)
     int lane_e = lane;                          // (laundered, as in the bf16 epilogue)
@@ -1122,31 +1180,31 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
         for (int it0 = 0; it0 < RPW; ++it0) {
           const int it = (it0 + rot) & (RPW - 1);
           const int row = ((wave + w.zsplit) & (NW - 1)) * RPW + it, gi = i0 + half * 128 + row;
-          if (gi >= p.M) continue;
+          if (gi >= dim_m()) continue;
 #pragma unroll
           for (int k = 0; k < GB / 64; ++k) {
             const int col = lane_e + 64 * k, gjc = j0 + col;
-            if (gjc < p.N) atomicAdd(Cf + (int64_t)gi * p.ldc + gjc, Ct[row * GB + ((((col >> 2)) ^ (row & 7)) << 2) + (col & 3)]);
+            if (gjc < dim_n()) atomicAdd(Cf + (int64_t)gi * ld_c() + gjc, Ct[row * GB + ((((col >> 2)) ^ (row & 7)) << 2) + (col & 3)]);
           }
         }
       } else {
         f32x2 bv[4] = {splat2(0.f), splat2(0.f), splat2(0.f), splat2(0.f)};
-        if (p.bias && lead && gj < p.N) load8f(p.bias + gj, bv);
+        if (p.bias && lead && gj < dim_n()) load8f(p.bias + gj, bv);
 #pragma unroll 2
         for (int it = 0; it < RPW / RPI; ++it) {
           const int row = wave * RPW + it * RPI + rsub, gi = i0 + half * 128 + row;
-          if (gi >= p.M || gj >= p.N) continue;
+          if (gi >= dim_m() || gj >= dim_n()) continue;
           const f32x4 lo = *reinterpret_cast<const f32x4*>(Ct + row * GB + ((c0 ^ (row & 7)) << 2));
           const f32x4 hi = *reinterpret_cast<const f32x4*>(Ct + row * GB + (((c0 + 1) ^ (row & 7)) << 2));
           f32x2 v[4] = {f32x2{lo[0], lo[1]} + bv[0], f32x2{lo[2], lo[3]} + bv[1], f32x2{hi[0], hi[1]} + bv[2], f32x2{hi[2], hi[3]} + bv[3]};
           float* cf = Cout + (int64_t)gi * ldo + gj;
           if (rmw) {
             f32x2 o[4];
-            load8f(cf, o);
+            if constexpr (BATCH) load8f_global(cf, o); else load8f(cf, o);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = v[e] + o[e];
           }
-          store8f(cf, v);
+          if constexpr (BATCH) store8f_global(cf, v); else store8f(cf, v);
           if (p.colsum) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) csum[e] = csum[e] + v[e];
@@ -1173,7 +1231,7 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
         float t = 0.f;
 #pragma unroll
         for (int w8 = 0; w8 < NW; ++w8) t += red[w8 * GB + tid_e];
-        if (j0 + tid_e < p.N) atomicAdd(p.colsum + j0 + tid_e, t);
+        if (j0 + tid_e < dim_n()) atomicAdd(p.colsum + j0 + tid_e, t);
       }
       lds_barrier();
     }
@@ -1476,11 +1534,11 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_tile256k64_n128_kernel(GemmP
 __global__ __launch_bounds__(512, 1) void gemm_bf16_tile256k64_n64_kernel(GemmParams p) {
   gemm_bf16_tile256_body<false, false, bf16_t, FCMF_EPI_NONE, 2, 64, false, false, 1>(p);
 }
-// up to BATCH_MAX same-shape weight gradients dW_i (+)= dY_i^T X_i in ONE launch: the tiles of all matrices form one work list
-// (a layer's 768 x 768 gradient alone is 9 tiles: it filled the chip only through a 28-way split of K, whose partial tiles then
-// cost a reduce pass per matrix)
-__global__ __launch_bounds__(512, 1) void gemm_bf16_dw_batched_kernel(GemmParams p, BatchPtrs bp) {
-  gemm_bf16_tile256_body<true, true, float, FCMF_EPI_NONE, 8, 32, false, true>(p, &bp);
+// the weight gradients dW_i (+)= dY_i^T X_i of a whole flush in ONE launch: the tiles of all matrices, of any shapes, form one work
+// list (a layer's 768 x 768 gradient alone is 9 tiles: it filled the chip only through a 28-way split of K, whose partial tiles
+// then cost a reduce pass per matrix).  p carries the list's length, the workspace and `accumulate`; the rest comes per item.
+__global__ __launch_bounds__(512, 1) void gemm_bf16_dw_batched_kernel(GemmParams p, DwList dw) {
+  gemm_bf16_tile256_body<true, true, float, FCMF_EPI_NONE, 8, 32, false, true>(p, &dw);
 }
 template <bool B_TR, int EPI>
 __global__ __launch_bounds__(512, 1) void gemm_bf16_tile192_kernel(GemmParams p) {
@@ -1529,23 +1587,26 @@ __global__ __launch_bounds__(256) void splitk_reduce_frag_kernel(const float* __
   }
 }
 
-// the same over the tiles of a batched launch: tile t belongs to matrix t / tiles_per_mat
-__global__ __launch_bounds__(256) void splitk_reduce_frag_batched_kernel(const float* __restrict__ ws, BatchPtrs bp, int tiles_per_mat, int M,
-                                                                         int N, int64_t ldc, int ksplit, int tiles, int tiles_n,
-                                                                         int accumulate) {
-  const int64_t total = (int64_t)tiles * (GB * GB / 4);
+// the reduce pass of a weight-gradient work list: one table entry per C tile that has partial tiles.  The partials of ALL producers
+// of that tile (the pieces of a split contraction; the several uses of a shared weight) lie in consecutive slots and are summed in
+// slot order with plain stores: the same bits every run.
+__global__ __launch_bounds__(256) void splitk_reduce_list_kernel(const float* __restrict__ ws, const DwRed* __restrict__ red,
+                                                                 const DwMat* __restrict__ mats, int entries, int accumulate) {
+  const int64_t total = (int64_t)entries * (GB * GB / 4);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int tile = (int)(i >> 14), r = (int)(i & 16383);
-    const int b = tile / tiles_per_mat, local = tile - b * tiles_per_mat;
+    const int e = (int)(i >> 14), r = (int)(i & 16383);
+    const DwRed t = red[e];
+    const DwMat& m = mats[t.mat];
     const int lane = r & 63, frag = (r >> 6) & 31, wave = r >> 11;
     const int fj = frag >> 3, fi = frag & 7, wm = wave >> 2, wn = wave & 3;
-    const int row = (local / tiles_n) * GB + wm * 128 + fi * 16 + (lane & 15);
-    const int col = (local % tiles_n) * GB + wn * 64 + fj * 16 + (lane >> 4) * 4;
-    if (row >= M || col >= N) continue;
-    float* c = reinterpret_cast<float*>(bp.C[b]) + (int64_t)row * ldc + col;
+    const int row = (t.tile & 0xFFFF) * GB + wm * 128 + fi * 16 + (lane & 15);
+    const int col = (t.tile >> 16) * GB + wn * 64 + fj * 16 + (lane >> 4) * 4;
+    if (row >= m.M || col >= m.N) continue;
+    float* c = m.C + (int64_t)row * m.ldc + col;
     f32x4 s = accumulate ? *reinterpret_cast<const f32x4*>(c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* q = ws + (int64_t)t.slot0 * (GB * GB) + (int64_t)r * 4;
 #pragma unroll 4
-    for (int z = 0; z < ksplit; ++z) s += *reinterpret_cast<const f32x4*>(ws + ((int64_t)z * tiles + tile) * (GB * GB) + (int64_t)r * 4);
+    for (int z = 0; z < t.count; ++z) s += *reinterpret_cast<const f32x4*>(q + (int64_t)z * (GB * GB));
     *reinterpret_cast<f32x4*>(c) = s;
   }
 }
@@ -1566,7 +1627,25 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 // Everything fcmf_gemm uses beyond its arguments lives in a caller-owned context (include/fcmf_hip.h): the split-K
 // workspace, the tuning knobs of benchmarks / tests and the name of the kernel the last call dispatched.  The library
 // itself holds no mutable process-global state; a NULL context means defaults (no workspace: float atomics for split-K).
+// the work list of a weight-gradient flush (plan_dw_list) and what it was planned from
+struct DwPlan {
+  std::vector<DwItem> items;     // in launch order: item i runs on workgroup i % slots
+  std::vector<DwRed> red;
+  int slots = 0;                 // partial tiles in the workspace
+  int64_t table_bytes = 0;       // head of the workspace reserved for the uploaded tables
+  double efficiency = 1.0;       // mean / max k-tiles per workgroup
+  std::vector<int> sig;          // (M, N, K, dest) per matrix, workgroups, workspace slots: an equal signature reuses the plan
+};
+constexpr int DW_STAGES = 4;     // staging buffers of the table upload
+
 struct fcmf_gemm_ctx {
+  // weight-gradient lists: the last plan, and pinned staging buffers for the table upload.  A buffer is rewritten only after the
+  // event recorded behind its last copy has completed.
+  DwPlan dw_plan;
+  char* dw_stage[DW_STAGES] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t dw_event[DW_STAGES] = {nullptr, nullptr, nullptr, nullptr};
+  size_t dw_stage_bytes = 0;
+  int dw_next = 0;
   float* ws = nullptr;          // split-K partial tiles (device memory owned by the caller)
   int64_t ws_bytes = 0;
   int force_tile = 0;           // 0 = heuristic, 128 / 192 / 256 = forced kernel
@@ -1582,7 +1661,15 @@ extern "C" int fcmf_gemm_ctx_create(fcmf_gemm_ctx** ctx) {
   *ctx = new fcmf_gemm_ctx();
   return FCMF_OK;
 }
+static void dw_stage_free(fcmf_gemm_ctx* ctx) {
+  for (int i = 0; i < DW_STAGES; ++i) {
+    if (ctx->dw_event[i]) { (void)hipEventSynchronize(ctx->dw_event[i]); (void)hipEventDestroy(ctx->dw_event[i]); ctx->dw_event[i] = nullptr; }
+    if (ctx->dw_stage[i]) { (void)hipHostFree(ctx->dw_stage[i]); ctx->dw_stage[i] = nullptr; }
+  }
+  ctx->dw_stage_bytes = 0;
+}
 extern "C" int fcmf_gemm_ctx_destroy(fcmf_gemm_ctx* ctx) {
+  if (ctx) dw_stage_free(ctx);
   delete ctx;
   return FCMF_OK;
 }
@@ -1629,7 +1716,7 @@ struct GemmArgs {
 };
 
 enum GemmKernel { GK_NONE, GK_GENERIC, GK_TILE128, GK_SMALL, GK_NARROW, GK_PERSISTENT, GK_FP8, GK_DW_BATCHED };
-enum GemmReduce { RED_NONE, RED_ROWS, RED_FRAG, RED_FRAG_BATCHED };
+enum GemmReduce { RED_NONE, RED_ROWS, RED_FRAG, RED_LIST };
 struct GemmPlan {
   GemmKernel kernel;               // GK_NONE: nothing to launch (an empty output)
   int tm, kb, trans_a, trans_b, in_dtype, out_dtype, epilogue;   // what selects the kernel's instantiation
@@ -1637,7 +1724,9 @@ struct GemmPlan {
   size_t smem;
   GemmParams p;                    // every kernel but the generic one
   GenericParams g;                 // GK_GENERIC
-  const BatchPtrs* batch;          // GK_DW_BATCHED: the chunk's pointer tables (the caller's)
+  DwList dw;                       // GK_DW_BATCHED: the uploaded tables (device memory)
+  const DwRed* dw_red;             // RED_LIST: the reduce table (device memory), reduce_entries entries
+  int reduce_entries;
   GemmReduce reduce;               // pass over the split-K partial tiles in p.ws
   int reduce_blocks, cblk;
   int64_t cblk_stride;
@@ -1652,7 +1741,7 @@ static const char* const epi_names[] = {"NONE", "GELU", "TANH", "DGELU", "DTANH"
 static void plan_begin(GemmPlan* pl, const GemmArgs& a, GemmKernel kernel) {
   pl->kernel = kernel; pl->tm = 0; pl->kb = 32;
   pl->trans_a = a.trans_a; pl->trans_b = a.trans_b; pl->in_dtype = a.in_dtype; pl->out_dtype = a.out_dtype; pl->epilogue = a.epilogue;
-  pl->batch = nullptr; pl->reduce = RED_NONE; pl->reduce_blocks = 0; pl->cblk = a.cblk; pl->cblk_stride = a.cblk_stride;
+  pl->dw = DwList{nullptr, nullptr}; pl->dw_red = nullptr; pl->reduce_entries = 0; pl->reduce = RED_NONE; pl->reduce_blocks = 0; pl->cblk = a.cblk; pl->cblk_stride = a.cblk_stride;
 }
 
 static int64_t c_extent_bytes(const GemmArgs& a) { return (((int64_t)a.M - 1) * a.ldc + a.N) * 2; }   // (of a 2-byte output)
@@ -1948,7 +2037,7 @@ static int run_plan(const GemmPlan& pl, hipStream_t st) {
       break;
     case GK_PERSISTENT: rc = FCMF_BY_TRANS(launch_persistent, pl, st); break;
     case GK_FP8: rc = launch_fp8(pl, st); break;
-    case GK_DW_BATCHED: rc = fcmf_launch(gemm_bf16_dw_batched_kernel, pl.grid, pl.block, pl.smem, st, p, *pl.batch); break;
+    case GK_DW_BATCHED: rc = fcmf_launch(gemm_bf16_dw_batched_kernel, pl.grid, pl.block, pl.smem, st, p, pl.dw); break;
   }
   if (rc != FCMF_OK) return rc;
   const dim3 rgrid(pl.reduce_blocks), rblock(256);
@@ -1960,9 +2049,8 @@ static int run_plan(const GemmPlan& pl, hipStream_t st) {
     case RED_FRAG:
       return fcmf_launch(splitk_reduce_frag_kernel, rgrid, rblock, 0, st, p.ws, C, p.M, p.N, p.ldc, p.ksplit, p.tiles, tiles_n, p.accumulate,
                          pl.cblk, pl.cblk_stride);
-    case RED_FRAG_BATCHED:
-      return fcmf_launch(splitk_reduce_frag_batched_kernel, rgrid, rblock, 0, st, p.ws, *pl.batch, p.tiles_per_mat, p.M, p.N, p.ldc, p.ksplit,
-                         p.tiles, tiles_n, p.accumulate);
+    case RED_LIST:
+      return fcmf_launch(splitk_reduce_list_kernel, rgrid, rblock, 0, st, p.ws, pl.dw_red, pl.dw.mats, pl.reduce_entries, p.accumulate);
   }
   return FCMF_OK;
 }
@@ -2147,71 +2235,395 @@ extern "C" int fcmf_gemm_colblocks(fcmf_gemm_ctx* ctx, const void* A, const void
   return gemm_impl(ctx, a, stream);
 }
 
-// ---- batched weight gradients -----------------------------------------------------------------------------------------
-// C_i [M, N] float32 (+)= A_i^T B_i for `count` same-shape problems (A_i = dY_i [K, M], B_i = X_i [K, N], bf16, K = tokens): the
-// weight gradients of the layers of an encoder, queued during the backward pass and multiplied together.  Chunks of up to
-// BATCH_MAX matrices form one work list of (matrix, tile, k-split) items for the persistent 256 x 256 kernel; the split factor
-// is chosen for whole rounds of the chip (a 768 x 768 gradient alone is 9 tiles: alone it needed a 28-way split and a 64 MB
-// partial-tile round trip).  Shapes the persistent kernel does not take, and count == 1, run as `count` fcmf_gemm calls.
-// k-split of a batched chunk for whole rounds: the smallest split whose last round is at least 92 % full (else the fullest), each
-// split at least 8 k-tiles deep, partial tiles within the context's workspace
-static int batched_ksplit(const fcmf_gemm_ctx& cfg, int tiles, int nk) {
-  const int slots = cfg.num_cus;
-  int best = 1;
-  double best_eff = 0.0;
-  const int64_t ws_tiles = cfg.ws ? cfg.ws_bytes / ((int64_t)GB * GB * 4) : 0;
-  for (int sp = 1; sp <= 16; ++sp) {
-    if (sp > 1 && ((int64_t)sp * tiles > ws_tiles || nk / sp < 8)) break;
-    const int64_t items = (int64_t)tiles * sp, rounds = (items + slots - 1) / slots;
-    const double eff = (double)items / (double)(rounds * slots);
-    if (eff > best_eff + 1e-9) { best_eff = eff; best = sp; }
-    if (eff >= 0.92) { best = sp; break; }
-  }
-  return best;
+// ---- weight-gradient work lists -------------------------------------------------------------------------------------------
+// C_i [M_i, N_i] float32 (+)= A_i^T B_i for `count` problems of ANY shapes (A_i = dY_i [K_i, M_i], B_i = X_i [K_i, N_i], bf16,
+// K_i = tokens): the weight gradients of a whole backward pass, queued by the host and multiplied in ONE launch of the persistent
+// 256 x 256 kernel plus at most one reduce launch.  plan_dw_list (pure) turns the shapes into the work list:
+//  * a step has more tiles than the chip has CUs, so most tiles need no split of K at all: per depth (k-tiles of the contraction),
+//    as many WHOLE rounds of tiles as exist run unsplit and write C themselves (row epilogue, adding to C when `accumulate`);
+//  * the remaining tiles -- the last part round of every depth, and every tile of a destination with several producers -- form the
+//    tail: P pieces of near-equal depth, P a multiple of the workgroup count, each piece at least DW_MIN_KT k-tiles deep unless
+//    its tile is shallower.  A tile cut into several pieces, or one of a shared destination, writes fragment-layout partial tiles
+//    into consecutive workspace slots; the reduce pass sums the slots of a C tile in slot order.  No two items write the same
+//    C tile, so the several uses of a shared weight may sit in one list;
+//  * items are sorted by depth, longest first, and dealt in rounds of one item per workgroup; inside a round of unequal items the
+//    longest goes to the workgroup with the least work so far (a round of equal items keeps the tile order: the workgroups of an
+//    XCD then walk neighbouring tiles of one matrix through the same k-slices, sharing the operand panels in L2).
+constexpr int DW_MIN_KT = 8;            // k-tiles of a piece, at least (256 tokens)
+constexpr int DW_PIECE_KT = 256;        // depth the tail's pieces aim at: one more round of the chip per 256 k-tiles of tail work
+constexpr int64_t DW_SLOT_BYTES = (int64_t)GB * GB * 4;
+constexpr int DW_MAX_SLOTS = 8191;      // (32-bit byte offsets behind one 2 GB buffer descriptor)
+
+// bytes at the head of the workspace reserved for the tables of a list of `tiles` tiles, `nk` k-tiles in all, `count` matrices
+static int64_t dw_table_reserve(int64_t tiles, int64_t nk, int count, int slots) {
+  const int64_t items = 2 * tiles + nk / DW_PIECE_KT + 2 * slots;     // (upper bound: unsplit tiles + pieces)
+  const int64_t bytes = items * (int64_t)sizeof(DwItem) + tiles * (int64_t)sizeof(DwRed) + (int64_t)count * (int64_t)sizeof(DwMat) + 1024;
+  return (bytes + DW_SLOT_BYTES - 1) / DW_SLOT_BYTES * DW_SLOT_BYTES;
 }
 
-extern "C" int fcmf_gemm_dw_batched(fcmf_gemm_ctx* ctx, int count, const void* const* A, const void* const* B, void* const* C, int M, int N,
-                                    int K, int64_t lda, int64_t ldb, int64_t ldc, int accumulate, void* stream) {
-  if (count < 0 || !A || !B || !C || M < 0 || N < 0 || K < 0) return FCMF_ERR_ARG;
-  for (int i = 0; i < count; ++i)
-    if (!A[i] || !B[i] || !C[i]) return FCMF_ERR_ARG;
-  if (count == 0 || M == 0 || N == 0) return FCMF_OK;
-  const fcmf_gemm_ctx& cfg = ctx ? *ctx : g_default_ctx;
-  bool ok = count > 1 && cfg.force_tile != 128 && K > 0 && M >= 256 && N >= 256 && lda % 8 == 0 && ldb % 8 == 0 && M % 8 == 0 && N % 8 == 0 &&
-            ldc % 8 == 0 && (int64_t)K * lda < (1ll << 30) && (int64_t)K * ldb < (1ll << 30);
-  for (int i = 0; ok && i < count; ++i) ok = al16(A[i]) && al16(B[i]) && al16(C[i]);
-  GemmArgs a = grad_args(M, N, K, 1, 1, accumulate);
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-  if (!ok) {
-    for (int i = 0; i < count; ++i) {
-      a.A = A[i]; a.B = B[i]; a.C = C[i];
-      const int rc = gemm_impl(ctx, a, stream);
-      if (rc != FCMF_OK) return rc;
+// dest[i] = index of the first matrix that shares matrix i's destination (i itself where it is the only or the first producer).
+// FCMF_ERR_UNSUPPORTED: the workspace cannot hold the partial tiles the list cannot do without.
+static int plan_dw_list(int count, const int* M, const int* N, const int* K, const int* dest, int slots, int64_t ws_bytes, DwPlan* out) {
+  if (count < 0 || slots < 1 || ws_bytes < 0) return FCMF_ERR_ARG;
+  struct Tile { int mat, tm, tn, nk, pieces, slot0; bool shared; };
+  std::vector<Tile> tail;
+  std::vector<DwItem> items;
+  std::vector<char> shared(count, 0);
+  std::vector<int> first_tail(count, -1);
+  int64_t tiles_all = 0, nk_all = 0;
+  for (int i = 0; i < count; ++i) {
+    if (M[i] < 1 || N[i] < 1 || K[i] < 1 || M[i] > 255 * GB || N[i] > 255 * GB || dest[i] < 0 || dest[i] > i || dest[dest[i]] != dest[i] || count > 65535)
+      return FCMF_ERR_ARG;
+    if (dest[i] != i) {
+      if (M[dest[i]] != M[i] || N[dest[i]] != N[i]) return FCMF_ERR_ARG;
+      shared[i] = shared[dest[i]] = 1;
     }
-    return FCMF_OK;
+    const int64_t t = (int64_t)((M[i] + GB - 1) / GB) * ((N[i] + GB - 1) / GB);
+    tiles_all += t; nk_all += t * ((K[i] + 31) / 32);
   }
-  const int tpm = ((M + GB - 1) / GB) * ((N + GB - 1) / GB), nk = (K + 31) / 32;
-  const int chunks = (count + BATCH_MAX - 1) / BATCH_MAX;
-  for (int c = 0, first = 0; c < chunks; ++c) {
-    const int n = (count - first + (chunks - c) - 1) / (chunks - c);          // near-equal chunks
-    BatchPtrs bp{};
-    for (int i = 0; i < n; ++i) { bp.A[i] = A[first + i]; bp.B[i] = B[first + i]; bp.C[i] = C[first + i]; }
-    a.A = bp.A[0]; a.B = bp.B[0]; a.C = bp.C[0];
+  out->items.clear(); out->red.clear(); out->slots = 0; out->efficiency = 1.0;
+  out->table_bytes = dw_table_reserve(tiles_all, nk_all, count, slots);
+  const int64_t ws_slots = std::min<int64_t>(DW_MAX_SLOTS, ws_bytes > out->table_bytes ? (ws_bytes - out->table_bytes) / DW_SLOT_BYTES : 0);
+  auto mt_of = [](int mat, int tm, int tn) { return mat | (tm << 16) | (tn << 24); };
+
+  // unsplit whole rounds per depth; the rest is the tail
+  std::map<int, std::vector<int>, std::greater<int>> by_depth;          // depth -> matrices with a single producer, in list order
+  for (int i = 0; i < count; ++i)
+    if (!shared[i]) by_depth[(K[i] + 31) / 32].push_back(i);
+  for (const auto& cls : by_depth) {
+    const int nk = cls.first;
+    int64_t n = 0;
+    for (int i : cls.second) n += (int64_t)((M[i] + GB - 1) / GB) * ((N[i] + GB - 1) / GB);
+    int64_t whole = n / slots * slots;
+    for (int i : cls.second) {
+      const int tm_n = (M[i] + GB - 1) / GB, tn_n = (N[i] + GB - 1) / GB;
+      for (int tm = 0; tm < tm_n; ++tm)
+        for (int tn = 0; tn < tn_n; ++tn) {
+          if (whole > 0) { items.push_back(DwItem{mt_of(i, tm, tn), 0, nk, -1}); --whole; }
+          else tail.push_back(Tile{i, tm, tn, nk, 1, -1, false});
+        }
+    }
+  }
+  for (int i = 0; i < count; ++i) {
+    if (!shared[i]) continue;
+    first_tail[i] = (int)tail.size();
+    const int tm_n = (M[i] + GB - 1) / GB, tn_n = (N[i] + GB - 1) / GB, nk = (K[i] + 31) / 32;
+    for (int tm = 0; tm < tm_n; ++tm)
+      for (int tn = 0; tn < tn_n; ++tn) tail.push_back(Tile{i, tm, tn, nk, 1, -1, true});
+  }
+
+  if (!tail.empty()) {
+    // pieces per tile: P in all, depths as equal as whole k-tiles and the minimum depth allow
+    int64_t W = 0;
+    for (const Tile& t : tail) W += t.nk;
+    const int64_t T = (int64_t)tail.size();
+    int64_t rounds = std::max<int64_t>(1, (W + (int64_t)slots * DW_PIECE_KT - 1) / ((int64_t)slots * DW_PIECE_KT));
+    rounds = std::max(rounds, (T + slots - 1) / slots);
+    const int64_t P = rounds * slots;
+    const double d = (double)W / (double)P;
+    auto cmax = [](const Tile& t) { return std::max(1, t.nk / DW_MIN_KT); };
+    int64_t sum = 0;
+    for (Tile& t : tail) { t.pieces = std::min(cmax(t), std::max(1, (int)((double)t.nk / d + 0.5))); sum += t.pieces; }
+    while (sum < P) {                      // one more piece for the tile whose pieces are deepest
+      Tile* best = nullptr;
+      for (Tile& t : tail)
+        if (t.pieces < cmax(t) && (!best || (int64_t)t.nk * best->pieces > (int64_t)best->nk * t.pieces)) best = &t;
+      if (!best) break;
+      ++best->pieces; ++sum;
+    }
+    while (sum > P) {                      // one piece fewer for the tile whose pieces stay shallowest
+      Tile* best = nullptr;
+      for (Tile& t : tail)
+        if (t.pieces > 1 && (!best || (int64_t)t.nk * (best->pieces - 1) < (int64_t)best->nk * (t.pieces - 1))) best = &t;
+      if (!best) break;
+      --best->pieces; --sum;
+    }
+    auto slots_needed = [&]() { int64_t n = 0; for (const Tile& t : tail) n += (t.shared || t.pieces > 1) ? t.pieces : 0; return n; };
+    if (slots_needed() > ws_slots) {       // a workspace that small: whole tiles, partial tiles only where a destination is shared
+      for (Tile& t : tail) t.pieces = 1;
+      if (slots_needed() > ws_slots) return FCMF_ERR_UNSUPPORTED;
+    }
+    // slots and reduce entries: single producers tile by tile, then every shared destination's tiles over all its producers
+    int slot = 0;
+    for (Tile& t : tail)
+      if (!t.shared && t.pieces > 1) { t.slot0 = slot; out->red.push_back(DwRed{slot, t.pieces, t.mat, t.tm | (t.tn << 16)}); slot += t.pieces; }
+    for (int i = 0; i < count; ++i) {
+      if (!shared[i] || dest[i] != i) continue;
+      const int tm_n = (M[i] + GB - 1) / GB, tn_n = (N[i] + GB - 1) / GB;
+      for (int tm = 0; tm < tm_n; ++tm)
+        for (int tn = 0; tn < tn_n; ++tn) {
+          const int slot0 = slot;
+          for (int j = i; j < count; ++j) {
+            if (dest[j] != i) continue;
+            Tile& t = tail[first_tail[j] + tm * tn_n + tn];
+            t.slot0 = slot; slot += t.pieces;
+          }
+          out->red.push_back(DwRed{slot0, slot - slot0, i, tm | (tn << 16)});
+        }
+    }
+    out->slots = slot;
+    // the pieces, matrix by matrix, k-range by k-range, tile by tile (neighbours in the walk share operand panels)
+    for (size_t b = 0; b < tail.size();) {
+      size_t e = b;
+      int zmax = 0;
+      while (e < tail.size() && tail[e].mat == tail[b].mat) { zmax = std::max(zmax, tail[e].pieces); ++e; }
+      for (int z = 0; z < zmax; ++z)
+        for (size_t k = b; k < e; ++k) {
+          const Tile& t = tail[k];
+          if (z >= t.pieces) continue;
+          const int k0 = (int)((int64_t)t.nk * z / t.pieces), k1 = (int)((int64_t)t.nk * (z + 1) / t.pieces);
+          items.push_back(DwItem{mt_of(t.mat, t.tm, t.tn), k0, k1 - k0, t.slot0 < 0 ? -1 : t.slot0 + z});
+        }
+      b = e;
+    }
+  }
+
+  // launch order: longest first, in rounds; a round of unequal items gives its longest item to the least loaded workgroup.  (Loads
+  // are sums, so the rounds may be dealt last to first: the part round at the end of the list has its places fixed.)
+  std::stable_sort(items.begin(), items.end(), [](const DwItem& a, const DwItem& b) { return a.nkt > b.nkt; });
+  const int64_t n_items = (int64_t)items.size();
+  std::vector<int64_t> load(slots, 0);
+  std::vector<int> order(slots);
+  out->items.resize(items.size());
+  for (int64_t r = (n_items + slots - 1) / slots - 1; r >= 0; --r) {
+    const int64_t i0 = r * slots, n = std::min<int64_t>(slots, n_items - i0);
+    const bool deal = n == slots && items[i0].nkt != items[i0 + n - 1].nkt;
+    for (int s = 0; s < slots; ++s) order[s] = s;
+    if (deal) std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return load[a] < load[b]; });
+    for (int64_t k = 0; k < n; ++k) { out->items[i0 + order[k]] = items[i0 + k]; load[order[k]] += items[i0 + k].nkt; }
+  }
+  int64_t total = 0, most = 0;
+  for (int s = 0; s < slots; ++s) { total += load[s]; most = std::max(most, load[s]); }
+  out->efficiency = most > 0 ? (double)total / ((double)most * slots) : 1.0;
+  return FCMF_OK;
+}
+
+// The planner alone, for tests and tools (no device).  items: [max_items][6] = matrix, tile row, tile column, first k-tile, k-tiles,
+// slot (-1: writes C); reduce: [max_reduce][5] = first slot, slots, matrix (the destination's first producer), tile row, tile
+// column; either may be NULL (sizes only).  info[6] = items, reduce entries, slots, table bytes, workspace bytes needed
+// (tables + slots), efficiency in millionths.
+extern "C" int fcmf_gemm_dw_list_plan(int count, const int* M, const int* N, const int* K, const int* dest, int num_cus, int64_t ws_bytes,
+                                      int* items, int max_items, int* reduce, int max_reduce, int64_t* info) {
+  if (!M || !N || !K || !dest || !info) return FCMF_ERR_ARG;
+  DwPlan pl;
+  const int rc = plan_dw_list(count, M, N, K, dest, num_cus, ws_bytes, &pl);
+  if (rc != FCMF_OK) return rc;
+  info[0] = (int64_t)pl.items.size(); info[1] = (int64_t)pl.red.size(); info[2] = pl.slots; info[3] = pl.table_bytes;
+  info[4] = pl.table_bytes + pl.slots * DW_SLOT_BYTES; info[5] = (int64_t)(pl.efficiency * 1e6);
+  if (items) {
+    if ((int64_t)max_items < info[0]) return FCMF_ERR_ARG;
+    for (size_t i = 0; i < pl.items.size(); ++i) {
+      const DwItem& it = pl.items[i];
+      int* o = items + 6 * i;
+      o[0] = it.mt & 0xFFFF; o[1] = (it.mt >> 16) & 0xFF; o[2] = (it.mt >> 24) & 0xFF; o[3] = it.kt_begin; o[4] = it.nkt; o[5] = it.slot;
+    }
+  }
+  if (reduce) {
+    if ((int64_t)max_reduce < info[1]) return FCMF_ERR_ARG;
+    for (size_t i = 0; i < pl.red.size(); ++i) {
+      const DwRed& r = pl.red[i];
+      int* o = reduce + 5 * i;
+      o[0] = r.slot0; o[1] = r.count; o[2] = r.mat; o[3] = r.tile & 0xFFFF; o[4] = r.tile >> 16;
+    }
+  }
+  return FCMF_OK;
+}
+
+// a staging buffer of at least `bytes` that no earlier upload still reads
+static char* dw_stage_get(fcmf_gemm_ctx* ctx, size_t bytes, int* which) {
+  if (bytes > ctx->dw_stage_bytes) {
+    dw_stage_free(ctx);
+    const size_t cap = (bytes + 65535) / 65536 * 65536 * 2;
+    for (int i = 0; i < DW_STAGES; ++i) {
+      if (hipHostMalloc(reinterpret_cast<void**>(&ctx->dw_stage[i]), cap, hipHostMallocDefault) != hipSuccess ||
+          hipEventCreateWithFlags(&ctx->dw_event[i], hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        dw_stage_free(ctx);
+        return nullptr;
+      }
+    }
+    ctx->dw_stage_bytes = cap;
+    ctx->dw_next = 0;
+  }
+  const int i = ctx->dw_next;
+  ctx->dw_next = (i + 1) % DW_STAGES;
+  if (hipEventSynchronize(ctx->dw_event[i]) != hipSuccess) { (void)hipGetLastError(); return nullptr; }   // (never recorded: returns at once)
+  *which = i;
+  return ctx->dw_stage[i];
+}
+
+// what the 256 x 256 transposed kernel takes
+static bool dw_tile_ok(const fcmf_gemm_ctx& cfg, const void* A, const void* B, const void* C, int M, int N, int K, int64_t lda, int64_t ldb,
+                       int64_t ldc) {
+  return cfg.force_tile != 128 && K > 0 && M >= 256 && N >= 256 && M <= 255 * GB && N <= 255 * GB && lda % 8 == 0 && ldb % 8 == 0 &&
+         M % 8 == 0 && N % 8 == 0 && ldc % 8 == 0 && (int64_t)K * lda < (1ll << 30) && (int64_t)K * ldb < (1ll << 30) && al16(A) && al16(B) &&
+         al16(C);
+}
+
+struct DwProb { const char* A; const char* B; char* C; int M, N, K; int64_t lda, ldb, ldc; };
+static const char* dw_c_end(const DwProb& q) { return q.C + (((int64_t)q.M - 1) * q.ldc + q.N) * 4; }
+static bool dw_same_dest(const DwProb& a, const DwProb& b) { return a.C == b.C && a.M == b.M && a.N == b.N && a.ldc == b.ldc; }
+static bool dw_overlap(const DwProb& a, const DwProb& b) { return a.C < dw_c_end(b) && b.C < dw_c_end(a); }
+
+// A producer whose destination covers several others' (the fused query | key | value gradient of a layer whose key and value
+// weights have further uses) is the same as one producer per row panel: C, and the columns of A = dY, advance together.  Cut
+// every problem at the row boundaries of the destinations that overlap it, where the panels stay matrices the tile kernel takes.
+static void dw_split_rows(const fcmf_gemm_ctx& cfg, std::vector<DwProb>* probs) {
+  std::vector<DwProb> out;
+  out.reserve(probs->size());
+  for (size_t i = 0; i < probs->size(); ++i) {
+    const DwProb& q = (*probs)[i];
+    std::vector<int> cuts;
+    const int64_t row_bytes = q.ldc * 4;
+    for (size_t j = 0; j < probs->size() && q.M > 0 && q.N > 0; ++j) {
+      const DwProb& o = (*probs)[j];
+      if (j == i || o.M == 0 || o.N == 0 || o.N != q.N || o.ldc != q.ldc || !dw_overlap(q, o) || dw_same_dest(q, o) || (o.C - q.C) % row_bytes) continue;
+      const int64_t r0 = (o.C - q.C) / row_bytes, r1 = r0 + o.M;
+      if (r0 > 0 && r0 < q.M) cuts.push_back((int)r0);
+      if (r1 > 0 && r1 < q.M) cuts.push_back((int)r1);
+    }
+    std::sort(cuts.begin(), cuts.end());
+    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    bool ok = !cuts.empty();
+    cuts.push_back(q.M);
+    for (size_t c = 0, r = 0; ok && c < cuts.size(); r = cuts[c++])
+      ok = dw_tile_ok(cfg, q.A + r * 2, q.B, q.C + r * row_bytes, cuts[c] - (int)r, q.N, q.K, q.lda, q.ldb, q.ldc);
+    if (!ok) { out.push_back(q); continue; }
+    for (size_t c = 0, r = 0; c < cuts.size(); r = cuts[c++]) {
+      DwProb panel = q;
+      panel.A = q.A + r * 2; panel.C = q.C + r * row_bytes; panel.M = cuts[c] - (int)r;
+      out.push_back(panel);
+    }
+  }
+  probs->swap(out);
+}
+
+extern "C" int fcmf_gemm_dw_list(fcmf_gemm_ctx* ctx, int count, const void* const* A, const void* const* B, void* const* C, const int* M,
+                                 const int* N, const int* K, const int64_t* lda, const int64_t* ldb, const int64_t* ldc, int accumulate,
+                                 void* stream) {
+  if (count < 0 || !A || !B || !C) return FCMF_ERR_ARG;
+  if (count == 0) return FCMF_OK;
+  if (!M || !N || !K || !lda || !ldb || !ldc) return FCMF_ERR_ARG;
+  std::vector<DwProb> pr(count);
+  for (int i = 0; i < count; ++i) {
+    if (!A[i] || !B[i] || !C[i] || M[i] < 0 || N[i] < 0 || K[i] < 0) return FCMF_ERR_ARG;
+    pr[i] = DwProb{reinterpret_cast<const char*>(A[i]), reinterpret_cast<const char*>(B[i]), reinterpret_cast<char*>(C[i]), M[i], N[i], K[i],
+                   lda[i], ldb[i], ldc[i]};
+  }
+  const fcmf_gemm_ctx& cfg = ctx ? *ctx : g_default_ctx;
+  bool listed = ctx && cfg.ws && count > 1;
+  if (listed) dw_split_rows(cfg, &pr);
+  const int n = (int)pr.size();
+  // the matrices the tile kernel takes (`take`: their indices), and who shares a destination with an earlier one.  A destination
+  // that still overlaps an earlier one WITHOUT being the same matrix stays out of the list: it is added behind it, by a GEMM of
+  // its own.
+  std::vector<int> take, tM, tN, tK, tdest;
+  std::vector<char> overlaps(n, 0);
+  for (int i = 0; i < n; ++i) {
+    const DwProb& q = pr[i];
+    if (q.M == 0 || q.N == 0 || !dw_tile_ok(cfg, q.A, q.B, q.C, q.M, q.N, q.K, q.lda, q.ldb, q.ldc)) continue;
+    int d = (int)take.size();
+    for (size_t k = 0; k < take.size() && !overlaps[i]; ++k) {
+      const DwProb& o = pr[take[k]];
+      if (dw_same_dest(q, o)) { if (d == (int)take.size()) d = (int)k; }
+      else if (dw_overlap(q, o)) overlaps[i] = 1;
+    }
+    if (overlaps[i]) {
+      if (!accumulate) return FCMF_ERR_ARG;      // (which of the two would the overlap keep?)
+      continue;
+    }
+    take.push_back(i); tM.push_back(q.M); tN.push_back(q.N); tK.push_back(q.K); tdest.push_back(d);
+  }
+  listed = listed && take.size() > 1 && take.size() < 65536;
+  if (listed) {
+    std::vector<int> sig;
+    sig.reserve(4 * take.size() + 2);
+    for (size_t j = 0; j < take.size(); ++j) { sig.push_back(tM[j]); sig.push_back(tN[j]); sig.push_back(tK[j]); sig.push_back(tdest[j]); }
+    sig.push_back(cfg.num_cus); sig.push_back((int)(cfg.ws_bytes / DW_SLOT_BYTES));
+    if (sig != ctx->dw_plan.sig) {
+      ctx->dw_plan.sig.clear();
+      const int rc = plan_dw_list((int)take.size(), tM.data(), tN.data(), tK.data(), tdest.data(), cfg.num_cus, cfg.ws_bytes, &ctx->dw_plan);
+      if (rc == FCMF_ERR_UNSUPPORTED) listed = false;
+      else if (rc != FCMF_OK) return rc;
+      else ctx->dw_plan.sig = sig;
+    }
+  }
+  if (listed) {
+    const DwPlan& plan = ctx->dw_plan;
+    const size_t mats_bytes = take.size() * sizeof(DwMat), items_bytes = plan.items.size() * sizeof(DwItem), red_bytes = plan.red.size() * sizeof(DwRed);
+    const size_t bytes = mats_bytes + items_bytes + red_bytes;
+    if ((int64_t)bytes > plan.table_bytes) return FCMF_ERR_UNSUPPORTED;
+    int which = 0;
+    char* stage = dw_stage_get(ctx, bytes, &which);
+    if (!stage) return FCMF_ERR_LAUNCH;
+    DwMat* mats = reinterpret_cast<DwMat*>(stage);
+    for (size_t j = 0; j < take.size(); ++j) {
+      const DwProb& q = pr[take[j]];
+      DwMat m{};
+      m.A = q.A; m.B = q.B; m.C = reinterpret_cast<float*>(q.C); m.M = q.M; m.N = q.N; m.lda = (int)q.lda; m.ldb = (int)q.ldb; m.ldc = q.ldc;
+      m.a_bytes = (unsigned)((((int64_t)q.K - 1) * q.lda + q.M) * 2);
+      m.b_bytes = (unsigned)((((int64_t)q.K - 1) * q.ldb + q.N) * 2);
+      mats[j] = m;
+    }
+    memcpy(stage + mats_bytes, plan.items.data(), items_bytes);
+    if (red_bytes) memcpy(stage + mats_bytes + items_bytes, plan.red.data(), red_bytes);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    char* table = reinterpret_cast<char*>(cfg.ws);
+    if (hipMemcpyAsync(table, stage, bytes, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord(ctx->dw_event[which], st) != hipSuccess) {
+      (void)hipGetLastError();
+      return FCMF_ERR_LAUNCH;
+    }
+    const DwProb& q0 = pr[take[0]];
+    GemmArgs a = grad_args(q0.M, q0.N, q0.K, 1, 1, accumulate);
+    a.A = q0.A; a.B = q0.B; a.C = q0.C; a.lda = q0.lda; a.ldb = q0.ldb; a.ldc = q0.ldc;
     GemmPlan pl;
     plan_begin(&pl, a, GK_DW_BATCHED);
-    pl.tm = 256; pl.batch = &bp;
-    pl.p = base_params(a, 2);
-    pl.p.c_bytes = 0;            // (as this path always had it: the f32 epilogue does not range-check C)
-    pl.p.tiles_per_mat = tpm;
-    const int tiles = n * tpm;
-    plan_persistent_launch(&pl, persistent_list(cfg, pl.p, tiles, nk, batched_ksplit(cfg, tiles, nk), false));
-    if (pl.p.ksplit > 1) { pl.p.ws = cfg.ws; plan_frag_reduce(&pl, RED_FRAG_BATCHED); }
+    pl.tm = 256;
+    pl.p = base_params(a, 2);          // (the first matrix: the kernel reads every item's own from the tables)
+    pl.p.c_bytes = 0;
+    pl.p.tiles = pl.p.total_items = (int)plan.items.size();
+    pl.p.ws = reinterpret_cast<float*>(table + plan.table_bytes);
+    pl.dw = DwList{reinterpret_cast<const DwMat*>(table), reinterpret_cast<const DwItem*>(table + mats_bytes)};
+    plan_persistent_launch(&pl, dim3(pl.p.total_items < cfg.num_cus ? pl.p.total_items : cfg.num_cus));
+    if (!plan.red.empty()) {
+      pl.reduce = RED_LIST;
+      pl.dw_red = reinterpret_cast<const DwRed*>(table + mats_bytes + items_bytes);
+      pl.reduce_entries = (int)plan.red.size();
+      pl.reduce_blocks = (int)std::min<int64_t>(4096, (int64_t)plan.red.size() * (GB * GB / 4 / 256));
+    }
     snprintf(pl.name, sizeof pl.name, "gemm_bf16_dw_batched_kernel");
     const int rc = run_named(ctx, pl, stream);
     if (rc != FCMF_OK) return rc;
-    first += n;
   }
+  // the rest, one GEMM each, in list order behind the list's launch: a destination somebody has already written is added to
+  std::vector<const DwProb*> written;
+  if (listed)
+    for (int i : take) written.push_back(&pr[i]);
+  size_t next_taken = 0;
+  for (int i = 0; i < n; ++i) {
+    if (next_taken < take.size() && take[next_taken] == i) { ++next_taken; if (listed) continue; }
+    const DwProb& q = pr[i];
+    if (q.M == 0 || q.N == 0) continue;
+    bool seen = false;
+    for (const DwProb* o : written) seen = seen || dw_overlap(q, *o);
+    GemmArgs a = grad_args(q.M, q.N, q.K, 1, 1, accumulate || seen);
+    a.A = q.A; a.B = q.B; a.C = q.C; a.lda = q.lda; a.ldb = q.ldb; a.ldc = q.ldc;
+    const int rc = gemm_impl(ctx, a, stream);
+    if (rc != FCMF_OK) return rc;
+    written.push_back(&q);
+  }
+  // (the call's name is the list's: the single GEMMs behind it ride along)
+  if (listed && ctx) snprintf(ctx->last_kernel, sizeof ctx->last_kernel, "gemm_bf16_dw_batched_kernel");
   return FCMF_OK;
+}
+
+// `count` same-shape problems: the list above with one shape
+extern "C" int fcmf_gemm_dw_batched(fcmf_gemm_ctx* ctx, int count, const void* const* A, const void* const* B, void* const* C, int M, int N,
+                                    int K, int64_t lda, int64_t ldb, int64_t ldc, int accumulate, void* stream) {
+  if (count < 0 || !A || !B || !C || M < 0 || N < 0 || K < 0) return FCMF_ERR_ARG;
+  const std::vector<int> vM(count, M), vN(count, N), vK(count, K);
+  const std::vector<int64_t> va(count, lda), vb(count, ldb), vc(count, ldc);
+  return fcmf_gemm_dw_list(ctx, count, A, B, C, vM.data(), vN.data(), vK.data(), va.data(), vb.data(), vc.data(), accumulate, stream);
 }
 
 // Implicit-GEMM convolution on the MFMA GEMM kernels: y[(n, oy, ox), co] = sum_{ky, kx, c} x[n, oy s + ky, ox s + kx, c] w[co, (ky, kx, c)].

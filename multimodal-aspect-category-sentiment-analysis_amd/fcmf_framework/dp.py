@@ -222,7 +222,7 @@ class GradReducer:
                 `torch.distributed.all_reduce`; fp32 exchange, CUDA tensors, one GPU per process.
     group_mb  : launch granularity.  Buckets are SENT in groups of consecutive ready buckets of at least this many MB (160 by
                 default = four to five encoder layers): the weight-gradient GEMMs of a group's parameters are queued by
-                `ops.deferred_dw` until the group goes out and are multiplied together per shape (`fcmf_gemm_dw_batched`), and
+                `ops.deferred_dw` until the group goes out and are multiplied together as one work list (`fcmf_gemm_dw_list`), and
                 only the queue entries whose destination lies in the group's arena range are flushed -- later layers keep
                 batching.  (Round 3 flushed the whole queue before every 32 MB bucket: one matrix per shape per flush, i.e. the
                 batched kernel never ran under data parallelism.)  The collectives stay one per bucket, back to back.

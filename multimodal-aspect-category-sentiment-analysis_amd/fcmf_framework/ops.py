@@ -200,7 +200,7 @@ def gemm_trace_end():
     if not tr:
         return []
     torch.cuda.synchronize()
-    return [(name, fl, e0.elapsed_time(e1)) for name, fl, e0, e1 in tr]
+    return [(name, fl, e0.elapsed_time(e1) * share) for name, fl, e0, e1, share in tr]
 
 
 def tracing():
@@ -210,7 +210,9 @@ def tracing():
 class trace_launch:
     """`with trace_launch(flops):` around a library call that multiplies on the GEMM context of the current stream (`gemm`, the
     trunk's implicit-GEMM convolutions): records (kernel name, flops, start event, end event) when a trace is open and the call
-    did not raise, free otherwise.  A call that launched nothing sets `.flops = None`: nothing is recorded."""
+    did not raise, free otherwise.  A call that launched nothing sets `.flops = None`: nothing is recorded.  `flops` may be a list:
+    the launch multiplied several groups of matrices (a weight-gradient list: one group per shape) and is recorded once per group,
+    with the group's FLOPs and its share, by FLOPs, of the launch's time -- sums per kernel name are those of the launch."""
 
     def __init__(self, flops):
         self.flops = flops
@@ -224,7 +226,11 @@ class trace_launch:
     def __exit__(self, *exc):
         if _gemm_trace is not None and exc[0] is None and self.flops is not None:
             self.e1.record()
-            _gemm_trace.append((H.lib().fcmf_gemm_ctx_last_kernel(H.gemm_ctx()).decode(), float(self.flops), self.e0, self.e1))
+            name = H.lib().fcmf_gemm_ctx_last_kernel(H.gemm_ctx()).decode()
+            parts = [float(f) for f in self.flops] if isinstance(self.flops, (list, tuple)) else [float(self.flops)]
+            total = sum(parts)
+            for f in parts:
+                _gemm_trace.append((name, f, self.e0, self.e1, f / total if total else 1.0 / len(parts)))
         return False
 
 
@@ -232,13 +238,15 @@ class trace_launch:
 # dW = dY^T X of an nn.Linear is needed only once the backward pass is over (grad clipping, the optimizer, the gradient
 # exchange of its bucket), and one layer's dW is a handful of 256 x 256 tiles: alone it fills the chip only through a deep
 # split of K plus a reduce pass per matrix.  During loss.backward() the weight-gradient GEMMs whose destination is a slice of the
-# step's gradient arena are therefore QUEUED (operands kept alive) and multiplied together, all same-shape matrices of a group in
-# one fcmf_gemm_dw_batched launch: at the end of the backward pass (an autograd-engine callback), before a data-parallel bucket that
-# contains queued gradients is sent (dp.GradReducer), before anything else reads the arena (flush_deferred_dw), or when the queue
-# holds more than DEFER_DW_MAX_BYTES of operands.  Only parameters with exactly ONE forward use in the step qualify (the arena
-# counts them in gemm_nt): a weight applied twice has two gradient producers whose results autograd adds the moment each
-# Function returns.  The destination is remembered by address, never by tensor: autograd must stay the only holder of the
-# returned slice, or AccumulateGrad clones it -- unwritten -- instead of adopting it as p.grad.
+# step's gradient arena are therefore QUEUED (operands kept alive) and multiplied together, everything that is flushed -- whatever
+# its shape -- as ONE work list (fcmf_gemm_dw_list: one GEMM launch, one reduce launch): at the end of the backward pass (an
+# autograd-engine callback), before a data-parallel bucket that contains queued gradients is sent (dp.GradReducer), before anything
+# else reads the arena (flush_deferred_dw), or when the queue holds more than DEFER_DW_MAX_BYTES of operands.  A weight applied
+# SEVERAL times (the mm layer's key / value weights: text keys, ROI keys, the fusion layer) has several producers; every one of them
+# accumulates in place into the slice the first one claimed and hands autograd None (grad_dest / GradArena.claim), so they all wait
+# for the flush too: the list gives a destination with several producers partial tiles only, which its reduce pass adds in a
+# fixed order -- no two work items write the same tile.  The destination is remembered by address, never by tensor: autograd must
+# stay the only holder of the returned slice, or AccumulateGrad clones it -- unwritten -- instead of adopting it as p.grad.
 DEFER_DW = os.environ.get("FCMF_DEFER_DW", "1") == "1"
 DEFER_DW_MAX_BYTES = 48 << 30
 
@@ -259,13 +267,8 @@ class _DeferredDW:
         if not (arena is not None and C.device == arena.flat.device
                 and C.untyped_storage().data_ptr() == arena.flat.untyped_storage().data_ptr()):
             return False
-        # A weight applied SEVERAL times (the mm layer's key / value weights: text keys, ROI keys, the fusion layer) has several
-        # producers, but since round 4 every one of them accumulates in place into the slice the first one claimed and hands
-        # autograd None (grad_dest / GradArena.claim): nothing is added by the engine, so they may all wait for the flush and
-        # batch with the same-shape gradients of the text encoder.  (A destination outside the arena -- the temporaries of a
-        # gradient-accumulation micro-step -- never gets here.)
-        n = arena.uses(C.data_ptr())
-        return n == 1 or (n > 1 and DEFER_SHARED_DW)
+        # (a destination outside the arena -- the temporaries of a gradient-accumulation micro-step -- never gets here)
+        return arena.uses(C.data_ptr()) >= 1
 
     def push(self, A, B, C, M, N, K, lda, ldb, ldc, acc):
         if not self.armed:
@@ -295,20 +298,30 @@ class _DeferredDW:
             q, self.q, self.bytes = self.q, [], 0
         if final:
             self.armed = False
-        groups = {}
+        groups = {}      # (one list per device and accumulate flag: in a training step, one)
         for e in q:
-            groups.setdefault((e[0].device,) + e[3:], []).append(e)
-        for key, es in groups.items():
-            _, M, N, K, lda, ldb, ldc, acc = key
+            groups.setdefault((e[0].device, e[9]), []).append(e)
+        for (device, acc), es in groups.items():
             H.require_cuda(es[0][0])
-            with torch.cuda.device(key[0]):
+            n = len(es)
+            with torch.cuda.device(device):
                 ctx = H.gemm_ctx(workspace=True)
-                arr = lambda i: (ctypes.c_void_p * len(es))(*[e[i] if i == 2 else e[i].data_ptr() for e in es])
-                with trace_launch(2.0 * M * N * K * len(es)):
-                    H.check(H.lib().fcmf_gemm_dw_batched(ctx, len(es), arr(0), arr(1), arr(2), M, N, K, lda, ldb, ldc, int(acc), H.stream()),
-                            "fcmf_gemm_dw_batched")
+                ptrs = lambda i: (ctypes.c_void_p * n)(*[e[i] if i == 2 else e[i].data_ptr() for e in es])
+                ints = lambda i: (ctypes.c_int * n)(*[e[i] for e in es])
+                lds = lambda i: (ctypes.c_int64 * n)(*[e[i] for e in es])
+                by_shape = {}
+                for e in es:
+                    by_shape[e[3:6]] = by_shape.get(e[3:6], 0.0) + 2.0 * e[3] * e[4] * e[5]
+                with trace_launch(list(by_shape.values())):
+                    if all(e[3:9] == es[0][3:9] for e in es):      # one shape: the same list through the same-shape entry point
+                        M, N, K, lda, ldb, ldc = es[0][3:9]
+                        H.check(H.lib().fcmf_gemm_dw_batched(ctx, n, ptrs(0), ptrs(1), ptrs(2), M, N, K, lda, ldb, ldc, int(acc), H.stream()),
+                                "fcmf_gemm_dw_batched")
+                    else:
+                        H.check(H.lib().fcmf_gemm_dw_list(ctx, n, ptrs(0), ptrs(1), ptrs(2), ints(3), ints(4), ints(5), lds(6), lds(7), lds(8),
+                                                          int(acc), H.stream()), "fcmf_gemm_dw_list")
             self.batched_launches += 1
-            self.batched_matrices += len(es)
+            self.batched_matrices += n
 
 
 deferred_dw = _DeferredDW()
@@ -331,10 +344,6 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, ta, tb, bias=None, aux=None, epi=H.EPI
                                   int(ta), int(tb), H.dt(A), H.dt(C), epi, int(acc), H.stream()), "fcmf_gemm")
 
 
-# (see _DeferredDW.wanted; measured on one box, 20 steps, twice each: 36.76 / 36.85 ms off, 36.70 / 36.67 ms on -- 168 instead of 176 GEMM
-#  launches, 26.43 instead of 26.70 ms of GEMM time -- but the batched kernel then also runs the small shared-weight batches and its
-#  per-launch average drops from 1223 to 1194 TFLOP/s.  Off by default: the two configurations are within the box-to-box spread)
-DEFER_SHARED_DW = os.environ.get("FCMF_DEFER_SHARED_DW", "0") == "1"
 HEAD_WGRAD_DIRECT = os.environ.get("FCMF_HEAD_WGRAD_DIRECT", "1") == "1"      # (A/B switch)
 
 

@@ -8,7 +8,7 @@
 //   clang++ -std=c++17 -O1 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I../../include -c ../../tools/gemm_dispatch_probe.cpp -o probe.o
 //   hipcc --offload-arch=gfx950 -rdynamic probe.o gemm.o -ldl -o gemm_dispatch_probe
 //   ./gemm_dispatch_probe | sha256sum        # the dump; the summary (counts per stub / last_kernel / return code) goes to stderr
-// GemmParams / GenericParams / BatchPtrs below mirror gemm.hip: keep them in step with it.
+// GemmParams / GenericParams / DwList below mirror gemm.hip: keep them in step with it.
 #include <hip/hip_runtime_api.h>
 #include <dlfcn.h>
 #include <cstdio>
@@ -31,9 +31,9 @@ struct GemmParams {
   const float* sa; const float* sb;
   int cv_C, cv_logC, cv_Hp, cv_Wp, cv_Ho, cv_Wo, cv_kw, cv_inv_kw, cv_stride;
   float* colstats;
-  int cv_logP, tiles_per_mat;
+  int cv_logP;
 };
-struct BatchPtrs { const void* A[32]; const void* B[32]; void* C[32]; };
+struct DwList { const void* mats; const void* items; };
 struct GenericParams {
   const void* A; const void* B; void* C; const float* bias; void* aux;
   int M, N, K;
@@ -53,9 +53,6 @@ static std::string stub_name(const void* f) {
   static std::map<const void*, int> seen;
   return "kernel#" + std::to_string(seen.emplace(f, (int)seen.size()).first->second);
 }
-static void print_batch(const BatchPtrs& b) {
-  for (int i = 0; i < 32 && b.A[i]; ++i) printf(" [%d]=%p,%p,%p", i, b.A[i], b.B[i], b.C[i]);
-}
 #define I(a, i) (*(int*)(a)[i])
 #define L(a, i) ((long long)*(int64_t*)(a)[i])
 #define P(a, i) (*(void**)(a)[i])
@@ -73,14 +70,27 @@ extern "C" hipError_t hipFuncSetAttribute(const void* f, hipFuncAttribute attr, 
   return hipSuccess;
 }
 extern "C" hipError_t hipGetLastError(void) { return hipSuccess; }
+// the table upload of a weight-gradient list: staging memory from the heap, events that are always complete, and the copy printed
+// as its size and an FNV-1a hash of what it carries (the matrices, the items and the reduce table)
+extern "C" hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
+extern "C" hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+extern "C" hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)malloc(1); return hipSuccess; }
+extern "C" hipError_t hipEventDestroy(hipEvent_t e) { free((void*)e); return hipSuccess; }
+extern "C" hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+extern "C" hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+extern "C" hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t) {
+  unsigned long long h = 1469598103934665603ull;
+  for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char*)src)[i]) * 1099511628211ull;
+  printf("  upload %p %zu bytes fnv=%016llx\n", dst, n, h);
+  return hipSuccess;
+}
 extern "C" hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { printf("  memset %p %d %zu\n", p, v, n); return hipSuccess; }
 extern "C" hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** a, size_t smem, hipStream_t st) {
   const std::string name = stub_name(f);
   ++g_count["launch " + name];
   printf("  %s grid=(%u,%u,%u) block=%u smem=%zu attr=%d stream=%p\n", name.c_str(), g.x, g.y, g.z, b.x, smem, g_attr.count(f) ? g_attr[f] : -1, (void*)st);
-  if (name.find("splitk_reduce_frag_batched") != std::string::npos) {
-    printf("   ws=%p tiles_per_mat=%d M=%d N=%d ldc=%lld ksplit=%d tiles=%d tiles_n=%d accumulate=%d bp:", P(a, 0), I(a, 2), I(a, 3), I(a, 4), L(a, 5), I(a, 6), I(a, 7), I(a, 8), I(a, 9));
-    print_batch(*(BatchPtrs*)a[1]);
+  if (name.find("splitk_reduce_list") != std::string::npos) {
+    printf("   ws=%p red=%p mats=%p entries=%d accumulate=%d", P(a, 0), P(a, 1), P(a, 2), I(a, 3), I(a, 4));
   } else if (name.find("splitk_reduce_frag") != std::string::npos) {
     printf("   ws=%p C=%p M=%d N=%d ldc=%lld ksplit=%d tiles=%d tiles_n=%d accumulate=%d cblk=%d cblk_stride=%lld", P(a, 0), P(a, 1), I(a, 2), I(a, 3), L(a, 4), I(a, 5), I(a, 6), I(a, 7), I(a, 8), I(a, 9), L(a, 10));
   } else if (name.find("splitk_reduce") != std::string::npos) {
@@ -92,11 +102,11 @@ extern "C" hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** a, s
   } else {
     const GemmParams& p = *(GemmParams*)a[0];
     printf("   A=%p B=%p C=%p bias=%p aux=%p M=%d N=%d K=%d lda=%lld ldb=%lld ldc=%lld epilogue=%d accumulate=%d ksplit=%d ktiles_per_split=%d a_bytes=%u b_bytes=%u c_bytes=%u"
-           " colsum=%p tiles=%d total_items=%d ws=%p nt_out=%d sa=%p sb=%p cv=%d,%d,%d,%d,%d,%d,%d,%d,%d colstats=%p cv_logP=%d tiles_per_mat=%d",
+           " colsum=%p tiles=%d total_items=%d ws=%p nt_out=%d sa=%p sb=%p cv=%d,%d,%d,%d,%d,%d,%d,%d,%d colstats=%p cv_logP=%d",
            p.A, p.B, p.C, (void*)p.bias, p.aux, p.M, p.N, p.K, (long long)p.lda, (long long)p.ldb, (long long)p.ldc, p.epilogue, p.accumulate, p.ksplit, p.ktiles_per_split, p.a_bytes, p.b_bytes, p.c_bytes,
            (void*)p.colsum, p.tiles, p.total_items, (void*)p.ws, p.nt_out, (void*)p.sa, (void*)p.sb, p.cv_C, p.cv_logC, p.cv_Hp, p.cv_Wp, p.cv_Ho, p.cv_Wo, p.cv_kw, p.cv_inv_kw, p.cv_stride,
-           (void*)p.colstats, p.cv_logP, p.tiles_per_mat);
-    if (name.find("dw_batched") != std::string::npos) { printf(" bp:"); print_batch(*(BatchPtrs*)a[1]); }
+           (void*)p.colstats, p.cv_logP);
+    if (name.find("dw_batched") != std::string::npos) { const DwList& l = *(DwList*)a[1]; printf(" mats=%p items=%p", l.mats, l.items); }
   }
   printf("\n");
   return hipSuccess;
@@ -175,7 +185,8 @@ static void sweep_rest(const Ctx& c) {
   static const int counts[] = {0, 1, 2, 12, 33, 40};
   static const int shapes[][3] = {{768, 768, 8192}, {768, 3072, 8192}, {768, 128, 8192} /* falls back: N < 256 */};
   const void* pa[40]; const void* pb[40]; void* pc[40];
-  for (int i = 0; i < 40; ++i) { pa[i] = A0 + i * 0x100000; pb[i] = B0 + i * 0x100000; pc[i] = C0 + i * 0x100000; }
+  // (outputs 16 MiB apart: destinations that overlap without being the same matrix stay out of a list)
+  for (int i = 0; i < 40; ++i) { pa[i] = A0 + i * 0x100000; pb[i] = B0 + i * 0x100000; pc[i] = C0 + (size_t)i * 0x1000000; }
   for (int cnt : counts) for (const auto& s : shapes) for (int acc = 0; acc < 2; ++acc) {
     snprintf(what, sizeof what, "dw_batched n%d %dx%dx%d a%d", cnt, s[0], s[1], s[2], acc);
     done(c, what, fcmf_gemm_dw_batched(c.c, cnt, pa, pb, pc, s[0], s[1], s[2], s[0], s[1], s[1], acc, STREAM));
