@@ -11,7 +11,10 @@
 //             [key][query] of the chunk in LDS, phase 2 adds the chunk to dQ (wave = 32 queries, accumulators
 //             live across chunks) and finishes dV / dK of the chunk's keys (wave = 16 head-dim columns, the
 //             transposed dO / Q operands stay in registers).  80 KiB of LDS: two workgroups per CU overlap
-//             each other's loads, barriers and stores; no atomics.
+//             each other's loads, barriers and stores; no atomics.  Every global read of a workgroup (tiles, O rows,
+//             lse, mask row) is requested in one batch up front and the chunk loop holds no load and no wait on the
+//             vector-memory counter, so its stores drain under the next chunk; dq / dk / dv leave as whole 128-byte
+//             rows, put together in LDS that is dead by then.
 // One LDS image per tile serves both row reads (ds_read_b128) and transposed reads
 // (ds_read_b64_tr_b16); swizzles verified conflict-free with tools/lds_conflicts.py.
 #include "attn_tiles.h"
@@ -26,9 +29,13 @@
 // (mask_lds != NULL: the additive key mask of the tile was staged in LDS with K / V -- the persistent kernel must not issue a
 // global load inside the tile: the counter of vector-memory operations retires in order, so waiting for it would also wait
 // for the next tile's operands that are in flight behind it)
-template <int NKT>
-__device__ __forceinline__ void attn_mfma_fwd_tile(const AttnMfmaParams& P, int g, int h, int q0, int lane, const bf16x8 (&qf)[2][2],
-                                                   const char* Ks, const char* Vs, const float* mask_lds = nullptr) {
+// The tile in two halves, arithmetic and stores, so that the persistent kernel can put the wait for the NEXT tile's operands
+// between them: oc = O^T accumulators, lv[f] = logsumexp of query q0 + 16 f + (lane & 15), stored by the first half unless
+// LSE_LATE (the one-tile kernels, which have no such wait, keep their registers: fwd256 fits three workgroups per CU only so).
+template <int NKT, bool LSE_LATE>
+__device__ __forceinline__ void attn_mfma_fwd_tile_compute(const AttnMfmaParams& P, int g, int h, int q0, int lane, const bf16x8 (&qf)[2][2],
+                                                           const char* Ks, const char* Vs, const float* mask_lds, f32x4 (&oc)[4][2],
+                                                           float (&lv)[2]) {
   constexpr int NKF = 8 * NKT;       // 16-key fragments
   const float* mrow = P.mask ? P.mask + (int64_t)g * P.Tk : nullptr;
   // trailing keys under the "hard" additive mask (<= -1e30: HF's finfo.min padding mask) get probabilities that are EXACTLY
@@ -95,7 +102,8 @@ __device__ __forceinline__ void attn_mfma_fwd_tile(const AttnMfmaParams& P, int 
     sum += __shfl_xor(sum, 16, 64);
     sum += __shfl_xor(sum, 32, 64);
     const float inv = 1.0f / sum;
-    if (q < P.Tq && (lane >> 4) == 0 && P.lse) P.lse[((int64_t)g * P.heads + h) * P.Tq + q] = m + __logf(sum);
+    lv[f] = m + __logf(sum);
+    if (!LSE_LATE && q < P.Tq && (lane >> 4) == 0 && P.lse) P.lse[((int64_t)g * P.heads + h) * P.Tq + q] = lv[f];
 #pragma unroll
     for (int kf = 0; kf < NKF; ++kf) {
       if (16 * kf >= nvalid) continue;
@@ -108,7 +116,6 @@ __device__ __forceinline__ void attn_mfma_fwd_tile(const AttnMfmaParams& P, int 
     }
   }
   // O^T[d][q] = sum_key V[key][d] P[q][key]
-  f32x4 oc[4][2];
 #pragma unroll
   for (int df = 0; df < 4; ++df)
 #pragma unroll
@@ -129,15 +136,28 @@ __device__ __forceinline__ void attn_mfma_fwd_tile(const AttnMfmaParams& P, int 
       for (int f = 0; f < 2; ++f) oc[df][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pb[f], oc[df][f], 0, 0, 0);
     }
   }
+}
+template <bool LSE_LATE>
+__device__ __forceinline__ void attn_mfma_fwd_tile_store(const AttnMfmaParams& P, int g, int h, int q0, int lane, const f32x4 (&oc)[4][2],
+                                                         const float (&lv)[2]) {
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
     const int q = q0 + 16 * f + (lane & 15);
     if (q < P.Tq) {
+      if (LSE_LATE && (lane >> 4) == 0 && P.lse) P.lse[((int64_t)g * P.heads + h) * P.Tq + q] = lv[f];
       bf16_t* orow = P.out + ((int64_t)g * P.Tq + q) * P.ldo + h * AD + 4 * (lane >> 4);
 #pragma unroll
       for (int df = 0; df < 4; ++df) store4(orow + 16 * df, oc[df][f]);
     }
   }
+}
+template <int NKT>
+__device__ __forceinline__ void attn_mfma_fwd_tile(const AttnMfmaParams& P, int g, int h, int q0, int lane, const bf16x8 (&qf)[2][2],
+                                                   const char* Ks, const char* Vs, const float* mask_lds = nullptr) {
+  f32x4 oc[4][2];
+  float lv[2];
+  attn_mfma_fwd_tile_compute<NKT, false>(P, g, h, q0, lane, qf, Ks, Vs, mask_lds, oc, lv);
+  attn_mfma_fwd_tile_store<false>(P, g, h, q0, lane, oc, lv);
 }
 
 template <int NKT>
@@ -170,7 +190,8 @@ __device__ __forceinline__ void attn_mfma_fwd_body(const AttnMfmaParams& P) {
 // tiles blockIdx.x, + gridDim.x, ...; the K / V / Q loads of the NEXT tile are put in flight (into registers) before the
 // current tile is computed and land in the other half of a double-buffered LDS image afterwards, so the global-load
 // latency -- 58 % of a wave's lifetime in the one-tile-per-workgroup kernel (SQ_WAIT_ANY) -- hides under the softmax.
-// 64 KiB of LDS, two workgroups per CU.
+// Per tile: prefetch, arithmetic, wait for the prefetch (nothing but loads outstanding), LDS writes, THEN the tile's global
+// stores, barrier: no wait for loads ever stands behind younger stores.  64 KiB of LDS, two workgroups per CU.
 __global__ __launch_bounds__(256, 2) void attn_mfma_fwd_persist_kernel(AttnMfmaParams P, int ntiles, int qtiles) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -184,36 +205,43 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_fwd_persist_kernel(AttnMfmaP
   int g, h, q0;
   where(tile, g, h, q0);
   bf16x8 qf[2][2];
-  auto mask_of = [&](int gg) { return (P.mask && tid < P.Tk) ? P.mask[(int64_t)gg * P.Tk + tid] : 0.f; };
+  // (every load of a tile's operands is unconditional -- indices past the end are clamped, the values cleared or never read --
+  // so that the compiler keeps them one batch and counts its waits; mask entries of keys >= Tk are never read)
+  auto mask_of = [&](int gg) { return P.mask ? P.mask[(int64_t)gg * P.Tk + min(tid, P.Tk - 1)] : 0.f; };
   {
-    const TileRegs kt = load_tile(P.k + (int64_t)g * P.Tk * P.ldk + h * AD, P.ldk, P.Tk, tid);
-    const TileRegs vt = load_tile(P.v + (int64_t)g * P.Tk * P.ldk + h * AD, P.ldk, P.Tk, tid);
+    TileRegs kt = load_tile_clamped(P.k + (int64_t)g * P.Tk * P.ldk + h * AD, P.ldk, P.Tk, tid);
+    TileRegs vt = load_tile_clamped(P.v + (int64_t)g * P.Tk * P.ldk + h * AD, P.ldk, P.Tk, tid);
     const float mv = mask_of(g);
-    load_q_frags(P, g, h, q0, lane, qf);
+    load_q_frags_clamped(P, g, h, q0, lane, qf);
+    zero_tail(kt, P.Tk, tid);
+    zero_tail(vt, P.Tk, tid);
+    zero_q_tail(P, q0, lane, qf);
     store_tile<false>(smem, kt, tid);
     store_tile<true>(smem + TILE_B, vt, tid);
     if (tid < AT) reinterpret_cast<float*>(smem + 2 * TILE_B)[tid] = mv;
   }
   __syncthreads();
   int cur = 0;
-  for (;;) {
-    const int nxt = tile + gridDim.x;
-    const bool more = nxt < ntiles;
-    int g2 = g, h2 = h, q2 = q0;
-    TileRegs kt, vt;
+  // The loop body is a tile that HAS a successor; the last tile of the walk is computed behind the loop.  (With both in one
+  // body the path that skips the prefetch joins the back edge, and the compiler then waits at the loop top, where it
+  // redefines the prefetch registers, for most of the previous tile's stores.)
+  for (int nxt = tile + gridDim.x; nxt < ntiles; nxt += gridDim.x) {
+    int g2, h2, q2;
     bf16x8 qn[2][2];
-    float mv = 0.f;
-    if (more) {                              // next tile's operands: in flight under this tile's arithmetic
-      where(nxt, g2, h2, q2);
-      kt = load_tile(P.k + (int64_t)g2 * P.Tk * P.ldk + h2 * AD, P.ldk, P.Tk, tid);
-      vt = load_tile(P.v + (int64_t)g2 * P.Tk * P.ldk + h2 * AD, P.ldk, P.Tk, tid);
-      mv = mask_of(g2);
-      load_q_frags(P, g2, h2, q2, lane, qn);
-    }
+    where(nxt, g2, h2, q2);                  // next tile's operands: in flight under this tile's arithmetic
+    TileRegs kt = load_tile_clamped(P.k + (int64_t)g2 * P.Tk * P.ldk + h2 * AD, P.ldk, P.Tk, tid);
+    TileRegs vt = load_tile_clamped(P.v + (int64_t)g2 * P.Tk * P.ldk + h2 * AD, P.ldk, P.Tk, tid);
+    const float mv = mask_of(g2);
+    load_q_frags_clamped(P, g2, h2, q2, lane, qn);
     const char* buf = smem + cur * BUF;
-    attn_mfma_fwd_tile<1>(P, g, h, q0, lane, qf, buf, buf + TILE_B, reinterpret_cast<const float*>(buf + 2 * TILE_B));
-    if (!more) break;
+    f32x4 oc[4][2];
+    float lv[2];
+    attn_mfma_fwd_tile_compute<1, true>(P, g, h, q0, lane, qf, buf, buf + TILE_B, reinterpret_cast<const float*>(buf + 2 * TILE_B), oc, lv);
+    // The next tile's operands go to LDS BEFORE this tile's results are stored: loads and stores retire through one in-order
+    // counter, so a wait for the operands placed behind the stores would also wait for the stores' acknowledgement.
     cur ^= 1;                                // (the other buffer was last read before the previous barrier)
+    zero_tail(kt, P.Tk, tid);
+    zero_tail(vt, P.Tk, tid);
     store_tile<false>(smem + cur * BUF, kt, tid);
     store_tile<true>(smem + cur * BUF + TILE_B, vt, tid);
     if (tid < AT) reinterpret_cast<float*>(smem + cur * BUF + 2 * TILE_B)[tid] = mv;
@@ -221,9 +249,15 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_fwd_persist_kernel(AttnMfmaP
     for (int f = 0; f < 2; ++f)
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) qf[f][s2] = qn[f][s2];
-    g = g2; h = h2; q0 = q2; tile = nxt;
+    zero_q_tail(P, q2, lane, qf);
+    // (pinned: the compiler otherwise sinks this last use of the loaded fragments below the stores, and its wait with it)
+    asm volatile("" : "+v"(qf[0][0]), "+v"(qf[0][1]), "+v"(qf[1][0]), "+v"(qf[1][1]) : : "memory");
+    attn_mfma_fwd_tile_store<true>(P, g, h, q0, lane, oc, lv);
+    g = g2; h = h2; q0 = q2;
     __syncthreads();
   }
+  const char* buf = smem + cur * BUF;
+  attn_mfma_fwd_tile<1>(P, g, h, q0, lane, qf, buf, buf + TILE_B, reinterpret_cast<const float*>(buf + 2 * TILE_B));
 }
 
 __global__ __launch_bounds__(256, 3) void attn_mfma_fwd_kernel(AttnMfmaParams P) { attn_mfma_fwd_body<1>(P); }
@@ -250,61 +284,83 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
   const int64_t qbase = (int64_t)g * P.Tq, kbase = (int64_t)g * P.Tk;
   // delta[q] = sum_d dO[q][d] O[q][d] for the wave's 32 query rows of every query tile: two lanes per row, then every
   // lane picks the values of the rows its accumulator registers hold
+  // ALL global reads of the workgroup -- the Q / dO / K / V tiles, the O rows of delta, lse and the mask row -- are requested
+  // here in one batch, none of them under a branch (indices past the end are clamped, the values cleared afterwards), and
+  // waited for once: one round trip to memory, and none in the chunk loop below.
   float dl4[NQT][2][4], lse4[NQT][2][4];
+  float mreg[2 * NKT];       // additive mask of key 64 i + lane (0 without a mask and past Tk)
   {
-    TileRegs tq[NQT], td[NQT];
+    TileRegs tq[NQT], td[NQT], tk[NKT], tv[NKT];
+    uint4 og[NQT][4];        // O[q][32 half + 8 i ..], q = the wave's row lane >> 1, half = lane & 1
 #pragma unroll
     for (int qt = 0; qt < NQT; ++qt) {
-      tq[qt] = load_tile(P.q + (qbase + qt * AT) * P.ldq + h * AD, P.ldq, P.Tq - qt * AT, tid);
-      td[qt] = load_tile(P.dout + (qbase + qt * AT) * P.ldo + h * AD, P.ldo, P.Tq - qt * AT, tid);
+      tq[qt] = load_tile_clamped(P.q + (qbase + qt * AT) * P.ldq + h * AD, P.ldq, P.Tq - qt * AT, tid);
+      td[qt] = load_tile_clamped(P.dout + (qbase + qt * AT) * P.ldo + h * AD, P.ldo, P.Tq - qt * AT, tid);
     }
-    TileRegs tk = load_tile(P.k + kbase * P.ldk + h * AD, P.ldk, P.Tk, tid);
-    TileRegs tv = load_tile(P.v + kbase * P.ldk + h * AD, P.ldk, P.Tk, tid);
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+      tk[kt] = load_tile_clamped(P.k + (kbase + kt * AT) * P.ldk + h * AD, P.ldk, P.Tk - kt * AT, tid);
+      tv[kt] = load_tile_clamped(P.v + (kbase + kt * AT) * P.ldk + h * AD, P.ldk, P.Tk - kt * AT, tid);
+    }
 #pragma unroll
     for (int qt = 0; qt < NQT; ++qt) {
-      const int q = qt * AT + 32 * w + (lane >> 1), half = lane & 1;
-      float sd = 0.f;
-      if (q < P.Tq) {
-        const bf16_t* a = P.dout + (qbase + q) * P.ldo + h * AD + 32 * half;
-        const bf16_t* b = P.o + (qbase + q) * P.ldo + h * AD + 32 * half;
+      const int q = min(qt * AT + 32 * w + (lane >> 1), P.Tq - 1);
+      const bf16_t* b = P.o + (qbase + q) * P.ldo + h * AD + 32 * (lane & 1);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const bf16x8 x = *reinterpret_cast<const bf16x8*>(a + 8 * i);
-          const bf16x8 y = *reinterpret_cast<const bf16x8*>(b + 8 * i);
+      for (int i = 0; i < 4; ++i) og[qt][i] = *reinterpret_cast<const uint4*>(b + 8 * i);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) sd += (float)x[j] * (float)y[j];
+      for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int q2 = qt * AT + 32 * w + 16 * f + 4 * (lane >> 4) + r;
+          lse4[qt][f][r] = P.lse[((int64_t)g * P.heads + h) * P.Tq + min(q2, P.Tq - 1)];
         }
+    }
+#pragma unroll
+    for (int i = 0; i < 2 * NKT; ++i) mreg[i] = P.mask ? P.mask[kbase + min(64 * i + lane, P.Tk - 1)] : 0.f;
+#pragma unroll
+    for (int qt = 0; qt < NQT; ++qt) {
+      zero_tail(tq[qt], P.Tq - qt * AT, tid);
+      zero_tail(td[qt], P.Tq - qt * AT, tid);
+      store_tile<false>(Qs + qt * TILE_B, tq[qt], tid);
+      store_tile<false>(dOs + qt * TILE_B, td[qt], tid);
+    }
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+      zero_tail(tk[kt], P.Tk - kt * AT, tid);
+      zero_tail(tv[kt], P.Tk - kt * AT, tid);
+      store_tile<false>(Ks + kt * TILE_B, tk[kt], tid);
+      store_tile<false>(Vs + kt * TILE_B, tv[kt], tid);
+    }
+    __syncthreads();
+    // delta[q] = sum_d dO[q][d] O[q][d]: dO from its LDS image (not a second time from memory), O from the registers
+#pragma unroll
+    for (int qt = 0; qt < NQT; ++qt) {
+      const int ql = 32 * w + (lane >> 1), half = lane & 1;
+      float sd = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bf16x8 x = *reinterpret_cast<const bf16x8*>(dOs + qt * TILE_B + off64(ql, 4 * half + i));
+        const bf16x8 y = *reinterpret_cast<const bf16x8*>(&og[qt][i]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sd += (float)x[j] * (float)y[j];
       }
+      if (qt * AT + ql >= P.Tq) sd = 0.f;
       sd += __shfl_xor(sd, 1, 64);
 #pragma unroll
       for (int f = 0; f < 2; ++f)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int ql = 16 * f + 4 * (lane >> 4) + r;          // row inside the wave's 32
-          dl4[qt][f][r] = __shfl(sd, 2 * ql, 64);
-          const int q2 = qt * AT + 32 * w + ql;
-          lse4[qt][f][r] = q2 < P.Tq ? P.lse[((int64_t)g * P.heads + h) * P.Tq + q2] : 0.f;
+          const int qr = 16 * f + 4 * (lane >> 4) + r;          // row inside the wave's 32
+          dl4[qt][f][r] = __shfl(sd, 2 * qr, 64);
+          if (qt * AT + 32 * w + qr >= P.Tq) lse4[qt][f][r] = 0.f;
         }
     }
-#pragma unroll
-    for (int qt = 0; qt < NQT; ++qt) {     // (every global read of the prologue was requested before the first LDS write)
-      store_tile<false>(Qs + qt * TILE_B, tq[qt], tid);
-      store_tile<false>(dOs + qt * TILE_B, td[qt], tid);
-    }
-    store_tile<false>(Ks, tk, tid);
-    store_tile<false>(Vs, tv, tid);
-    if constexpr (NKT == 2) {
-      tk = load_tile(P.k + (kbase + AT) * P.ldk + h * AD, P.ldk, P.Tk - AT, tid);
-      tv = load_tile(P.v + (kbase + AT) * P.ldk + h * AD, P.ldk, P.Tk - AT, tid);
-      store_tile<false>(Ks + TILE_B, tk, tid);
-      store_tile<false>(Vs + TILE_B, tv, tid);
-    }
   }
-  __syncthreads();
 
   const float inv_keep = P.p > 0.f ? 1.0f / (1.0f - P.p) : 1.0f;
   const uint64_t drop_base = ((uint64_t)g * P.heads + h) * P.Tq * P.Tk;      // dropout counter of (query 0, key 0)
-  const float* mrow = P.mask ? P.mask + kbase : nullptr;
+  bool masked = P.mask != nullptr;
   float score_scale = P.scale;            // (0 for a sequence whose every key is hard-masked: see below)
   // operands that stay in registers, per query tile: the wave's 32 query rows of Q and dO (phase 1) and the transposed
   // 16-column slices dO^T / Q^T [d = 16w ..][q] that dV / dK of every key chunk multiply (phase 2)
@@ -338,12 +394,13 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
   // are EXACTLY zero (exp underflows), so whole 32-key chunks of them contribute nothing to dQ and get dK = dV = 0: they
   // are skipped, with bit-identical results.  nvalid = index of the last key that is not hard-masked, + 1 (wave-uniform).
   int nvalid = P.Tk;
-  if (mrow) {
+  if (masked) {
     int last = -1;
 #pragma unroll
     for (int i = 0; i < 2 * NKT; ++i) {
       const int key = 64 * i + lane;
-      const bool live = key < P.Tk && mrow[key] > -1e30f;
+      const bool live = key < P.Tk && mreg[i] > -1e30f;
+      if (key >= P.Tk) mreg[i] = 0.f;
       const unsigned long long b = __ballot(live);
       if (b) last = 64 * i + 63 - __builtin_clzll(b);
     }
@@ -352,7 +409,7 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
     // would recompute probabilities of 1 instead of 1 / Tk.  Wave-uniform substitution, no per-element work: drop the mask and
     // the scores and take lse = log Tk.
     if (last < 0) {
-      mrow = nullptr;
+      masked = false;
       score_scale = 0.f;
       const float ltk = __logf((float)P.Tk);
 #pragma unroll
@@ -377,10 +434,32 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
   const uint32_t drop_thr = dropout_threshold(P.p);
   const int odd = lane & 1;
   f32x4 cV = f32x4{0.f, 0.f, 0.f, 0.f}, cK = f32x4{0.f, 0.f, 0.f, 0.f};   // column sums of dV / dK over the keys (this lane's keys)
+  // dk / dv leave in whole 128-byte rows too: wave w owns 16 of a row's 64 columns, so the chunk's [32 keys][64 d] blocks
+  // are put together in LDS -- in the K / V rows of the chunk itself, dead once the chunk is done (16-byte piece XOR
+  // ((key >> 1) & 7), as for dq below) -- and go out 16 bytes per lane behind the NEXT barrier the loop has anyway.
+  auto flush_dkv = [&](int cc) {
+    const int r = tid >> 3, ch = tid & 7, key = 32 * cc + r;
+    const int o = cc * (TILE_B / 4) + r * 128 + ((ch ^ ((r >> 1) & 7)) << 4);
+    const uint4 dvv = *reinterpret_cast<const uint4*>(Vs + o), dkk = *reinterpret_cast<const uint4*>(Ks + o);
+    if (key < P.Tk) {
+      *reinterpret_cast<uint4*>(P.dv + (kbase + key) * P.ldk + h * AD + 8 * ch) = dvv;
+      *reinterpret_cast<uint4*>(P.dk + (kbase + key) * P.ldk + h * AD + 8 * ch) = dkk;
+    }
+  };
   for (int c = 0; c < nchunks; ++c) {
     f32x4 aV[2], aK[2];
 #pragma unroll
     for (int kf = 0; kf < 2; ++kf) { aV[kf] = f32x4{0.f, 0.f, 0.f, 0.f}; aK[kf] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    // mask of the chunk's keys 32 c + 16 k4 + (lane & 15) from the lanes that loaded them: no global load in this loop, so no
+    // wait that the dk / dv stores of the previous chunk (same in-order counter) could hold up
+    float mk2[2] = {0.f, 0.f};
+    if (masked) {
+      float mc = mreg[0];
+#pragma unroll
+      for (int i = 1; i < 2 * NKT; ++i) mc = (c >> 1) == i ? mreg[i] : mc;
+#pragma unroll
+      for (int k4 = 0; k4 < 2; ++k4) mk2[k4] = __shfl(mc, 32 * (c & 1) + 16 * k4 + (lane & 15), 64);
+    }
 #pragma unroll
     for (int qt = 0; qt < NQT; ++qt) {
       f32x4 sS[2][2], sP[2][2];
@@ -403,7 +482,7 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
 #pragma unroll
       for (int k4 = 0; k4 < 2; ++k4) {
         const int kl = 16 * k4 + (lane & 15), key = 32 * c + kl;
-        const float mk = (mrow && key < P.Tk) ? mrow[key] : 0.f;
+        const float mk = mk2[k4];
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
           f32x4 pdv, dsv;
@@ -437,6 +516,7 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
         }
       }
       __syncthreads();
+      if (qt == 0 && c > 0) flush_dkv(c - 1);      // (staged by all four waves before the barrier just passed)
       // dQ^T[d][q] += K^T[d][keys of the chunk] dS^T[keys][q]
       {
         bf16x8 tb[2];
@@ -461,46 +541,51 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
         }
       __syncthreads();   // the chunk images are rewritten by the next query tile / chunk
     }
-    const int dcol = h * AD + 16 * w + 4 * (lane >> 4);
     cV += aV[0] + aV[1];        // (keys past Tk carry zero probabilities: no mask needed)
     cK += aK[0] + aK[1];
+    // staged over the chunk's own K / V rows, which nobody reads again (every wave has passed the closing barrier above)
 #pragma unroll
     for (int kf = 0; kf < 2; ++kf) {
-      const int key = 32 * c + 16 * kf + (lane & 15);
-      if (key < P.Tk) {
-        store4(P.dv + (kbase + key) * P.ldk + dcol, aV[kf]);
-        f32x4 t = aK[kf];
-        t[0] *= P.scale; t[1] *= P.scale; t[2] *= P.scale; t[3] *= P.scale;
-        store4(P.dk + (kbase + key) * P.ldk + dcol, t);
-      }
+      const int kl = 16 * kf + (lane & 15);
+      const int o = c * (TILE_B / 4) + kl * 128 + (((2 * w + (lane >> 5)) ^ ((kl >> 1) & 7)) << 4) + ((lane >> 4) & 1) * 8;
+      store4(reinterpret_cast<bf16_t*>(Vs + o), aV[kf]);
+      f32x4 t = aK[kf];
+      t[0] *= P.scale; t[1] *= P.scale; t[2] *= P.scale; t[3] *= P.scale;
+      store4(reinterpret_cast<bf16_t*>(Ks + o), t);
     }
   }
+  __syncthreads();
+  flush_dkv(nchunks - 1);
   for (int c = nchunks; c < nchunks_all; ++c) {      // the skipped (fully hard-masked) chunks: dK = dV = 0
-    const int dcol = h * AD + 16 * w + 4 * (lane >> 4);
-#pragma unroll
-    for (int kf = 0; kf < 2; ++kf) {
-      const int key = 32 * c + 16 * kf + (lane & 15);
-      if (key < P.Tk) {
-        store4(P.dv + (kbase + key) * P.ldk + dcol, f32x4{0.f, 0.f, 0.f, 0.f});
-        store4(P.dk + (kbase + key) * P.ldk + dcol, f32x4{0.f, 0.f, 0.f, 0.f});
-      }
+    const int key = 32 * c + (tid >> 3);
+    if (key < P.Tk) {
+      *reinterpret_cast<uint4*>(P.dv + (kbase + key) * P.ldk + h * AD + 8 * (tid & 7)) = make_uint4(0, 0, 0, 0);
+      *reinterpret_cast<uint4*>(P.dk + (kbase + key) * P.ldk + h * AD + 8 * (tid & 7)) = make_uint4(0, 0, 0, 0);
     }
   }
+  // dq leaves in whole 128-byte rows: the wave turns its 64 x 32 block of dQ^T into [q][d] through its own quarter of the
+  // two chunk images (free now: every wave has passed the last chunk's closing barrier; wave-private, so no barrier here)
+  // and stores 16 bytes per lane, 8 rows per instruction.  16-byte piece XOR ((q >> 1) & 7): conflict free both ways.
+  char* stg = PdT + w * (TILE_B / 4);
 #pragma unroll
-  for (int qt = 0; qt < NQT; ++qt)
+  for (int qt = 0; qt < NQT; ++qt) {
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
-      const int x = qt * AT + 32 * w + 16 * f + (lane & 15);
-      if (x < P.Tq) {
-        const int dcol = h * AD + 4 * (lane >> 4);
+      const int ql = 16 * f + (lane & 15);
 #pragma unroll
-        for (int df = 0; df < 4; ++df) {
-          f32x4 t = aQ[qt][df][f];
-          t[0] *= P.scale; t[1] *= P.scale; t[2] *= P.scale; t[3] *= P.scale;
-          store4(P.dq + (qbase + x) * P.ldq + dcol + 16 * df, t);
-        }
+      for (int df = 0; df < 4; ++df) {
+        f32x4 t = aQ[qt][df][f];
+        t[0] *= P.scale; t[1] *= P.scale; t[2] *= P.scale; t[3] *= P.scale;
+        store4(reinterpret_cast<bf16_t*>(stg + ql * 128 + (((2 * df + (lane >> 5)) ^ ((ql >> 1) & 7)) << 4) + ((lane >> 4) & 1) * 8), t);
       }
     }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int ql = 8 * i + (lane >> 3), ch = lane & 7, x = qt * AT + 32 * w + ql;
+      const uint4 v = *reinterpret_cast<const uint4*>(stg + ql * 128 + ((ch ^ ((ql >> 1) & 7)) << 4));
+      if (x < P.Tq) *reinterpret_cast<uint4*>(P.dq + (qbase + x) * P.ldq + h * AD + 8 * ch) = v;
+    }
+  }
   // ---- optional: column sums of this (sequence, head)'s dq | dk | dv (f32 accumulators, before the bf16 rounding): the
   // bias gradient of the fused q|k|v projection is their sum over the sequences -- saves a pass over dqkv
   if (P.colsum) {
@@ -513,8 +598,10 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) { row[2 * HD + d0 + r] = cV[r]; row[HD + d0 + r] = cK[r] * P.scale; }
     }
-    // dq: rows q = .. + (lane & 15) over the fragments, query tiles and the four waves (through LDS; PdT is free now)
-    float* red = reinterpret_cast<float*>(PdT);    // [4 waves][64 d]
+    // dq: rows q = .. + (lane & 15) over the fragments, query tiles and the four waves (through LDS: 64 floats at the start of
+    // each wave's own dq staging quarter, which only that wave has read)
+    constexpr int RW = TILE_B / 4 / 4;             // floats between the waves' rows
+    float* red = reinterpret_cast<float*>(PdT);    // [4 waves][RW], 64 d used
 #pragma unroll
     for (int df = 0; df < 4; ++df) {
       f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -526,11 +613,11 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
       for (int r = 0; r < 4; ++r) t[r] = row16_sum(t[r]);
       if ((lane & 15) == 0) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) red[w * 64 + 16 * df + 4 * (lane >> 4) + r] = t[r];
+        for (int r = 0; r < 4; ++r) red[w * RW + 16 * df + 4 * (lane >> 4) + r] = t[r];
       }
     }
     __syncthreads();
-    if (tid < 64) row[tid] = (red[tid] + red[64 + tid] + red[128 + tid] + red[192 + tid]) * P.scale;
+    if (tid < 64) row[tid] = (red[tid] + red[RW + tid] + red[2 * RW + tid] + red[3 * RW + tid]) * P.scale;
   }
 }
 

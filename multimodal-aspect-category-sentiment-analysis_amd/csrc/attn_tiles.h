@@ -69,6 +69,24 @@ __device__ __forceinline__ TileRegs load_tile(const bf16_t* __restrict__ src, in
   }
   return t;
 }
+// load_tile without a branch per piece: a row past the end reads the last valid row of the matrix instead (src[(rows - 1) * ld]
+// must exist; rows may be <= 0 for a tile that starts past the end, as long as the matrix has a row before it) and zero_tail()
+// clears it before store_tile.  hipcc turns every conditional piece of load_tile into a branch and gives up counting across them:
+// it drains the loads in flight (vmcnt(0)) in the middle of a batch.  Unconditional loads stay one batch with one wait.
+__device__ __forceinline__ TileRegs load_tile_clamped(const bf16_t* __restrict__ src, int64_t ld, int rows, int tid) {
+  TileRegs t;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = tid + 256 * i, r = c >> 3, c8 = c & 7;
+    t.v[i] = *reinterpret_cast<const uint4*>(src + (int64_t)min(r, rows - 1) * ld + c8 * 8);
+  }
+  return t;
+}
+__device__ __forceinline__ void zero_tail(TileRegs& t, int rows, int tid) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (((tid + 256 * i) >> 3) >= rows) t.v[i] = make_uint4(0, 0, 0, 0);
+}
 template <bool PERMUTED>
 __device__ __forceinline__ void store_tile(char* lds, const TileRegs& t, int tid) {
 #pragma unroll
@@ -141,5 +159,26 @@ __device__ __forceinline__ void load_q_frags(const AttnMfmaParams& P, int g, int
       uint4 v = make_uint4(0, 0, 0, 0);
       if (row < P.Tq) v = *reinterpret_cast<const uint4*>(P.q + ((int64_t)g * P.Tq + row) * P.ldq + h * AD + 32 * s + 8 * (lane >> 4));
       qf[f][s] = *reinterpret_cast<bf16x8*>(&v);
+    }
+}
+// the same without a branch per fragment (see load_tile_clamped): rows past Tq read row Tq - 1; zero_q_tail() clears them
+__device__ __forceinline__ void load_q_frags_clamped(const AttnMfmaParams& P, int g, int h, int q0, int lane, bf16x8 (&qf)[2][2]) {
+#pragma unroll
+  for (int f = 0; f < 2; ++f)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int row = min(q0 + 16 * f + (lane & 15), P.Tq - 1);
+      const uint4 v = *reinterpret_cast<const uint4*>(P.q + ((int64_t)g * P.Tq + row) * P.ldq + h * AD + 32 * s + 8 * (lane >> 4));
+      qf[f][s] = *reinterpret_cast<const bf16x8*>(&v);
+    }
+}
+__device__ __forceinline__ void zero_q_tail(const AttnMfmaParams& P, int q0, int lane, bf16x8 (&qf)[2][2]) {
+#pragma unroll
+  for (int f = 0; f < 2; ++f)
+    if (q0 + 16 * f + (lane & 15) >= P.Tq) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[f][s][j] = (bf16_t)0.f;
     }
 }
