@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256, 2) void attn_long_fwd_kernel(AttnLongParams L)
   {
     const TileRegs kt = load_tile(kp + (int64_t)t * AT * P.ldk, P.ldk, P.Tk - t * AT, tid);
     const TileRegs vt = load_tile(vp + (int64_t)t * AT * P.ldk, P.ldk, P.Tk - t * AT, tid);
-    load_q_frags(P, g, h, q0, lane, qf);
+    load_q_frags(P.q, P.ldq, P.Tq, g, h, q0, lane, qf);
     store_tile<false>(Ks, kt, tid);
     store_tile<true>(Vs, vt, tid);
   }
@@ -88,19 +88,7 @@ __global__ __launch_bounds__(256, 2) void attn_long_fwd_kernel(AttnLongParams L)
     const int rows = min(AT, P.Tk - k0);      // keys of this tile; 16-key fragments past them are skipped
     // S^T[key][q]: 8 key fragments x 2 query fragments
     f32x4 sc[8][2];
-#pragma unroll
-    for (int kf = 0; kf < 8; ++kf)
-#pragma unroll
-      for (int f = 0; f < 2; ++f) sc[kf][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int kf = 0; kf < 8; ++kf) {
-        if (16 * kf >= rows) continue;
-        const bf16x8 ka = frag_row64(Ks, 16 * kf, s, lane);
-#pragma unroll
-        for (int f = 0; f < 2; ++f) sc[kf][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[f][s], sc[kf][f], 0, 0, 0);
-      }
+    fwd_score_frags<8>([&](int x0, int s) { return frag_row64(Ks, x0, s, lane); }, qf, rows, sc);
     // lane holds, for query q0+16f+(lane&15), keys k0 + 16kf + 4(lane>>4) + r
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
@@ -144,22 +132,7 @@ __global__ __launch_bounds__(256, 2) void attn_long_fwd_kernel(AttnLongParams L)
 #pragma unroll
       for (int df = 0; df < 4; ++df) oc[df][f] *= alpha;
     }
-    // O^T[d][q] += sum_key V[key][d] P[q][key]
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      if (32 * s >= rows) continue;
-      bf16x8 pb[2];
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { pb[f][r] = (bf16_t)sc[2 * s][f][r]; pb[f][4 + r] = (bf16_t)sc[2 * s + 1][f][r]; }
-#pragma unroll
-      for (int df = 0; df < 4; ++df) {
-        const bf16x8 va = frag_tr64p(Vs, 16 * df, s, lane);
-#pragma unroll
-        for (int f = 0; f < 2; ++f) oc[df][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pb[f], oc[df][f], 0, 0, 0);
-      }
-    }
+    fwd_pv_step<8>(Vs, sc, rows, lane, oc);      // O^T[d][q] += sum_key V[key][d] P[q][key]
     __syncthreads();                          // every wave is done with the images
     if (tn < ntiles) {
       store_tile<false>(Ks, kt, tid);
@@ -229,8 +202,6 @@ __device__ __forceinline__ void attn_long_bwd_body(const AttnLongParams& L) {
   const bf16_t* kp = P.k + kbase * P.ldk + h * AD;
   const bf16_t* vp = P.v + kbase * P.ldk + h * AD;
   const int ntiles = (P.Tk + AT - 1) / AT;
-  const float inv_keep = P.p > 0.f ? 1.0f / (1.0f - P.p) : 1.0f;
-  const uint32_t drop_thr = dropout_threshold(P.p);
   // One workgroup per CU (NQT = 2) has the registers to hold the next tile while it computes; two per CU (NQT = 1, 256
   // registers each) overlap each other's loads instead.
   constexpr bool PREFETCH = NQT == 2;
@@ -242,7 +213,7 @@ __device__ __forceinline__ void attn_long_bwd_body(const AttnLongParams& L) {
     //  hoisted out of THIS loop too and stays live across the prologue, which costs ~100 spilled registers)
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
-    const int lane = tid & 63, w = tid >> 6, odd = lane & 1;
+    const int lane = tid & 63, w = tid >> 6;
     const int g = ks * L.kv_share + sm;
     const int64_t qbase = (int64_t)g * P.Tq;
     const float* mrow = P.mask ? P.mask + (int64_t)g * P.Tk : nullptr;
@@ -302,50 +273,14 @@ __device__ __forceinline__ void attn_long_bwd_body(const AttnLongParams& L) {
       store_tile<false>(Vs, tv, tid);
     }
     __syncthreads();
-    if (!live_any) {
-      // no live key: softmax is uniform over ALL keys, and the forward's logsumexp is finfo.min itself (log Tk is absorbed),
-      // from which exp(s + mask - lse) would give 1 instead of 1 / Tk: drop the mask and the scores and take lse = log Tk
-      mrow = nullptr;
-      score_scale = 0.f;
-      const float ltk = __logf((float)P.Tk);
-#pragma unroll
-      for (int qt = 0; qt < NQT; ++qt)
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) lse4[qt][f][r] = ltk;
-    }
-    // operands that stay in registers, per query tile: the wave's 32 query rows of Q and dO (phase 1) and the transposed
-    // 16-column slices dO^T / Q^T [d = 16w ..][q] that dV / dK of every key chunk multiply (phase 2)
+    if (uniform_if_no_live_key(live_any, P.Tk, score_scale, lse4)) mrow = nullptr;
     bf16x8 qa[NQT][2][2], da[NQT][2][2], oT[NQT][4], qT[NQT][4];
-    f32x4 aQ[NQT][4][2];
+    f32x4 aQ[NQT][4][2] = {};
 #pragma unroll
-    for (int qt = 0; qt < NQT; ++qt) {
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          qa[qt][f][s] = frag_row64(Qs + qt * TILE_B, 32 * w + 16 * f, s, lane);
-          da[qt][f][s] = frag_row64(dOs + qt * TILE_B, 32 * w + 16 * f, s, lane);
-        }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        oT[qt][s] = frag_tr64(dOs + qt * TILE_B, 16 * w, s, lane);     // A[row = d][k = q]
-        qT[qt][s] = frag_tr64(Qs + qt * TILE_B, 16 * w, s, lane);
-      }
-#pragma unroll
-      for (int df = 0; df < 4; ++df)
-#pragma unroll
-        for (int f = 0; f < 2; ++f) aQ[qt][df][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    // dropout mask shared between neighbouring lanes (see attn_mfma.hip): one hash decides the element pair (q, key & ~1),
-    // (q, key | 1).  Needs an even Tk and a 32-bit pair index that does not wrap inside this (group, head).
-    const uint64_t drop_base = ((uint64_t)g * P.heads + h) * P.Tq * P.Tk;      // dropout counter of (query 0, key 0)
-    const uint64_t pair_base = drop_base >> 1;
-    const uint32_t pb_lo = (uint32_t)pair_base, pb_hi = (uint32_t)(pair_base >> 32);
-    const bool share_hash = P.p > 0.f && (P.Tk & 1) == 0 &&
-                            (uint64_t)pb_lo + (uint64_t)(2 * AT + 2) * (uint64_t)(P.Tk >> 1) + (uint64_t)P.Tk < 0xFFFFFFFFull;
-    const uint32_t hash_k0 = (uint32_t)P.seed ^ ((pb_hi << 7) | (pb_hi >> 25)), hash_s1 = (uint32_t)(P.seed >> 32);
+    for (int qt = 0; qt < NQT; ++qt)
+      bwd_resident_frags(Qs + qt * TILE_B, dOs + qt * TILE_B, w, lane, qa[qt], da[qt], oT[qt], qT[qt]);
+    // (pair offsets: a query row below 2 AT + 2 times Tk / 2, plus a key)
+    const BwdDropout D = bwd_dropout_state(P, g, h, lane, (uint64_t)(2 * AT + 2) * (uint64_t)(P.Tk >> 1) + (uint64_t)P.Tk + 1);
 
     // dead tiles before the first live one
 #pragma unroll 1
@@ -371,81 +306,15 @@ __device__ __forceinline__ void attn_long_bwd_body(const AttnLongParams& L) {
         for (int kf = 0; kf < 2; ++kf) { aV[kf] = f32x4{0.f, 0.f, 0.f, 0.f}; aK[kf] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
         for (int qt = 0; qt < NQT; ++qt) {
-          // ---- phase 1 (wave = 32 query rows): Pdrop^T and dS^T [key][q] of (chunk, query tile) into LDS
-          f32x4 sS[2][2], sP[2][2];
-#pragma unroll
-          for (int k4 = 0; k4 < 2; ++k4)
-#pragma unroll
-            for (int f = 0; f < 2; ++f) { sS[k4][f] = f32x4{0.f, 0.f, 0.f, 0.f}; sP[k4][f] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-          for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int k4 = 0; k4 < 2; ++k4) {
-              const bf16x8 kb = frag_row64(Ks, 32 * c + 16 * k4, s, lane);
-              const bf16x8 vb = frag_row64(Vs, 32 * c + 16 * k4, s, lane);
-#pragma unroll
-              for (int f = 0; f < 2; ++f) {
-                sS[k4][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[qt][f][s], kb, sS[k4][f], 0, 0, 0);   // D[q][key]
-                sP[k4][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da[qt][f][s], vb, sP[k4][f], 0, 0, 0);
-              }
-            }
+          float mk2[2];
 #pragma unroll
           for (int k4 = 0; k4 < 2; ++k4) {
-            const int kl = 16 * k4 + (lane & 15), key = 32 * cg + kl;
-            const float mk = (mrow && key < P.Tk) ? mrow[key] : 0.f;
-#pragma unroll
-            for (int f = 0; f < 2; ++f) {
-              f32x4 pdv, dsv;
-              float mult4[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-              if (share_hash) {
-                const unsigned q0 = qt * AT + 32 * w + 16 * f + 4 * (lane >> 4);
-                const uint32_t o0 = pb_lo + __umul24(q0 + 2 * odd, (unsigned)P.Tk >> 1) + ((unsigned)key >> 1);
-                const uint32_t hA = fcmf_hash32_rounds(o0 ^ hash_k0, hash_s1);
-                const uint32_t hB = fcmf_hash32_rounds((o0 + ((unsigned)P.Tk >> 1)) ^ hash_k0, hash_s1);
-                const uint32_t nA = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hA, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]: lane ^ 1
-                const uint32_t nB = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hB, 0xB1, 0xf, 0xf, true);
-                const uint32_t hr[4] = {odd ? nA : hA, odd ? nB : hB, odd ? hA : nA, odd ? hB : nB};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mult4[r] = ((hr[r] >> (16 * odd)) & 0xFFFFu) >= drop_thr ? inv_keep : 0.f;   // (key & 1 == lane & 1)
-              }
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const int q = qt * AT + 32 * w + 16 * f + 4 * (lane >> 4) + r;
-                float pr = 0.f, mult = mult4[r];
-                if (key < P.Tk && q < P.Tq) pr = __expf(sS[k4][f][r] * score_scale + mk - lse4[qt][f][r]);
-                if (P.p > 0.f && !share_hash) mult = dropout_mult(P.seed, drop_base + (__umul24((unsigned)q, (unsigned)P.Tk) + (unsigned)key), P.p, inv_keep);
-                pdv[r] = pr * mult;
-                dsv[r] = pr * (sP[k4][f][r] * mult - dl4[qt][f][r]);
-              }
-              const int ch = 4 * w + 2 * f + (lane >> 5);
-              const int o = off128(kl, ch) + ((lane >> 4) & 1) * 8;
-              store4(reinterpret_cast<bf16_t*>(PdT + o), pdv);
-              store4(reinterpret_cast<bf16_t*>(dST + o), dsv);
-            }
+            const int key = 32 * cg + 16 * k4 + (lane & 15);
+            mk2[k4] = (mrow && key < P.Tk) ? mrow[key] : 0.f;
           }
+          bwd_chunk_phase1(P, D, Ks, Vs, PdT, dST, c, 32 * cg, qt * AT, mk2, score_scale, qa[qt], da[qt], lse4[qt], dl4[qt], w, lane);
           __syncthreads();
-          // ---- phase 2: dQ^T[d][q] += K^T[d][keys of the chunk] dS^T[keys][q]  (wave = 32 queries)
-          {
-            bf16x8 tb[2];
-#pragma unroll
-            for (int f = 0; f < 2; ++f) tb[f] = frag_tr128(dST, 32 * w + 16 * f, 0, lane);    // B[k = key][col = q]
-#pragma unroll
-            for (int df = 0; df < 4; ++df) {
-              const bf16x8 ka2 = frag_tr64(Ks, 16 * df, c, lane);                              // A[row = d][k = key]
-#pragma unroll
-              for (int f = 0; f < 2; ++f) aQ[qt][df][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka2, tb[f], aQ[qt][df][f], 0, 0, 0);
-            }
-          }
-          // dV^T / dK^T [d = 16w..][key of the chunk] += dO^T / Q^T [d][q of this tile] x Pdrop / dS [q][key]
-#pragma unroll
-          for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int kf = 0; kf < 2; ++kf) {
-              const bf16x8 pb = frag_row128(PdT, 16 * kf, s, lane);   // B[k = q][col = key]
-              const bf16x8 sb = frag_row128(dST, 16 * kf, s, lane);
-              aV[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oT[qt][s], pb, aV[kf], 0, 0, 0);
-              aK[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qT[qt][s], sb, aK[kf], 0, 0, 0);
-            }
+          bwd_chunk_phase2(Ks, PdT, dST, c, oT[qt], qT[qt], aQ[qt], aV, aK, w, lane);
           __syncthreads();   // the chunk images are rewritten by the next query tile / chunk
         }
         finish_chunk(L, kbase, h, w, lane, cg, sm, true, aV, aK);
@@ -482,7 +351,6 @@ __global__ __launch_bounds__(256, 2) void attn_long_bwd_kernel(AttnLongParams L)
 __global__ __launch_bounds__(256, 1) void attn_long_bwd256_kernel(AttnLongParams L) { attn_long_bwd_body<2>(L); }
 
 // =========================================================================================
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 constexpr int LONG_MAX_TK = 1 << 20;      // (q * Tk of the dropout counter is a 24-bit multiply; far above any visual token count)
 
 extern "C" int fcmf_attn_mfma_long_fwd(const void* q, const void* k, const void* v, const float* mask, void* out, float* lse,
@@ -491,12 +359,7 @@ extern "C" int fcmf_attn_mfma_long_fwd(const void* q, const void* k, const void*
   if (!q || !k || !v || !out || G <= 0 || heads <= 0 || Tq <= 0 || Tk <= 0 || kv_share <= 0 || G % kv_share) return FCMF_ERR_ARG;
   if (Tq > 2 * AT || Tk > LONG_MAX_TK || ldq % 8 || ldk % 8 || ldo % 4 || !al16(q) || !al16(k) || !al16(v) || !al16(out))
     return FCMF_ERR_UNSUPPORTED;
-  AttnLongParams L{};
-  AttnMfmaParams& P = L.a;
-  P.q = (const bf16_t*)q; P.k = (const bf16_t*)k; P.v = (const bf16_t*)v; P.mask = mask; P.out = (bf16_t*)out; P.lse = lse;
-  P.G = G; P.heads = heads; P.Tq = Tq; P.Tk = Tk; P.ldq = ldq; P.ldk = ldk; P.ldo = ldo;
-  P.scale = scale; P.p = dropout_p; P.seed = seed;
-  L.kv_share = kv_share;
+  const AttnLongParams L{attn_mfma_params(q, k, v, mask, out, lse, G, heads, Tq, Tk, ldq, ldk, ldo, scale, dropout_p, seed), kv_share, nullptr};
   const dim3 grid(G * heads, (Tq + AT - 1) / AT);
   static bool attr = false;      // (this kernel's dynamic LDS is one constant: its limit is raised once)
   return fcmf_launch_flagged(&attr, attn_long_fwd_kernel, grid, dim3(256), 2 * TILE_B, reinterpret_cast<hipStream_t>(stream), L);
@@ -518,13 +381,9 @@ extern "C" int fcmf_attn_mfma_long_bwd(const void* q, const void* k, const void*
   if (Tq > 2 * AT || Tk > LONG_MAX_TK || ldq % 8 || ldk % 8 || ldo % 8 || !al16(q) || !al16(k) || !al16(v) || !al16(out) ||
       !al16(dout) || !al16(dq) || !al16(dk) || !al16(dv) || !al16(workspace))
     return FCMF_ERR_UNSUPPORTED;
-  AttnLongParams L{};
-  AttnMfmaParams& P = L.a;
-  P.q = (const bf16_t*)q; P.k = (const bf16_t*)k; P.v = (const bf16_t*)v; P.mask = mask; P.o = (const bf16_t*)out;
-  P.dout = (const bf16_t*)dout; P.lse = const_cast<float*>(lse); P.dq = (bf16_t*)dq; P.dk = (bf16_t*)dk; P.dv = (bf16_t*)dv;
-  P.G = G; P.heads = heads; P.Tq = Tq; P.Tk = Tk; P.ldq = ldq; P.ldk = ldk; P.ldo = ldo;
-  P.scale = scale; P.p = dropout_p; P.seed = seed;
-  L.kv_share = kv_share; L.ws = workspace;
+  const AttnLongParams L{attn_mfma_params(q, k, v, mask, nullptr, const_cast<float*>(lse), G, heads, Tq, Tk, ldq, ldk, ldo, scale, dropout_p,
+                                          seed, out, dout, dq, dk, dv),
+                         kv_share, workspace};
   const dim3 grid((G / kv_share) * heads);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (Tq > AT) {

@@ -43,31 +43,12 @@ __device__ __forceinline__ void attn_mfma_fwd_tile_compute(const AttnMfmaParams&
   // nvalid = index of the last key that is not hard-masked, + 1 (wave-uniform).
   int nvalid = P.Tk;
   if (mask_lds || mrow) {
-    int last = -1;
-#pragma unroll
-    for (int i = 0; i < 2 * NKT; ++i) {
-      const int key = 64 * i + lane;
-      const bool live = key < P.Tk && (mask_lds ? mask_lds[key] : mrow[key]) > -1e30f;
-      const unsigned long long b = __ballot(live);
-      if (b) last = 64 * i + 63 - __builtin_clzll(b);
-    }
+    const int last = last_live_key<2 * NKT>([&](int, int key) { return mask_lds ? mask_lds[key] : mrow[key]; }, P.Tk, lane);
     nvalid = last >= 0 ? last + 1 : P.Tk;    // no live key at all: nothing may be skipped (softmax over finfo.min scores is uniform over ALL keys)
   }
   // S^T[key][q]: NKF key fragments x 2 query fragments
   f32x4 sc[NKF][2];
-#pragma unroll
-  for (int kf = 0; kf < NKF; ++kf)
-#pragma unroll
-    for (int f = 0; f < 2; ++f) sc[kf][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int kf = 0; kf < NKF; ++kf) {
-      if (16 * kf >= nvalid) continue;
-      const bf16x8 ka = frag_row64(Ks, 16 * kf, s, lane);
-#pragma unroll
-      for (int f = 0; f < 2; ++f) sc[kf][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[f][s], sc[kf][f], 0, 0, 0);
-    }
+  fwd_score_frags<NKF>([&](int x0, int s) { return frag_row64(Ks, x0, s, lane); }, qf, nvalid, sc);
   // lane holds, for query q0+16f+(lane&15), keys 16kf + 4(lane>>4) + r
   const float inv_keep = P.p > 0.f ? 1.0f / (1.0f - P.p) : 1.0f;
 #pragma unroll
@@ -120,22 +101,7 @@ __device__ __forceinline__ void attn_mfma_fwd_tile_compute(const AttnMfmaParams&
   for (int df = 0; df < 4; ++df)
 #pragma unroll
     for (int f = 0; f < 2; ++f) oc[df][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 4 * NKT; ++s) {
-    if (32 * s >= nvalid) continue;
-    // P^T operand of k-step s straight from the accumulators of key fragments 2s and 2s+1
-    bf16x8 pb[2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { pb[f][r] = (bf16_t)sc[2 * s][f][r]; pb[f][4 + r] = (bf16_t)sc[2 * s + 1][f][r]; }
-#pragma unroll
-    for (int df = 0; df < 4; ++df) {
-      const bf16x8 va = frag_tr64p(Vs, 16 * df, s, lane);
-#pragma unroll
-      for (int f = 0; f < 2; ++f) oc[df][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pb[f], oc[df][f], 0, 0, 0);
-    }
-  }
+  fwd_pv_step<NKF>(Vs, sc, nvalid, lane, oc);
 }
 template <bool LSE_LATE>
 __device__ __forceinline__ void attn_mfma_fwd_tile_store(const AttnMfmaParams& P, int g, int h, int q0, int lane, const f32x4 (&oc)[4][2],
@@ -173,7 +139,7 @@ __device__ __forceinline__ void attn_mfma_fwd_body(const AttnMfmaParams& P) {
   const TileRegs kt = load_tile(kbase_p, P.ldk, P.Tk, tid);
   const TileRegs vt = load_tile(vbase_p, P.ldk, P.Tk, tid);
   bf16x8 qf[2][2];
-  load_q_frags(P, g, h, q0, lane, qf);
+  load_q_frags(P.q, P.ldq, P.Tq, g, h, q0, lane, qf);
   store_tile<false>(Ks, kt, tid);      // (all of K, V and Q were requested before the first LDS write)
   store_tile<true>(Vs, vt, tid);
   if constexpr (NKT == 2) {
@@ -358,33 +324,14 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
     }
   }
 
-  const float inv_keep = P.p > 0.f ? 1.0f / (1.0f - P.p) : 1.0f;
-  const uint64_t drop_base = ((uint64_t)g * P.heads + h) * P.Tq * P.Tk;      // dropout counter of (query 0, key 0)
   bool masked = P.mask != nullptr;
   float score_scale = P.scale;            // (0 for a sequence whose every key is hard-masked: see below)
-  // operands that stay in registers, per query tile: the wave's 32 query rows of Q and dO (phase 1) and the transposed
-  // 16-column slices dO^T / Q^T [d = 16w ..][q] that dV / dK of every key chunk multiply (phase 2)
+  // operands that stay in registers, per query tile
   bf16x8 qa[NQT][2][2], da[NQT][2][2], oT[NQT][4], qT[NQT][4];
-  f32x4 aQ[NQT][4][2];
+  f32x4 aQ[NQT][4][2] = {};
 #pragma unroll
-  for (int qt = 0; qt < NQT; ++qt) {
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        qa[qt][f][s] = frag_row64(Qs + qt * TILE_B, 32 * w + 16 * f, s, lane);
-        da[qt][f][s] = frag_row64(dOs + qt * TILE_B, 32 * w + 16 * f, s, lane);
-      }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      oT[qt][s] = frag_tr64(dOs + qt * TILE_B, 16 * w, s, lane);     // A[row = d][k = q]
-      qT[qt][s] = frag_tr64(Qs + qt * TILE_B, 16 * w, s, lane);
-    }
-#pragma unroll
-    for (int df = 0; df < 4; ++df)
-#pragma unroll
-      for (int f = 0; f < 2; ++f) aQ[qt][df][f] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
+  for (int qt = 0; qt < NQT; ++qt)
+    bwd_resident_frags(Qs + qt * TILE_B, dOs + qt * TILE_B, w, lane, qa[qt], da[qt], oT[qt], qT[qt]);
 
   // ---- key chunks of 32; per chunk the query tiles take turns: phase 1 (wave = 32 query rows) builds Pdrop^T and dS^T
   // [key][q] of (chunk, query tile) in LDS, phase 2 adds them to dQ of that tile (wave = 32 queries) and to dV / dK of
@@ -395,44 +342,15 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
   // are skipped, with bit-identical results.  nvalid = index of the last key that is not hard-masked, + 1 (wave-uniform).
   int nvalid = P.Tk;
   if (masked) {
-    int last = -1;
+    const int last = last_live_key<2 * NKT>([&](int i, int) { return mreg[i]; }, P.Tk, lane);
 #pragma unroll
-    for (int i = 0; i < 2 * NKT; ++i) {
-      const int key = 64 * i + lane;
-      const bool live = key < P.Tk && mreg[i] > -1e30f;
-      if (key >= P.Tk) mreg[i] = 0.f;
-      const unsigned long long b = __ballot(live);
-      if (b) last = 64 * i + 63 - __builtin_clzll(b);
-    }
+    for (int i = 0; i < 2 * NKT; ++i)
+      if (64 * i + lane >= P.Tk) mreg[i] = 0.f;
     nvalid = last >= 0 ? last + 1 : P.Tk;    // no live key at all: nothing may be skipped (softmax over finfo.min scores is uniform over ALL keys)
-    // ... and the forward's logsumexp of such a sequence is finfo.min itself (log Tk is absorbed), from which exp(s + mask - lse)
-    // would recompute probabilities of 1 instead of 1 / Tk.  Wave-uniform substitution, no per-element work: drop the mask and
-    // the scores and take lse = log Tk.
-    if (last < 0) {
-      masked = false;
-      score_scale = 0.f;
-      const float ltk = __logf((float)P.Tk);
-#pragma unroll
-      for (int qt = 0; qt < NQT; ++qt)
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) lse4[qt][f][r] = ltk;
-    }
+    if (uniform_if_no_live_key(last >= 0, P.Tk, score_scale, lse4)) masked = false;
   }
   const int nchunks = (nvalid + 31) >> 5;
-  // Dropout mask, shared between neighbouring lanes.  One hash decides the element PAIR (q, key & ~1), (q, key | 1); here the two
-  // elements sit in lanes l and l ^ 1 (key = .. + (lane & 15)), each holding rows q0 .. q0+3 -- computed per element, both lanes
-  // would evaluate the same four hashes (two 32-bit multiplies each, quarter rate: two thirds of this kernel's vector
-  // instructions).  Even lanes hash rows q0, q0+1, odd lanes q0+2, q0+3, and a quad-permute DPP move swaps them: two hashes per
-  // four elements.  Needs an even Tk (then every row starts on a pair boundary); the high word of the 64-bit pair index is
-  // wave-uniform unless the low word wraps inside this (sequence, head) -- checked, else the per-element form below.
-  const uint64_t pair_base = drop_base >> 1;
-  const uint32_t pb_lo = (uint32_t)pair_base, pb_hi = (uint32_t)(pair_base >> 32);
-  const bool share_hash = P.p > 0.f && (P.Tk & 1) == 0 && pb_lo <= 0xFFFF0000u;      // (pair offsets stay below 2^15: Tq, Tk <= 256)
-  const uint32_t hash_k0 = (uint32_t)P.seed ^ ((pb_hi << 7) | (pb_hi >> 25)), hash_s1 = (uint32_t)(P.seed >> 32);
-  const uint32_t drop_thr = dropout_threshold(P.p);
-  const int odd = lane & 1;
+  const BwdDropout D = bwd_dropout_state(P, g, h, lane, 0xFFFFu);      // (pair offsets stay below 2^15: Tq, Tk <= 256)
   f32x4 cV = f32x4{0.f, 0.f, 0.f, 0.f}, cK = f32x4{0.f, 0.f, 0.f, 0.f};   // column sums of dV / dK over the keys (this lane's keys)
   // dk / dv leave in whole 128-byte rows too: wave w owns 16 of a row's 64 columns, so the chunk's [32 keys][64 d] blocks
   // are put together in LDS -- in the K / V rows of the chunk itself, dead once the chunk is done (16-byte piece XOR
@@ -462,83 +380,10 @@ __device__ __forceinline__ void attn_mfma_bwd_body(const AttnMfmaParams& P) {
     }
 #pragma unroll
     for (int qt = 0; qt < NQT; ++qt) {
-      f32x4 sS[2][2], sP[2][2];
-#pragma unroll
-      for (int k4 = 0; k4 < 2; ++k4)
-#pragma unroll
-        for (int f = 0; f < 2; ++f) { sS[k4][f] = f32x4{0.f, 0.f, 0.f, 0.f}; sP[k4][f] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int k4 = 0; k4 < 2; ++k4) {
-          const bf16x8 kb = frag_row64(Ks, 32 * c + 16 * k4, s, lane);
-          const bf16x8 vb = frag_row64(Vs, 32 * c + 16 * k4, s, lane);
-#pragma unroll
-          for (int f = 0; f < 2; ++f) {
-            sS[k4][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[qt][f][s], kb, sS[k4][f], 0, 0, 0);   // D[q][key]
-            sP[k4][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da[qt][f][s], vb, sP[k4][f], 0, 0, 0);
-          }
-        }
-#pragma unroll
-      for (int k4 = 0; k4 < 2; ++k4) {
-        const int kl = 16 * k4 + (lane & 15), key = 32 * c + kl;
-        const float mk = mk2[k4];
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-          f32x4 pdv, dsv;
-          float mult4[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-          if (share_hash) {
-            const unsigned q0 = qt * AT + 32 * w + 16 * f + 4 * (lane >> 4);
-            const uint32_t o0 = pb_lo + __umul24(q0 + 2 * odd, (unsigned)P.Tk >> 1) + ((unsigned)key >> 1);
-            const uint32_t hA = fcmf_hash32_rounds(o0 ^ hash_k0, hash_s1);
-            const uint32_t hB = fcmf_hash32_rounds((o0 + ((unsigned)P.Tk >> 1)) ^ hash_k0, hash_s1);
-            const uint32_t nA = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hA, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]: lane ^ 1
-            const uint32_t nB = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hB, 0xB1, 0xf, 0xf, true);
-            const uint32_t hr[4] = {odd ? nA : hA, odd ? nB : hB, odd ? hA : nA, odd ? hB : nB};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mult4[r] = ((hr[r] >> (16 * odd)) & 0xFFFFu) >= drop_thr ? inv_keep : 0.f;   // (key & 1 == lane & 1)
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int q = qt * AT + 32 * w + 16 * f + 4 * (lane >> 4) + r;
-            float pr = 0.f, mult = mult4[r];
-            if (key < P.Tk && q < P.Tq) pr = __expf(sS[k4][f][r] * score_scale + mk - lse4[qt][f][r]);
-            // element index ((g heads + h) Tq + q) Tk + key = a wave-uniform 64-bit base + a small 24-bit product: no
-            // 64-bit vector multiply per element (integer multiplies are quarter rate; the kernel is VALU-bound)
-            if (P.p > 0.f && !share_hash) mult = dropout_mult(P.seed, drop_base + (__umul24((unsigned)q, (unsigned)P.Tk) + (unsigned)key), P.p, inv_keep);
-            pdv[r] = pr * mult;
-            dsv[r] = pr * (sP[k4][f][r] * mult - dl4[qt][f][r]);
-          }
-          const int ch = 4 * w + 2 * f + (lane >> 5);
-          const int o = off128(kl, ch) + ((lane >> 4) & 1) * 8;
-          store4(reinterpret_cast<bf16_t*>(PdT + o), pdv);
-          store4(reinterpret_cast<bf16_t*>(dST + o), dsv);
-        }
-      }
+      bwd_chunk_phase1(P, D, Ks, Vs, PdT, dST, c, 32 * c, qt * AT, mk2, score_scale, qa[qt], da[qt], lse4[qt], dl4[qt], w, lane);
       __syncthreads();
       if (qt == 0 && c > 0) flush_dkv(c - 1);      // (staged by all four waves before the barrier just passed)
-      // dQ^T[d][q] += K^T[d][keys of the chunk] dS^T[keys][q]
-      {
-        bf16x8 tb[2];
-#pragma unroll
-        for (int f = 0; f < 2; ++f) tb[f] = frag_tr128(dST, 32 * w + 16 * f, 0, lane);    // B[k = key][col = q]
-#pragma unroll
-        for (int df = 0; df < 4; ++df) {
-          const bf16x8 ka2 = frag_tr64(Ks, 16 * df, c, lane);                              // A[row = d][k = key]
-#pragma unroll
-          for (int f = 0; f < 2; ++f) aQ[qt][df][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka2, tb[f], aQ[qt][df][f], 0, 0, 0);
-        }
-      }
-      // dV^T / dK^T [d = 16w..][key of the chunk] += dO^T / Q^T [d][q of this tile] x Pdrop / dS [q][key]
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int kf = 0; kf < 2; ++kf) {
-          const bf16x8 pb = frag_row128(PdT, 16 * kf, s, lane);   // B[k = q][col = key]
-          const bf16x8 sb = frag_row128(dST, 16 * kf, s, lane);
-          aV[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(oT[qt][s], pb, aV[kf], 0, 0, 0);
-          aK[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qT[qt][s], sb, aK[kf], 0, 0, 0);
-        }
+      bwd_chunk_phase2(Ks, PdT, dST, c, oT[qt], qT[qt], aQ[qt], aV, aK, w, lane);
       __syncthreads();   // the chunk images are rewritten by the next query tile / chunk
     }
     cV += aV[0] + aV[1];        // (keys past Tk carry zero probabilities: no mask needed)
@@ -625,17 +470,12 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_bwd_kernel(AttnMfmaParams P)
 __global__ __launch_bounds__(256, 1) void attn_mfma_bwd256_kernel(AttnMfmaParams P) { attn_mfma_bwd_body<2, 2>(P); }
 
 // =========================================================================================
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 extern "C" int fcmf_attn_mfma_fwd(const void* q, const void* k, const void* v, const float* mask, void* out, float* lse,
                                   int G, int heads, int Tq, int Tk, int64_t ldq, int64_t ldk, int64_t ldo, float scale,
                                   float dropout_p, uint64_t seed, void* stream) {
   if (!q || !k || !v || !out || G <= 0 || heads <= 0 || Tq <= 0 || Tk <= 0) return FCMF_ERR_ARG;
   if (Tk > 2 * AT || ldq % 8 || ldk % 8 || ldo % 4 || !al16(q) || !al16(k) || !al16(v) || !al16(out)) return FCMF_ERR_UNSUPPORTED;
-  AttnMfmaParams P{};
-  P.q = (const bf16_t*)q; P.k = (const bf16_t*)k; P.v = (const bf16_t*)v; P.mask = mask; P.out = (bf16_t*)out; P.lse = lse;
-  P.G = G; P.heads = heads; P.Tq = Tq; P.Tk = Tk; P.ldq = ldq; P.ldk = ldk; P.ldo = ldo;
-  P.scale = scale; P.p = dropout_p; P.seed = seed;
+  const AttnMfmaParams P = attn_mfma_params(q, k, v, mask, out, lse, G, heads, Tq, Tk, ldq, ldk, ldo, scale, dropout_p, seed);
   const dim3 grid(G * heads, (Tq + AT - 1) / AT);
   if (Tk > AT) {
     const int smem = 4 * TILE_B;
@@ -662,11 +502,8 @@ extern "C" int fcmf_attn_mfma_bwd(const void* q, const void* k, const void* v, c
   if (Tk > 2 * AT || Tq > 2 * AT || ldq % 8 || ldk % 8 || ldo % 8 || !al16(q) || !al16(k) || !al16(v) || !al16(out) || !al16(dout) ||
       !al16(dq) || !al16(dk) || !al16(dv))
     return FCMF_ERR_UNSUPPORTED;
-  AttnMfmaParams P{};
-  P.q = (const bf16_t*)q; P.k = (const bf16_t*)k; P.v = (const bf16_t*)v; P.mask = mask; P.o = (const bf16_t*)out;
-  P.dout = (const bf16_t*)dout; P.lse = const_cast<float*>(lse); P.dq = (bf16_t*)dq; P.dk = (bf16_t*)dk; P.dv = (bf16_t*)dv;
-  P.G = G; P.heads = heads; P.Tq = Tq; P.Tk = Tk; P.ldq = ldq; P.ldk = ldk; P.ldo = ldo;
-  P.scale = scale; P.p = dropout_p; P.seed = seed; P.colsum = colsum;
+  const AttnMfmaParams P = attn_mfma_params(q, k, v, mask, nullptr, const_cast<float*>(lse), G, heads, Tq, Tk, ldq, ldk, ldo, scale,
+                                            dropout_p, seed, out, dout, dq, dk, dv, colsum);
   if (Tk > AT || Tq > AT) {
     const int smem = 9 * TILE_B;   // 2 x (Q, dO) + 2 x (K, V) tiles + the two 8 KiB chunk images = 144 KiB: one workgroup per CU
     static bool attr2 = false;      // (this kernel's dynamic LDS is one constant: its limit is raised once)

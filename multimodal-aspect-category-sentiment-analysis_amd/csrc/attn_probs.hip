@@ -13,7 +13,7 @@
 //                           row maximum / sum are in-lane plus two shuffles and every lane stores 16 contiguous bytes along the key axis.
 // Output element (g, slot h, r, t) at probs + g*p_sg + h*p_sh + r*T + t: [G, heads, R, T] (p_sg = heads*R*T, p_sh = R*T) or the decoder's
 // slot-major [heads*G, R, T] (p_sg = R*T, p_sh = G*R*T: index h*G + g, the order of the reference's torch.split(output, mb_size, dim=0)).
-#include "common.h"
+#include "attn_tiles.h"
 
 constexpr int AP_MAXT = 512;   // T1 + T2 (limits of fcmf_attn_small_bwd)
 constexpr int AP_MAXD = 128;
@@ -115,7 +115,6 @@ extern "C" int fcmf_attn_probs(const fcmf_attn_desc* desc, float* probs, int64_t
   AttnProbsK P{};
   P.a = *a; P.probs = probs; P.p_sg = p_sg; P.p_sh = p_sh;
   const int V = a->dtype == FCMF_F32 ? 4 : 8;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   P.vec1 = a->T1 > 0 && a->d % V == 0 && a->k1_sg % V == 0 && a->k1_st % V == 0 && al16(a->k1);
   P.vec2 = a->T2 > 0 && a->d % V == 0 && a->k2_sg % V == 0 && a->k2_sr % V == 0 && a->k2_st % V == 0 && al16(a->k2);
   const dim3 grid(a->G * a->heads, (a->R + 3) / 4);
@@ -161,17 +160,8 @@ __global__ __launch_bounds__(256, 2) void attn_probs_mfma_kernel(AttnProbsMfmaK 
     *reinterpret_cast<uint4*>(Ks + probs_koff(r, c8)) = v;
   }
   if (tid < NKT * PT) Ms[tid] = (P.mask && tid < P.Tk) ? P.mask[(int64_t)g * P.Tk + tid] : 0.f;
-  // Q fragments of the wave's 32 query rows straight from global memory in operand layout
   bf16x8 qf[2][2];
-#pragma unroll
-  for (int f = 0; f < 2; ++f)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int row = q0 + 16 * f + (lane & 15);
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (row < P.Tq) v = *reinterpret_cast<const uint4*>(P.q + ((int64_t)g * P.Tq + row) * P.ldq + h * PD + 32 * s + 8 * (lane >> 4));
-      qf[f][s] = *reinterpret_cast<bf16x8*>(&v);
-    }
+  load_q_frags(P.q, P.ldq, P.Tq, g, h, q0, lane, qf);
   __syncthreads();
   if (q0 >= P.Tq) return;      // (wave-uniform; after the only barrier)
   const int nkf = (P.Tk + 15) >> 4;      // key fragments that hold a key
@@ -242,7 +232,6 @@ __global__ __launch_bounds__(256, 2) void attn_probs_mfma_kernel(AttnProbsMfmaK 
 extern "C" int fcmf_attn_mfma_probs(const void* q, const void* k, const float* mask, float* probs, int G, int heads, int Tq, int Tk,
                                     int64_t ldq, int64_t ldk, int64_t p_sg, int64_t p_sh, float scale, void* stream) {
   if (!q || !k || !probs || G <= 0 || heads <= 0 || Tq <= 0 || Tk <= 0) return FCMF_ERR_ARG;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (Tk > 2 * PT || Tq > 2 * PT || ldq % 8 || ldk % 8 || !al16(q) || !al16(k)) return FCMF_ERR_UNSUPPORTED;
   AttnProbsMfmaK P{};
   P.q = (const bf16_t*)q; P.k = (const bf16_t*)k; P.mask = mask; P.probs = probs;

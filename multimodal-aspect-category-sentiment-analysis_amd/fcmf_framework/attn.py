@@ -1,7 +1,9 @@
 """The one way from attention operands to a launch: a descriptor (fcmf_attn_desc, include/fcmf_hip.h), the MFMA / VALU choice
 made from the descriptor's own fields, and one function per kernel pair.  ops, fused and iaog_modeling normalise their
 operands, build a descriptor here and call these; nothing else in the package launches an fcmf_attn_small / _mfma / _probs
-kernel or fills an AttnDesc."""
+kernel or fills an AttnDesc.  The long pair (long_forward / long_backward: fcmf_attn_mfma_long_fwd / _bwd, any number of keys,
+one key/value set per `kv_share` consecutive query groups) takes dense tensors instead of a descriptor: its key sets are not
+the descriptor's per-group keys."""
 import torch
 
 from . import _hip as H
@@ -79,6 +81,24 @@ def mfma_backward(a, out, dout, lse, dq, dk, dv, colsum_part=None):
     H.check(H.lib().fcmf_attn_mfma_bwd(a.q, a.k1, a.v1, a.mask, H.ptr(out), H.ptr(dout), H.ptr(lse), dq, dk, dv, a.G, a.heads,
                                        a.R, a.T1, *_ld(a), a.o_sr, a.scale, a.dropout_p, a.seed, H.ptr(colsum_part), H.stream()),
             "fcmf_attn_mfma_bwd")
+
+
+def long_forward(q, k, v, mask, out, lse, heads, kv_share, scale, p, seed):
+    """q / out [G,Tq,heads*64], k / v [G/kv_share,Tk,heads*64], all dense bf16; mask [G,Tk] float32 or None; lse [G,heads,Tq]"""
+    G, Tq, HD = q.shape
+    H.check(H.lib().fcmf_attn_mfma_long_fwd(H.ptr(q), H.ptr(k), H.ptr(v), H.ptr(mask), H.ptr(out), H.ptr(lse), G, heads, Tq,
+                                            k.shape[1], kv_share, HD, HD, HD, scale, p, seed, H.stream()), "fcmf_attn_mfma_long_fwd")
+
+
+def long_backward(q, k, v, mask, out, dout, lse, dq, dk, dv, heads, kv_share, scale, p, seed):
+    """dq / dk / dv: dense tensors like q / k / v"""
+    G, Tq, HD = q.shape
+    # running float32 sums of dk | dv over the sharing groups (written before they are read: no fill)
+    ws = torch.empty(2 * k.numel(), dtype=torch.float32, device=q.device) if kv_share > 1 else None
+    H.check(H.lib().fcmf_attn_mfma_long_bwd(H.ptr(q), H.ptr(k), H.ptr(v), H.ptr(mask), H.ptr(out), H.ptr(dout), H.ptr(lse),
+                                            H.ptr(dq), H.ptr(dk), H.ptr(dv), G, heads, Tq, k.shape[1], kv_share, HD, HD, HD, scale,
+                                            p, seed, H.ptr(ws), 0 if ws is None else ws.numel() * 4, H.stream()),
+            "fcmf_attn_mfma_long_bwd")
 
 
 def sum_leading(x):

@@ -1143,11 +1143,9 @@ class SharedKVAttentionFn(torch.autograd.Function):
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         mask = None if mask is None else mask.contiguous().float()
         G, Tq, HD = q.shape
-        Tk = k.shape[1]
         out = torch.empty_like(q)
         lse = torch.empty((G, heads, Tq), dtype=torch.float32, device=q.device)
-        H.check(H.lib().fcmf_attn_mfma_long_fwd(H.ptr(q), H.ptr(k), H.ptr(v), H.ptr(mask), H.ptr(out), H.ptr(lse), G, heads, Tq, Tk,
-                                                kv_share, HD, HD, HD, scale, p, seed, H.stream()), "fcmf_attn_mfma_long_fwd")
+        attn.long_forward(q, k, v, mask, out, lse, heads, kv_share, scale, p, seed)
         ctx.save_for_backward(q, k, v, mask, out, lse)
         ctx.cfg = (heads, kv_share, scale, p, seed)
         return out
@@ -1156,16 +1154,9 @@ class SharedKVAttentionFn(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, mask, out, lse = ctx.saved_tensors
         heads, kv_share, scale, p, seed = ctx.cfg
-        G, Tq, HD = q.shape
-        Tk = k.shape[1]
         dout = dout.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        # running float32 sums of dk | dv over the sharing groups (written before they are read: no fill)
-        ws = torch.empty(2 * k.numel(), dtype=torch.float32, device=q.device) if kv_share > 1 else None
-        H.check(H.lib().fcmf_attn_mfma_long_bwd(H.ptr(q), H.ptr(k), H.ptr(v), H.ptr(mask), H.ptr(out), H.ptr(dout), H.ptr(lse),
-                                                H.ptr(dq), H.ptr(dk), H.ptr(dv), G, heads, Tq, Tk, kv_share, HD, HD, HD, scale, p,
-                                                seed, H.ptr(ws), 0 if ws is None else ws.numel() * 4, H.stream()),
-                "fcmf_attn_mfma_long_bwd")
+        attn.long_backward(q, k, v, mask, out, dout, lse, dq, dk, dv, heads, kv_share, scale, p, seed)
         return dq, dk, dv, None, None, None, None, None, None
 
 
