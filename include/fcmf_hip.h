@@ -198,6 +198,18 @@ int fcmf_attn_mfma_long_bwd(const void* q, const void* k, const void* v, const f
                             void* dq, void* dk, void* dv, int G, int heads, int Tq, int Tk, int kv_share,
                             int64_t ldq, int64_t ldk, int64_t ldo, float scale,
                             float dropout_p, uint64_t seed, float* workspace, int64_t workspace_bytes, void* stream);
+/* The probabilities of that attention as float32, BEFORE dropout: softmax(scale QK^T + mask) with exactly the score and
+ * mask semantics above (a finfo.min key gets probability exactly 0; a group without a live key is uniform over all Tk keys).
+ * Same operands and limits as fcmf_attn_mfma_long_fwd without V (bf16, head dim 64, Tq <= 256, 1 <= Tk <= 2^20, ldq / ldk
+ * multiples of 8, 16-byte aligned q / k); no logsumexp of a forward is needed, the kernel finds each row's maximum and sum.
+ *   head_mean == 0: probs [G, heads, Tq, Tk];
+ *   head_mean != 0: probs [G, Tq, Tk] = (1/heads) * sum_h P_h (torch's average_attn_weights), heads <= 32.  The heads are
+ *                   summed in float32 in ascending order inside the kernel: no per-head tensor exists in memory, there are no
+ *                   atomics, every element is stored exactly once -- two launches on the same operands agree bit for bit.
+ * probs is dense and need not be initialised: every element is written, those of skipped (all hard-masked) key tiles too. */
+int fcmf_attn_mfma_long_probs(const void* q, const void* k, const float* mask, float* probs, int G, int heads,
+                              int Tq, int Tk, int kv_share, int64_t ldq, int64_t ldk, float scale, int head_mean,
+                              void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Attention probabilities on request: P = softmax(score) as float32, BEFORE dropout, recomputed from Q and K with exactly the

@@ -351,7 +351,209 @@ __global__ __launch_bounds__(256, 2) void attn_long_bwd_kernel(AttnLongParams L)
 __global__ __launch_bounds__(256, 1) void attn_long_bwd256_kernel(AttnLongParams L) { attn_long_bwd_body<2>(L); }
 
 // =========================================================================================
-constexpr int LONG_MAX_TK = 1 << 20;      // (q * Tk of the dropout counter is a 24-bit multiply; far above any visual token count)
+// Probabilities of the long kernels: P = softmax(scale Q K^T + mask) as float32, before dropout, with the score and mask
+// semantics of attn_long_fwd_kernel, per head [G, heads, Tq, Tk] or as the head mean [G, Tq, Tk].  No V, no logsumexp of a
+// forward: a first pass over the keys leaves each row's maximum and 1 / sum (the running pair of the forward) in LDS, a second
+// pass recomputes the scores, normalises and stores.  One workgroup owns a 128-query tile of `nh` heads of a group: one head
+// (per-head mode, grid.x = G * heads) or all of them (head mean, grid.x = G).  In the second pass the heads are the INNER
+// loop: the float32 sum over the heads, in ascending order, stays in the accumulator registers of the lane that stores the
+// element -- once, with no per-head tensor in memory and no atomics, so two launches agree bit for bit.  Q K^T is computed
+// twice; the kernel is bound by its writes.  Tiles whose keys are all hard-masked are not multiplied (unless the group has no
+// live key at all), but their zeros are stored: the output is not initialised by the caller.
+// Dynamic LDS: the K tile, the tile's 128 additive mask values, (maximum, 1 / sum) per (head, query of the tile).
+struct AttnLongProbsParams {
+  const bf16_t *q, *k;
+  const float* mask;
+  float* probs;
+  int G, heads, Tq, Tk, kv_share, head_mean;
+  int64_t ldq, ldk;
+  float scale;
+  int vec;      // every 4-key group of a row is 16-byte aligned: one 16-byte store per accumulator
+};
+
+// four consecutive keys of one output row (prow = the row's element of key `key`); keys at or past Tk are not written
+__device__ __forceinline__ void store_probs4(float* prow, f32x4 v, int key, int Tk, bool vec) {
+  if (vec) {      // Tk % 4 == 0: a group that starts inside the row ends inside it
+    if (key < Tk) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(prow));
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (key + r < Tk) prow[r] = v[r];
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void attn_long_probs_kernel(AttnLongProbsParams P) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Ks = smem;
+  float* Ms = reinterpret_cast<float*>(smem + TILE_B);                    // [128] additive mask of the tile's keys, -inf past Tk
+  float2* St = reinterpret_cast<float2*>(smem + TILE_B + AT * 4);         // [nh][128] (maximum, 1 / sum)
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nh = P.head_mean ? P.heads : 1;
+  const int g = P.head_mean ? blockIdx.x : blockIdx.x / P.heads;
+  const int h0 = P.head_mean ? 0 : blockIdx.x % P.heads;
+  const int q0 = blockIdx.y * AT + w * 32;
+  const bool active = q0 < P.Tq;      // (wave-uniform: an idle wave only stages tiles and keeps the barriers matched)
+  const bf16_t* kp = P.k + (int64_t)(g / P.kv_share) * P.Tk * P.ldk;
+  const float* mrow = P.mask ? P.mask + (int64_t)g * P.Tk : nullptr;
+  float* out = P.probs + (int64_t)(P.head_mean ? g : g * P.heads + h0) * P.Tq * P.Tk;
+  const int ntiles = (P.Tk + AT - 1) / AT;
+  const bool skip_dead = mrow && any_live_key(mrow, P.Tk, lane);
+  auto next_live = [&](int t) {      // first tile >= t with a live key (the same in every wave: barriers stay matched)
+    while (skip_dead && t < ntiles && !any_live_in(mrow, P.Tk, t * AT, AT, lane)) ++t;
+    return t;
+  };
+  const int t_first = next_live(0);      // (< ntiles: tiles are skipped only when some key is live)
+  // what one (head, tile) step reads, loaded a step ahead: the K tile, the tile's mask values, the head's Q fragments
+  struct Step { TileRegs kt; float mk; bf16x8 qf[2][2]; };
+  auto load_step = [&](int h, int t, Step& s) {
+    s.kt = load_tile(kp + (int64_t)t * AT * P.ldk + (h0 + h) * AD, P.ldk, P.Tk - t * AT, tid);
+    const int key = t * AT + tid;
+    s.mk = (tid < AT && key < P.Tk) ? (mrow ? mrow[key] : 0.f) : -INFINITY;
+    load_q_frags(P.q, P.ldq, P.Tq, g, h0 + h, q0, lane, s.qf);
+  };
+  auto stage_step = [&](const Step& s) {
+    store_tile<false>(Ks, s.kt, tid);
+    if (tid < AT) Ms[tid] = s.mk;
+  };
+  // scores of the staged tile: lane holds, for query q0 + 16 f + (lane & 15), keys k0 + 16 kf + 4 (lane >> 4) + r
+  auto scores = [&](const bf16x8 (&qf)[2][2], int rows, f32x4 (&sc)[8][2]) {
+    fwd_score_frags<8>([&](int x0, int s) { return frag_row64(Ks, x0, s, lane); }, qf, rows, sc);
+#pragma unroll
+    for (int kf = 0; kf < 8; ++kf) {
+      if (16 * kf >= rows) continue;
+      const f32x4 mk = *reinterpret_cast<const f32x4*>(Ms + 16 * kf + 4 * (lane >> 4));
+#pragma unroll
+      for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sc[kf][f][r] = sc[kf][f][r] * P.scale + mk[r];      // (-inf past Tk)
+    }
+  };
+
+  // ---- zeros of the skipped tiles
+  if (skip_dead && active) {
+    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < ntiles; ++t) {
+      if (any_live_in(mrow, P.Tk, t * AT, AT, lane)) continue;
+      const int k0 = t * AT, rows = min(AT, P.Tk - k0);
+#pragma unroll
+      for (int f = 0; f < 2; ++f) {
+        const int q = q0 + 16 * f + (lane & 15);
+        if (q >= P.Tq) continue;
+#pragma unroll
+        for (int kf = 0; kf < 8; ++kf) {
+          const int key = k0 + 16 * kf + 4 * (lane >> 4);
+          if (16 * kf < rows) store_probs4(out + (int64_t)q * P.Tk + key, zero, key, P.Tk, P.vec);
+        }
+      }
+    }
+  }
+
+  Step cur, nxt;
+  // ---- pass 1: heads outside, live tiles inside: the running maximum and sum of every (head, row)
+  {
+    float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+    int h = 0, t = t_first;
+    load_step(h, t, cur);
+#pragma unroll 1
+    while (h < nh) {
+      stage_step(cur);
+      __syncthreads();
+      int hn = h, tn = next_live(t + 1);
+      if (tn >= ntiles) { hn = h + 1; tn = t_first; }
+      if (hn < nh) load_step(hn, tn, nxt);      // in flight under this step's arithmetic
+      if (active) {
+        const int rows = min(AT, P.Tk - t * AT);
+        f32x4 sc[8][2];
+        scores(cur.qf, rows, sc);
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          float m = -INFINITY;
+#pragma unroll
+          for (int kf = 0; kf < 8; ++kf) {
+            if (16 * kf >= rows) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) m = fmaxf(m, sc[kf][f][r]);
+          }
+          m = fmaxf(m, __shfl_xor(m, 16, 64));
+          m = fmaxf(m, __shfl_xor(m, 32, 64));
+          const float m_new = fmaxf(m_run[f], m);            // (finite: every tile has a key below Tk)
+          float sum = 0.f;
+#pragma unroll
+          for (int kf = 0; kf < 8; ++kf) {
+            if (16 * kf >= rows) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sum += __expf(sc[kf][f][r] - m_new);
+          }
+          sum += __shfl_xor(sum, 16, 64);
+          sum += __shfl_xor(sum, 32, 64);
+          l_run[f] = l_run[f] * __expf(m_run[f] - m_new) + sum;      // (factor 0 at the first tile)
+          m_run[f] = m_new;
+        }
+        if (hn != h) {      // the head's last tile
+#pragma unroll
+          for (int f = 0; f < 2; ++f) {
+            if ((lane >> 4) == 0) St[h * AT + 32 * w + 16 * f + lane] = make_float2(m_run[f], 1.0f / l_run[f]);
+            m_run[f] = -INFINITY;
+            l_run[f] = 0.f;
+          }
+        }
+      }
+      __syncthreads();                          // every wave is done with the images
+      cur = nxt;
+      h = hn; t = tn;
+    }
+  }
+  // ---- pass 2: live tiles outside, heads inside: normalise, sum over the heads in registers, store each tile once
+  {
+    const float inv_heads = 1.0f / (float)nh;
+    int t = t_first, h = 0;
+    load_step(h, t, cur);
+    f32x4 acc[8][2] = {};
+#pragma unroll 1
+    while (t < ntiles) {
+      stage_step(cur);
+      __syncthreads();                          // (also: the statistics of pass 1 are visible)
+      int hn = h + 1, tn = t;
+      if (hn == nh) { hn = 0; tn = next_live(t + 1); }
+      if (tn < ntiles) load_step(hn, tn, nxt);
+      if (active) {
+        const int k0 = t * AT, rows = min(AT, P.Tk - k0);
+        f32x4 sc[8][2];
+        scores(cur.qf, rows, sc);
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+          const float2 st = St[h * AT + 32 * w + 16 * f + (lane & 15)];
+#pragma unroll
+          for (int kf = 0; kf < 8; ++kf) {
+            if (16 * kf >= rows) continue;
+            f32x4 p;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[r] = __expf(sc[kf][f][r] - st.x) * st.y;
+            acc[kf][f] = h == 0 ? p : acc[kf][f] + p;
+          }
+        }
+        if (hn == 0) {      // the tile's last head
+#pragma unroll
+          for (int f = 0; f < 2; ++f) {
+            const int q = q0 + 16 * f + (lane & 15);
+            if (q >= P.Tq) continue;
+#pragma unroll
+            for (int kf = 0; kf < 8; ++kf) {
+              const int key = k0 + 16 * kf + 4 * (lane >> 4);
+              if (16 * kf < rows) store_probs4(out + (int64_t)q * P.Tk + key, acc[kf][f] * inv_heads, key, P.Tk, P.vec);
+            }
+          }
+        }
+      }
+      __syncthreads();
+      cur = nxt;
+      h = hn; t = tn;
+    }
+  }
+}
+
+// =========================================================================================
+constexpr int LONG_MAX_TK = 1 << 20;     // (q * Tk of the dropout counter is a 24-bit multiply; far above any visual token count)
 
 extern "C" int fcmf_attn_mfma_long_fwd(const void* q, const void* k, const void* v, const float* mask, void* out, float* lse,
                                        int G, int heads, int Tq, int Tk, int kv_share, int64_t ldq, int64_t ldk, int64_t ldo,
@@ -392,4 +594,21 @@ extern "C" int fcmf_attn_mfma_long_bwd(const void* q, const void* k, const void*
   }
   static bool attr = false;
   return fcmf_launch_flagged(&attr, attn_long_bwd_kernel, grid, dim3(256), 5 * TILE_B, st, L);          // 80 KiB: two per CU
+}
+
+// LDS of attn_long_probs_kernel for `nh` heads per workgroup
+static size_t long_probs_lds(int nh) { return TILE_B + AT * sizeof(float) + (size_t)nh * AT * sizeof(float2); }
+
+extern "C" int fcmf_attn_mfma_long_probs(const void* q, const void* k, const float* mask, float* probs, int G, int heads, int Tq,
+                                         int Tk, int kv_share, int64_t ldq, int64_t ldk, float scale, int head_mean, void* stream) {
+  if (!q || !k || !probs || G <= 0 || heads <= 0 || Tq <= 0 || Tk <= 0 || kv_share <= 0 || G % kv_share) return FCMF_ERR_ARG;
+  if (Tq > 2 * AT || Tk > LONG_MAX_TK || ldq % 8 || ldk % 8 || !al16(q) || !al16(k) || (head_mean && heads > 32))
+    return FCMF_ERR_UNSUPPORTED;      // (32 heads: 48.5 KiB of LDS, below the default dynamic limit)
+  AttnLongProbsParams P{};
+  P.q = (const bf16_t*)q; P.k = (const bf16_t*)k; P.mask = mask; P.probs = probs;
+  P.G = G; P.heads = heads; P.Tq = Tq; P.Tk = Tk; P.kv_share = kv_share; P.head_mean = head_mean != 0;
+  P.ldq = ldq; P.ldk = ldk; P.scale = scale;
+  P.vec = Tk % 4 == 0 && al16(probs);
+  const dim3 grid(head_mean ? G : G * heads, (Tq + AT - 1) / AT);
+  return fcmf_launch(attn_long_probs_kernel, grid, dim3(256), long_probs_lds(head_mean ? heads : 1), reinterpret_cast<hipStream_t>(stream), P);
 }

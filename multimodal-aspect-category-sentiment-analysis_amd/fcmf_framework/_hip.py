@@ -64,6 +64,7 @@ SIGNATURES = {
     "fcmf_attn_mfma_long_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _i64, _f, _f, _u64, _vp],
     "fcmf_attn_mfma_long_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _i64, _f,
                                 _f, _u64, _vp, _i64, _vp],
+    "fcmf_attn_mfma_long_probs": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i64, _f, _i, _vp],
     "fcmf_attn_probs": [_c.POINTER(AttnDesc), _vp, _i64, _i64, _vp],
     "fcmf_attn_mfma_probs": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _f, _vp],
     "fcmf_bertscore": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i, _vp],

@@ -1,9 +1,9 @@
 """The one way from attention operands to a launch: a descriptor (fcmf_attn_desc, include/fcmf_hip.h), the MFMA / VALU choice
 made from the descriptor's own fields, and one function per kernel pair.  ops, fused and iaog_modeling normalise their
 operands, build a descriptor here and call these; nothing else in the package launches an fcmf_attn_small / _mfma / _probs
-kernel or fills an AttnDesc.  The long pair (long_forward / long_backward: fcmf_attn_mfma_long_fwd / _bwd, any number of keys,
-one key/value set per `kv_share` consecutive query groups) takes dense tensors instead of a descriptor: its key sets are not
-the descriptor's per-group keys."""
+kernel or fills an AttnDesc.  The long kernels (long_forward / long_backward / long_probs: fcmf_attn_mfma_long_fwd / _bwd /
+_probs, any number of keys, one key/value set per `kv_share` consecutive query groups) take dense tensors instead of a
+descriptor: their key sets are not the descriptor's per-group keys."""
 import torch
 
 from . import _hip as H
@@ -99,6 +99,14 @@ def long_backward(q, k, v, mask, out, dout, lse, dq, dk, dv, heads, kv_share, sc
                                             H.ptr(dq), H.ptr(dk), H.ptr(dv), G, heads, Tq, k.shape[1], kv_share, HD, HD, HD, scale,
                                             p, seed, H.ptr(ws), 0 if ws is None else ws.numel() * 4, H.stream()),
             "fcmf_attn_mfma_long_bwd")
+
+
+def long_probs(q, k, mask, out, heads, kv_share, scale, head_mean):
+    """the pre-dropout softmax of long_forward as float32: out [G,heads,Tq,Tk], or with head_mean [G,Tq,Tk] = the mean over
+    the heads, formed inside the kernel.  q / k dense bf16 as long_forward's; every element of out is written"""
+    G, Tq, HD = q.shape
+    H.check(H.lib().fcmf_attn_mfma_long_probs(H.ptr(q), H.ptr(k), H.ptr(mask), H.ptr(out), G, heads, Tq, k.shape[1], kv_share,
+                                              HD, HD, scale, int(head_mean), H.stream()), "fcmf_attn_mfma_long_probs")
 
 
 def sum_leading(x):

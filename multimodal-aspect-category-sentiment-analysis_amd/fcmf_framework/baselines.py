@@ -20,6 +20,13 @@ from .roberta import RobertaModel
 from .torch_layers import MultiheadAttention, TransformerEncoder, TransformerEncoderLayer
 
 
+def _per_aspect(out, B, A):
+    """logits [B*A, C], or (logits, weights [B*A, Tq, Tk]), of an aspect-batched _fuse -> the same with [B, A] in front"""
+    if isinstance(out, tuple):
+        return tuple(t.view(B, A, *t.shape[1:]) for t in out)
+    return out.view(B, A, -1)
+
+
 class _Baseline(nn.Module):
     def _init_weights(self, module):
         if isinstance(module, nn.Linear):
@@ -82,22 +89,28 @@ class mRoBERTa(_Baseline):
         self.apply_custom_init(self.vis_projection)
         self.apply_custom_init(self.roi_projection)
 
-    def _fuse(self, text_feats, visual_feats, attention_mask, kv_share):
-        attn_output, _ = self.cross_attention(query=text_feats, key=visual_feats, value=visual_feats, kv_share=kv_share)
+    def _fuse(self, text_feats, visual_feats, attention_mask, kv_share, output_attentions=False):
+        """-> logits; with output_attentions (logits, the cross-attention weights [rows, S, visual tokens], head mean)"""
+        attn_output, weights = self.cross_attention(query=text_feats, key=visual_feats, value=visual_feats, kv_share=kv_share,
+                                                    need_weights=output_attentions)
         fused_feats = ops.add_layer_norm(attn_output, text_feats, self.norm_cross.weight, self.norm_cross.bias, self.norm_cross.eps)
         mm_output = self.mm_encoder(fused_feats, src_key_padding_mask=(attention_mask == 0))
-        return self._classify(mm_output[:, 0, :])
+        logits = self._classify(mm_output[:, 0, :])
+        return (logits, weights) if output_attentions else logits
 
-    def forward(self, input_ids, attention_mask, visual_embeds_att, roi_embeds_att):
+    def forward(self, input_ids, attention_mask, visual_embeds_att, roi_embeds_att, output_attentions=False):
+        """-> logits; with output_attentions (logits, cross-attention weights [B, S, visual tokens], head mean)"""
         text_feats = self._encode(input_ids, attention_mask)
-        return self._fuse(text_feats, self._visual_tokens(visual_embeds_att, roi_embeds_att), attention_mask, 1)
+        return self._fuse(text_feats, self._visual_tokens(visual_embeds_att, roi_embeds_att), attention_mask, 1, output_attentions)
 
-    def forward_aspects(self, input_ids, attention_mask, visual_embeds_att, roi_embeds_att):
-        """input_ids / attention_mask [B, A, S] -> logits [B, A, num_labels]"""
+    def forward_aspects(self, input_ids, attention_mask, visual_embeds_att, roi_embeds_att, output_attentions=False):
+        """input_ids / attention_mask [B, A, S] -> logits [B, A, num_labels]; with output_attentions also the cross-attention
+        weights [B, A, S, visual tokens] (head mean, float32): one row block per aspect prompt"""
         B, A, S = input_ids.shape
         text_feats = self._encode(input_ids, attention_mask)
-        logits = self._fuse(text_feats, self._visual_tokens(visual_embeds_att, roi_embeds_att), attention_mask.reshape(B * A, S), A)
-        return logits.view(B, A, -1)
+        out = self._fuse(text_feats, self._visual_tokens(visual_embeds_att, roi_embeds_att), attention_mask.reshape(B * A, S), A,
+                         output_attentions)
+        return _per_aspect(out, B, A)
 
 
 class TargetImageMatching(nn.Module):
@@ -113,15 +126,20 @@ class TargetImageMatching(nn.Module):
                                           nn.Dropout(dropout))
         self.dropout = nn.Dropout(dropout)
 
-    def forward(self, target_feats, image_feats, kv_share=1):
+    def forward(self, target_feats, image_feats, kv_share=1, need_weights=False):
+        """-> the layer's output; with need_weights (output, the target -> visual-token weights [rows, T, tokens], head mean)"""
         from .fused import PostAttentionFn
-        c = self.mha.context(target_feats, image_feats, image_feats, kv_share=kv_share)
+        q, k, v, mask, share = self.mha._project(target_feats, image_feats, image_feats, None, kv_share)
+        c = self.mha._attend(q, k, v, mask, share)
+        weights = (ops.shared_kv_attention_probs(q, k, heads=self.mha.num_heads, kv_share=share, average_heads=True)
+                   if need_weights else None)
         p = float(self.dropout.p) if self.training else 0.0
         s0, s1 = (ops.next_seed(), ops.next_seed()) if p > 0 else (0, 0)
         ff = self.feed_forward
-        return PostAttentionFn.apply(c, target_feats, self.mha.out_proj.weight, self.mha.out_proj.bias, self.norm1.weight,
-                                     self.norm1.bias, ff[0].weight, ff[0].bias, ff[2].weight, ff[2].bias, self.norm2.weight,
-                                     self.norm2.bias, float(self.norm1.eps), p, s0, s1)
+        out = PostAttentionFn.apply(c, target_feats, self.mha.out_proj.weight, self.mha.out_proj.bias, self.norm1.weight,
+                                    self.norm1.bias, ff[0].weight, ff[0].bias, ff[2].weight, ff[2].bias, self.norm2.weight,
+                                    self.norm2.bias, float(self.norm1.eps), p, s0, s1)
+        return (out, weights) if need_weights else out
 
 
 class TomBERT(_Baseline):
@@ -147,28 +165,37 @@ class TomBERT(_Baseline):
         self.apply_custom_init(self.vis_projection)
         self.apply_custom_init(self.roi_projection)
 
-    def _fuse(self, h_t, h_s, sentence_mask, g_visual, kv_share):
-        h_v = h_t
+    def _fuse(self, h_t, h_s, sentence_mask, g_visual, kv_share, output_attentions=False):
+        """-> logits; with output_attentions (logits, the matching layer's target -> visual-token weights [rows, T, tokens])"""
+        h_v, weights = h_t, None
         for layer in self.ti_matching:
-            h_v = layer(target_feats=h_v, image_feats=g_visual, kv_share=kv_share)
+            h_v = layer(target_feats=h_v, image_feats=g_visual, kv_share=kv_share, need_weights=output_attentions)
+            if output_attentions:
+                h_v, weights = h_v
         mm_input = torch.cat([h_v[:, 0:1, :], h_s], dim=1)
         valid_cls = torch.ones(sentence_mask.size(0), 1, dtype=sentence_mask.dtype, device=sentence_mask.device)
         mm_mask = torch.cat([valid_cls, sentence_mask], dim=1)
         h_mm = self.mm_encoder(mm_input, src_key_padding_mask=(mm_mask == 0))
-        return self._classify(h_mm[:, 0:2, :].reshape(h_mm.shape[0], -1))      # [visual CLS | first sentence token]
+        logits = self._classify(h_mm[:, 0:2, :].reshape(h_mm.shape[0], -1))      # [visual CLS | first sentence token]
+        return (logits, weights) if output_attentions else logits
 
-    def forward(self, target_ids, target_mask, sentence_ids, sentence_mask, visual_embeds_att, roi_embeds_att):
+    def forward(self, target_ids, target_mask, sentence_ids, sentence_mask, visual_embeds_att, roi_embeds_att,
+                output_attentions=False):
+        """-> logits; with output_attentions (logits, target -> visual-token weights [B, T, visual tokens], head mean)"""
         h_t = self._encode(target_ids, target_mask)
         h_s = self._encode(sentence_ids, sentence_mask)
-        return self._fuse(h_t, h_s, sentence_mask, self._visual_tokens(visual_embeds_att, roi_embeds_att), 1)
+        return self._fuse(h_t, h_s, sentence_mask, self._visual_tokens(visual_embeds_att, roi_embeds_att), 1, output_attentions)
 
-    def forward_aspects(self, target_ids, target_mask, sentence_ids, sentence_mask, visual_embeds_att, roi_embeds_att):
-        """target_* [B, A, T], sentence_* [B, A, S] -> logits [B, A, num_labels]"""
+    def forward_aspects(self, target_ids, target_mask, sentence_ids, sentence_mask, visual_embeds_att, roi_embeds_att,
+                        output_attentions=False):
+        """target_* [B, A, T], sentence_* [B, A, S] -> logits [B, A, num_labels]; with output_attentions also the target ->
+        visual-token weights [B, A, T, visual tokens] (head mean, float32)"""
         B, A, S = sentence_ids.shape
         h_t = self._encode(target_ids, target_mask)
         h_s = self._encode(sentence_ids, sentence_mask)
-        logits = self._fuse(h_t, h_s, sentence_mask.reshape(B * A, S), self._visual_tokens(visual_embeds_att, roi_embeds_att), A)
-        return logits.view(B, A, -1)
+        out = self._fuse(h_t, h_s, sentence_mask.reshape(B * A, S), self._visual_tokens(visual_embeds_att, roi_embeds_att), A,
+                         output_attentions)
+        return _per_aspect(out, B, A)
 
 
 class EFCapTrRoBERTa(_Baseline):

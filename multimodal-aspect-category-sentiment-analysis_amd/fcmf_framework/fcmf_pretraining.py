@@ -41,6 +41,7 @@ class FCMFEncoder(nn.Module):
         self.text2img_pooler = BertPooler(H)
         self.text2roi_pooler = BertPooler(H)
         self.mm_attention = MultimodalEncoder(H, nh, I)
+        self.fusion_attentions = None      # filled by encode_aspects under ops.set_output_fusion_attentions(True)
 
     # ------------------------------------------------------------------------------------
     def encode_aspects(self, input_ids, visual_embeds_att, roi_embeds_att, roi_coors, token_type_ids,
@@ -49,7 +50,14 @@ class FCMFEncoder(nn.Module):
         visual_embeds_att [B,NI,49,F]; roi_embeds_att [B,NI,NR,F]; roi_coors [B,NI,NR,4].
         Returns the fusion-layer output [B*A, 1+2*NI, H] (row b*A+a = sample b, aspect a); with return_attentions also what
         FeatureExtractor hands back as `enc_attentions` (fcmf_pretraining.py:41): () unless ops.set_output_attentions(True), then
-        one [B*A, heads, S, S] tensor per text-encoder layer."""
+        one [B*A, heads, S, S] tensor per text-encoder layer.
+        Under ops.set_output_fusion_attentions(True) every call also leaves the fusion layers' attention maps in
+        `self.fusion_attentions` (else None): float32, the softmax before dropout, from ops.attention_probs on the q / k /
+        mask / bias each layer used --
+          text2img [B*A, NI, heads, P]       the live [CLS] query over each photo's patches (:84-93),
+          text2roi [B*A, NI, heads, S+NR]    the live [CLS] query over the text and the photo's ROIs (:97-124),
+          fusion   [B*A, heads, 1+2NI, 1+2NI] (:127-140),
+          box      [B*NI, 8, NR, NR]         which box_head.box_attn also holds (roi_modeling.py:166)."""
         B, A, S = input_ids.shape
         Bt, NI, NR = B * A, self.num_imgs, self.num_roi
         tr = self.training
@@ -87,12 +95,16 @@ class FCMFEncoder(nn.Module):
         Kr, Vr = (t.view(B, NI, NR, H) for t in ops.linear_multi(rel, msa.key.weight, msa.key.bias, msa.value.weight, msa.value.bias))
 
         cls_rep = cls.unsqueeze(1).expand(Bt, NI, H)
+        maps = {"box": self.box_head.box_attn} if ops.output_fusion_attentions() else None
 
         # 3. text -> image-patch cross attention, live row 0 only              (:84-93)
         qc = ops.linear(cls, csa.query.weight, csa.query.bias)                           # [Bt,H]
         m_img = layers.additive_mask(added, P)                                           # (:53-56)
         ctx_c = ops.attention(qc.unsqueeze(1).expand(Bt, NI, H), k2=Kc, v2=Vc, mask=m_img, heads=nh,
                               group_div=A, p=csa.dropout.p, training=tr)                 # [Bt,NI,H]
+        if maps is not None:
+            maps["text2img"] = ops.attention_probs(qc.unsqueeze(1).expand(Bt, NI, H), k2=Kc, mask=m_img, heads=nh,
+                                                   group_div=A).transpose(1, 2)
         t2i = layers.post_attention(cross, ctx_c, cls_rep, eps, p_h, tr)
         pl = self.text2img_pooler
         h_feat = ops.linear(t2i, pl.dense.weight, pl.dense.bias, act="tanh")             # [Bt,NI,H]
@@ -102,6 +114,9 @@ class FCMFEncoder(nn.Module):
         m_roi = layers.additive_mask(added, S + NR)                                      # (:97-100)
         ctx_m = ops.attention(qm.unsqueeze(1).expand(Bt, NI, H), k1=Kt, v1=Vt, k2=Kr, v2=Vr, mask=m_roi,
                               heads=nh, group_div=A, p=p_a, training=tr)                 # [Bt,NI,H]
+        if maps is not None:
+            maps["text2roi"] = ops.attention_probs(qm.unsqueeze(1).expand(Bt, NI, H), k1=Kt, k2=Kr, mask=m_roi, heads=nh,
+                                                   group_div=A).transpose(1, 2)
         mmo = layers.post_attention(mm, ctx_m, cls_rep, eps, p_h, tr)
         pr = self.text2roi_pooler
         r_feat = ops.linear(mmo, pr.dense.weight, pr.dense.bias, act="tanh")             # [Bt,NI,H]
@@ -109,7 +124,11 @@ class FCMFEncoder(nn.Module):
         # 5. fusion: [CLS] + image features + ROI features through the SAME mm layer (:127-140)
         fusion = torch.cat((cls.unsqueeze(1), h_feat, r_feat), dim=1)                    # [Bt,1+2NI,H]
         m_f = layers.additive_mask(added, 1 + 2 * NI)
-        out = layers.transformer_layer(mm, fusion, fusion, m_f, nh, eps, p_h, p_a, tr)
+        if maps is not None:
+            maps["fusion"] = torch.empty((Bt, nh, 1 + 2 * NI, 1 + 2 * NI), dtype=torch.float32, device=fusion.device)
+        out = layers.transformer_layer(mm, fusion, fusion, m_f, nh, eps, p_h, p_a, tr,
+                                       probs=None if maps is None else maps["fusion"])
+        self.fusion_attentions = maps
         return (out, enc_attentions) if return_attentions else out
 
     def forward(self, input_ids, visual_embeds_att, roi_embeds_att, roi_coors=None, token_type_ids=None,

@@ -64,6 +64,22 @@ def output_attentions():
     return _output_attentions
 
 
+_output_fusion_attentions = False
+
+
+def set_output_fusion_attentions(on):
+    """Opt-in attention maps of the fusion layers, separate from set_output_attentions: FCMFEncoder.encode_aspects fills
+    `encoder.fusion_attentions` (text2img, text2roi, fusion, box) and BoxMultiHeadedAttention keeps `box_attn`, all float32, the
+    softmax BEFORE dropout, recomputed by attention_probs from the q / k / mask / bias each layer itself used.  Off (the default):
+    the attributes are None, nothing is allocated and no launch is added."""
+    global _output_fusion_attentions
+    _output_fusion_attentions = bool(on)
+
+
+def output_fusion_attentions():
+    return _output_fusion_attentions
+
+
 _seed_base = 0x5DEECE66D
 _seed_ctr = 0
 
@@ -1237,6 +1253,56 @@ def shared_kv_attention(q, k, v, mask=None, heads=12, kv_share=1, scale=None, p=
         return torch.stack(outs, 1).reshape(G, Tq, HD)
     raise H.HipLibraryError(f"shared_kv_attention: unsupported configuration ({q.dtype}, head dim {d}): bf16 with head dim 64, "
                             "or float32 with head dim <= 128")
+
+
+def shared_kv_attention_probs(q, k, mask=None, heads=12, kv_share=1, scale=None, average_heads=False, out=None):
+    """softmax(scale q k^T + mask) of `shared_kv_attention` as float32, before dropout, recomputed from q and k (no values, no
+    logsumexp of a forward): [G, heads, Tq, Tk], or with average_heads the mean over the heads [G, Tq, Tk] (what
+    torch.nn.MultiheadAttention returns by default).  Operands and refusals as shared_kv_attention.  bf16 with head dim 64:
+    fcmf_attn_mfma_long_probs, any Tk; the head mean is formed inside the kernel (float32, ascending head order, every
+    element stored once: deterministic, and no per-head tensor exists).  float32 (the parity mode): fcmf_attn_probs once per
+    sharing member, up to its 512 keys, the head mean a torch reduction.  Detached; there is no backward.  out: a contiguous
+    float32 tensor of the result's shape to fill instead of a new one."""
+    H.require_cuda(q, k)
+    G, Tq, HD = q.shape
+    d = HD // heads
+    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    if (kv_share < 1 or G % kv_share or k.dim() != 3 or k.shape[0] * kv_share != G or k.shape[2] != HD or k.dtype != q.dtype
+            or (mask is not None and tuple(mask.shape) != (G, k.shape[1]))):
+        raise H.HipLibraryError(f"shared_kv_attention_probs: q {tuple(q.shape)} / k {tuple(k.shape)} do not form {kv_share} "
+                                f"query groups per key set")
+    Tk = k.shape[1]
+    bf16 = q.dtype == torch.bfloat16 and d * heads == HD and d == 64
+    if not bf16 and not (q.dtype == torch.float32 and d * heads == HD and d <= 128):
+        raise H.HipLibraryError(f"shared_kv_attention_probs: unsupported configuration ({q.dtype}, head dim {d}): bf16 with "
+                                "head dim 64, or float32 with head dim <= 128")
+    if not bf16 and Tk > 512:
+        raise H.HipLibraryError(f"shared_kv_attention_probs: unsupported configuration (float32 with {Tk} keys: the parity "
+                                "mode takes up to 512)")
+    shape = (G, Tq, Tk) if average_heads else (G, heads, Tq, Tk)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=q.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != q.device:
+        raise H.HipLibraryError(f"shared_kv_attention_probs: out must be a contiguous float32 {shape} tensor on {q.device}")
+    q, k = q.detach().contiguous(), k.detach().contiguous()
+    mask = None if mask is None else mask.detach().contiguous().float()
+    if bf16:
+        attn.long_probs(q, k, mask, out, heads, kv_share, scale, average_heads)
+        return out
+    per_head = torch.empty((G, heads, Tq, Tk), dtype=torch.float32, device=q.device) if average_heads or kv_share > 1 else out
+    for m in range(kv_share):
+        qm = _query_rows(q[m::kv_share], False)
+        mm = None if mask is None else mask[m::kv_share].contiguous()
+        pm = per_head if kv_share == 1 else torch.empty((G // kv_share, heads, Tq, Tk), dtype=torch.float32, device=q.device)
+        a = attn.desc(qm, k, None, None, None, mm, None, heads, 1, scale, 0.0, 0, False, False)
+        attn.probs(a, pm, heads * Tq * Tk, Tq * Tk, False)
+        if kv_share > 1:
+            per_head[m::kv_share] = pm
+    if average_heads:
+        torch.mean(per_head, 1, out=out)
+    elif per_head is not out:
+        out.copy_(per_head)
+    return out
 
 
 def attention_probs(q, k1=None, k2=None, mask=None, bias=None, heads=12, group_div=1, scale=None, causal=False,

@@ -80,6 +80,9 @@ class BoxMultiHeadedAttention(nn.Module):
             v = ops.linear(v_in, self.linears[2].weight, self.linears[2].bias)
         x = ops.attention(q, k1=k, v1=v, bias=bias, heads=self.h, scale=1.0 / math.sqrt(self.d_k),
                           p=self.dropout.p, training=self.training)
+        # the reference keeps box_attention's w_mn (roi_modeling.py:166), after dropout; here on request, before dropout
+        self.box_attn = (ops.attention_probs(q, k1=k, bias=bias, heads=self.h, scale=1.0 / math.sqrt(self.d_k))
+                         if ops.output_fusion_attentions() else None)                   # [B, h, N, N] float32
         if self.legacy_extra_skip:
             x = v_in + x
         return ops.linear(x, self.linears[3].weight, self.linears[3].bias)

@@ -6,8 +6,12 @@ therefore carry torch's state-dict keys (`in_proj_weight`, `out_proj.*`, `self_a
 `in_proj_weight` [3E, E] is the fused q|k|v block that fused.SelfLayerFn multiplies in one GEMM, cross-attention goes
 through ops.shared_kv_attention (any number of keys, one key/value set per `kv_share` consecutive query groups), and a
 boolean key-padding mask becomes the hard additive mask (finfo(float32).min: probability exactly 0).
+`MultiheadAttention.forward(need_weights=True)` also returns the attention weights, averaged over the heads or per head
+(ops.shared_kv_attention_probs: recomputed from the projected q and k by their own kernel).  Two deviations from torch, as
+for the text encoder's `output_attentions`: in train() mode they are the softmax BEFORE dropout, and a row without a live
+key is uniform where torch gives NaN.  `need_weights` defaults to False here (torch: True).
 
-Only what the baselines use is built -- batch_first=True, post-norm, gelu, biases; anything else raises
+Only what the baselines use is built -- batch_first=True, post-norm, gelu, biases, no attn_mask; anything else raises
 NotImplementedError.  One difference under training: torch drops activations once more between the feed-forward's gelu and
 its second Linear; the fused layer (HF's RobertaLayer) does not, so a train()-mode step regularises slightly less.  In
 eval() mode the two are the same function.
@@ -56,8 +60,8 @@ class MultiheadAttention(nn.Module):
         E, W, b = self.embed_dim, self.in_proj_weight, self.in_proj_bias
         return W[:E], b[:E], W[E:2 * E], b[E:2 * E], W[2 * E:], b[2 * E:]
 
-    def context(self, query, key, value, key_padding_mask=None, kv_share=None):
-        """the heads' outputs before out_proj: [G, Tq, E]"""
+    def _project(self, query, key, value, key_padding_mask, kv_share):
+        """-> q, k, v, additive mask [G, Tk] or None, the sharing factor"""
         share = self.kv_share if kv_share is None else kv_share
         wq, bq, wk, bk, wv, bv = self.qkv_params()
         q = ops.linear(query, wq, bq)
@@ -66,14 +70,30 @@ class MultiheadAttention(nn.Module):
         mask = padding_to_additive(key_padding_mask)
         if mask is not None and mask.shape[0] != q.shape[0]:
             mask = mask.repeat_interleave(share, 0)          # given per key set
+        return q, k, v, mask, share
+
+    def _attend(self, q, k, v, mask, share):
         return ops.shared_kv_attention(q, k, v, mask=mask, heads=self.num_heads, kv_share=share, p=self.dropout,
                                        training=self.training)
 
-    def forward(self, query, key, value, key_padding_mask=None, need_weights=False, attn_mask=None, kv_share=None):
-        if need_weights or attn_mask is not None:
-            raise NotImplementedError("MultiheadAttention: attention weights and attn_mask are not built")
-        c = self.context(query, key, value, key_padding_mask, kv_share)
-        return ops.linear(c, self.out_proj.weight, self.out_proj.bias), None
+    def context(self, query, key, value, key_padding_mask=None, kv_share=None):
+        """the heads' outputs before out_proj: [G, Tq, E]"""
+        return self._attend(*self._project(query, key, value, key_padding_mask, kv_share))
+
+    def forward(self, query, key, value, key_padding_mask=None, need_weights=False, attn_mask=None, average_attn_weights=True,
+                kv_share=None):
+        """-> (output, weights).  weights is None unless need_weights (torch's default is True; here it is False, the
+        baselines throw the weights away): then the float32 softmax of the q and k projected for the output (no second
+        projection), [G, Tq, Tk] averaged over the heads or [G, heads, Tq, Tk] -- before dropout also in train() mode, and
+        uniform where torch gives NaN (a row without a live key); detached."""
+        if attn_mask is not None:
+            raise NotImplementedError("MultiheadAttention: attn_mask is not built")
+        q, k, v, mask, share = self._project(query, key, value, key_padding_mask, kv_share)
+        out = ops.linear(self._attend(q, k, v, mask, share), self.out_proj.weight, self.out_proj.bias)
+        if not need_weights:
+            return out, None
+        return out, ops.shared_kv_attention_probs(q, k, mask=mask, heads=self.num_heads, kv_share=share,
+                                                  average_heads=average_attn_weights)
 
 
 class TransformerEncoderLayer(nn.Module):

@@ -19,7 +19,8 @@ Batches reach the GPU through `device_prefetch.DevicePrefetcher` (pinned host me
 Process set-up, the checkpoint code, the extractors and the loop of one epoch are `train_harness.py`'s, shared with
 run_pretraining_fcmf.py; this file keeps the parser, the model and data, the 4 parameter groups, the loss and the evaluation.
 Extra flags (not in the reference): --bf16, --synthetic_steps N (seeded synthetic batches with
-precomputed features: no dataset / tokenizer / torchvision needed), --precomputed_features.
+precomputed features: no dataset / tokenizer / torchvision needed), --precomputed_features, --dump_attention_maps (the
+test-set pass also writes `test_attention_maps.npz`: where each review's [CLS] looks in its photos, per aspect).
 The host-side batch producer (vimacsa_dataset.MACSADataset, image decoding, ResNet-152 feature
 extraction) is the "next" row of SURVEY.md section 8(f); with real data this driver imports the
 user's `vimacsa_dataset` module and torchvision exactly as the reference does.
@@ -97,6 +98,9 @@ def build_parser():
                              "the step (reference :449-460); 0 = precomputed features")
     parser.add_argument('--resnet_checkpoint', default=None, type=str,
                         help="torchvision resnet152 state dict (.pth, loaded with weights_only=True) for the HIP trunk")
+    parser.add_argument('--dump_attention_maps', action='store_true',
+                        help="with --do_eval: the test-set pass also writes test_attention_maps.npz (head-averaged [CLS] "
+                             "attention over each photo's patches and ROIs, per review and aspect) into --output_dir")
     return parser
 
 
@@ -284,7 +288,7 @@ def main(argv=None):
             logger.warning("No best model found! Using current weights.")
         if resnet_img is not None:
             resnet_img.eval(); resnet_roi.eval()
-        test_evaluate(model, test_loader, device, features, ASPECT, args.output_dir, logger)
+        test_evaluate(model, test_loader, device, features, ASPECT, args.output_dir, logger, dump_maps=args.dump_attention_maps)
     arena.deactivate()
     if world > 1:
         torch.distributed.destroy_process_group()
@@ -299,22 +303,47 @@ def forward_batch(model, batch, features):
     return logits, labels, texts
 
 
+def cls_attention_maps(encoder, B, A):
+    """the head-averaged [CLS] rows of the batch's fusion_attentions (eval-only torch arithmetic, as in decoding.py) ->
+    patches [B, A, NI, P]: the text -> image-patch layer's row; rois [B, A, NI, NR]: the ROI columns of the text+ROI layer's
+    row, renormalised over the photo's ROIs (every row of both sums to 1); roi_mass [B, A, NI]: the share of that row which
+    lay on the ROIs and not on the text, i.e. what the renormalisation divided by"""
+    fa = encoder.fusion_attentions
+    patches = fa["text2img"].mean(2)                                      # [B*A, NI, P]
+    roi = fa["text2roi"].mean(2)[..., -encoder.num_roi:]                  # [B*A, NI, NR]
+    mass = roi.sum(-1, keepdim=True)
+    rois = roi / mass.clamp_min(torch.finfo(torch.float32).tiny)
+    return (patches.reshape(B, A, *patches.shape[1:]).cpu().numpy(), rois.reshape(B, A, *rois.shape[1:]).cpu().numpy(),
+            mass.reshape(B, A, -1).cpu().numpy())
+
+
 @torch.no_grad()
-def predict(model, loader, device, features):
-    """eval-mode forward + argmax over a loader: (predictions [B, aspects], labels [B, aspects], texts) per batch, as numpy"""
+def predict(model, loader, device, features, maps=None):
+    """eval-mode forward + argmax over a loader: (predictions [B, aspects], labels [B, aspects], texts) per batch, as numpy.
+    maps (a list): every batch also appends its cls_attention_maps (ops.set_output_fusion_attentions is on for the pass)."""
     model.eval()
-    for batch in DevicePrefetcher(loader, device, float32_fields=(1,)):
-        logits, labels, texts = forward_batch(model, batch, features)
-        yield logits.argmax(-1).cpu().numpy(), labels.cpu().numpy(), texts
+    was = ops.output_fusion_attentions()
+    ops.set_output_fusion_attentions(was or maps is not None)
+    try:
+        for batch in DevicePrefetcher(loader, device, float32_fields=(1,)):
+            logits, labels, texts = forward_batch(model, batch, features)
+            if maps is not None:
+                maps.append(cls_attention_maps(model.encoder, logits.shape[0], logits.shape[1]))
+            yield logits.argmax(-1).cpu().numpy(), labels.cpu().numpy(), texts
+    finally:
+        ops.set_output_fusion_attentions(was)
 
 
-def test_evaluate(model, loader, device, features, aspects, output_dir, logger):
+def test_evaluate(model, loader, device, features, aspects, output_dir, logger, dump_maps=False):
     """test-set pass of the reference (:600-694): per-aspect precision / recall / macro-F1 into `test_results_fcmf.txt`, and
-    one block per review with the predicted and gold polarity of every aspect into `test_predictions_formatted.txt`"""
+    one block per review with the predicted and gold polarity of every aspect into `test_predictions_formatted.txt`.
+    dump_maps: also `test_attention_maps.npz` with patches [N, aspects, NI, 49], rois [N, aspects, NI, NR] and roi_mass
+    [N, aspects, NI] (cls_attention_maps), review by review in the order of the loader."""
     true = {a: [] for a in aspects}
     pred = {a: [] for a in aspects}
     formatted = []
-    for p, y, texts in predict(model, loader, device, features):
+    maps = [] if dump_maps else None
+    for p, y, texts in predict(model, loader, device, features, maps):
         logs = [{"text": t, "aspects": {}} for t in (texts if texts is not None else [""] * len(p))]
         for i, a in enumerate(aspects):
             true[a].append(y[:, i]); pred[a].append(p[:, i])
@@ -347,6 +376,10 @@ def test_evaluate(model, loader, device, features, aspects, output_dir, logger):
                 f.write(f"   label:   {res['label']}\n")
             f.write("}\n")
     logger.info("Formatted predictions saved to %s", log_path)
+    if dump_maps:
+        maps_path = os.path.join(output_dir, "test_attention_maps.npz")
+        np.savez(maps_path, **{name: np.concatenate([m[i] for m in maps]) for i, name in enumerate(("patches", "rois", "roi_mass"))})
+        logger.info("Attention maps saved to %s", maps_path)
     return avg_f1
 
 
