@@ -383,6 +383,8 @@ int fcmf_additive_mask(const int64_t* mask, int64_t ld, float* out, int rows, in
 
 /* ---------------------------------------------------------------------------------------
  * elementwise helpers */
+/* dst[i] = (dst_dtype) src[i], float32 <-> bfloat16 (round to nearest even).  4 elements per lane when src is 16-byte and dst
+ * 8-byte aligned; any other element-aligned pair (a contiguous view inside a packed buffer) goes one element per lane. */
 int fcmf_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, void* stream);
 /* dst (bfloat16 [cols, rows]) = transpose(src float32 [rows, cols]): transposed weight copies for the dX GEMMs */
 int fcmf_cast_transpose(const float* src, void* dst, int rows, int cols, void* stream);

@@ -214,6 +214,14 @@ __global__ __launch_bounds__(256) void cast_kernel(const TS* __restrict__ s, TD*
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) d[n4 * 4 + threadIdx.x] = from_f32<TD>(to_f32<TS>(s[n4 * 4 + threadIdx.x]));
 }
 
+// the same, one element per lane: a source or destination that is not aligned for the 4-wide accesses (a contiguous view that
+// starts at an odd element offset of a packed buffer)
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void cast_unaligned_kernel(const TS* __restrict__ s, TD* __restrict__ d, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    d[i] = from_f32<TD>(to_f32<TS>(s[i]));
+}
+
 // dst[c][r] = bf16(src[r][c]): 64x64 tiles through LDS, coalesced on both sides (transposed bf16 weight copies, so
 // that dX = dY * W reads W as a K-contiguous operand)
 __global__ __launch_bounds__(256) void cast_transpose_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int R, int C) {
@@ -344,6 +352,10 @@ struct AdamArgs {
 };
 
 __global__ __launch_bounds__(256) void multi_adamw_kernel(AdamArgs a) {
+  // every product and sum rounded on its own: left to the compiler, the 4-wide body and the scalar loop below were contracted
+  // into different fused multiply-adds, and a parameter's trajectory depended on whether its storage is 16-byte aligned
+  // (arena slices and packed buffers are not always).  The kernel is bound by its 28 bytes per element, not by these few ops.
+#pragma clang fp contract(off)
   const int t = a.chunk_tensor[blockIdx.x];
   const int64_t off = a.chunk_offset[blockIdx.x];
   float* p = reinterpret_cast<float*>(a.p_ptrs[t]) + off;
@@ -518,8 +530,20 @@ extern "C" int fcmf_xent_bwd(const void* logits, int64_t ld, const int64_t* labe
 extern "C" int fcmf_cast(const void* src, void* dst, int64_t n, int src_dtype, int dst_dtype, void* stream) {
   if (!src || !dst || n < 0) return FCMF_ERR_ARG;
   if (n == 0) return FCMF_OK;
-  if ((reinterpret_cast<uintptr_t>(src) & 15) || (reinterpret_cast<uintptr_t>(dst) & 7)) return FCMF_ERR_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if ((reinterpret_cast<uintptr_t>(src) & 15) || (reinterpret_cast<uintptr_t>(dst) & 7)) {
+    // not aligned for the 4-wide accesses: one element per lane (the pointers must still be aligned to their element)
+    const uintptr_t sm = src_dtype == FCMF_F32 ? 3 : 1, dm = dst_dtype == FCMF_F32 ? 3 : 1;
+    if ((reinterpret_cast<uintptr_t>(src) & sm) || (reinterpret_cast<uintptr_t>(dst) & dm)) return FCMF_ERR_ARG;
+    dim3 g1(grid_for(n, 256));
+    if (src_dtype == FCMF_F32 && dst_dtype == FCMF_BF16) hipLaunchKernelGGL((cast_unaligned_kernel<float, bf16_t>), g1, dim3(256), 0, st, (const float*)src, (bf16_t*)dst, n);
+    else if (src_dtype == FCMF_BF16 && dst_dtype == FCMF_F32) hipLaunchKernelGGL((cast_unaligned_kernel<bf16_t, float>), g1, dim3(256), 0, st, (const bf16_t*)src, (float*)dst, n);
+    else if (src_dtype == FCMF_F32 && dst_dtype == FCMF_F32) hipLaunchKernelGGL((cast_unaligned_kernel<float, float>), g1, dim3(256), 0, st, (const float*)src, (float*)dst, n);
+    else if (src_dtype == FCMF_BF16 && dst_dtype == FCMF_BF16) hipLaunchKernelGGL((cast_unaligned_kernel<bf16_t, bf16_t>), g1, dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, n);
+    else return FCMF_ERR_UNSUPPORTED;
+    FCMF_CHECK_LAUNCH();
+    return FCMF_OK;
+  }
   dim3 grid(grid_for(n, 1024));
   if (src_dtype == FCMF_F32 && dst_dtype == FCMF_BF16) hipLaunchKernelGGL((cast_kernel<float, bf16_t>), grid, dim3(256), 0, st, (const float*)src, (bf16_t*)dst, n);
   else if (src_dtype == FCMF_BF16 && dst_dtype == FCMF_F32) hipLaunchKernelGGL((cast_kernel<bf16_t, float>), grid, dim3(256), 0, st, (const bf16_t*)src, (float*)dst, n);
