@@ -83,6 +83,89 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// ---- column sums of a row-major matrix (fcmf_colsum, the LayerNorm backward's reduce pass) -----------------------------------
+// out[c] += sum_r X[r, c] for the rows [blockIdx.y * rows_per_block, +rows_per_block) of the 256-column block blockIdx.x, by one
+// workgroup of COLSUM_WAVES waves.  A lane owns V adjacent columns, so one wave instruction reads 256 contiguous columns of
+// 64 * V / 256 rows (16 bytes per lane for float with V = 4 and bf16 with V = 8); a wave keeps COLSUM_INFLIGHT such
+// instructions in flight (8 KB), a workgroup 128 KB: one workgroup per CU streams.  The parallelism is inside the workgroup, not
+// in the number of row blocks, because every row block ends with one float atomic per column into the SAME addresses, which
+// the memory side serialises.  `vec` = the rows are aligned for V-wide loads; without it, and for a lane whose V columns
+// straddle N, the lane reads element by element.
+constexpr int COLSUM_WAVES = 16, COLSUM_INFLIGHT = 8, COLSUM_MAX_ROWS = 2048;
+
+template <typename T, int V>
+__device__ __forceinline__ void colsum_block(const T* __restrict__ X, float* __restrict__ out, int M, int N, int64_t ldx,
+                                             int rows_per_block, int vec) {
+  typedef T raw_t __attribute__((ext_vector_type(V)));
+  constexpr int LPR = 256 / V, RPI = 64 / LPR;             // lanes per row, rows per wave instruction
+  constexpr int STEP = RPI * COLSUM_WAVES, U = COLSUM_INFLIGHT;
+  static_assert(V % 4 == 0 && 256 % V == 0 && LPR <= 64 && U == 8, "colsum_block: lane layout");
+  __shared__ __attribute__((aligned(16))) float red[COLSUM_WAVES][RPI * 256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane / LPR, cl = (lane % LPR) * V;
+  const int col = blockIdx.x * 256 + cl;
+  const int r0 = blockIdx.y * rows_per_block;
+  const int r1 = min(M, r0 + rows_per_block);
+  float s[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) s[j] = 0.f;
+  int r = r0 + RPI * wave + sub;                            // this lane's rows: r, r + STEP, r + 2 STEP, ...
+  if (vec && col + V - 1 < N) {
+    raw_t v[U];
+    auto add = [&]() {
+#pragma unroll
+      for (int j = 0; j < V; ++j)
+        s[j] += (((float)v[0][j] + (float)v[1][j]) + ((float)v[2][j] + (float)v[3][j])) +
+                (((float)v[4][j] + (float)v[5][j]) + ((float)v[6][j] + (float)v[7][j]));
+    };
+    for (; r + (U - 1) * STEP < r1; r += U * STEP) {
+      const T* p = X + (int64_t)r * ldx + col;
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = *reinterpret_cast<const raw_t*>(p + (int64_t)u * STEP * ldx);
+      add();
+    }
+    if (r < r1) {                                           // the last, partial batch: the same loads, each behind its row test
+      const T* p = X + (int64_t)r * ldx + col;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        v[u] = raw_t{};
+        if (r + u * STEP < r1) v[u] = *reinterpret_cast<const raw_t*>(p + (int64_t)u * STEP * ldx);
+      }
+      add();
+    }
+  } else if (col < N) {
+    for (; r < r1; r += STEP) {
+      const T* p = X + (int64_t)r * ldx + col;
+#pragma unroll
+      for (int j = 0; j < V; ++j)
+        if (col + j < N) s[j] += to_f32<T>(p[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < V; j += 4)
+    *reinterpret_cast<float4*>(&red[wave][sub * 256 + cl + j]) = make_float4(s[j], s[j + 1], s[j + 2], s[j + 3]);
+  __syncthreads();
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (threadIdx.x < 256 && c < N) {                         // thread t finishes column t: 256 contiguous atomics per wave
+    float a = 0.f, b = 0.f;
+#pragma unroll
+    for (int w = 0; w < COLSUM_WAVES; w += 2)
+#pragma unroll
+      for (int h = 0; h < RPI; ++h) { a += red[w][h * 256 + threadIdx.x]; b += red[w + 1][h * 256 + threadIdx.x]; }
+    atomicAdd(out + c, a + b);
+  }
+}
+
+// rows per workgroup for `colblocks` column blocks in all: about one workgroup per CU (256), a whole number of the
+// workgroup's row groups (`rpi` = rows per wave instruction), at most COLSUM_MAX_ROWS (a lane's chain of additions stays short;
+// beyond it the row blocks, and with them the atomics per column, grow instead)
+static inline int colsum_rows_per_block(int M, int64_t colblocks, int rpi) {
+  const int64_t unit = COLSUM_WAVES * rpi;
+  int64_t rpb = ((int64_t)M * colblocks + 255) / 256;
+  rpb = (rpb + unit - 1) / unit * unit;
+  return (int)(rpb < unit ? unit : (rpb > COLSUM_MAX_ROWS ? COLSUM_MAX_ROWS : rpb));
+}
+
 // ---- counter-based dropout RNG --------------------------------------------------------------
 // Stateless hash of (seed, element index): forward and backward regenerate the same mask without storing
 // it.  One 32-bit hash (the "lowbias32" integer finaliser: two 32-bit multiplies -- integer multiplies are

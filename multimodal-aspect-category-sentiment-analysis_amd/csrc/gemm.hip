@@ -1476,48 +1476,12 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(GenericParams p) {
 }
 
 // column sums ----------------------------------------------------------------------------
-// block = 256 columns x rows_per_block rows: lane -> 4 adjacent columns (8/16-byte loads, a wave
-// reads 256 contiguous columns), the 4 waves stride the rows; LDS tree over the waves, then one
-// float atomic per column per block.
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ X, float* __restrict__ out, int M, int N,
-                                                     int64_t ldx, int rows_per_block, int vec) {
-  __shared__ float4 red[4][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = blockIdx.x * 256 + lane * 4;
-  const int r0 = blockIdx.y * rows_per_block;
-  const int r1 = min(M, r0 + rows_per_block);
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (vec && col + 3 < N) {
-    int r = r0 + wave;
-    for (; r + 12 < r1; r += 16) {        // four rows in flight per wave (one dependent load per iteration is latency-bound)
-      const float4 v0 = Vec4<T>::load(X + (int64_t)r * ldx + col), v1 = Vec4<T>::load(X + (int64_t)(r + 4) * ldx + col);
-      const float4 v2 = Vec4<T>::load(X + (int64_t)(r + 8) * ldx + col), v3 = Vec4<T>::load(X + (int64_t)(r + 12) * ldx + col);
-      s.x += (v0.x + v1.x) + (v2.x + v3.x); s.y += (v0.y + v1.y) + (v2.y + v3.y);
-      s.z += (v0.z + v1.z) + (v2.z + v3.z); s.w += (v0.w + v1.w) + (v2.w + v3.w);
-    }
-    for (; r < r1; r += 4) {
-      const float4 v = Vec4<T>::load(X + (int64_t)r * ldx + col);
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-  } else if (col < N) {
-    for (int r = r0 + wave; r < r1; r += 4) {
-      const T* p = X + (int64_t)r * ldx + col;
-      s.x += to_f32<T>(p[0]);
-      if (col + 1 < N) s.y += to_f32<T>(p[1]);
-      if (col + 2 < N) s.z += to_f32<T>(p[2]);
-      if (col + 3 < N) s.w += to_f32<T>(p[3]);
-    }
-  }
-  red[wave][lane] = s;
-  __syncthreads();
-  if (wave == 0 && col < N) {
-    const float4 a = red[0][lane], b = red[1][lane], c = red[2][lane], d = red[3][lane];
-    atomicAdd(out + col, a.x + b.x + c.x + d.x);
-    if (col + 1 < N) atomicAdd(out + col + 1, a.y + b.y + c.y + d.y);
-    if (col + 2 < N) atomicAdd(out + col + 2, a.z + b.z + c.z + d.z);
-    if (col + 3 < N) atomicAdd(out + col + 3, a.w + b.w + c.w + d.w);
-  }
+// colsum_block (common.h): V = 8 reads bf16 rows 16 bytes per lane, V = 4 is the layout for float and for bf16 rows that are
+// only 8-byte aligned; the scalar path rides on V = 4.
+template <typename T, int V>
+__global__ __launch_bounds__(COLSUM_WAVES * 64) void colsum_kernel(const T* __restrict__ X, float* __restrict__ out, int M, int N,
+                                                                   int64_t ldx, int rows_per_block, int vec) {
+  colsum_block<T, V>(X, out, M, N, ldx, rows_per_block, vec);
 }
 
 // ---- __global__ entry points of the persistent body ---------------------------------------------------------------------
@@ -2703,19 +2667,19 @@ extern "C" int fcmf_colsum(const void* X, float* out, int M, int N, int64_t ldx,
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (!accumulate) { if (hipMemsetAsync(out, 0, sizeof(float) * N, st) != hipSuccess) return FCMF_ERR_LAUNCH; }
   if (M == 0) return FCMF_OK;
-  const int vec = (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
-  // rows per block: 256, or ~1024 blocks of >= 16 rows where 256-row blocks would not fill the chip (a 384-row matrix on
-  // 18 blocks took 27 us: every wave walks its rows one dependent load at a time)
+  if (dtype != FCMF_F32 && dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
+  const bool al16 = (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  const int vec = (ldx % 4 == 0) && al16;
+  const bool wide = dtype == FCMF_BF16 && al16 && ldx % 8 == 0;      // 16 bytes per lane: two bf16 rows per wave instruction
+  // one workgroup of 16 waves per CU, each wave with 8 row groups in flight; few row blocks, because each of them ends with
+  // atomics into the same N floats (192 row blocks of a [49152, 768] input spent 6 us there).  A 384-row matrix still spreads
+  // over all CUs: 16 rows per workgroup, one per wave.
   const int bx = (N + 255) / 256;
-  int rpb = 256;
-  if ((int64_t)((M + 255) / 256) * bx < 256) {       // fewer blocks than CUs: shorter row runs
-    rpb = (int)(((int64_t)M * bx / 1024 + 3) & ~3ll);
-    rpb = rpb < 16 ? 16 : (rpb > 256 ? 256 : rpb);
-  }
-  dim3 grid(bx, (M + rpb - 1) / rpb);
-  if (dtype == FCMF_F32) hipLaunchKernelGGL((colsum_kernel<float>), grid, dim3(256), 0, st, (const float*)X, out, M, N, ldx, rpb, vec);
-  else if (dtype == FCMF_BF16) hipLaunchKernelGGL((colsum_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)X, out, M, N, ldx, rpb, vec);
-  else return FCMF_ERR_UNSUPPORTED;
+  const int rpb = colsum_rows_per_block(M, bx, wide ? 2 : 1);
+  const dim3 grid(bx, (M + rpb - 1) / rpb), block(COLSUM_WAVES * 64);
+  if (dtype == FCMF_F32) hipLaunchKernelGGL((colsum_kernel<float, 4>), grid, block, 0, st, (const float*)X, out, M, N, ldx, rpb, vec);
+  else if (wide) hipLaunchKernelGGL((colsum_kernel<bf16_t, 8>), grid, block, 0, st, (const bf16_t*)X, out, M, N, ldx, rpb, 1);
+  else hipLaunchKernelGGL((colsum_kernel<bf16_t, 4>), grid, block, 0, st, (const bf16_t*)X, out, M, N, ldx, rpb, vec);
   FCMF_CHECK_LAUNCH();
   return FCMF_OK;
 }

@@ -262,24 +262,15 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(const T* __restrict__ d
   }
 }
 
-// out[which][c] += sum_b partial[b][which][c].  grid (H/64, 3, 8): each workgroup sums one eighth of the
-// per-workgroup partial rows for 64 columns (4 waves stride the rows), then one float atomic per column.
-__global__ __launch_bounds__(256) void ln_partial_reduce_kernel(const float* __restrict__ partial, int nblocks, int H,
-                                                                float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                float* __restrict__ dxsum) {
-  __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int col = blockIdx.x * 64 + lane, which = blockIdx.y;
+// out[which][c] += sum_b partial[b][which][c]: the column sums of three [nblocks, H] float matrices with row stride 3 H
+// (colsum_block, common.h).  grid (H / 256, row blocks, 3).
+__global__ __launch_bounds__(COLSUM_WAVES * 64) void ln_partial_reduce_kernel(const float* __restrict__ partial, int nblocks, int H,
+                                                                              float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                              float* __restrict__ dxsum, int rows_per_block, int vec) {
+  const int which = blockIdx.z;
   float* out = which == 0 ? dgamma : (which == 1 ? dbeta : dxsum);
   if (!out) return;
-  const int per = (nblocks + gridDim.z - 1) / gridDim.z;
-  const int b0 = blockIdx.z * per, b1 = min(nblocks, b0 + per);
-  float s = 0.f;
-  if (col < H)
-    for (int b = b0 + w; b < b1; b += 4) s += partial[((int64_t)b * 3 + which) * H + col];
-  red[w][lane] = s;
-  __syncthreads();
-  if (w == 0 && col < H) atomicAdd(out + col, red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]);
+  colsum_block<float, 4>(partial + (int64_t)which * H, out, nblocks, H, 3 * (int64_t)H, rows_per_block, vec);
 }
 
 // ---- RoBERTa embeddings -----------------------------------------------------------------
@@ -512,6 +503,21 @@ __global__ __launch_bounds__(256) void embed_pos_type_bwd_kernel(const T* __rest
   } while (0)
 
 // ---- host ---------------------------------------------------------------------------------
+// The LayerNorm kernels walk their rows with a grid stride, so the right grid is what is resident at once.  The workgroups of a
+// second, partly filled round start only as the first ones finish and leave most of the chip idle at the end: at bf16,
+// [49152, 768] a CU holds 6 forward and 3 backward workgroups, and the grids of 2048 and 1024 ran 8 % and 10 % longer than 1536
+// and 768.  Asked of the runtime once per kernel; `cap` where it cannot say, and never more than `cap`.
+template <class K>
+static int ln_resident_blocks(K kernel, int cap) {
+  int dev = 0, cus = 0, per_cu = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
+    (void)hipGetLastError();
+    return cap;
+  }
+  return (int64_t)cus * per_cu < cap ? cus * per_cu : cap;
+}
+
 static int add_ln_fwd_impl(const void* x, const void* res, int64_t res_stride, const float* gamma, const float* beta, void* y,
                            void* z, float* mean, float* rstd, int rows, int H, float eps, float dropout_p, uint64_t seed,
                            int dtype, void* stream, void* q8, float* qscale);
@@ -534,10 +540,13 @@ static int add_ln_fwd_impl(const void* x, const void* res, int64_t res_stride, c
   if (rows == 0) return FCMF_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int nblk = (rows + 3) / 4;
-  dim3 grid(nblk > 2048 ? 2048 : nblk);      // 8 workgroups per CU; every wave walks its rows with the next one in flight
   if (dtype != FCMF_F32 && dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
-#define LAUNCH_(T, NP) hipLaunchKernelGGL((add_ln_fwd_kernel<T, NP>), grid, dim3(256), 0, st, (const T*)x, (const T*)res, \
-    res_stride, gamma, beta, (T*)y, (T*)z, mean, rstd, rows, H, eps, dropout_p, seed, (unsigned char*)q8, qscale)
+  // at most 8 workgroups per CU; every wave walks its rows with the next one in flight
+#define LAUNCH_(T, NP) do {                                                                                          \
+    static const int resident__ = ln_resident_blocks(add_ln_fwd_kernel<T, NP>, 2048);                                \
+    hipLaunchKernelGGL((add_ln_fwd_kernel<T, NP>), dim3(nblk < resident__ ? nblk : resident__), dim3(256), 0, st, (const T*)x, \
+        (const T*)res, res_stride, gamma, beta, (T*)y, (T*)z, mean, rstd, rows, H, eps, dropout_p, seed, (unsigned char*)q8, qscale); \
+  } while (0)
   LN_DISPATCH(dtype, H);
 #undef LAUNCH_
   FCMF_CHECK_LAUNCH();
@@ -546,7 +555,7 @@ static int add_ln_fwd_impl(const void* x, const void* res, int64_t res_stride, c
 
 static int ln_bwd_blocks(int rows) {
   int blocks = (rows + 3) / 4;
-  return blocks > 1024 ? 1024 : blocks;   // 4 workgroups per CU keep enough rows in flight; fewer partial rows for the reduce pass
+  return blocks > 1024 ? 1024 : blocks;   // at most 4 workgroups per CU: what the workspace is sized for (a launch may use fewer)
 }
 
 extern "C" int64_t fcmf_add_ln_bwd_workspace(int rows, int H) { return (int64_t)ln_bwd_blocks(rows) * 3 * H; }
@@ -573,15 +582,22 @@ static int add_ln_bwd_impl(const void* dy, const void* z, const float* gamma, co
   if (dropout_p > 0.f && !dx) return FCMF_ERR_ARG;
   if (rows == 0) return FCMF_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int blocks = ln_bwd_blocks(rows);
+  int blocks = ln_bwd_blocks(rows);
   if (dtype != FCMF_F32 && dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
-#define LAUNCH_(T, NP) hipLaunchKernelGGL((add_ln_bwd_kernel<T, NP>), dim3(blocks), dim3(256), 0, st, (const T*)dy, (const T*)z, \
-    gamma, mean, rstd, (T*)dz, (T*)(dropout_p > 0.f ? dx : nullptr), dgamma, dbeta, dxsum, workspace, rows, H, dropout_p, seed, \
-    (unsigned char*)q8, qscale)
+#define LAUNCH_(T, NP) do {                                                                                          \
+    static const int resident__ = ln_resident_blocks(add_ln_bwd_kernel<T, NP>, 1024);                                \
+    blocks = blocks < resident__ ? blocks : resident__;                                                              \
+    hipLaunchKernelGGL((add_ln_bwd_kernel<T, NP>), dim3(blocks), dim3(256), 0, st, (const T*)dy, (const T*)z, gamma, mean, rstd, \
+        (T*)dz, (T*)(dropout_p > 0.f ? dx : nullptr), dgamma, dbeta, dxsum, workspace, rows, H, dropout_p, seed,     \
+        (unsigned char*)q8, qscale);                                                                                 \
+  } while (0)
   LN_DISPATCH(dtype, H);
 #undef LAUNCH_
-  if (workspace)
-    hipLaunchKernelGGL(ln_partial_reduce_kernel, dim3((H + 63) / 64, 3, 8), dim3(256), 0, st, workspace, blocks, H, dgamma, dbeta, dxsum);
+  if (workspace) {
+    const int bx = (H + 255) / 256, rpb = colsum_rows_per_block(blocks, 3 * bx, 1);
+    hipLaunchKernelGGL(ln_partial_reduce_kernel, dim3(bx, (blocks + rpb - 1) / rpb, 3), dim3(COLSUM_WAVES * 64), 0, st, workspace,
+                       blocks, H, dgamma, dbeta, dxsum, rpb, (int)((reinterpret_cast<uintptr_t>(workspace) & 15) == 0));
+  }
   FCMF_CHECK_LAUNCH();
   return FCMF_OK;
 }
