@@ -158,6 +158,16 @@ int fcmf_attn_small_bwd(const fcmf_attn_desc* desc /*host*/, const void* out, co
 int fcmf_attn_small_bwd_grouped(const fcmf_attn_desc* desc, const void* out, const void* dout,
                                 const float* lse, void* dq, void* dk1, void* dv1, void* dk2, void* dv2,
                                 float* dbias, float* scratch, int64_t scratch_bytes, void* stream);
+/* What the three entry points above would launch for a descriptor, without a device (host only: nothing is launched, no
+ * pointer is read; tests, tools and the Python layer's key limit).  backward / grouped select the entry point; has_dbias /
+ * has_dv1: dbias / dv1 non-NULL; ptrs_aligned: the call's output and gradient pointers (out; out, dout, dq, dk1, dv1) are all
+ * 16-byte aligned.  Returns what the entry point would (its NULL-argument and scratch-size checks aside).  info[11] = kernel id,
+ * grid x, grid y, dynamic LDS bytes, RB (query rows staged per block), TLP, KVF (floats: pitch of the backward's key arrays,
+ * size of the shared K + V images), then the attn_private_grad_kernel launch behind a grouped backward: kernel id (-1 = none),
+ * grid x, grid y, dynamic LDS bytes; kernel id -1 and zeros unless FCMF_OK.  Every launch has 256 threads per workgroup.
+ * kernels (host, may be NULL): [2] names of the two kernels (static storage; NULL where there is none). */
+int fcmf_attn_small_plan(const fcmf_attn_desc* desc /*host*/, int backward, int grouped, int has_dbias, int has_dv1, int ptrs_aligned,
+                         int32_t* info /*host*/, const char** kernels /*host*/);
 
 /* ---------------------------------------------------------------------------------------
  * MFMA self/cross attention for bf16, head dim 64, Tq, Tk <= 256 (the text-encoder layers: 128 tokens in FCMF-base,

@@ -11,7 +11,11 @@
 // Used for every attention on the path in fp32 (parity) mode and, in bf16 mode, for the dead-row-pruned
 // fusion layers (1 live query row per image), the 15-token fusion layer, the geometry-biased ROI attention
 // and the IAOG decoder; the bf16 text-encoder attention runs on attn_mfma.hip instead.
-#include "common.h"
+// Three kernel families (ATTN_SMALL_KERNELS lists every instantiation): the general two-segment kernels below, the all-in-LDS
+// "dense" kernels (tiny: one shared segment of <= 128 keys on the matrix cores; rows_flat: <= 16 query rows) built from the
+// phases of the second part, and attn_private_grad_kernel.  The host side is attn_small_plan (descriptor -> kernel, grid, LDS:
+// no HIP call) and run_plan (the only place that launches).
+#include "attn_tiles.h"   // al16
 
 constexpr int AS_MAXT = 512;   // T1 + T2 <= 512 (forward: KPL = 4 or 8 keys per lane; FCMF-large fuses 256 text + 100 ROI keys)
 constexpr int AS_MAXD = 128;   // head dim <= 128 (two elements per lane)
@@ -141,6 +145,37 @@ __device__ __forceinline__ bool private_rows_vectorisable(const fcmf_attn_desc& 
          (reinterpret_cast<uintptr_t>(a.k2) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.v2) & 15) == 0;
 }
 
+// One wave's softmax with dropout over row r of (g, h), KPL keys per lane: sc[n] = score of key lane + 64 n (-inf past T).  The
+// dropped probabilities go to dst[t], the row's logsumexp to P.lse.  Used by every forward of this file.  DIV: p = e / sum (the
+// tiny kernels) instead of e * (1 / sum) -- the two round differently, and each family keeps the bits it has always produced.
+template <int KPL, bool DIV>
+__device__ __forceinline__ void softmax_dropout_row(float (&sc)[KPL], int T, int lane, const AttnK& P, int g, int h, int r, float inv_keep,
+                                                    float* dst) {
+  const fcmf_attn_desc& a = P.a;
+  float m = -INFINITY;
+#pragma unroll
+  for (int n = 0; n < KPL; ++n) m = fmaxf(m, sc[n]);
+  m = wave_max(m);
+  float sum = 0.f;
+#pragma unroll
+  for (int n = 0; n < KPL; ++n) {
+    sc[n] = lane + 64 * n < T ? __expf(sc[n] - m) : 0.f;
+    sum += sc[n];
+  }
+  sum = wave_sum(sum);
+  const float inv = 1.0f / sum;
+#pragma unroll
+  for (int n = 0; n < KPL; ++n) {
+    const int t = lane + 64 * n;
+    if (t < T) {
+      float pv = DIV ? sc[n] / sum : sc[n] * inv;
+      if (a.dropout_p > 0.f) pv *= dropout_mult(a.seed, (((uint64_t)g * a.heads + h) * a.R + r) * T + t, a.dropout_p, inv_keep);
+      dst[t] = pv;
+    }
+  }
+  if (lane == 0 && P.lse) P.lse[((int64_t)g * a.heads + h) * a.R + r] = m + __logf(sum);
+}
+
 // DC = head dimension when it is 64 (the text / fusion layers of FCMF: loops unroll, the 16-byte loads of a private key
 // row are all in flight together; 274 -> 120 us on the step's two fusion attentions), 0 = taken from the descriptor.
 // (Eight waves per workgroup -- one per query row of the 7-row fusion layers -- were measured slower than four.)
@@ -195,7 +230,6 @@ __global__ __launch_bounds__(256) void attn_small_fwd_kernel(AttnK P) {
         }
         sc[n] = accv;
       }
-      float m = -INFINITY;
 #pragma unroll
       for (int n = 0; n < KPL; ++n) {
         const int t = lane + 64 * n;
@@ -207,30 +241,8 @@ __global__ __launch_bounds__(256) void attn_small_fwd_kernel(AttnK P) {
           if (a.causal && t > r) s = -1e4f;
         }
         sc[n] = s;
-        m = fmaxf(m, s);
       }
-      m = wave_max(m);
-      float sum = 0.f;
-#pragma unroll
-      for (int n = 0; n < KPL; ++n) {
-        const int t = lane + 64 * n;
-        const float e = t < T ? __expf(sc[n] - m) : 0.f;
-        sc[n] = e;
-        sum += e;
-      }
-      sum = wave_sum(sum);
-      const float inv = 1.0f / sum;
-#pragma unroll
-      for (int n = 0; n < KPL; ++n) {
-        const int t = lane + 64 * n;
-        if (t < T) {
-          float pv = sc[n] * inv;
-          if (a.dropout_p > 0.f)
-            pv *= dropout_mult(a.seed, (((uint64_t)g * a.heads + h) * a.R + r) * T + t, a.dropout_p, inv_keep);
-          p[t] = pv;
-        }
-      }
-      if (lane == 0 && P.lse) P.lse[((int64_t)g * a.heads + h) * a.R + r] = m + __logf(sum);
+      softmax_dropout_row<KPL, false>(sc, T, lane, P, g, h, r, inv_keep, p);
       // out[c] = sum_t p[t] v[t][c]: lanes across the head dimension (p is read back by the wave that wrote it)
       float o0 = 0.f, o1 = 0.f;
       {
@@ -611,19 +623,56 @@ __global__ __launch_bounds__(256) void attn_private_grad_kernel(AttnK P) {
 }
 
 // =========================================================================================================================
-// "Tiny dense" attention: one shared key segment of <= 64 keys, <= 64 query rows, bf16, no causal fill (the geometry-biased
-// ROI attention: 36 x 36, 8 heads of 96; 4 us of arithmetic per (group, head)).  The general kernels above walk the query
-// rows one wave at a time (9 rounds of dependent LDS / reduction latencies here); with everything in LDS this one is a few
-// flat, fully parallel loops: thread = (row, key) for the scores, wave = row for the softmax, thread = (row, column) for the
-// outputs.  Same arithmetic, same dropout counters, same outputs as the general kernels.
+// The dense kernels: bf16, no causal fill, every operand of one (group, head) in LDS, a few flat, fully parallel loops instead
+// of the general kernels' wave-per-row rounds of dependent LDS / reduction latencies.  Same arithmetic, same dropout counters,
+// same outputs as the general kernels.  Two families share one LDS layout and the phases below:
+//   tiny       one shared key segment, <= 128 rows x 128 keys (the geometry-biased ROI attention: 36 x 36, 8 heads of 96; 4 us of
+//              arithmetic per (group, head)): thread = (row, key) scores -- on the matrix cores when d % 32 == 0 --, wave = row
+//              softmax, thread = (row, 8 columns) outputs, thread = (key, 8 columns) dK / dV;
+//   rows_flat  <= 16 query rows against <= 128 shared keys and / or each row's private keys, no bias (the step's two fusion
+//              attentions: 7 [CLS] rows, one per image): the private keys' K2 / V2 rows come straight from global memory and
+//              thread = (row, 8 columns, quarter of the keys) forms the outputs / dq; the private keys of grouped sequences
+//              leave through the pd2 / ds2 scratch exactly as in the general kernel.
 // =========================================================================================================================
 constexpr int TINY_MAX = 64;        // rows / keys of the one-block kernels
 constexpr int TINY_WIDE_MAX = 128;  // ... of the wide forward / row-blocked backward (LDS permitting)
-constexpr size_t TINY_LDS = 160 * 1024;
+constexpr size_t TINY_LDS = 160 * 1024, FLAT_LDS = 64 * 1024;
 
-__device__ __forceinline__ float dot_bf16_lds(const bf16_t* a, const bf16_t* b, int d) {      // d % 8 == 0, 16-byte aligned rows
-  // v_dot2c_f32_bf16: two bf16 products added to an f32 accumulator per instruction, no conversions (two interleaved
-  // accumulation chains)
+// The LDS layout of the dense kernels, for the host (bytes = the launch's dynamic LDS) and for the kernels (their pointers):
+//   bf16 images, row pitch dp = d + 8:   Q [R][dp] | dO [R][dp] (backward only) | K [T1][dp] | V [T1][dp]
+//   f32 arrays, row pitch TP = T1+T2+1:  PD [rows][TP] (forward: the scores, then the dropped probabilities)
+//                                        | DS [rows][TP] score offsets, then score gradients | delta [R]      (backward only)
+// rows = R, or the row block of attn_tiny_bwd_blocked_kernel.  frag_pad (the tiny kernels): frag_xyT reads 16 rows at a time,
+// so up to 15 rows (15 dp bf16) past the end of the last image it is given -- K in the forward, where V and the scores follow, V
+// in the backward, where the f32 arrays follow (counted at min(R, 16) rows: no launch has fewer).  Where that is less than the
+// 15 rows, a pad at the end of the allocation makes up the difference.
+struct AttnDenseLds {
+  int q, dout, k, v;     // in bf16 elements from the start of the dynamic LDS
+  int pd, ds, delta;     // in floats
+  size_t row_bytes;      // one more row of the f32 arrays
+  size_t bytes;          // everything, pad included
+};
+__host__ __device__ inline AttnDenseLds attn_dense_lds(int R, int rows, int T1, int T2, int d, bool backward, bool frag_pad) {
+  const int dp = d + 8, TP = T1 + T2 + 1;
+  AttnDenseLds L;
+  L.q = 0;
+  L.dout = R * dp;
+  L.k = backward ? 2 * R * dp : R * dp;
+  L.v = L.k + T1 * dp;
+  L.pd = (L.v + T1 * dp) / 2;
+  L.ds = L.pd + rows * TP;
+  L.delta = backward ? L.ds + rows * TP : L.ds;
+  L.row_bytes = sizeof(float) * (backward ? 2 : 1) * (size_t)TP;
+  L.bytes = sizeof(float) * (size_t)(backward ? L.delta + R : L.ds);
+  const size_t over = (size_t)15 * dp * 2;
+  const size_t behind = backward ? sizeof(float) * ((size_t)2 * (R < 16 ? R : 16) * TP + R) : (size_t)T1 * dp * 2 + sizeof(float) * (size_t)R * TP;
+  if (frag_pad && behind < over) L.bytes += over - behind;
+  return L;
+}
+
+// <a, b> over d bf16 (d % 8 == 0, 16-byte aligned rows; a in LDS, b in LDS or global memory).  v_dot2c_f32_bf16: two bf16
+// products added to an f32 accumulator per instruction, no conversions (two interleaved accumulation chains)
+__device__ __forceinline__ float dot_bf16(const bf16_t* a, const bf16_t* __restrict__ b, int d) {
   typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
   float s0 = 0.f, s1 = 0.f;
   for (int c = 0; c < d; c += 8) {
@@ -640,7 +689,7 @@ __device__ __forceinline__ float dot_bf16_lds(const bf16_t* a, const bf16_t* b, 
 // v_mfma_f32_16x16x32_bf16 wants 8 consecutive k per lane for row (lane & 15) of either operand at k offset 8 (lane >> 4) --
 // the same 16-byte read for both (pitch 2 (d + 8) bytes: the 16 rows of a quarter wave start in distinct bank groups).  The lane
 // ends up with rows x0 + 4 (lane >> 4) + i, i = 0..3, of column y0 + (lane & 15).  Rows past the end of an operand read whatever
-// follows it inside the workgroup's LDS allocation and only reach outputs that are never stored.
+// follows it inside the workgroup's LDS allocation (attn_dense_lds) and only reach outputs that are never stored.
 __device__ __forceinline__ f32x4 frag_xyT(const bf16_t* X, const bf16_t* Y, int dp, int d, int x0, int y0, int lane) {
   f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
   const bf16_t* xr = X + (x0 + (lane & 15)) * dp + (lane >> 4) * 8;
@@ -650,22 +699,168 @@ __device__ __forceinline__ f32x4 frag_xyT(const bf16_t* X, const bf16_t* Y, int 
   return acc;
 }
 
+// ---- the phases ----------------------------------------------------------------------------------------------------------
+// the images of head h of group g: Q (and dO), shared K and V
+__device__ __forceinline__ void stage_head(bf16_t* img, const AttnDenseLds& L, const AttnK& P, int g, int h, int w, int lane, bool backward) {
+  const fcmf_attn_desc& a = P.a;
+  const int d = a.d, dp = d + 8;
+  stage_rows<bf16_t, bf16_t>(img + L.q, dp, reinterpret_cast<const bf16_t*>(a.q) + (int64_t)g * a.q_sg + h * d, a.q_sr, a.R, d, w, lane);
+  if (backward)
+    stage_rows<bf16_t, bf16_t>(img + L.dout, dp, reinterpret_cast<const bf16_t*>(P.dout) + (int64_t)g * a.o_sg + h * d, a.o_sr, a.R, d, w, lane);
+  if (a.T1 > 0) {
+    stage_rows<bf16_t, bf16_t>(img + L.k, dp, reinterpret_cast<const bf16_t*>(a.k1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, a.T1, d, w, lane);
+    stage_rows<bf16_t, bf16_t>(img + L.v, dp, reinterpret_cast<const bf16_t*>(a.v1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, a.T1, d, w, lane);
+  }
+}
+
+// delta[r] = <dO[r], O[r]> straight from global memory: wave = row
+__device__ __forceinline__ void delta_rows(float* dl, const AttnK& P, int g, int h, int w, int lane) {
+  const fcmf_attn_desc& a = P.a;
+  for (int r = w; r < a.R; r += 4) {
+    const int64_t row = (int64_t)g * a.o_sg + (int64_t)r * a.o_sr + h * a.d;
+    const bf16_t* orow = reinterpret_cast<const bf16_t*>(P.o_in) + row;
+    const bf16_t* drow = reinterpret_cast<const bf16_t*>(P.dout) + row;
+    float part = 0.f;
+    for (int c = lane; c < a.d; c += 64) part += (float)drow[c] * (float)orow[c];
+    part = wave_sum(part);
+    if (lane == 0) dl[r] = part;
+  }
+}
+
+// score offsets of the rows [r0, r0 + rb) into DS: + mask + bias - logsumexp, one coalesced pass with all loads in flight
+// together (a global load per score inside the element loop serialises on its latency).  +inf marks a row whose every key
+// carries the hard finfo.min mask: its logsumexp IS finfo.min -- log T is absorbed -- and its probabilities are uniform, as in
+// the general kernel.
+__device__ __forceinline__ void score_offsets(float* DS, int TP, int T, const AttnK& P, int g, int g2, int h, int r0, int rb, int tid) {
+  const fcmf_attn_desc& a = P.a;
+  const int64_t bias0 = (((int64_t)g2 * a.heads + h) * a.R + r0) * T;      // (the block's rows are contiguous in the bias tile)
+  for (int idx = tid; idx < rb * T; idx += 256) {
+    const int rl = idx / T, t = idx - rl * T;
+    float add = a.mask ? a.mask[(int64_t)g * T + t] : 0.f;
+    if (a.bias) add += a.bias[bias0 + idx];
+    const float lse_r = P.lse[((int64_t)g * a.heads + h) * a.R + r0 + rl];
+    DS[rl * TP + t] = lse_r <= -1e30f ? INFINITY : add - lse_r;
+  }
+}
+
+// dropped probability and score gradient of (row r = block row rl, key t) from s = q.k and dpd = dO.v; DS holds the element's
+// score offset on entry.  FLAT: no dbias; a private key's pair also goes to the pd2 / ds2 scratch of the grouped backward.
+template <bool FLAT>
+__device__ __forceinline__ void bwd_element(float* PD, float* DS, const float* dl, int TP, int T, const AttnK& P, int g, int h, int r, int rl,
+                                            int t, float s, float dpd, float inv_keep) {
+  const fcmf_attn_desc& a = P.a;
+  const float off = DS[rl * TP + t];
+  const float pr = off == INFINITY ? 1.0f / (float)T : __expf(s * a.scale + off);
+  float mult = 1.0f;
+  if (a.dropout_p > 0.f) mult = dropout_mult(a.seed, (((uint64_t)g * a.heads + h) * a.R + r) * T + t, a.dropout_p, inv_keep);
+  const float dsv = pr * (dpd * mult - dl[r]);
+  PD[rl * TP + t] = pr * mult;
+  DS[rl * TP + t] = dsv;
+  if (!FLAT && P.dbias) P.dbias[(((int64_t)g * a.heads + h) * a.R + r) * T + t] = dsv;
+  if (FLAT && t >= a.T1 && P.pd2) {
+    const int64_t i2 = (((int64_t)g * a.heads + h) * a.R + r) * a.T2 + (t - a.T1);
+    P.pd2[i2] = pr * mult;
+    P.ds2[i2] = dsv;
+  }
+}
+
+// out[rl][c .. c+8) = mul * sum_t W[rl][t] * X[t][c .. c+8) for rb rows: thread = (row, 8 columns), one 16-byte read of X per key
+// (the tiny forward's outputs from the probabilities and V; the tiny backwards' dQ rows from the score gradients and K)
+__device__ __forceinline__ void row_sums8(const float* W, int TP, const bf16_t* X, int dp, int T, int rb, int d8, float mul, bf16_t* out,
+                                          int64_t out_sr, int tid) {
+  for (int idx = tid; idx < rb * d8; idx += 256) {
+    const int rl = idx / d8, c = (idx - rl * d8) * 8;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < T; ++t) {
+      const float wv = W[rl * TP + t];
+      const bf16x8 x = *reinterpret_cast<const bf16x8*>(X + t * dp + c);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += wv * (float)x[j];
+    }
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (bf16_t)(acc[j] * mul);
+    *reinterpret_cast<bf16x8*>(out + rl * out_sr + c) = o;
+  }
+}
+
+// the same sums for few rows, shared and private keys: thread = (row, 8 columns, quarter of the keys), the four quarters in
+// neighbouring lanes and summed across them.  X2 = the private rows of (g2, head h): row r, key t2 at X2 + r k2_sr + t2 k2_st.
+__device__ __forceinline__ void row_sums8_quarters(const float* W, int TP, const bf16_t* X1, int dp, const bf16_t* X2, const fcmf_attn_desc& a,
+                                                   float mul, bf16_t* out, int64_t out_sr, int tid) {
+  const int d8 = a.d >> 3;
+  for (int item = tid >> 2; item < a.R * d8; item += 64) {
+    const int r = item / d8, c = (item - r * d8) * 8, qt = tid & 3;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int t = qt; t < a.T1; t += 4) {
+      const float wv = W[r * TP + t];
+      const bf16x8 x = *reinterpret_cast<const bf16x8*>(X1 + t * dp + c);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += wv * (float)x[j];
+    }
+    for (int t2 = qt; t2 < a.T2; t2 += 4) {
+      const float wv = W[r * TP + a.T1 + t2];
+      const bf16x8 x = *reinterpret_cast<const bf16x8*>(X2 + (int64_t)r * a.k2_sr + c + (int64_t)t2 * a.k2_st);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += wv * (float)x[j];
+    }
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float v = acc[j];
+      v += __shfl_xor(v, 1, 64);
+      v += __shfl_xor(v, 2, 64);
+      o[j] = (bf16_t)(v * mul);
+    }
+    if (qt == 0) *reinterpret_cast<bf16x8*>(out + r * out_sr + c) = o;
+  }
+}
+
+// dK / dV of (key t, columns c .. c+8): k += sum_rl DS[rl][t] Q[rl][c ..], v += sum_rl PD[rl][t] dO[rl][c ..] over rb rows (Qs / dOs
+// = the first of them), and the store of the finished sums at element `off` of the dense [G, T1, heads*d] gradients
+__device__ __forceinline__ void dkv_accumulate(float (&k)[8], float (&v)[8], const float* DS, const float* PD, int TP, const bf16_t* Qs,
+                                               const bf16_t* dOs, int dp, int t, int c, int rb) {
+  for (int rl = 0; rl < rb; ++rl) {
+    const float dsv = DS[rl * TP + t], pv = PD[rl * TP + t];
+    const bf16x8 qq = *reinterpret_cast<const bf16x8*>(Qs + rl * dp + c), gg = *reinterpret_cast<const bf16x8*>(dOs + rl * dp + c);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { k[j] += dsv * (float)qq[j]; v[j] += pv * (float)gg[j]; }
+  }
+}
+__device__ __forceinline__ void dkv_store(const float (&k)[8], const float (&v)[8], const AttnK& P, int64_t off) {
+  bf16x8 ok, ov;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { ok[j] = (bf16_t)(k[j] * P.a.scale); ov[j] = (bf16_t)v[j]; }
+  *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16_t*>(P.dk1) + off) = ok;
+  *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16_t*>(P.dv1) + off) = ov;
+}
+// ... for every shared key, all R rows at once: thread = (key, 8 columns)
+__device__ __forceinline__ void dkv_keys(const float* DS, const float* PD, int TP, const bf16_t* Qs, const bf16_t* dOs, int dp, const AttnK& P,
+                                         int g, int h, int tid) {
+  const fcmf_attn_desc& a = P.a;
+  const int d8 = a.d >> 3;
+  for (int idx = tid; idx < a.T1 * d8; idx += 256) {
+    const int t = idx / d8, c = (idx - t * d8) * 8;
+    float k[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    dkv_accumulate(k, v, DS, PD, TP, Qs, dOs, dp, t, c, a.R);
+    dkv_store(k, v, P, ((int64_t)g * a.T1 + t) * a.heads * a.d + h * a.d + c);
+  }
+}
+
+// ---- the tiny kernels ------------------------------------------------------------------------------------------------------
 template <bool WIDE>      // WIDE: 65..128 keys, two per lane in the softmax
 __global__ __launch_bounds__(256) void attn_tiny_fwd_kernel(AttnK P) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const fcmf_attn_desc& a = P.a;
   const int d = a.d, T = a.T1, R = a.R, dp = d + 8, TP = T + 1;
-  bf16_t* Qs = reinterpret_cast<bf16_t*>(sm);
-  bf16_t* Ks = Qs + R * dp;
-  bf16_t* Vs = Ks + T * dp;
-  float* Ss = reinterpret_cast<float*>(Vs + T * dp);     // [R][TP]
+  const AttnDenseLds L = attn_dense_lds(R, R, T, 0, d, false, true);
+  bf16_t* img = reinterpret_cast<bf16_t*>(sm);
+  bf16_t *Qs = img + L.q, *Ks = img + L.k, *Vs = img + L.v;
+  float* Ss = sm + L.pd;                                  // [R][TP]
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int g = blockIdx.x / a.heads, h = blockIdx.x % a.heads, g2 = g / a.group_div;
-  stage_rows<bf16_t, bf16_t>(Qs, dp, reinterpret_cast<const bf16_t*>(a.q) + (int64_t)g * a.q_sg + h * d, a.q_sr, R, d, w, lane);
-  stage_rows<bf16_t, bf16_t>(Ks, dp, reinterpret_cast<const bf16_t*>(a.k1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, T, d, w, lane);
-  stage_rows<bf16_t, bf16_t>(Vs, dp, reinterpret_cast<const bf16_t*>(a.v1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, T, d, w, lane);
-  // additive terms (bias tile + key mask) staged with the operands: one coalesced pass, all loads in flight together (a
-  // global load per score inside the loop below serialises on its latency)
+  stage_head(img, L, P, g, h, w, lane, false);
+  // additive terms (bias tile + key mask) staged with the operands: one coalesced pass, all loads in flight together
   for (int idx = tid; idx < R * T; idx += 256) {
     const int r = idx / T, t = idx - r * T;
     float add = 0.f;
@@ -689,47 +884,47 @@ __global__ __launch_bounds__(256) void attn_tiny_fwd_kernel(AttnK P) {
   } else {
     for (int idx = tid; idx < R * T; idx += 256) {
       const int r = idx / T, t = idx - r * T;
-      Ss[r * TP + t] += dot_bf16_lds(Qs + r * dp, Ks + t * dp, d) * a.scale;
+      Ss[r * TP + t] += dot_bf16(Qs + r * dp, Ks + t * dp, d) * a.scale;
     }
   }
   __syncthreads();
   const float inv_keep = a.dropout_p > 0.f ? 1.0f / (1.0f - a.dropout_p) : 1.0f;
+  constexpr int KPL = WIDE ? 2 : 1;
   for (int r = w; r < R; r += 4) {
-    const float s = lane < T ? Ss[r * TP + lane] : -INFINITY;
-    float s1 = -INFINITY;
-    if (WIDE) s1 = lane + 64 < T ? Ss[r * TP + lane + 64] : -INFINITY;
-    const float m = wave_max(WIDE ? fmaxf(s, s1) : s);
-    const float e = lane < T ? __expf(s - m) : 0.f;
-    const float e1 = WIDE && lane + 64 < T ? __expf(s1 - m) : 0.f;
-    const float sum = wave_sum(WIDE ? e + e1 : e);
-    if (lane < T) {
-      float pv = e / sum;
-      if (a.dropout_p > 0.f) pv *= dropout_mult(a.seed, (((uint64_t)g * a.heads + h) * R + r) * T + lane, a.dropout_p, inv_keep);
-      Ss[r * TP + lane] = pv;
-    }
-    if (WIDE && lane + 64 < T) {
-      float pv = e1 / sum;
-      if (a.dropout_p > 0.f) pv *= dropout_mult(a.seed, (((uint64_t)g * a.heads + h) * R + r) * T + lane + 64, a.dropout_p, inv_keep);
-      Ss[r * TP + lane + 64] = pv;
-    }
-    if (lane == 0 && P.lse) P.lse[((int64_t)g * a.heads + h) * R + r] = m + __logf(sum);
+    float sc[KPL];
+#pragma unroll
+    for (int n = 0; n < KPL; ++n) sc[n] = lane + 64 * n < T ? Ss[r * TP + lane + 64 * n] : -INFINITY;
+    softmax_dropout_row<KPL, true>(sc, T, lane, P, g, h, r, inv_keep, Ss + r * TP);
   }
   __syncthreads();
-  bf16_t* O = reinterpret_cast<bf16_t*>(P.out);
-  const int d8 = d >> 3;
-  for (int idx = tid; idx < R * d8; idx += 256) {        // thread = (row, 8 columns): one 16-byte V read per key
-    const int r = idx / d8, c = (idx - r * d8) * 8;
-    float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t < T; ++t) {
-      const float pv = Ss[r * TP + t];
-      const bf16x8 v = *reinterpret_cast<const bf16x8*>(Vs + t * dp + c);
+  row_sums8(Ss, TP, Vs, dp, T, R, d >> 3, 1.0f, reinterpret_cast<bf16_t*>(P.out) + (int64_t)g * a.o_sg + h * d, a.o_sr, tid);
+}
+
+// probabilities and score gradients of the rows [r0, r0 + rb) of a tiny backward: Q K^T and dO V^T on the matrix cores (see
+// frag_xyT) when d % 32 == 0, else thread = (row, key) -- the thread that staged the element's offset
+__device__ __forceinline__ void tiny_bwd_elements(float* PD, float* DS, const float* dl, int TP, const bf16_t* img, const AttnDenseLds& L,
+                                                  const AttnK& P, int g, int h, int r0, int rb, float inv_keep, int tid) {
+  const fcmf_attn_desc& a = P.a;
+  const int d = a.d, T = a.T1, dp = d + 8, lane = tid & 63, w = tid >> 6;
+  const bf16_t *Qs = img + L.q, *dOs = img + L.dout, *Ks = img + L.k, *Vs = img + L.v;
+  if ((d & 31) == 0) {
+    const int nfc = (T + 15) >> 4, nf = ((rb + 15) >> 4) * nfc;
+    for (int f = w; f < nf; f += 4) {
+      const int rl0 = (f / nfc) * 16, t0 = (f % nfc) * 16;
+      const f32x4 sv = frag_xyT(Qs, Ks, dp, d, r0 + rl0, t0, lane), dv = frag_xyT(dOs, Vs, dp, d, r0 + rl0, t0, lane);
+      const int t = t0 + (lane & 15);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] += pv * (float)v[j];
+      for (int i = 0; i < 4; ++i) {
+        const int rl = rl0 + 4 * (lane >> 4) + i;
+        if (rl < rb && t < T) bwd_element<false>(PD, DS, dl, TP, T, P, g, h, r0 + rl, rl, t, sv[i], dv[i], inv_keep);
+      }
     }
-    bf16x8 ov;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ov[j] = (bf16_t)o[j];
-    *reinterpret_cast<bf16x8*>(O + (int64_t)g * a.o_sg + (int64_t)r * a.o_sr + h * d + c) = ov;
+  } else {
+    for (int idx = tid; idx < rb * T; idx += 256) {
+      const int rl = idx / T, t = idx - rl * T;
+      bwd_element<false>(PD, DS, dl, TP, T, P, g, h, r0 + rl, rl, t, dot_bf16(Qs + (r0 + rl) * dp, Ks + t * dp, d),
+                         dot_bf16(dOs + (r0 + rl) * dp, Vs + t * dp, d), inv_keep);
+    }
   }
 }
 
@@ -737,104 +932,21 @@ __global__ __launch_bounds__(256) void attn_tiny_bwd_kernel(AttnK P) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const fcmf_attn_desc& a = P.a;
   const int d = a.d, T = a.T1, R = a.R, dp = d + 8, TP = T + 1;
-  bf16_t* Qs = reinterpret_cast<bf16_t*>(sm);
-  bf16_t* dOs = Qs + R * dp;
-  bf16_t* Ks = dOs + R * dp;
-  bf16_t* Vs = Ks + T * dp;
-  float* PD = reinterpret_cast<float*>(Vs + T * dp);     // [R][TP] dropped probabilities
-  float* DS = PD + R * TP;                               // [R][TP] score gradients
-  float* dl = DS + R * TP;                               // [R] delta = <dO, O>
+  const AttnDenseLds L = attn_dense_lds(R, R, T, 0, d, true, true);
+  bf16_t* img = reinterpret_cast<bf16_t*>(sm);
+  float *PD = sm + L.pd, *DS = sm + L.ds, *dl = sm + L.delta;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int g = blockIdx.x / a.heads, h = blockIdx.x % a.heads, g2 = g / a.group_div;
-  const int64_t HD = (int64_t)a.heads * d;
-  const bf16_t* dO = reinterpret_cast<const bf16_t*>(P.dout);
-  const bf16_t* O = reinterpret_cast<const bf16_t*>(P.o_in);
-  stage_rows<bf16_t, bf16_t>(Qs, dp, reinterpret_cast<const bf16_t*>(a.q) + (int64_t)g * a.q_sg + h * d, a.q_sr, R, d, w, lane);
-  stage_rows<bf16_t, bf16_t>(dOs, dp, dO + (int64_t)g * a.o_sg + h * d, a.o_sr, R, d, w, lane);
-  stage_rows<bf16_t, bf16_t>(Ks, dp, reinterpret_cast<const bf16_t*>(a.k1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, T, d, w, lane);
-  stage_rows<bf16_t, bf16_t>(Vs, dp, reinterpret_cast<const bf16_t*>(a.v1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, T, d, w, lane);
-  for (int idx = tid; idx < R * T; idx += 256) {         // additive terms staged up front (see the forward kernel)
-    const int r = idx / T, t = idx - r * T;
-    float add = 0.f;
-    if (a.mask) add = a.mask[(int64_t)g * T + t];
-    if (a.bias) add += a.bias[(((int64_t)g2 * a.heads + h) * R) * T + idx];
-    // score offset: + mask + bias - logsumexp (+inf marks a row whose every key carries the hard finfo.min mask: its
-    // logsumexp IS finfo.min -- log T is absorbed -- and its probabilities are uniform, as in the general kernel)
-    const float lse_r = P.lse[((int64_t)g * a.heads + h) * R + r];
-    DS[r * TP + t] = lse_r <= -1e30f ? INFINITY : add - lse_r;
-  }
-  for (int r = w; r < R; r += 4) {                       // delta[r] straight from global memory (dO, O rows)
-    const bf16_t* orow = O + (int64_t)g * a.o_sg + (int64_t)r * a.o_sr + h * d;
-    const bf16_t* drow = dO + (int64_t)g * a.o_sg + (int64_t)r * a.o_sr + h * d;
-    float part = 0.f;
-    for (int c = lane; c < d; c += 64) part += (float)drow[c] * (float)orow[c];
-    part = wave_sum(part);
-    if (lane == 0) dl[r] = part;
-  }
+  stage_head(img, L, P, g, h, w, lane, true);
+  score_offsets(DS, TP, T, P, g, g2, h, 0, R, tid);
+  delta_rows(dl, P, g, h, w, lane);
   __syncthreads();
   const float inv_keep = a.dropout_p > 0.f ? 1.0f / (1.0f - a.dropout_p) : 1.0f;
-  auto element = [&](int r, int t, float s, float dpd) {  // probability and score gradient of (row r, key t) from q.k and dO.v
-    const float off = DS[r * TP + t];                     // (staged above: + mask + bias - logsumexp)
-    const float pr = off == INFINITY ? 1.0f / (float)T : __expf(s * a.scale + off);
-    float mult = 1.0f;
-    if (a.dropout_p > 0.f) mult = dropout_mult(a.seed, (((uint64_t)g * a.heads + h) * R + r) * T + t, a.dropout_p, inv_keep);
-    const float dsv = pr * (dpd * mult - dl[r]);
-    PD[r * TP + t] = pr * mult;
-    DS[r * TP + t] = dsv;
-    if (P.dbias) P.dbias[(((int64_t)g * a.heads + h) * R + r) * T + t] = dsv;
-  };
-  if ((d & 31) == 0) {                                   // Q K^T and dO V^T on the matrix cores (see frag_xyT)
-    const int nfc = (T + 15) >> 4, nf = ((R + 15) >> 4) * nfc;
-    for (int f = w; f < nf; f += 4) {
-      const int r0 = (f / nfc) * 16, t0 = (f % nfc) * 16;
-      const f32x4 sv = frag_xyT(Qs, Ks, dp, d, r0, t0, lane), dv = frag_xyT(dOs, Vs, dp, d, r0, t0, lane);
-      const int t = t0 + (lane & 15);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r = r0 + 4 * (lane >> 4) + i;
-        if (r < R && t < T) element(r, t, sv[i], dv[i]);
-      }
-    }
-  } else {
-    for (int idx = tid; idx < R * T; idx += 256) {
-      const int r = idx / T, t = idx - r * T;
-      element(r, t, dot_bf16_lds(Qs + r * dp, Ks + t * dp, d), dot_bf16_lds(dOs + r * dp, Vs + t * dp, d));
-    }
-  }
+  tiny_bwd_elements(PD, DS, dl, TP, img, L, P, g, h, 0, R, inv_keep, tid);
   __syncthreads();
-  bf16_t* dQ = reinterpret_cast<bf16_t*>(P.dq);
-  bf16_t* dK = reinterpret_cast<bf16_t*>(P.dk1);
-  bf16_t* dV = reinterpret_cast<bf16_t*>(P.dv1);
-  const int d8 = d >> 3;
-  for (int idx = tid; idx < R * d8; idx += 256) {        // thread = (row, 8 columns)
-    const int r = idx / d8, c = (idx - r * d8) * 8;
-    float q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t < T; ++t) {
-      const float dsv = DS[r * TP + t];
-      const bf16x8 kk = *reinterpret_cast<const bf16x8*>(Ks + t * dp + c);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) q[j] += dsv * (float)kk[j];
-    }
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (bf16_t)(q[j] * a.scale);
-    *reinterpret_cast<bf16x8*>(dQ + ((int64_t)g * R + r) * HD + h * d + c) = o;
-  }
-  for (int idx = tid; idx < T * d8; idx += 256) {        // thread = (key, 8 columns)
-    const int t = idx / d8, c = (idx - t * d8) * 8;
-    float k[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int r = 0; r < R; ++r) {
-      const float dsv = DS[r * TP + t], pv = PD[r * TP + t];
-      const bf16x8 qq = *reinterpret_cast<const bf16x8*>(Qs + r * dp + c), gg = *reinterpret_cast<const bf16x8*>(dOs + r * dp + c);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { k[j] += dsv * (float)qq[j]; v[j] += pv * (float)gg[j]; }
-    }
-    bf16x8 ok, ov;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { ok[j] = (bf16_t)(k[j] * a.scale); ov[j] = (bf16_t)v[j]; }
-    *reinterpret_cast<bf16x8*>(dK + ((int64_t)g * T + t) * HD + h * d + c) = ok;
-    *reinterpret_cast<bf16x8*>(dV + ((int64_t)g * T + t) * HD + h * d + c) = ov;
-  }
+  row_sums8(DS, TP, img + L.k, dp, T, R, d >> 3, a.scale, reinterpret_cast<bf16_t*>(P.dq) + (int64_t)g * R * a.heads * d + h * d,
+            (int64_t)a.heads * d, tid);
+  dkv_keys(DS, PD, TP, img + L.q, img + L.dout, dp, P, g, h, tid);
 }
 
 // The same backward for geometries whose two [R][T] f32 arrays no longer fit beside the operands (FCMF-large's ROI box
@@ -847,34 +959,15 @@ __global__ __launch_bounds__(256) void attn_tiny_bwd_blocked_kernel(AttnK P) {
   constexpr int NI = 8;
   const fcmf_attn_desc& a = P.a;
   const int d = a.d, T = a.T1, R = a.R, dp = d + 8, TP = T + 1, RBK = P.RB;
-  bf16_t* Qs = reinterpret_cast<bf16_t*>(sm);
-  bf16_t* dOs = Qs + R * dp;
-  bf16_t* Ks = dOs + R * dp;
-  bf16_t* Vs = Ks + T * dp;
-  float* PD = reinterpret_cast<float*>(Vs + T * dp);     // [RBK][TP] dropped probabilities of the current row block
-  float* DS = PD + RBK * TP;                             // [RBK][TP] score gradients
-  float* dl = DS + RBK * TP;                             // [R] delta = <dO, O>
+  const AttnDenseLds L = attn_dense_lds(R, RBK, T, 0, d, true, true);
+  bf16_t* img = reinterpret_cast<bf16_t*>(sm);
+  float *PD = sm + L.pd, *DS = sm + L.ds, *dl = sm + L.delta;   // PD / DS: [RBK][TP], of the current row block
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int g = blockIdx.x / a.heads, h = blockIdx.x % a.heads, g2 = g / a.group_div;
   const int64_t HD = (int64_t)a.heads * d;
-  const bf16_t* dO = reinterpret_cast<const bf16_t*>(P.dout);
-  const bf16_t* O = reinterpret_cast<const bf16_t*>(P.o_in);
-  stage_rows<bf16_t, bf16_t>(Qs, dp, reinterpret_cast<const bf16_t*>(a.q) + (int64_t)g * a.q_sg + h * d, a.q_sr, R, d, w, lane);
-  stage_rows<bf16_t, bf16_t>(dOs, dp, dO + (int64_t)g * a.o_sg + h * d, a.o_sr, R, d, w, lane);
-  stage_rows<bf16_t, bf16_t>(Ks, dp, reinterpret_cast<const bf16_t*>(a.k1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, T, d, w, lane);
-  stage_rows<bf16_t, bf16_t>(Vs, dp, reinterpret_cast<const bf16_t*>(a.v1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, T, d, w, lane);
-  for (int r = w; r < R; r += 4) {
-    const bf16_t* orow = O + (int64_t)g * a.o_sg + (int64_t)r * a.o_sr + h * d;
-    const bf16_t* drow = dO + (int64_t)g * a.o_sg + (int64_t)r * a.o_sr + h * d;
-    float part = 0.f;
-    for (int c = lane; c < d; c += 64) part += (float)drow[c] * (float)orow[c];
-    part = wave_sum(part);
-    if (lane == 0) dl[r] = part;
-  }
+  stage_head(img, L, P, g, h, w, lane, true);
+  delta_rows(dl, P, g, h, w, lane);
   const float inv_keep = a.dropout_p > 0.f ? 1.0f / (1.0f - a.dropout_p) : 1.0f;
-  bf16_t* dQ = reinterpret_cast<bf16_t*>(P.dq);
-  bf16_t* dK = reinterpret_cast<bf16_t*>(P.dk1);
-  bf16_t* dV = reinterpret_cast<bf16_t*>(P.dv1);
   const int d8 = d >> 3, nkv = T * d8;
   float kacc[NI][8], vacc[NI][8];
 #pragma unroll
@@ -884,332 +977,147 @@ __global__ __launch_bounds__(256) void attn_tiny_bwd_blocked_kernel(AttnK P) {
   for (int r0 = 0; r0 < R; r0 += RBK) {
     const int rb = R - r0 < RBK ? R - r0 : RBK;
     __syncthreads();                                     // operands + delta staged / the previous block's arrays read
-    for (int idx = tid; idx < rb * T; idx += 256) {      // additive terms of the block, all loads in flight together
-      const int rl = idx / T, t = idx - rl * T, r = r0 + rl;
-      float add = 0.f;
-      if (a.mask) add = a.mask[(int64_t)g * T + t];
-      if (a.bias) add += a.bias[(((int64_t)g2 * a.heads + h) * R + r) * T + t];
-      const float lse_r = P.lse[((int64_t)g * a.heads + h) * R + r];
-      DS[rl * TP + t] = lse_r <= -1e30f ? INFINITY : add - lse_r;      // (+inf: fully masked row, see the one-block kernel)
-    }
-    auto element = [&](int rl, int t, float s, float dpd) {
-      const int r = r0 + rl;
-      const float off = DS[rl * TP + t];
-      const float pr = off == INFINITY ? 1.0f / (float)T : __expf(s * a.scale + off);
-      float mult = 1.0f;
-      if (a.dropout_p > 0.f) mult = dropout_mult(a.seed, (((uint64_t)g * a.heads + h) * R + r) * T + t, a.dropout_p, inv_keep);
-      const float dsv = pr * (dpd * mult - dl[r]);
-      PD[rl * TP + t] = pr * mult;
-      DS[rl * TP + t] = dsv;
-      if (P.dbias) P.dbias[(((int64_t)g * a.heads + h) * R + r) * T + t] = dsv;
-    };
-    if ((d & 31) == 0) {                                 // Q K^T and dO V^T of the row block on the matrix cores (see frag_xyT)
-      __syncthreads();                                   // (another thread staged the element's offset)
-      const int nfc = (T + 15) >> 4, nf = ((rb + 15) >> 4) * nfc;
-      for (int f = w; f < nf; f += 4) {
-        const int rl0 = (f / nfc) * 16, t0 = (f % nfc) * 16;
-        const f32x4 sv = frag_xyT(Qs, Ks, dp, d, r0 + rl0, t0, lane), dv = frag_xyT(dOs, Vs, dp, d, r0 + rl0, t0, lane);
-        const int t = t0 + (lane & 15);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int rl = rl0 + 4 * (lane >> 4) + i;
-          if (rl < rb && t < T) element(rl, t, sv[i], dv[i]);
-        }
-      }
-    } else {
-      for (int idx = tid; idx < rb * T; idx += 256) {    // (same thread per element as the staging loop: no barrier)
-        const int rl = idx / T, t = idx - rl * T;
-        element(rl, t, dot_bf16_lds(Qs + (r0 + rl) * dp, Ks + t * dp, d), dot_bf16_lds(dOs + (r0 + rl) * dp, Vs + t * dp, d));
-      }
-    }
+    score_offsets(DS, TP, T, P, g, g2, h, r0, rb, tid);
+    if ((d & 31) == 0) __syncthreads();                  // (the fragments' elements were staged by other threads)
+    tiny_bwd_elements(PD, DS, dl, TP, img, L, P, g, h, r0, rb, inv_keep, tid);
     __syncthreads();
-    for (int idx = tid; idx < rb * d8; idx += 256) {     // dQ rows of the block: thread = (row, 8 columns)
-      const int rl = idx / d8, c = (idx - rl * d8) * 8;
-      float q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      for (int t = 0; t < T; ++t) {
-        const float dsv = DS[rl * TP + t];
-        const bf16x8 kk = *reinterpret_cast<const bf16x8*>(Ks + t * dp + c);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) q[j] += dsv * (float)kk[j];
-      }
-      bf16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = (bf16_t)(q[j] * a.scale);
-      *reinterpret_cast<bf16x8*>(dQ + ((int64_t)g * R + r0 + rl) * HD + h * d + c) = o;
-    }
+    row_sums8(DS, TP, img + L.k, dp, T, rb, d8, a.scale, reinterpret_cast<bf16_t*>(P.dq) + ((int64_t)g * R + r0) * HD + h * d, HD, tid);
 #pragma unroll
     for (int i = 0; i < NI; ++i) {                       // dK / dV partial sums: thread = (key, 8 columns), in registers
       const int idx = tid + 256 * i;
-      if (idx < nkv) {
-        const int t = idx / d8, c = (idx - t * d8) * 8;
-        for (int rl = 0; rl < rb; ++rl) {
-          const float dsv = DS[rl * TP + t], pv = PD[rl * TP + t];
-          const bf16x8 qq = *reinterpret_cast<const bf16x8*>(Qs + (r0 + rl) * dp + c);
-          const bf16x8 gg = *reinterpret_cast<const bf16x8*>(dOs + (r0 + rl) * dp + c);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) { kacc[i][j] += dsv * (float)qq[j]; vacc[i][j] += pv * (float)gg[j]; }
-        }
-      }
+      if (idx < nkv) dkv_accumulate(kacc[i], vacc[i], DS, PD, TP, img + L.q + r0 * dp, img + L.dout + r0 * dp, dp, idx / d8, (idx % d8) * 8, rb);
     }
   }
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int idx = tid + 256 * i;
-    if (idx < nkv) {
-      const int t = idx / d8, c = (idx - t * d8) * 8;
-      bf16x8 ok, ov;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { ok[j] = (bf16_t)(kacc[i][j] * a.scale); ov[j] = (bf16_t)vacc[i][j]; }
-      *reinterpret_cast<bf16x8*>(dK + ((int64_t)g * T + t) * HD + h * d + c) = ok;
-      *reinterpret_cast<bf16x8*>(dV + ((int64_t)g * T + t) * HD + h * d + c) = ov;
-    }
+    if (idx < nkv) dkv_store(kacc[i], vacc[i], P, ((int64_t)g * T + idx / d8) * HD + h * d + (idx % d8) * 8);
   }
 }
 
-// =========================================================================================================================
-// "Few query rows" backward: the two fusion attentions of the step (R = 7 [CLS] rows, one per image, against <= 128 shared
-// text keys and / or each row's own private keys; bf16, no bias, no causal fill).  The general kernel gives a wave a row (7
-// rows on 4 waves: two rounds, the second three quarters full) and then a shared key (32 keys per wave one after the other,
-// 7-long dependent sums, 128-byte stores).  Nothing here needs a reduction -- the probabilities come from the saved
-// logsumexp -- so the work is flat: thread = (row, key) for probabilities / score gradients, thread = (row, 8 columns,
-// quarter of the keys) for dq, thread = (shared key, 8 columns) for dk1 / dv1 with 16-byte stores.  Same dropout counters;
-// the private keys of grouped sequences leave through the pd2 / ds2 scratch exactly as in the general kernel.
-// =========================================================================================================================
-__device__ __forceinline__ float dot_bf16_lds_gl(const bf16_t* a_lds, const bf16_t* __restrict__ b_gl, int d) {   // d % 8 == 0
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  float s0 = 0.f, s1 = 0.f;
-  for (int c = 0; c < d; c += 8) {
-    const bf16x8 x = *reinterpret_cast<const bf16x8*>(a_lds + c), y = *reinterpret_cast<const bf16x8*>(b_gl + c);
-    s0 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2_t{x[0], x[1]}, bf16x2_t{y[0], y[1]}, s0, false);
-    s1 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2_t{x[2], x[3]}, bf16x2_t{y[2], y[3]}, s1, false);
-    s0 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2_t{x[4], x[5]}, bf16x2_t{y[4], y[5]}, s0, false);
-    s1 = __builtin_amdgcn_fdot2_f32_bf16(bf16x2_t{x[6], x[7]}, bf16x2_t{y[6], y[7]}, s1, false);
-  }
-  return s0 + s1;
-}
-
+// ---- the rows_flat kernels ---------------------------------------------------------------------------------------------------
+// Nothing in the backward needs a reduction -- the probabilities come from the saved logsumexp -- so the work is flat.  (The
+// general kernel gives a wave a row -- 7 rows on 4 waves: two rounds, the second three quarters full -- and then a shared key: 32
+// keys per wave one after the other, 7-long dependent sums, 128-byte stores.)
 __global__ __launch_bounds__(256) void attn_rows_flat_bwd_kernel(AttnK P) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const fcmf_attn_desc& a = P.a;
-  const int d = a.d, T1 = a.T1, T2 = a.T2, T = T1 + T2, R = a.R, dp = d + 8, TP = T + 1, d8 = d >> 3;
-  bf16_t* Qs = reinterpret_cast<bf16_t*>(sm);            // [R][dp]
-  bf16_t* dOs = Qs + R * dp;                             // [R][dp]
-  bf16_t* Ks = dOs + R * dp;                             // [T1][dp]
-  bf16_t* Vs = Ks + T1 * dp;                             // [T1][dp]
-  float* PD = reinterpret_cast<float*>(Vs + T1 * dp);    // [R][TP] dropped probabilities
-  float* DS = PD + R * TP;                               // [R][TP] score gradients
-  float* dl = DS + R * TP;                               // [R] delta = <dO, O>
+  const int d = a.d, T1 = a.T1, T = T1 + a.T2, R = a.R, dp = d + 8, TP = T + 1;
+  const AttnDenseLds L = attn_dense_lds(R, R, T1, a.T2, d, true, false);
+  bf16_t* img = reinterpret_cast<bf16_t*>(sm);
+  bf16_t *Qs = img + L.q, *dOs = img + L.dout, *Ks = img + L.k, *Vs = img + L.v;
+  float *PD = sm + L.pd, *DS = sm + L.ds, *dl = sm + L.delta;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int g = blockIdx.x / a.heads, h = blockIdx.x % a.heads, g2 = g / a.group_div;
-  const int64_t HD = (int64_t)a.heads * d;
-  const bf16_t* dO = reinterpret_cast<const bf16_t*>(P.dout);
-  const bf16_t* O = reinterpret_cast<const bf16_t*>(P.o_in);
-  const bf16_t* K2 = reinterpret_cast<const bf16_t*>(a.k2);
-  const bf16_t* V2 = reinterpret_cast<const bf16_t*>(a.v2);
-  stage_rows<bf16_t, bf16_t>(Qs, dp, reinterpret_cast<const bf16_t*>(a.q) + (int64_t)g * a.q_sg + h * d, a.q_sr, R, d, w, lane);
-  stage_rows<bf16_t, bf16_t>(dOs, dp, dO + (int64_t)g * a.o_sg + h * d, a.o_sr, R, d, w, lane);
-  if (T1 > 0) {
-    stage_rows<bf16_t, bf16_t>(Ks, dp, reinterpret_cast<const bf16_t*>(a.k1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, T1, d, w, lane);
-    stage_rows<bf16_t, bf16_t>(Vs, dp, reinterpret_cast<const bf16_t*>(a.v1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, T1, d, w, lane);
-  }
-  for (int idx = tid; idx < R * T; idx += 256) {         // score offsets: + mask - logsumexp (+inf: fully hard-masked row)
-    const int r = idx / T, t = idx - r * T;
-    const float add = a.mask ? a.mask[(int64_t)g * T + t] : 0.f;
-    const float lse_r = P.lse[((int64_t)g * a.heads + h) * R + r];
-    DS[r * TP + t] = lse_r <= -1e30f ? INFINITY : add - lse_r;
-  }
-  for (int r = w; r < R; r += 4) {
-    const bf16_t* orow = O + (int64_t)g * a.o_sg + (int64_t)r * a.o_sr + h * d;
-    const bf16_t* drow = dO + (int64_t)g * a.o_sg + (int64_t)r * a.o_sr + h * d;
-    float part = 0.f;
-    for (int c = lane; c < d; c += 64) part += (float)drow[c] * (float)orow[c];
-    part = wave_sum(part);
-    if (lane == 0) dl[r] = part;
-  }
+  const bf16_t* K2 = reinterpret_cast<const bf16_t*>(a.k2) + (int64_t)g2 * a.k2_sg + h * d;
+  const bf16_t* V2 = reinterpret_cast<const bf16_t*>(a.v2) + (int64_t)g2 * a.k2_sg + h * d;
+  stage_head(img, L, P, g, h, w, lane, true);
+  score_offsets(DS, TP, T, P, g, g2, h, 0, R, tid);
+  delta_rows(dl, P, g, h, w, lane);
   __syncthreads();
   const float inv_keep = a.dropout_p > 0.f ? 1.0f / (1.0f - a.dropout_p) : 1.0f;
-  for (int idx = tid; idx < R * T; idx += 256) {         // thread = (row, key)
+  for (int idx = tid; idx < R * T; idx += 256) {         // thread = (row, key): the thread that staged the element's offset
     const int r = idx / T, t = idx - r * T;
     float s, dpd;
     if (t < T1) {
-      s = dot_bf16_lds(Qs + r * dp, Ks + t * dp, d);
-      dpd = dot_bf16_lds(dOs + r * dp, Vs + t * dp, d);
+      s = dot_bf16(Qs + r * dp, Ks + t * dp, d);
+      dpd = dot_bf16(dOs + r * dp, Vs + t * dp, d);
     } else {                                             // private key: its K2 / V2 rows straight from global memory
-      const int64_t o2 = (int64_t)g2 * a.k2_sg + (int64_t)r * a.k2_sr + (int64_t)(t - T1) * a.k2_st + h * d;
-      s = dot_bf16_lds_gl(Qs + r * dp, K2 + o2, d);
-      dpd = dot_bf16_lds_gl(dOs + r * dp, V2 + o2, d);
+      const int64_t o2 = (int64_t)r * a.k2_sr + (int64_t)(t - T1) * a.k2_st;
+      s = dot_bf16(Qs + r * dp, K2 + o2, d);
+      dpd = dot_bf16(dOs + r * dp, V2 + o2, d);
     }
-    const float off = DS[r * TP + t];                    // (staged by this same thread)
-    const float pr = off == INFINITY ? 1.0f / (float)T : __expf(s * a.scale + off);
-    float mult = 1.0f;
-    if (a.dropout_p > 0.f) mult = dropout_mult(a.seed, (((uint64_t)g * a.heads + h) * R + r) * T + t, a.dropout_p, inv_keep);
-    const float dsv = pr * (dpd * mult - dl[r]);
-    PD[r * TP + t] = pr * mult;
-    DS[r * TP + t] = dsv;
-    if (t >= T1 && P.pd2) {
-      const int64_t i2 = (((int64_t)g * a.heads + h) * R + r) * T2 + (t - T1);
-      P.pd2[i2] = pr * mult;
-      P.ds2[i2] = dsv;
-    }
+    bwd_element<true>(PD, DS, dl, TP, T, P, g, h, r, r, t, s, dpd, inv_keep);
   }
   __syncthreads();
-  // dq[r][c] = scale * sum_t ds[r][t] k[t][c]: thread = (row, 8 columns, quarter of the keys), the four quarters in
-  // neighbouring lanes and summed across them
-  bf16_t* dQ = reinterpret_cast<bf16_t*>(P.dq);
-  for (int item = tid >> 2; item < R * d8; item += 64) {
-    const int r = item / d8, c = (item - r * d8) * 8, qt = tid & 3;
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int t = qt; t < T1; t += 4) {
-      const float dsv = DS[r * TP + t];
-      const bf16x8 kk = *reinterpret_cast<const bf16x8*>(Ks + t * dp + c);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += dsv * (float)kk[j];
-    }
-    const int64_t p2 = (int64_t)g2 * a.k2_sg + (int64_t)r * a.k2_sr + h * d + c;
-    for (int t2 = qt; t2 < T2; t2 += 4) {
-      const float dsv = DS[r * TP + T1 + t2];
-      const bf16x8 kk = *reinterpret_cast<const bf16x8*>(K2 + p2 + (int64_t)t2 * a.k2_st);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += dsv * (float)kk[j];
-    }
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float v = acc[j];
-      v += __shfl_xor(v, 1, 64);
-      v += __shfl_xor(v, 2, 64);
-      o[j] = (bf16_t)(v * a.scale);
-    }
-    if (qt == 0) *reinterpret_cast<bf16x8*>(dQ + ((int64_t)g * R + r) * HD + h * d + c) = o;
-  }
-  // dk1 / dv1 [t][c] = sum_r ds / pd [r][t] * q / dO [r][c]: thread = (shared key, 8 columns)
-  bf16_t* dK = reinterpret_cast<bf16_t*>(P.dk1);
-  bf16_t* dV = reinterpret_cast<bf16_t*>(P.dv1);
-  for (int idx = tid; idx < T1 * d8; idx += 256) {
-    const int t = idx / d8, c = (idx - t * d8) * 8;
-    float k[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int r = 0; r < R; ++r) {
-      const float dsv = DS[r * TP + t], pv = PD[r * TP + t];
-      const bf16x8 qq = *reinterpret_cast<const bf16x8*>(Qs + r * dp + c), gg = *reinterpret_cast<const bf16x8*>(dOs + r * dp + c);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { k[j] += dsv * (float)qq[j]; v[j] += pv * (float)gg[j]; }
-    }
-    bf16x8 ok, ov;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { ok[j] = (bf16_t)(k[j] * a.scale); ov[j] = (bf16_t)v[j]; }
-    *reinterpret_cast<bf16x8*>(dK + ((int64_t)g * T1 + t) * HD + h * d + c) = ok;
-    *reinterpret_cast<bf16x8*>(dV + ((int64_t)g * T1 + t) * HD + h * d + c) = ov;
-  }
+  row_sums8_quarters(DS, TP, Ks, dp, K2, a, a.scale, reinterpret_cast<bf16_t*>(P.dq) + (int64_t)g * R * a.heads * d + h * d,
+                     (int64_t)a.heads * d, tid);
+  dkv_keys(DS, PD, TP, Qs, dOs, dp, P, g, h, tid);
 }
 
-// the forward of the same geometry, flat as well: thread = (row, key) scores, wave = row softmax (a few elements per lane),
-// thread = (row, 8 columns, quarter of the keys) outputs
+// the forward of the same geometry: thread = (row, key) scores, wave = row softmax (T <= 384 keys: up to 6 per lane), thread =
+// (row, 8 columns, quarter of the keys) outputs
 __global__ __launch_bounds__(256) void attn_rows_flat_fwd_kernel(AttnK P) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const fcmf_attn_desc& a = P.a;
-  const int d = a.d, T1 = a.T1, T2 = a.T2, T = T1 + T2, R = a.R, dp = d + 8, TP = T + 1, d8 = d >> 3;
-  bf16_t* Qs = reinterpret_cast<bf16_t*>(sm);            // [R][dp]
-  bf16_t* Ks = Qs + R * dp;                              // [T1][dp]
-  bf16_t* Vs = Ks + T1 * dp;                             // [T1][dp]
-  float* Ss = reinterpret_cast<float*>(Vs + T1 * dp);    // [R][TP] scores, then dropped probabilities
+  const int d = a.d, T1 = a.T1, T = T1 + a.T2, R = a.R, dp = d + 8, TP = T + 1;
+  const AttnDenseLds L = attn_dense_lds(R, R, T1, a.T2, d, false, false);
+  bf16_t* img = reinterpret_cast<bf16_t*>(sm);
+  bf16_t *Qs = img + L.q, *Ks = img + L.k, *Vs = img + L.v;
+  float* Ss = sm + L.pd;                                  // [R][TP] scores, then dropped probabilities
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int g = blockIdx.x / a.heads, h = blockIdx.x % a.heads, g2 = g / a.group_div;
-  const bf16_t* K2 = reinterpret_cast<const bf16_t*>(a.k2);
-  const bf16_t* V2 = reinterpret_cast<const bf16_t*>(a.v2);
-  stage_rows<bf16_t, bf16_t>(Qs, dp, reinterpret_cast<const bf16_t*>(a.q) + (int64_t)g * a.q_sg + h * d, a.q_sr, R, d, w, lane);
-  if (T1 > 0) {
-    stage_rows<bf16_t, bf16_t>(Ks, dp, reinterpret_cast<const bf16_t*>(a.k1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, T1, d, w, lane);
-    stage_rows<bf16_t, bf16_t>(Vs, dp, reinterpret_cast<const bf16_t*>(a.v1) + (int64_t)g * a.k1_sg + h * d, a.k1_st, T1, d, w, lane);
-  }
+  const bf16_t* K2 = reinterpret_cast<const bf16_t*>(a.k2) + (int64_t)g2 * a.k2_sg + h * d;
+  const bf16_t* V2 = reinterpret_cast<const bf16_t*>(a.v2) + (int64_t)g2 * a.k2_sg + h * d;
+  stage_head(img, L, P, g, h, w, lane, false);
   __syncthreads();
   for (int idx = tid; idx < R * T; idx += 256) {         // thread = (row, key)
     const int r = idx / T, t = idx - r * T;
     float s;
-    if (t < T1) s = dot_bf16_lds(Qs + r * dp, Ks + t * dp, d);
-    else s = dot_bf16_lds_gl(Qs + r * dp, K2 + (int64_t)g2 * a.k2_sg + (int64_t)r * a.k2_sr + (int64_t)(t - T1) * a.k2_st + h * d, d);
+    if (t < T1) s = dot_bf16(Qs + r * dp, Ks + t * dp, d);
+    else s = dot_bf16(Qs + r * dp, K2 + (int64_t)r * a.k2_sr + (int64_t)(t - T1) * a.k2_st, d);
     s *= a.scale;
     if (a.mask) s += a.mask[(int64_t)g * T + t];
     Ss[r * TP + t] = s;
   }
   __syncthreads();
   const float inv_keep = a.dropout_p > 0.f ? 1.0f / (1.0f - a.dropout_p) : 1.0f;
-  for (int r = w; r < R; r += 4) {                       // wave = row: T <= 384 keys, up to 6 per lane
-    float sv[6], m = -INFINITY;
+  for (int r = w; r < R; r += 4) {
+    float sc[6];
 #pragma unroll
-    for (int n = 0; n < 6; ++n) {
-      const int t = lane + 64 * n;
-      sv[n] = t < T ? Ss[r * TP + t] : -INFINITY;
-      m = fmaxf(m, sv[n]);
-    }
-    m = wave_max(m);
-    float sum = 0.f;
-#pragma unroll
-    for (int n = 0; n < 6; ++n) {
-      const int t = lane + 64 * n;
-      sv[n] = t < T ? __expf(sv[n] - m) : 0.f;
-      sum += sv[n];
-    }
-    sum = wave_sum(sum);
-    const float inv = 1.0f / sum;
-#pragma unroll
-    for (int n = 0; n < 6; ++n) {
-      const int t = lane + 64 * n;
-      if (t < T) {
-        float pv = sv[n] * inv;
-        if (a.dropout_p > 0.f) pv *= dropout_mult(a.seed, (((uint64_t)g * a.heads + h) * R + r) * T + t, a.dropout_p, inv_keep);
-        Ss[r * TP + t] = pv;
-      }
-    }
-    if (lane == 0 && P.lse) P.lse[((int64_t)g * a.heads + h) * R + r] = m + __logf(sum);
+    for (int n = 0; n < 6; ++n) sc[n] = lane + 64 * n < T ? Ss[r * TP + lane + 64 * n] : -INFINITY;
+    softmax_dropout_row<6, false>(sc, T, lane, P, g, h, r, inv_keep, Ss + r * TP);
   }
   __syncthreads();
-  bf16_t* O = reinterpret_cast<bf16_t*>(P.out);
-  for (int item = tid >> 2; item < R * d8; item += 64) {  // thread = (row, 8 columns, quarter of the keys)
-    const int r = item / d8, c = (item - r * d8) * 8, qt = tid & 3;
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int t = qt; t < T1; t += 4) {
-      const float pv = Ss[r * TP + t];
-      const bf16x8 vv = *reinterpret_cast<const bf16x8*>(Vs + t * dp + c);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += pv * (float)vv[j];
-    }
-    const int64_t p2 = (int64_t)g2 * a.k2_sg + (int64_t)r * a.k2_sr + h * d + c;
-    for (int t2 = qt; t2 < T2; t2 += 4) {
-      const float pv = Ss[r * TP + T1 + t2];
-      const bf16x8 vv = *reinterpret_cast<const bf16x8*>(V2 + p2 + (int64_t)t2 * a.k2_st);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] += pv * (float)vv[j];
-    }
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float v = acc[j];
-      v += __shfl_xor(v, 1, 64);
-      v += __shfl_xor(v, 2, 64);
-      o[j] = (bf16_t)v;
-    }
-    if (qt == 0) *reinterpret_cast<bf16x8*>(O + (int64_t)g * a.o_sg + (int64_t)r * a.o_sr + h * d + c) = o;
-  }
+  row_sums8_quarters(Ss, TP, Vs, dp, V2, a, 1.0f, reinterpret_cast<bf16_t*>(P.out) + (int64_t)g * a.o_sg + h * d, a.o_sr, tid);
 }
 
-// the flat few-rows backward's preconditions (host)
-static bool rows_flat_ok(const fcmf_attn_desc* a) {
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!(a->dtype == FCMF_BF16 && !a->causal && !a->head_quirk && !a->bias && a->R <= 16 && a->T1 <= 128 && a->d % 8 == 0 &&
-        a->q_sr % 8 == 0 && a->q_sg % 8 == 0 && a->o_sr % 8 == 0 && a->o_sg % 8 == 0 && al16(a->q)))
-    return false;
-  if (a->T1 > 0 && !(a->k1_st % 8 == 0 && a->k1_sg % 8 == 0 && al16(a->k1) && al16(a->v1))) return false;
-  if (a->T2 > 0 && !(a->k2_sg % 8 == 0 && a->k2_sr % 8 == 0 && a->k2_st % 8 == 0 && al16(a->k2) && al16(a->v2))) return false;
-  return true;
-}
+// =========================================================================================================================
+// Host: descriptor -> plan -> launch
+// =========================================================================================================================
+// Every kernel instantiation of this file, once: the enum, the name table and run_plan's switch are all made from this list.
+// (attn_small_plan counts on the order inside the two general families: K4, K4_D64, K8, K8_D64 and plain, GROUPED, ONE, ONE_GROUPED.)
+#define ATTN_SMALL_KERNELS(X)                                        \
+  X(AK_FWD_F32_K4, attn_small_fwd_kernel<float, 4, 0>)               \
+  X(AK_FWD_F32_K4_D64, attn_small_fwd_kernel<float, 4, 64>)          \
+  X(AK_FWD_F32_K8, attn_small_fwd_kernel<float, 8, 0>)               \
+  X(AK_FWD_F32_K8_D64, attn_small_fwd_kernel<float, 8, 64>)          \
+  X(AK_FWD_BF16_K4, attn_small_fwd_kernel<bf16_t, 4, 0>)             \
+  X(AK_FWD_BF16_K4_D64, attn_small_fwd_kernel<bf16_t, 4, 64>)        \
+  X(AK_FWD_BF16_K8, attn_small_fwd_kernel<bf16_t, 8, 0>)             \
+  X(AK_FWD_BF16_K8_D64, attn_small_fwd_kernel<bf16_t, 8, 64>)        \
+  X(AK_TINY_FWD, attn_tiny_fwd_kernel<false>)                        \
+  X(AK_TINY_FWD_WIDE, attn_tiny_fwd_kernel<true>)                    \
+  X(AK_ROWS_FLAT_FWD, attn_rows_flat_fwd_kernel)                     \
+  X(AK_BWD_F32, attn_small_bwd_kernel<float, false, false>)          \
+  X(AK_BWD_F32_GROUPED, attn_small_bwd_kernel<float, false, true>)   \
+  X(AK_BWD_F32_ONE, attn_small_bwd_kernel<float, true, false>)       \
+  X(AK_BWD_F32_ONE_GROUPED, attn_small_bwd_kernel<float, true, true>) \
+  X(AK_BWD_BF16, attn_small_bwd_kernel<bf16_t, false, false>)        \
+  X(AK_BWD_BF16_GROUPED, attn_small_bwd_kernel<bf16_t, false, true>) \
+  X(AK_BWD_BF16_ONE, attn_small_bwd_kernel<bf16_t, true, false>)     \
+  X(AK_BWD_BF16_ONE_GROUPED, attn_small_bwd_kernel<bf16_t, true, true>) \
+  X(AK_TINY_BWD, attn_tiny_bwd_kernel)                               \
+  X(AK_TINY_BWD_BLOCKED, attn_tiny_bwd_blocked_kernel)               \
+  X(AK_ROWS_FLAT_BWD, attn_rows_flat_bwd_kernel)                     \
+  X(AK_PRIVATE_GRAD_F32, attn_private_grad_kernel<float>)            \
+  X(AK_PRIVATE_GRAD_BF16, attn_private_grad_kernel<bf16_t>)
+#define X(id, ...) id,
+enum AttnSmallKernel { AK_NONE = -1, ATTN_SMALL_KERNELS(X) AK_COUNT };
+#undef X
+#define X(id, ...) #__VA_ARGS__,
+static const char* const ATTN_SMALL_KERNEL_NAMES[AK_COUNT] = {ATTN_SMALL_KERNELS(X)};
+#undef X
 
-// the tiny kernels' preconditions (host)
-static bool tiny_ok(const fcmf_attn_desc* a) {
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return a->dtype == FCMF_BF16 && a->T2 == 0 && a->T1 > 0 && a->T1 <= TINY_WIDE_MAX && a->R <= TINY_WIDE_MAX && !a->causal && !a->head_quirk &&
-         a->d % 8 == 0 && a->q_sr % 8 == 0 && a->q_sg % 8 == 0 && a->k1_st % 8 == 0 && a->k1_sg % 8 == 0 && a->o_sr % 8 == 0 &&
-         a->o_sg % 8 == 0 && al16(a->q) && al16(a->k1) && al16(a->v1);      // (+ 16-byte aligned outputs: checked by the callers)
-}
+struct AttnSmallPlan {
+  int rc;                      // FCMF_OK, or why nothing is launched
+  bool desc_ok;                // the descriptor itself passed (rc then speaks of what this file supports)
+  int kernel, grid_x, grid_y;  // AttnSmallKernel; 256 threads per workgroup throughout
+  size_t smem;
+  int RB, TLP, KVF;            // -> AttnK
+  int kernel2, grid2_x, grid2_y;   // attn_private_grad_kernel behind a grouped backward, or AK_NONE
+  size_t smem2;
+};
 
 static int check_desc(const fcmf_attn_desc* a) {
   if (!a || !a->q) return FCMF_ERR_ARG;
@@ -1222,8 +1130,22 @@ static int check_desc(const fcmf_attn_desc* a) {
   return FCMF_OK;
 }
 
-// query rows per staged block: all R if the workgroup then stays within 80 KiB of LDS (two or more workgroups
-// per CU); else blocks of >= 8 rows within 80 KiB if they fit; else as many rows as fit in 160 KiB
+// what both dense families ask of the inputs: bf16, no causal fill, no head quirk, 16-byte rows
+static bool dense_inputs_ok(const fcmf_attn_desc* a) {
+  if (!(a->dtype == FCMF_BF16 && !a->causal && !a->head_quirk && a->d % 8 == 0 && a->q_sr % 8 == 0 && a->q_sg % 8 == 0 && a->o_sr % 8 == 0 &&
+        a->o_sg % 8 == 0 && al16(a->q)))
+    return false;
+  if (a->T1 > 0 && !(a->k1_st % 8 == 0 && a->k1_sg % 8 == 0 && al16(a->k1) && al16(a->v1))) return false;
+  if (a->T2 > 0 && !(a->k2_sg % 8 == 0 && a->k2_sr % 8 == 0 && a->k2_st % 8 == 0 && al16(a->k2) && al16(a->v2))) return false;
+  return true;
+}
+static bool tiny_ok(const fcmf_attn_desc* a) {
+  return dense_inputs_ok(a) && a->T2 == 0 && a->T1 > 0 && a->T1 <= TINY_WIDE_MAX && a->R <= TINY_WIDE_MAX;
+}
+static bool rows_flat_ok(const fcmf_attn_desc* a) { return dense_inputs_ok(a) && !a->bias && a->R <= 16 && a->T1 <= 128; }
+
+// query rows per staged block of the general kernels: all R if the workgroup then stays within 80 KiB of LDS (two or more
+// workgroups per CU); else blocks of >= 8 rows within 80 KiB if they fit; else as many rows as fit in 160 KiB
 static int rows_per_block(int R, size_t base_bytes, size_t per_row_bytes) {
   const size_t soft = 80 * 1024, hard = 160 * 1024;
   if (base_bytes + (size_t)R * per_row_bytes <= soft) return R;
@@ -1233,131 +1155,135 @@ static int rows_per_block(int R, size_t base_bytes, size_t per_row_bytes) {
   return (int)(rb > (size_t)R ? R : rb);
 }
 
+// The plan: which kernel runs a descriptor, and with what grid and LDS.  Pure: no HIP call, and of the pointers only their
+// presence and alignment.  io_al16 = the output / gradient pointers of the call (out; out, dout, dq, dk1, dv1) are 16-byte aligned.
+static AttnSmallPlan attn_small_plan(const fcmf_attn_desc* a, bool backward, bool grouped, bool has_dbias, bool has_dv1, bool io_al16) {
+  AttnSmallPlan p{};
+  p.kernel = p.kernel2 = AK_NONE;
+  p.rc = check_desc(a);
+  if (p.rc) return p;
+  p.desc_ok = true;
+  p.rc = FCMF_ERR_UNSUPPORTED;
+  const int R = a->R, T1 = a->T1, T2 = a->T2, d = a->d;
+  const bool f32 = a->dtype == FCMF_F32;
+  p.grid_x = a->G * a->heads; p.grid_y = 1;
+  auto found = [&p](int kernel, size_t smem) { p.kernel = kernel; p.smem = smem; p.rc = FCMF_OK; return p; };
+  if (backward && grouped) {
+    // dk2 / dv2 summed over the group by attn_private_grad_kernel: 4 key ranges per (review, row), ~1800 workgroups on the step
+    p.smem2 = sizeof(float) * 2 * (size_t)a->group_div * a->heads * T2;
+    if (T2 <= 0 || a->group_div > 8 || a->G % a->group_div || a->head_quirk || p.smem2 > 150 * 1024) return p;
+    p.kernel2 = f32 ? AK_PRIVATE_GRAD_F32 : AK_PRIVATE_GRAD_BF16;
+    p.grid2_x = (a->G / a->group_div) * R; p.grid2_y = 4;
+  }
+  // the general kernels' LDS: the K and V images of the shared keys (of one 128-key chunk in the backward; rows of d + 16 bytes,
+  // together rounded to 16 bytes, KVF floats), then per staged query row d floats (forward; + 4 waves' probability rows of
+  // 64 KPL floats in all) or 2 d + 2 TLP floats (backward: Q, dO and the row's probabilities and score gradients)
+  const size_t esz = f32 ? 4 : 2;
+  const int nsh = backward && T1 > 128 ? 128 : T1;
+  const int KVF = (int)((2 * (size_t)nsh * (d + 16 / esz) * esz + 15) / 16 * 4);
+  if (!backward) {
+    if (tiny_ok(a) && io_al16) {
+      const AttnDenseLds L = attn_dense_lds(R, R, T1, 0, d, false, true);
+      if (L.bytes <= TINY_LDS) return found(T1 > 64 ? AK_TINY_FWD_WIDE : AK_TINY_FWD, L.bytes);
+    }
+    if (rows_flat_ok(a) && T1 + T2 <= 384 && io_al16) {
+      const AttnDenseLds L = attn_dense_lds(R, R, T1, T2, d, false, false);
+      if (L.bytes <= FLAT_LDS) return found(AK_ROWS_FLAT_FWD, L.bytes);
+    }
+    const int kpl = T1 + T2 <= 256 ? 4 : 8;              // keys per lane
+    const size_t base = sizeof(float) * ((size_t)KVF + 4 * 64 * kpl), per_row = sizeof(float) * (size_t)d;
+    p.RB = rows_per_block(R, base, per_row);
+    if (p.RB <= 0) return p;
+    p.KVF = KVF;
+    return found((f32 ? AK_FWD_F32_K4 : AK_FWD_BF16_K4) + (kpl == 8 ? 2 : 0) + (d == 64 ? 1 : 0), base + p.RB * per_row);
+  }
+  if (!grouped && has_dv1 && tiny_ok(a) && io_al16) {
+    const AttnDenseLds L = attn_dense_lds(R, 0, T1, 0, d, true, true);      // without the [rows][T + 1] arrays
+    if (R <= TINY_MAX && T1 <= TINY_MAX && L.bytes + R * L.row_bytes <= TINY_LDS) return found(AK_TINY_BWD, L.bytes + R * L.row_bytes);
+    if (L.bytes + 16 * L.row_bytes <= TINY_LDS) {        // row blocks of >= 16 rows, as even as the LDS allows
+      const int fit = (int)((TINY_LDS - L.bytes) / L.row_bytes), nblk = (R + fit - 1) / fit;
+      p.RB = (R + nblk - 1) / nblk;
+      return found(AK_TINY_BWD_BLOCKED, L.bytes + p.RB * L.row_bytes);
+    }
+  }
+  if (rows_flat_ok(a) && !has_dbias && (T2 == 0 || grouped) && (T1 == 0 || has_dv1) && io_al16) {
+    const AttnDenseLds L = attn_dense_lds(R, R, T1, T2, d, true, false);
+    if (L.bytes <= FLAT_LDS) return found(AK_ROWS_FLAT_BWD, L.bytes);
+  }
+  p.TLP = (nsh + T2 + 3) & ~3;         // multiple of 4: rows of the key arrays stay 16-byte aligned
+  const size_t base = sizeof(float) * (size_t)KVF, per_row = sizeof(float) * (2 * (size_t)d + 2 * (size_t)p.TLP);
+  p.RB = rows_per_block(R, base, per_row);
+  if (p.RB <= 0) return p;             // (cannot happen: <= 132 KiB of images + 3 KiB per row)
+  p.KVF = KVF;
+  p.grid_y = T1 > 0 ? (T1 + 127) / 128 : 1;
+  return found((f32 ? AK_BWD_F32 : AK_BWD_BF16) + (p.RB >= R ? 2 : 0) + (grouped ? 1 : 0), base + p.RB * per_row);
+}
+
+// The only place that names kernel instantiations.  The rows_flat kernels stay below the 64 KiB every kernel may take
+// and are launched as they are; every other launch first raises its kernel's dynamic-LDS limit (fcmf_launch).
+static int launch_kernel(int kernel, dim3 grid, size_t smem, hipStream_t st, const AttnK& P) {
+  bool attr_set = kernel == AK_ROWS_FLAT_FWD || kernel == AK_ROWS_FLAT_BWD;
+  switch (kernel) {
+#define X(id, ...) case id: return fcmf_launch_flagged(&attr_set, __VA_ARGS__, grid, dim3(256), smem, st, P);
+    ATTN_SMALL_KERNELS(X)
+#undef X
+  }
+  return FCMF_ERR_ARG;
+}
+static int run_plan(const AttnSmallPlan& pl, AttnK& P, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  P.RB = pl.RB; P.TLP = pl.TLP; P.KVF = pl.KVF;
+  const int rc = launch_kernel(pl.kernel, dim3(pl.grid_x, pl.grid_y), pl.smem, st, P);
+  if (rc != FCMF_OK || pl.kernel2 == AK_NONE) return rc;
+  return launch_kernel(pl.kernel2, dim3(pl.grid2_x, pl.grid2_y), pl.smem2, st, P);
+}
+
+extern "C" int fcmf_attn_small_plan(const fcmf_attn_desc* desc, int backward, int grouped, int has_dbias, int has_dv1, int ptrs_aligned,
+                                    int32_t* info, const char** kernels) {
+  if (!info) return FCMF_ERR_ARG;
+  const AttnSmallPlan pl = attn_small_plan(desc, backward != 0, grouped != 0, has_dbias != 0, has_dv1 != 0, ptrs_aligned != 0);
+  const bool ok = pl.rc == FCMF_OK;
+  const int32_t v[11] = {pl.kernel, pl.grid_x, pl.grid_y, (int32_t)pl.smem, pl.RB, pl.TLP, pl.KVF,
+                         ok ? pl.kernel2 : AK_NONE, pl.grid2_x, pl.grid2_y, (int32_t)pl.smem2};
+  for (int i = 0; i < 11; ++i) info[i] = ok || i == 0 || i == 7 ? v[i] : 0;
+  if (kernels) {
+    kernels[0] = ok ? ATTN_SMALL_KERNEL_NAMES[pl.kernel] : nullptr;
+    kernels[1] = ok && pl.kernel2 != AK_NONE ? ATTN_SMALL_KERNEL_NAMES[pl.kernel2] : nullptr;
+  }
+  return pl.rc;
+}
+
 extern "C" int fcmf_attn_small_fwd(const fcmf_attn_desc* desc, void* out, float* lse, void* stream) {
-  int rc = check_desc(desc);
-  if (rc) return rc;
+  const AttnSmallPlan pl = attn_small_plan(desc, false, false, false, false, al16(out));
+  if (!pl.desc_ok) return pl.rc;
   if (!out) return FCMF_ERR_ARG;
+  if (pl.rc) return pl.rc;
   AttnK P{};
   P.a = *desc; P.out = out; P.lse = lse;
-  if (tiny_ok(desc) && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
-    const int dp = desc->d + 8;
-    // (the matrix-core score fragments read up to 15 rows past the end of the K image: into V and the score array, or the pad)
-    size_t smem = (size_t)(desc->R + 2 * desc->T1) * dp * 2 + sizeof(float) * (size_t)desc->R * (desc->T1 + 1);
-    const size_t after_k = (size_t)desc->T1 * dp * 2 + sizeof(float) * (size_t)desc->R * (desc->T1 + 1), over = (size_t)15 * dp * 2;
-    if (after_k < over) smem += over - after_k;
-    if (smem <= TINY_LDS) {
-      auto k = desc->T1 > 64 ? attn_tiny_fwd_kernel<true> : attn_tiny_fwd_kernel<false>;
-      return fcmf_launch(k, dim3(desc->G * desc->heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
-    }
-  }
-  if (rows_flat_ok(desc) && desc->T1 + desc->T2 <= 384 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
-    const int dp = desc->d + 8, TP = desc->T1 + desc->T2 + 1;
-    const size_t smem = (size_t)(desc->R + 2 * desc->T1) * dp * 2 + sizeof(float) * (size_t)desc->R * TP;
-    if (smem <= 64 * 1024) {
-      hipLaunchKernelGGL(attn_rows_flat_fwd_kernel, dim3(desc->G * desc->heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
-      FCMF_CHECK_LAUNCH();
-      return FCMF_OK;
-    }
-  }
-  const size_t esz = desc->dtype == FCMF_F32 ? 4 : 2;
-  P.KVF = (int)((2 * (size_t)desc->T1 * (desc->d + 16 / esz) * esz + 15) / 16 * 4);   // K and V images, rounded to 16 B, in floats
-  const int kpl = desc->T1 + desc->T2 <= 256 ? 4 : 8;     // keys per lane of the forward
-  const int nw = 4;
-  const size_t base = sizeof(float) * ((size_t)P.KVF + (size_t)nw * 64 * kpl);
-  const size_t per_row = sizeof(float) * (size_t)desc->d;
-  P.RB = rows_per_block(desc->R, base, per_row);
-  if (P.RB <= 0) return FCMF_ERR_UNSUPPORTED;
-  const size_t smem = base + (size_t)P.RB * per_row;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  dim3 grid(desc->G * desc->heads);
-#define FCMF_ATTN_FWD(TT, KPL, DC) fcmf_launch(attn_small_fwd_kernel<TT, KPL, DC>, grid, dim3(256), smem, st, P)
-#define FCMF_ATTN_FWD_T(TT)                                                                                                \
-  (desc->d == 64 ? (kpl == 4 ? FCMF_ATTN_FWD(TT, 4, 64) : FCMF_ATTN_FWD(TT, 8, 64))                                        \
-                 : (kpl == 4 ? FCMF_ATTN_FWD(TT, 4, 0) : FCMF_ATTN_FWD(TT, 8, 0)))
-  return desc->dtype == FCMF_F32 ? FCMF_ATTN_FWD_T(float) : FCMF_ATTN_FWD_T(bf16_t);
-#undef FCMF_ATTN_FWD_T
-#undef FCMF_ATTN_FWD
+  return run_plan(pl, P, stream);
 }
 
 static int attn_small_bwd_impl(const fcmf_attn_desc* desc, const void* out, const void* dout, const float* lse,
                                void* dq, void* dk1, void* dv1, void* dk2, void* dv2, float* dbias,
                                float* scratch, int64_t scratch_bytes, void* stream) {
-  int rc = check_desc(desc);
-  if (rc) return rc;
+  const bool grouped = scratch != nullptr;
+  const AttnSmallPlan pl = attn_small_plan(desc, true, grouped, dbias != nullptr, dv1 != nullptr,
+                                           al16(out) && al16(dout) && al16(dq) && al16(dk1) && al16(dv1));
+  if (!pl.desc_ok) return pl.rc;
   if (!out || !dout || !lse || !dq) return FCMF_ERR_ARG;
   if (desc->T1 > 0 && !dk1) return FCMF_ERR_ARG;
   if (desc->T1 > 0 && !dv1 && desc->v1 != desc->k1) return FCMF_ERR_ARG;
   if (desc->T2 > 0 && (!dk2 || !dv2)) return FCMF_ERR_ARG;
+  if (pl.rc) return pl.rc;
   AttnK P{};
   P.a = *desc; P.o_in = out; P.dout = dout; P.lse = const_cast<float*>(lse);
   P.dq = dq; P.dk1 = dk1; P.dv1 = dv1; P.dk2 = dk2; P.dv2 = dv2; P.dbias = dbias;
-  const bool grouped = scratch != nullptr;
-  const int64_t n2 = (int64_t)desc->G * desc->heads * desc->R * desc->T2;
-  const size_t smem2 = sizeof(float) * 2 * (size_t)desc->group_div * desc->heads * desc->T2;
   if (grouped) {
-    if (desc->T2 <= 0 || desc->group_div > 8 || desc->G % desc->group_div || desc->head_quirk || smem2 > 150 * 1024)
-      return FCMF_ERR_UNSUPPORTED;
+    const int64_t n2 = (int64_t)desc->G * desc->heads * desc->R * desc->T2;
     if (scratch_bytes < 2 * n2 * (int64_t)sizeof(float)) return FCMF_ERR_ARG;
     P.pd2 = scratch; P.ds2 = scratch + n2;
   }
-  if (!grouped && dv1 && tiny_ok(desc) &&
-      ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dq) |
-        reinterpret_cast<uintptr_t>(dk1) | reinterpret_cast<uintptr_t>(dv1)) & 15) == 0) {
-    const int dp = desc->d + 8;
-    size_t opnd = (size_t)(2 * desc->R + 2 * desc->T1) * dp * 2 + sizeof(float) * (size_t)desc->R;
-    {   // the score fragments read up to 15 rows past the end of the V image: into the f32 arrays behind it, or a pad
-      const size_t tail = sizeof(float) * ((size_t)2 * (desc->R < 16 ? desc->R : 16) * (desc->T1 + 1) + desc->R), over = (size_t)15 * dp * 2;
-      if (tail < over) opnd += over - tail;
-    }
-    const size_t row = sizeof(float) * 2 * (size_t)(desc->T1 + 1);      // one row of the two [rows][T + 1] f32 arrays
-    if (desc->R <= TINY_MAX && desc->T1 <= TINY_MAX && opnd + desc->R * row <= TINY_LDS) {
-      const size_t smem = opnd + desc->R * row;
-      return fcmf_launch(attn_tiny_bwd_kernel, dim3(desc->G * desc->heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
-    }
-    if (opnd + 16 * row <= TINY_LDS) {                   // row blocks of >= 16 rows, as even as the LDS allows
-      const int fit = (int)((TINY_LDS - opnd) / row);
-      const int nblk = (desc->R + fit - 1) / fit;
-      P.RB = (desc->R + nblk - 1) / nblk;
-      const size_t smem = opnd + P.RB * row;
-      return fcmf_launch(attn_tiny_bwd_blocked_kernel, dim3(desc->G * desc->heads), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), P);
-    }
-  }
-  if (rows_flat_ok(desc) && !dbias && (desc->T2 == 0 || grouped) && (desc->T1 == 0 || dv1) &&
-      ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dq) |
-        reinterpret_cast<uintptr_t>(dk1) | reinterpret_cast<uintptr_t>(dv1)) & 15) == 0) {
-    const int dp = desc->d + 8, TP = desc->T1 + desc->T2 + 1;
-    const size_t smem = (size_t)(2 * desc->R + 2 * desc->T1) * dp * 2 + sizeof(float) * ((size_t)2 * desc->R * TP + desc->R);
-    if (smem <= 64 * 1024) {
-      hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-      hipLaunchKernelGGL(attn_rows_flat_bwd_kernel, dim3(desc->G * desc->heads), dim3(256), smem, st, P);
-      FCMF_CHECK_LAUNCH();
-      if (!grouped) return FCMF_OK;
-      return fcmf_launch(attn_private_grad_kernel<bf16_t>, dim3((desc->G / desc->group_div) * desc->R, 4), dim3(256), smem2, st, P);
-    }
-  }
-  const int nsh = desc->T1 < 128 ? desc->T1 : 128;
-  const size_t esz = desc->dtype == FCMF_F32 ? 4 : 2;
-  P.KVF = (int)((2 * (size_t)nsh * (desc->d + 16 / esz) * esz + 15) / 16 * 4);
-  const size_t base = sizeof(float) * (size_t)P.KVF;
-  P.TLP = (nsh + desc->T2 + 3) & ~3;   // multiple of 4: rows of the key arrays stay 16-byte aligned
-  const size_t per_row = sizeof(float) * (2 * (size_t)desc->d + 2 * (size_t)P.TLP);
-  P.RB = rows_per_block(desc->R, base, per_row);
-  if (P.RB <= 0) return FCMF_ERR_UNSUPPORTED;
-  const size_t smem = base + (size_t)P.RB * per_row;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int nchunks = desc->T1 > 0 ? (desc->T1 + 127) / 128 : 1;
-  dim3 grid(desc->G * desc->heads, nchunks);
-  const bool one = P.RB >= desc->R;
-#define LAUNCH_(T, ONE, GR) fcmf_launch(attn_small_bwd_kernel<T, ONE, GR>, grid, dim3(256), smem, st, P)
-#define LAUNCH_T(T)                                                                                                        \
-  (grouped ? (one ? LAUNCH_(T, true, true) : LAUNCH_(T, false, true)) : (one ? LAUNCH_(T, true, false) : LAUNCH_(T, false, false)))
-  rc = desc->dtype == FCMF_F32 ? LAUNCH_T(float) : LAUNCH_T(bf16_t);
-#undef LAUNCH_T
-#undef LAUNCH_
-  if (rc != FCMF_OK || !grouped) return rc;
-  const dim3 grid2((desc->G / desc->group_div) * desc->R, 4);    // 4 key ranges per (review, row): ~1800 workgroups on the step
-  if (desc->dtype == FCMF_F32) return fcmf_launch(attn_private_grad_kernel<float>, grid2, dim3(256), smem2, st, P);
-  return fcmf_launch(attn_private_grad_kernel<bf16_t>, grid2, dim3(256), smem2, st, P);
+  return run_plan(pl, P, stream);
 }
 
 extern "C" int fcmf_attn_small_bwd(const fcmf_attn_desc* desc, const void* out, const void* dout, const float* lse,

@@ -58,6 +58,7 @@ SIGNATURES = {
     "fcmf_attn_small_fwd": [_c.POINTER(AttnDesc), _vp, _vp, _vp],
     "fcmf_attn_small_bwd": [_c.POINTER(AttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fcmf_attn_small_bwd_grouped": [_c.POINTER(AttnDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "fcmf_attn_small_plan": [_c.POINTER(AttnDesc), _i, _i, _i, _i, _i, _vp, _vp],      # host only: nothing is launched
     "fcmf_attn_mfma_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _f, _f, _u64, _vp],
     "fcmf_attn_mfma_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _f, _f,
                            _u64, _vp, _vp],
@@ -129,6 +130,9 @@ SIGNATURES = {
     "fcmf_dp_comm_destroy": [_vp],
     "fcmf_dp_allreduce_bucket": [_vp, _vp, _i64, _i, _i, _vp],
 }
+
+# entry points that plan on the host and launch nothing (their answers depend on the arguments alone: callers may cache them)
+HOST_ONLY = frozenset({"fcmf_attn_small_plan", "fcmf_gemm_dw_list_plan"})
 
 _lib = None
 

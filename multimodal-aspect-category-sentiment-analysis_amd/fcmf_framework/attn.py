@@ -4,6 +4,9 @@ operands, build a descriptor here and call these; nothing else in the package la
 kernel or fills an AttnDesc.  The long kernels (long_forward / long_backward / long_probs: fcmf_attn_mfma_long_fwd / _bwd /
 _probs, any number of keys, one key/value set per `kv_share` consecutive query groups) take dense tensors instead of a
 descriptor: their key sets are not the descriptor's per-group keys."""
+import ctypes
+import functools
+
 import torch
 
 from . import _hip as H
@@ -123,12 +126,24 @@ def sum_groups(x, reps):
     return out
 
 
+def small_plan(a, backward=False, grouped=False, has_dbias=False, has_dv1=True, ptrs_aligned=True):
+    """what fcmf_attn_small_fwd / _bwd / _bwd_grouped would launch for the descriptor (host only, nothing is launched) ->
+    (return code, info[11] as fcmf_attn_small_plan documents it, (kernel name, name of the follow-up kernel or None))"""
+    info = (ctypes.c_int32 * 11)()
+    names = (ctypes.c_char_p * 2)()
+    rc = H.lib().fcmf_attn_small_plan(a, int(backward), int(grouped), int(has_dbias), int(has_dv1), int(ptrs_aligned), info, names)
+    return rc, list(info), tuple(None if n is None else n.decode() for n in names)
+
+
+@functools.lru_cache(maxsize=None)
 def valu_float32_key_limit(d):
-    """most shared keys the float32 VALU attention takes at head dim d: its K and V images (rows of d + 4 floats), the waves'
-    score rows and one query row must fit the 160 KiB of LDS (fcmf_attn_small_fwd), and never more than its 512-key limit"""
-    def fits(T):
-        return 4 * (2 * T * (d + 4) + 4 * 64 * (4 if T <= 256 else 8) + d) <= 160 * 1024
-    T = 512
-    while T > 0 and not fits(T):
-        T -= 1
-    return T
+    """most shared keys the float32 VALU attention takes at head dim d: the largest T whose forward plan the library accepts
+    (its K and V images, the waves' score rows and one query row must fit the LDS; never more than its 512-key limit)"""
+    a = H.AttnDesc()
+    a.dtype, a.G, a.heads, a.d, a.R, a.group_div = H.F32, 1, 1, d, 1, 1
+    a.q = a.k1 = a.v1 = 16              # presence and alignment are all the plan reads of an address
+    for T in range(512, 0, -1):
+        a.T1 = T
+        if small_plan(a)[0] == 0:
+            return T
+    return 0

@@ -47,8 +47,8 @@ class _CallRecorder:
     whether v1 == k1)."""
 
     def __init__(self, real, signatures, desc=False):
-        from fcmf_framework._hip import AttnDesc
-        self._AttnDesc = AttnDesc
+        from fcmf_framework._hip import HOST_ONLY, AttnDesc
+        self._AttnDesc, self._host_only = AttnDesc, HOST_ONLY
         self._real, self.calls, self._desc = real, [], desc
         self._scalars = {n: [i for i, t in enumerate(sig) if t is not ctypes.c_void_p and not issubclass(t, ctypes._Pointer)]
                          for n, sig in signatures.items()}
@@ -56,7 +56,7 @@ class _CallRecorder:
 
     def __getattr__(self, name):
         fn, keep = getattr(self._real, name), self._scalars.get(name)
-        if keep is None:
+        if keep is None or name in self._host_only:      # (a cached planning query launches nothing: not part of a pass)
             return fn
         floats = self._floats[name]
 

@@ -419,18 +419,18 @@ ATTN_CASES = [
     (4, 36, 8, 96, 36, 0, 1, False, True, False),     # the step's ROI box attention (bf16: the all-in-LDS "tiny dense" kernels)
     (4, 36, 8, 96, 36, 0, 2, True, True, False),      # the same with a key mask and a bias shared by groups of 2
     (2, 64, 2, 64, 64, 0, 1, True, False, False),     # the tiny kernels' limits: 64 rows x 64 keys
-    (2, 65, 2, 64, 64, 0, 1, True, False, False),     # one row more: the wide forward / row-blocked backward (one block)
+    (2, 65, 2, 64, 64, 0, 1, True, False, False),     # one row more: the row-blocked backward, all 65 rows in one block (the forward stays the 64-key kernel)
     (2, 100, 8, 128, 100, 0, 1, False, True, False),  # FCMF-large's ROI box attention: 100 x 100, heads of 128 (two row blocks)
     (4, 100, 2, 128, 100, 0, 2, True, True, False),   # the same with a key mask and a bias shared by groups of 2
     (2, 128, 2, 64, 128, 0, 1, True, True, False),    # the wide kernels' limits: 128 rows x 128 keys
-    (2, 128, 1, 128, 128, 0, 1, True, False, False),  # ... with heads of 128: the backward in three row blocks (forward: general kernel)
+    (2, 128, 1, 128, 128, 0, 1, True, False, False),  # ... with heads of 128: the backward in six blocks of 22 rows (forward: general kernel)
     (2, 30, 2, 96, 100, 0, 1, True, True, False),     # few rows, > 64 keys
     (2, 100, 2, 96, 30, 0, 1, False, True, False),    # > 64 rows, few keys
     (2, 129, 2, 64, 64, 0, 1, True, False, False),    # one row more than the wide limit: the general kernel
-    (2, 16, 2, 128, 100, 20, 1, True, False, False),  # the flat few-rows kernels at their row limit, heads of 128, ungrouped private keys
-    (3, 1, 2, 64, 0, 2, 1, False, False, False),      # ... one row, two private keys
+    (2, 16, 2, 128, 100, 20, 1, True, False, False),  # the flat kernels' row limit, but heads of 128: 65 KiB of LDS, past their 64 -- the general kernels
+    (3, 1, 2, 64, 0, 2, 1, False, False, False),      # the flat few-rows kernels: one row, two private keys
     (6, 2, 4, 32, 17, 3, 3, True, False, False),      # ... groups of 3, odd key counts
-    (2, 17, 2, 64, 100, 20, 1, True, False, False),   # one row more: the general kernels
+    (2, 17, 2, 64, 100, 20, 1, True, False, False),   # one row past the flat kernels' limit: the general kernels
 ]
 
 

@@ -1,21 +1,14 @@
 // CPU-only probe of the GEMM host dispatch (csrc/gemm.hip): calls the extern "C" entry points with fake device addresses and
 // prints, for every call, the return code, the last_kernel string and every launch the call made -- host stub, grid, block,
 // dynamic LDS, the dynamic-LDS limit set for that kernel, and every field of the parameter struct by name.  The HIP launch
-// calls are defined HERE (definitions in the executable take precedence over the runtime's), so nothing reaches a device
-// and no address is dereferenced.  Two builds of gemm.hip dispatch alike exactly when their dumps are byte-identical.
+// calls are defined in hip_launch_stubs.h (definitions in the executable take precedence over the runtime's), so nothing reaches
+// a device and no address is dereferenced.  Two builds of gemm.hip dispatch alike exactly when their dumps are byte-identical.
 //
 // Build and run (no GPU needed), from csrc/ after `make gemm.o`:
-//   clang++ -std=c++17 -O1 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I../../include -c ../../tools/gemm_dispatch_probe.cpp -o probe.o
+//   clang++ -std=c++17 -O1 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I../../include -I../../tools -c ../../tools/gemm_dispatch_probe.cpp -o probe.o
 //   hipcc --offload-arch=gfx950 -rdynamic probe.o gemm.o -ldl -o gemm_dispatch_probe
 //   ./gemm_dispatch_probe | sha256sum        # the dump; the summary (counts per stub / last_kernel / return code) goes to stderr
 // GemmParams / GenericParams / DwList below mirror gemm.hip: keep them in step with it.
-#include <hip/hip_runtime_api.h>
-#include <dlfcn.h>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
 #include "fcmf_hip.h"
 
 struct GemmParams {
@@ -43,52 +36,12 @@ struct GenericParams {
   int kchunk;
 };
 
-static std::map<const void*, int> g_attr;            // kernel -> dynamic-LDS limit last set
-static std::map<std::string, long> g_count;          // summary
-static dim3 g_grid, g_block; static size_t g_smem; static hipStream_t g_stream;
-
-static std::string stub_name(const void* f) {
-  Dl_info di;
-  if (dladdr(f, &di) && di.dli_sname) return di.dli_sname;
-  static std::map<const void*, int> seen;
-  return "kernel#" + std::to_string(seen.emplace(f, (int)seen.size()).first->second);
-}
+#include "hip_launch_stubs.h"
 #define I(a, i) (*(int*)(a)[i])
 #define L(a, i) ((long long)*(int64_t*)(a)[i])
 #define P(a, i) (*(void**)(a)[i])
 
-extern "C" hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t smem, hipStream_t st) {
-  g_grid = grid; g_block = block; g_smem = smem; g_stream = st;
-  return hipSuccess;
-}
-extern "C" hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* smem, hipStream_t* st) {
-  *grid = g_grid; *block = g_block; *smem = g_smem; *st = g_stream;
-  return hipSuccess;
-}
-extern "C" hipError_t hipFuncSetAttribute(const void* f, hipFuncAttribute attr, int value) {
-  if (attr == hipFuncAttributeMaxDynamicSharedMemorySize) g_attr[f] = value;
-  return hipSuccess;
-}
-extern "C" hipError_t hipGetLastError(void) { return hipSuccess; }
-// the table upload of a weight-gradient list: staging memory from the heap, events that are always complete, and the copy printed
-// as its size and an FNV-1a hash of what it carries (the matrices, the items and the reduce table)
-extern "C" hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
-extern "C" hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
-extern "C" hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)malloc(1); return hipSuccess; }
-extern "C" hipError_t hipEventDestroy(hipEvent_t e) { free((void*)e); return hipSuccess; }
-extern "C" hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
-extern "C" hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-extern "C" hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t) {
-  unsigned long long h = 1469598103934665603ull;
-  for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char*)src)[i]) * 1099511628211ull;
-  printf("  upload %p %zu bytes fnv=%016llx\n", dst, n, h);
-  return hipSuccess;
-}
-extern "C" hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { printf("  memset %p %d %zu\n", p, v, n); return hipSuccess; }
-extern "C" hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** a, size_t smem, hipStream_t st) {
-  const std::string name = stub_name(f);
-  ++g_count["launch " + name];
-  printf("  %s grid=(%u,%u,%u) block=%u smem=%zu attr=%d stream=%p\n", name.c_str(), g.x, g.y, g.z, b.x, smem, g_attr.count(f) ? g_attr[f] : -1, (void*)st);
+static void print_launch_params(const std::string& name, void** a) {
   if (name.find("splitk_reduce_list") != std::string::npos) {
     printf("   ws=%p red=%p mats=%p entries=%d accumulate=%d", P(a, 0), P(a, 1), P(a, 2), I(a, 3), I(a, 4));
   } else if (name.find("splitk_reduce_frag") != std::string::npos) {
@@ -108,8 +61,6 @@ extern "C" hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** a, s
            (void*)p.colstats, p.cv_logP);
     if (name.find("dw_batched") != std::string::npos) { const DwList& l = *(DwList*)a[1]; printf(" mats=%p items=%p", l.mats, l.items); }
   }
-  printf("\n");
-  return hipSuccess;
 }
 
 // ---- the sweep ---------------------------------------------------------------------------------------------------------------
@@ -225,7 +176,6 @@ int main(int argc, char** argv) {
     if (i == 0 || i == 2) { sweep_gemm(g_ctx[i], 1); sweep_gemm(g_ctx[i], 2); }
     sweep_rest(g_ctx[i]);
   }
-  fflush(stdout);
-  for (const auto& kv : g_count) fprintf(stderr, "%10ld  %s\n", kv.second, kv.first.c_str());
+  print_summary();
   return 0;
 }
