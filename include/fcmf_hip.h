@@ -117,6 +117,15 @@ int fcmf_colsum(const void* X, float* out, int M, int N, int64_t ldx, int dtype,
  *   score[t] = scale * <q, k_t> + mask[g, t] + bias[g / group_div, h, r, t]
  *   causal != 0: score[t] = -1e4 where t > r   (IAOG `Attention`, mm_modeling.py:115-124)
  *   p = dropout(softmax(score)); out = sum_t p[t] v_t ; lse[g,h,r] = logsumexp(score)
+ * Dropout (dropout_p > 0) is a stateless function of (seed, counter), so the backward regenerates the forward's mask.  The
+ * counter of probability (g, h, r, t) is its row-major element index in the [G, heads, R, T1+T2] probability tensor,
+ *   idx = ((g*heads + h)*R + r)*(T1+T2) + t            (t counts the shared keys first, then the private ones)
+ * and in the MFMA kernels below idx = ((g*heads + h)*Tq + q)*Tk + key with g the QUERY group (also under kv_share > 1).
+ * One 32-bit hash of (seed, idx >> 1) decides a pair of elements: its low 16 bits the even one, its high 16 bits the odd
+ * one; an element is kept iff its 16 bits >= (uint32_t)(dropout_p * 65536 + 0.5) (float32 arithmetic), and kept
+ * probabilities are multiplied by the float32 1 / (1 - dropout_p).  The hash is fcmf_hash32 of csrc/common.h;
+ * tests/rowwise_ref.py (dropout_mask, mask_tensor, inv_keep) is the executable statement of all of this, and
+ * tests/attn_ref.py the attention under it.
  * Layouts (elements): Q  (g,r,h,:) at q  + g*q_sg  + r*q_sr  + h*d
  *                     K1 (g,t,h,:) at k1 + g*k1_sg + t*k1_st + h*d          (V1 same strides)
  *                     K2 (g2,r,t,h,:) at k2 + g2*k2_sg + r*k2_sr + t*k2_st + h*d  (V2 same)
@@ -195,7 +204,7 @@ int fcmf_attn_mfma_bwd(const void* q, const void* k, const void* v, const float*
  *   mask [G,Tk] additive float32 or NULL; out [G,Tq,heads*64]; lse [G,heads,Tq].
  * Semantics, row strides and alignment rules are those of fcmf_attn_mfma_fwd / _bwd: softmax(scale QK^T + mask) with the
  * mask added in float32 (a finfo.min key gets probability exactly 0; a row whose every key is masked is uniform over all
- * Tk keys), dropout on the probabilities with the same counter function of (seed, group, head, query, key), then V.
+ * Tk keys), dropout on the probabilities with the same counter function of (seed, group, head, query, key) (stated at fcmf_attn_desc), then V.
  * Backward: dq [G,Tq,.]; dk / dv [G/kv_share,Tk,.] are the sums over the sharing groups, accumulated in float32 and rounded
  * to bf16 once.  kv_share > 1 needs `workspace`: caller-owned device memory of at least
  * 2 * (G/kv_share) * Tk * heads*64 * 4 bytes, 16-byte aligned (contents need not be initialised; FCMF_ERR_ARG if too small). */
