@@ -9,8 +9,6 @@ views of, and all weight-gradient buffers of a layer come from a single zero fil
 """
 import math
 
-import os
-
 import torch
 
 from . import _hip as H
@@ -71,49 +69,6 @@ def _fused_weight(ws, dtype):
 
 
 # --------------------------------------------------------------------------------------
-# weight-gradient GEMMs on a side HIP stream
-# --------------------------------------------------------------------------------------
-# dW = dY^T X depends only on tensors that already exist when it is issued and nothing downstream in the layer's
-# backward reads it, so it CAN run on a second stream (FCMF_SIDE_STREAM=1); the main stream re-joins at the end of
-# the layer's backward, before autograd sees the gradients.  It paid while the GEMM left LDS to spare; the 160 KiB
-# persistent GEMM owns its CU, nothing overlaps any more (60.0 vs 59.8 ms/step measured), so the default is one stream.
-USE_SIDE_STREAM = os.environ.get("FCMF_SIDE_STREAM", "0") == "1"
-_side = {}
-
-
-def _side_stream(device):
-    st = _side.get(device)
-    if st is None:
-        st = _side[device] = torch.cuda.Stream(device=device)
-    return st
-
-
-class _SideGemms:
-    """context for one layer backward: launch() runs a GEMM on the side stream after everything issued
-    so far on the main stream; join() makes the main stream wait for all of them"""
-
-    def __init__(self, device):
-        self.dev = device
-        self.on = USE_SIDE_STREAM and not ops.tracing()   # event timing assumes one stream
-        self.used = False
-
-    def launch(self, tensors, *a, **kw):
-        if not self.on:
-            return ops.gemm(*a, **kw)
-        main, side = torch.cuda.current_stream(self.dev), _side_stream(self.dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            ops.gemm(*a, **kw)
-        for t in tensors:
-            t.record_stream(side)     # keep the caching allocator from recycling operands early
-        self.used = True
-
-    def join(self):
-        if self.on and self.used:
-            torch.cuda.current_stream(self.dev).wait_stream(_side_stream(self.dev))
-
-
-# --------------------------------------------------------------------------------------
 # self-attention over a fused [G,T,3H] q|k|v buffer
 # --------------------------------------------------------------------------------------
 def _self_desc(qkv, mask, G, T, Hd, heads, p, seed):
@@ -167,44 +122,6 @@ def _want_q(rows, Hd, dtype):
     return ops.fp8_enabled() and dtype == torch.bfloat16 and Hd % 128 == 0 and rows >= 256
 
 
-def _q_buffers(rows, Hd, device):
-    return torch.empty((rows, Hd), dtype=torch.uint8, device=device), torch.empty(rows, dtype=torch.float32, device=device)
-
-
-def _ln_fwd(x, res, res_ld, g, b, eps, p, seed, quant=False):
-    """-> y, z, mean, rstd, yq (= (e4m3 y, row scales) when `quant`, else None)"""
-    rows, Hd = x.shape
-    y = torch.empty_like(x)
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    # z (the pre-LN sum) overwrites x in place
-    if quant:
-        q, sc = _q_buffers(rows, Hd, x.device)
-        H.check(H.lib().fcmf_add_ln_fwd_fp8(H.ptr(x), H.ptr(res), res_ld, H.ptr(g), H.ptr(b), H.ptr(y), H.ptr(x), H.ptr(mean),
-                                            H.ptr(rstd), rows, Hd, eps, p, seed, H.dt(x), H.ptr(q), H.ptr(sc), H.stream()), "fcmf_add_ln_fwd_fp8")
-        return y, x, mean, rstd, (q, sc)
-    H.check(H.lib().fcmf_add_ln_fwd(H.ptr(x), H.ptr(res), res_ld, H.ptr(g), H.ptr(b), H.ptr(y), H.ptr(x), H.ptr(mean),
-                                    H.ptr(rstd), rows, Hd, eps, p, seed, H.dt(x), H.stream()), "fcmf_add_ln_fwd")
-    return y, x, mean, rstd, None
-
-
-def _ln_bwd(dy, z, g, mean, rstd, p, seed, dg, db, dxsum, quant=False):
-    """-> dz, dx (the gradient into the producing Linear), dxq (its e4m3 copy + row scales when `quant`)"""
-    dz = torch.empty_like(z)
-    dx = torch.empty_like(z) if p > 0 else None
-    ws = ops.ln_workspace(z.shape[0], z.shape[1], z.device)
-    if quant:
-        q, sc = _q_buffers(z.shape[0], z.shape[1], z.device)
-        H.check(H.lib().fcmf_add_ln_bwd_fp8(H.ptr(dy), H.ptr(z), H.ptr(g), H.ptr(mean), H.ptr(rstd), H.ptr(dz), H.ptr(dx), H.ptr(dg),
-                                            H.ptr(db), H.ptr(dxsum), H.ptr(ws), z.shape[0], z.shape[1], p, seed, H.dt(z), H.ptr(q),
-                                            H.ptr(sc), H.stream()), "fcmf_add_ln_bwd_fp8")
-        return dz, (dx if dx is not None else dz), (q, sc)
-    H.check(H.lib().fcmf_add_ln_bwd(H.ptr(dy), H.ptr(z), H.ptr(g), H.ptr(mean), H.ptr(rstd), H.ptr(dz), H.ptr(dx), H.ptr(dg),
-                                    H.ptr(db), H.ptr(dxsum), H.ptr(ws), z.shape[0], z.shape[1], p, seed, H.dt(z), H.stream()),
-            "fcmf_add_ln_bwd")
-    return dz, (dx if dx is not None else dz), None
-
-
 def _post_fwd(c, res, res_ld, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2, eps, p, seeds):
     """c [M,H] attention context; res rows at stride res_ld.  Returns y and the tensors the backward needs."""
     dt = c.dtype
@@ -213,34 +130,34 @@ def _post_fwd(c, res, res_ld, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2, eps, p, 
     co, c1, c2 = ops.as_compute(wo, dt), ops.as_compute(w1, dt), ops.as_compute(w2, dt)
     h = torch.empty((M, Hd), dtype=dt, device=c.device)
     ops.gemm_nt(c, wo, co, h, M, Hd, Hd, Hd, bias=bo.detach())
-    h1, z1, m1, r1, h1q = _ln_fwd(h, res, res_ld, g1, be1, eps, p, seeds[0], quant=_want_q(M, Hd, dt))
+    h1, m1, r1, h1q = ops.ln_fwd(h, res, res_ld, g1, be1, eps, p, seeds[0], h, quant=_want_q(M, Hd, dt))     # (the pre-LN sum z1 overwrites h)
     u = torch.empty((M, I), dtype=dt, device=c.device)
     a = torch.empty((M, I), dtype=dt, device=c.device)
     ops.gemm_nt(h1, w1, c1, a, M, I, Hd, Hd, bias=b1.detach(), aux=u, epi=H.EPI_GELU, xq=h1q)
     f = torch.empty((M, Hd), dtype=dt, device=c.device)
     ops.gemm_nt(a, w2, c2, f, M, Hd, I, I, bias=b2.detach())
-    y, z2, m2, r2, _ = _ln_fwd(f, h1, Hd, g2, be2, eps, p, seeds[1])
-    return y, (z1, m1, r1, h1, u, a, z2, m2, r2)
+    y, m2, r2, _ = ops.ln_fwd(f, h1, Hd, g2, be2, eps, p, seeds[1], f)                                       # (z2 overwrites f)
+    return y, (h, m1, r1, h1, u, a, f, m2, r2)
 
 
-def _post_bwd(dy, c, saved, wo, w1, w2, g1, g2, p, seeds, G, side):
+def _post_bwd(dy, c, saved, wo, w1, w2, g1, g2, p, seeds, G):
     """-> dc [M,H], dres (= dz1) [M,H]; weight / bias / LN gradients are accumulated into the views in G"""
     z1, m1, r1, h1, u, a, z2, m2, r2 = saved
     dt = c.dtype
     M, Hd = c.shape
     I = w1.shape[0]
     co, c1, c2 = ops.as_compute(wo, dt), ops.as_compute(w1, dt), ops.as_compute(w2, dt)
-    dz2, df, dfq = _ln_bwd(dy, z2, g2, m2, r2, p, seeds[1], G["g2"], G["be2"], G["b2"], quant=_want_q(M, Hd, dt))
+    dz2, df, dfq = ops.ln_bwd(dy, z2, g2, m2, r2, p, seeds[1], G["g2"], G["be2"], G["b2"], quant=_want_q(M, Hd, dt))
     du = torch.empty((M, I), dtype=dt, device=c.device)
     ops.gemm_dx(df, w2, c2, du, M, I, Hd, aux=u, epi=H.EPI_DGELU, colsum=G["b1"], dyq=dfq)      # (df W2) * gelu'(u); db1
-    side.launch((df, a), df, a, G["w2"], Hd, I, M, Hd, I, I, 1, 1, acc=True)                   # dW2 = df^T a
+    ops.gemm(df, a, G["w2"], Hd, I, M, Hd, I, I, 1, 1, acc=True)                   # dW2 = df^T a
     dh1 = torch.empty((M, Hd), dtype=dt, device=c.device)
     ops.gemm_dx(du, w1, c1, dh1, M, Hd, I, aux=dz2, epi=H.EPI_ADD)                             # du W1 + dz2 (residual)
-    side.launch((du, h1), du, h1, G["w1"], I, Hd, M, I, Hd, Hd, 1, 1, acc=True)                # dW1 = du^T h1
-    dz1, dh, dhq = _ln_bwd(dh1, z1, g1, m1, r1, p, seeds[0], G["g1"], G["be1"], G["bo"], quant=_want_q(M, Hd, dt))
+    ops.gemm(du, h1, G["w1"], I, Hd, M, I, Hd, Hd, 1, 1, acc=True)                # dW1 = du^T h1
+    dz1, dh, dhq = ops.ln_bwd(dh1, z1, g1, m1, r1, p, seeds[0], G["g1"], G["be1"], G["bo"], quant=_want_q(M, Hd, dt))
     dc = torch.empty((M, Hd), dtype=dt, device=c.device)
     ops.gemm_dx(dh, wo, co, dc, M, Hd, Hd, dyq=dhq)
-    side.launch((dh, c), dh, c, G["wo"], Hd, Hd, M, Hd, Hd, Hd, 1, 1, acc=True)
+    ops.gemm(dh, c, G["wo"], Hd, Hd, M, Hd, Hd, Hd, 1, 1, acc=True)
     return dc, dz1
 
 
@@ -290,9 +207,7 @@ class PostAttentionFn(torch.autograd.Function):
         p, s0, s1, cshape, rshape = ctx.cfg
         G, R = _layer_grads(c2.device, c2.shape[1], w1.shape[0],
                             dict(wo=wo, w1=w1, w2=w2, bo=bo, b1=b1, b2=b2, g1=g1, be1=be1, g2=g2, be2=be2))
-        side = _SideGemms(c2.device)
-        dc, dres = _post_bwd(dy.reshape(c2.shape).contiguous(), c2, saved, wo, w1, w2, g1, g2, p, (s0, s1), G, side)
-        side.join()
+        dc, dres = _post_bwd(dy.reshape(c2.shape).contiguous(), c2, saved, wo, w1, w2, g1, g2, p, (s0, s1), G)
         return (dc.view(cshape), dres.view(rshape), R["wo"], R["bo"], R["g1"], R["be1"], R["w1"], R["b1"], R["w2"], R["b2"],
                 R["g2"], R["be2"], None, None, None, None)
 
@@ -334,15 +249,13 @@ class SelfLayerFn(torch.autograd.Function):
         G, R = _layer_grads(x2.device, Hd, w1.shape[0],
                             dict(wqkv=[wq, wk, wv], bqkv=[bq, bk, bv], wo=wo, w1=w1, w2=w2, bo=bo, b1=b1, b2=b2, g1=g1, be1=be1,
                                  g2=g2, be2=be2))
-        side = _SideGemms(x2.device)
-        dc, dz1 = _post_bwd(dy.reshape(M, Hd).contiguous(), c, saved, wo, w1, w2, g1, g2, p_h, (s0, s1), G, side)
+        dc, dz1 = _post_bwd(dy.reshape(M, Hd).contiguous(), c, saved, wo, w1, w2, g1, g2, p_h, (s0, s1), G)
         dqkv = self_attention_bwd(qkv, mk, c, lse, dc, G_, T, Hd, heads, p_a, seed_a, bias_grad=G["bqkv"])
         wqkv = _fused_weight([wq, wk, wv], dt)
         dx = torch.empty((M, Hd), dtype=dt, device=x2.device)
         wm = _fused_weight([wq, wk, wv], torch.float32)
         ops.gemm_dx(dqkv, wm if wm.data_ptr() == wq.data_ptr() else None, wqkv, dx, M, Hd, 3 * Hd, aux=dz1, epi=H.EPI_ADD, owner=wq)   # + residual gradient
-        side.launch((dqkv, x2), dqkv, x2, G["wqkv"], 3 * Hd, Hd, M, 3 * Hd, Hd, Hd, 1, 1, acc=True)
-        side.join()
+        ops.gemm(dqkv, x2, G["wqkv"], 3 * Hd, Hd, M, 3 * Hd, Hd, Hd, 1, 1, acc=True)
         Ws, bs = _split3(R["wqkv"], Hd), _split3(R["bqkv"], Hd)
         return (dx.view(xshape), None, Ws[0], bs[0], Ws[1], bs[1], Ws[2], bs[2], R["wo"], R["bo"],
                 R["g1"], R["be1"], R["w1"], R["b1"], R["w2"], R["b2"], R["g2"], R["be2"],

@@ -393,14 +393,15 @@ def head_weight_grad(x2, dy2, params):
     return [a.grad_alias(p, (nh, E, d)) for p in params]
 
 
+def _fp8_buffers(rows, K, device):
+    """(q [rows, K] uint8 for e4m3 values, scale [rows] float32), uninitialised"""
+    return torch.empty((rows, K), dtype=torch.uint8, device=device), torch.empty(rows, dtype=torch.float32, device=device)
+
+
 def quant_fp8_rows(x, rows, K, ldx, out=None):
     """x [rows, K] (bf16 / f32 rows at stride ldx) -> (q [rows, K] uint8 e4m3, scale [rows] float32) through fcmf_quant_fp8_rows"""
     H.require_cuda(x)
-    if out is None:
-        q = torch.empty((rows, K), dtype=torch.uint8, device=x.device)
-        sc = torch.empty(rows, dtype=torch.float32, device=x.device)
-    else:
-        q, sc = out
+    q, sc = _fp8_buffers(rows, K, x.device) if out is None else out
     H.check(H.lib().fcmf_quant_fp8_rows(H.ptr(x), ldx, H.ptr(q), K, H.ptr(sc), rows, K, H.dt(x), H.stream()), "fcmf_quant_fp8_rows")
     return q, sc
 
@@ -501,126 +502,68 @@ def _linear_bwd(x, w, dy, need_dx=True, need_dw=True, need_db=True, dx_epi=H.EPI
     return dx, dw, db
 
 
-class LinearFn(torch.autograd.Function):
-    """y = act(x W^T + b), act in {none, tanh}.  nn.Linear (+ BertPooler's tanh, mm_modeling.py:425-431)"""
+class ProjectFn(torch.autograd.Function):
+    """n nn.Linear on the SAME [..., K] input as one autograd node: (x, act, row0, w1, b1, w2, b2, ...) -> one output per pair.
+    n = 1 is nn.Linear itself, with act = "tanh" BertPooler's (mm_modeling.py:425-431); n > 1 are q / k / v of the box attention on
+    the ROI features (roi_modeling.py:170-173) and key / value of a cross attention.  With row0 (the text encoder's output [G, S, H]
+    in FCMFEncoder, fcmf_pretraining.py:97-124: key and value projection of the text+ROI layer plus the [CLS] row) x[:, 0] is one
+    more output.  As separate nodes the n (+ 1) gradient contributions to x are materialised and added by the engine -- for the
+    row a zero-filled [G, S, H] tensor (select_backward) -- 0.5 GB of traffic per step for nothing.  Here dx = dy1 W1, then
+    dx = dx + dy_i W_i in the later dX GEMMs' epilogue (FCMF_EPI_ADD), then the row's gradient added to dx[:, 0]."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, act):
-        x2 = _rows(x)
-        w = as_compute(weight, x2.dtype)
-        epi = H.EPI_TANH if act == "tanh" else H.EPI_NONE
-        y = _linear_fwd(x2, w, None if bias is None else bias.detach(), epi, master=weight)
-        ctx.save_for_backward(x2, weight, y if act == "tanh" else None)
-        ctx.act = act
-        ctx.has_bias = bias is not None
-        ctx.bias_param = bias
-        ctx.xshape = x.shape
-        return y.view(*x.shape[:-1], weight.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, weight, y = ctx.saved_tensors
-        dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
-        if ctx.act == "tanh":
-            d = torch.empty_like(dy2)
-            H.check(H.lib().fcmf_act_bwd(H.ptr(dy2), H.ptr(y), H.ptr(d), dy2.numel(), 0, H.dt(dy2), H.stream()), "act_bwd")
-            dy2 = d
-        w = as_compute(weight, x2.dtype)
-        dx, dw, db = _linear_bwd(x2, w, dy2, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
-                                 ctx.has_bias and ctx.needs_input_grad[2], master=weight, bias_param=ctx.bias_param)
-        return (None if dx is None else dx.view(ctx.xshape)), dw, db, None
-
-
-def linear(x, weight, bias=None, act=None):
-    return LinearFn.apply(x, weight, bias, act)
-
-
-class SeqFanFn(torch.autograd.Function):
-    """The three consumers of the text encoder's output in FCMFEncoder (fcmf_pretraining.py:97-124 after pruning): the key and
-    the value projection of the text+ROI layer (two nn.Linear on the SAME [G, S, H] tensor) and the [CLS] row.  As separate
-    autograd nodes their three gradient contributions to the sequence are materialised and added by the engine: a zero-filled
-    [G, S, H] tensor for the row (select_backward) and two full-size adds -- 0.5 GB of traffic per step for nothing.  Here:
-    dx = dy1 W1, then dx = dx + dy2 W2 in the second GEMM's epilogue (FCMF_EPI_ADD), then the [CLS] gradient added to row 0."""
-
-    @staticmethod
-    def forward(ctx, seq, w1, b1, w2, b2):
-        G, S, Hd = seq.shape
-        x2 = _rows(seq)
-        c1, c2 = as_compute(w1, x2.dtype), as_compute(w2, x2.dtype)
-        y1 = _linear_fwd(x2, c1, None if b1 is None else b1.detach(), master=w1)
-        y2 = _linear_fwd(x2, c2, None if b2 is None else b2.detach(), master=w2)
-        cls = seq[:, 0].contiguous()
-        ctx.save_for_backward(x2, w1, w2)
-        ctx.biases = (b1, b2)
-        ctx.shape = (G, S, Hd)
-        return y1.view(G, S, -1), y2.view(G, S, -1), cls
-
-    @staticmethod
-    def backward(ctx, dy1, dy2, dcls):
-        x2, w1, w2 = ctx.saved_tensors
-        b1, b2 = ctx.biases
-        G, S, Hd = ctx.shape
-        need_dx = ctx.needs_input_grad[0]
-        dx = dw1 = db1 = dw2 = db2 = None
-        if dy1 is not None:
-            d1 = dy1.reshape(G * S, -1).contiguous()
-            dx, dw1, db1 = _linear_bwd(x2, as_compute(w1, x2.dtype), d1, need_dx, ctx.needs_input_grad[1],
-                                       b1 is not None and ctx.needs_input_grad[2], master=w1, bias_param=b1)
-        if dy2 is not None:
-            d2 = dy2.reshape(G * S, -1).contiguous()
-            dx, dw2, db2 = _linear_bwd(x2, as_compute(w2, x2.dtype), d2, need_dx, ctx.needs_input_grad[3],
-                                       b2 is not None and ctx.needs_input_grad[4], dx_epi=H.EPI_NONE if dx is None else H.EPI_ADD,
-                                       dx_aux=dx, master=w2, bias_param=b2)
-        if need_dx:
-            if dx is None:
-                dx = torch.zeros((G * S, Hd), dtype=x2.dtype, device=x2.device)
-            dx = dx.view(G, S, Hd)
-            if dcls is not None:
-                dx[:, 0] += dcls
-        return dx, dw1, db1, dw2, db2
-
-
-class MultiLinearFn(torch.autograd.Function):
-    """several nn.Linear on the SAME input (q / k / v of the box attention on the ROI features, roi_modeling.py:170-173; key / value
-    of the cross attention on the patch features) as one autograd node: the input gradient is accumulated by the dX GEMMs' add
-    epilogue instead of n - 1 full-size adds by the engine.  Arguments: x, w1, b1, w2, b2, ...; returns one output per pair."""
-
-    @staticmethod
-    def forward(ctx, x, *wb):
+    def forward(ctx, x, act, row0, *wb):
         x2 = _rows(x)
         ws, bs = wb[0::2], wb[1::2]
-        ys = tuple(_linear_fwd(x2, as_compute(w, x2.dtype), None if b is None else b.detach(), master=w) for w, b in zip(ws, bs))
-        ctx.save_for_backward(x2, *ws)
-        ctx.biases = bs
-        ctx.xshape = x.shape
-        return tuple(y.view(*x.shape[:-1], w.shape[0]) for y, w in zip(ys, ws))
+        epi = H.EPI_TANH if act == "tanh" else H.EPI_NONE
+        cs = (as_compute(w, x2.dtype) for w in ws)      # lazily: a stale weight shadow is cast right before its GEMM ...
+        if row0:
+            cs = list(cs)                               # ... but the row0 node has always cast all of them first (the first step's call order)
+        ys = [_linear_fwd(x2, c, None if b is None else b.detach(), epi, master=w) for c, w, b in zip(cs, ws, bs)]
+        ctx.save_for_backward(x2, *ws, *(ys if act == "tanh" else ()))
+        ctx.biases = bs            # (the Parameters themselves: grad_dest looks up their arena slices by identity)
+        ctx.act, ctx.row0, ctx.xshape = act, row0, x.shape
+        outs = tuple(y.view(*x.shape[:-1], y.shape[1]) for y in ys)
+        return outs + (x[:, 0].contiguous(),) if row0 else outs
 
     @staticmethod
     def backward(ctx, *dys):
-        x2, *ws = ctx.saved_tensors
-        need_dx = ctx.needs_input_grad[0]
-        dx = None
-        grads = []
-        for i, (dy, w, b) in enumerate(zip(dys, ws, ctx.biases)):
-            if dy is None:
+        x2, *saved = ctx.saved_tensors
+        n, need = len(ctx.biases), ctx.needs_input_grad
+        dx, grads = None, []
+        for i, (dy, w, b) in enumerate(zip(dys, saved, ctx.biases)):
+            if dy is None:             # an unused output
                 grads += [None, None]
                 continue
             d = dy.reshape(-1, dy.shape[-1]).contiguous()
-            dx, dw, db = _linear_bwd(x2, as_compute(w, x2.dtype), d, need_dx, ctx.needs_input_grad[1 + 2 * i],
-                                     b is not None and ctx.needs_input_grad[2 + 2 * i],
+            if ctx.act == "tanh":
+                dpre = torch.empty_like(d)
+                H.check(H.lib().fcmf_act_bwd(H.ptr(d), H.ptr(saved[n + i]), H.ptr(dpre), d.numel(), 0, H.dt(d), H.stream()), "act_bwd")
+                d = dpre
+            dx, dw, db = _linear_bwd(x2, as_compute(w, x2.dtype), d, need[0], need[3 + 2 * i], b is not None and need[4 + 2 * i],
                                      dx_epi=H.EPI_NONE if dx is None else H.EPI_ADD, dx_aux=dx, master=w, bias_param=b)
             grads += [dw, db]
-        return (None if dx is None else dx.view(ctx.xshape), *grads)
+        if ctx.row0 and need[0]:
+            if dx is None:
+                dx = torch.zeros(x2.shape, dtype=x2.dtype, device=x2.device)
+            if dys[n] is not None:
+                dx.view(ctx.xshape)[:, 0] += dys[n]
+        return (None if dx is None else dx.view(ctx.xshape), None, None, *grads)
+
+
+def linear(x, weight, bias=None, act=None):
+    """y = act(x W^T + b), act in {None, "tanh"}"""
+    return ProjectFn.apply(x, act, False, weight, bias)[0]
 
 
 def linear_multi(x, *wb):
-    """(x W1^T + b1, x W2^T + b2, ...) with ONE gradient tensor for x (see MultiLinearFn)"""
-    return MultiLinearFn.apply(x, *wb)
+    """(x W1^T + b1, x W2^T + b2, ...) with ONE gradient tensor for x (see ProjectFn)"""
+    return ProjectFn.apply(x, None, False, *wb)
 
 
 def seq_fan(seq, w1, b1, w2, b2):
-    """-> (seq W1^T + b1, seq W2^T + b2, seq[:, 0]) with ONE gradient tensor for `seq` (see SeqFanFn)"""
-    return SeqFanFn.apply(seq, w1, b1, w2, b2)
+    """-> (seq W1^T + b1, seq W2^T + b2, seq[:, 0]) with ONE gradient tensor for `seq` (see ProjectFn)"""
+    return ProjectFn.apply(seq, None, True, w1, b1, w2, b2)
 
 
 def head_layouts(ws, dtype):
@@ -707,83 +650,84 @@ def head_linear(x, *ws):
     return ys[0] if len(ws) == 1 else ys
 
 
+def _vocab_logits(x2, weight, bias, cache_bias=False):
+    """the vocabulary projection x2 [M, K] by weight [V, K] (+ bias [V]) -> (logits [M, Vp], the weight operand [Vp, K] it used).
+    bf16 and a ragged vocabulary (V no multiple of VOCAB_PAD; IAOG: the tied 64001 x 768 matrix, fcmf_pretraining.py:159-166): the
+    row-padded weight shadow (rows >= V zero) into column-padded logits, so that the GEMM runs on the MFMA kernels instead of
+    the any-stride f32-MFMA one -- the padding logits are exactly the padding bias, zero; else Vp = V and the plain weight.
+    cache_bias: the zero-padded bias is kept on the Parameter (shadows.derived: once per parameter version, the decode loop)
+    instead of being built for this call."""
+    V, K = weight.shape
+    M = x2.shape[0]
+    w = shadows.padded(weight) if x2.dtype == torch.bfloat16 and V % VOCAB_PAD != 0 else as_compute(weight, x2.dtype)
+    Vp = w.shape[0]
+    bp = None if bias is None else bias.detach()
+    if bp is not None and Vp != V:
+        pad = lambda b: torch.cat((b.float(), b.new_zeros(Vp - V, dtype=torch.float32)))
+        bp = shadows.derived(bias, ("vocab_pad", Vp), pad) if cache_bias else pad(bp)
+    logits = torch.empty((M, Vp), dtype=x2.dtype, device=x2.device)
+    gemm(x2, w, logits, M, Vp, K, _ld(x2), K, Vp, 0, 0, bias=bp)
+    return logits, w
+
+
+def _vocab_bwd(d, x2, w, V, need_dx, need_db, dwp):
+    """backward of _vocab_logits: d [M, Vp] the logit gradient (padding columns zero), w the weight operand the forward used ->
+    (dx [M, K] or None, db [V] or None); dW = d^T x2 is ACCUMULATED into dwp [Vp, K] float32 where one is given"""
+    M, Vp = d.shape
+    K = x2.shape[1]
+    dx = gemm_dx_long_k(d, w, M, K, Vp, K) if need_dx else None
+    if dwp is not None:
+        gemm(d, x2, dwp, Vp, K, M, Vp, _ld(x2), K, 1, 1, acc=True)
+    return dx, (colsum(d, M, Vp, Vp)[:V] if need_db else None)
+
+
 class VocabLinearFn(torch.autograd.Function):
-    """logits = x W^T + b for a weight whose row count is not a multiple of 8 (IAOG: the tied 64001 x 768
-    vocabulary matrix, fcmf_pretraining.py:159-166), bf16 mode: every GEMM runs on the MFMA kernels over the
-    row-padded weight copy and column-padded logits / logit gradients (the padding columns are exact zeros);
-    without it all three GEMMs of the projection fall to the any-stride f32-MFMA kernel."""
+    """logits = x W^T + b for a ragged vocabulary in bf16 mode (_vocab_logits) in the reference's shape [..., V]: one compaction
+    copy of the padded logits forward, one padded re-copy of their gradient backward"""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
         x2 = _rows(x)
-        V, K = weight.shape
-        wp = shadows.padded(weight)                       # [Vp, K] bf16, rows >= V zero
-        Vp = wp.shape[0]
-        M = x2.shape[0]
-        bp = None
-        if bias is not None:
-            bp = torch.zeros(Vp, dtype=torch.float32, device=x2.device)
-            bp[:V] = bias.detach()
-        y = torch.empty((M, Vp), dtype=x2.dtype, device=x2.device)
-        gemm(x2, wp, y, M, Vp, K, _ld(x2), K, Vp, 0, 0, bias=bp)
+        V = weight.shape[0]
+        y, ctx.w = _vocab_logits(x2, weight, bias)
         ctx.save_for_backward(x2, weight)
         ctx.has_bias = bias is not None
         ctx.xshape = x.shape
-        return y[:, :V].reshape(*x.shape[:-1], V)          # one compaction copy: consumers see the reference shape
+        return y[:, :V].reshape(*x.shape[:-1], V)
 
     @staticmethod
     def backward(ctx, dy):
         x2, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
         V, K = weight.shape
-        wp = shadows.padded(weight)
-        Vp = wp.shape[0]
-        M = x2.shape[0]
+        M, Vp = x2.shape[0], ctx.w.shape[0]
         dyp = torch.zeros((M, Vp), dtype=x2.dtype, device=x2.device)
         dyp[:, :V] = dy.reshape(M, V)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = gemm_dx_long_k(dyp, wp, M, K, Vp, K).view(ctx.xshape)
-        if ctx.needs_input_grad[1]:
-            dwp = torch.zeros((Vp, K), dtype=torch.float32, device=x2.device)
-            gemm(dyp, x2, dwp, Vp, K, M, Vp, _ld(x2), K, 1, 1, acc=True)
-            dw = dwp[:V]
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = colsum(dyp, M, Vp, Vp)[:V]
-        return dx, dw, db
+        dwp = torch.zeros((Vp, K), dtype=torch.float32, device=x2.device) if need[1] else None
+        dx, db = _vocab_bwd(dyp, x2, ctx.w, V, need[0], ctx.has_bias and need[2], dwp)
+        return None if dx is None else dx.view(ctx.xshape), None if dwp is None else dwp[:V], db
 
 
 def vocab_linear(x, weight, bias=None):
     """nn.Linear onto a vocabulary: the padded MFMA path for ragged vocabularies in bf16 mode, else `linear`"""
     if compute_dtype() == torch.bfloat16 and x.dtype == torch.bfloat16 and weight.shape[0] % VOCAB_PAD != 0:
         return VocabLinearFn.apply(x, weight, bias)
-    return LinearFn.apply(x, weight, bias, None)
+    return linear(x, weight, bias)
 
 
 class VocabCrossEntropyFn(torch.autograd.Function):
     """loss = CrossEntropy(x W^T + b, labels; ignore_index) in ONE autograd node: the IAOG head
     (mm_modeling.py:662 logits -> run_pretraining_fcmf.py:322-324 loss).  The [rows, V] logits live only inside the
-    node, in a column-padded buffer the MFMA kernels can write (64001 -> 64032 columns); the loss kernel reads it with
+    node, in _vocab_logits' column-padded buffer (64001 -> 64032 columns); the loss kernel reads it with
     its row stride, the logit gradient overwrites it IN PLACE and feeds the dX / dW GEMMs directly -- no compaction
     copy to the reference's [B, Ld, V] shape, no padded re-copy and no zero-filled gradient buffer in the backward."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, labels, ignore_index):
         x2 = _rows(x)
-        V, K = weight.shape
-        M = x2.shape[0]
-        if x2.dtype == torch.bfloat16 and V % VOCAB_PAD != 0:
-            w = shadows.padded(weight)                     # [Vp, K] bf16, rows >= V zero
-        else:
-            w = as_compute(weight, x2.dtype)
-        Vp = w.shape[0]
-        bp = None
-        if bias is not None:
-            bp = bias.detach()
-            if Vp != V:
-                bp = torch.zeros(Vp, dtype=torch.float32, device=x2.device)
-                bp[:V] = bias.detach()
-        logits = torch.empty((M, Vp), dtype=x2.dtype, device=x2.device)
-        gemm(x2, w, logits, M, Vp, K, _ld(x2), K, Vp, 0, 0, bias=bp)
+        V = weight.shape[0]
+        logits, ctx.w = _vocab_logits(x2, weight, bias)
+        M, Vp = logits.shape
         lb = labels.reshape(-1).contiguous()
         rows = torch.empty(M, dtype=torch.float32, device=x2.device)
         nvalid = torch.zeros(1, dtype=torch.float32, device=x2.device)
@@ -797,27 +741,21 @@ class VocabCrossEntropyFn(torch.autograd.Function):
     def backward(ctx, g):
         x2, weight, logits, lb, nvalid = ctx.saved_tensors
         ignore_index, has_bias, xshape = ctx.cfg
+        need = ctx.needs_input_grad
         V, K = weight.shape
         M, Vp = logits.shape
-        w = shadows.padded(weight) if (x2.dtype == torch.bfloat16 and V % VOCAB_PAD != 0) else as_compute(weight, x2.dtype)
         scale = (g.float() / nvalid[0]).reshape(1).contiguous()
         d = logits                                          # in place: the node owns the buffer
         H.check(H.lib().fcmf_xent_bwd(H.ptr(logits), Vp, H.ptr(lb), H.ptr(d), Vp, H.ptr(scale), 1.0, M, V, ignore_index,
                                       H.dt(logits), H.stream()), "fcmf_xent_bwd")
         if Vp != V:
             d[:, V:].zero_()                                # the padding logits (= bias 0) must not leak into dX / dW
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = gemm_dx_long_k(d, w, M, K, Vp, K).view(xshape)
-        if ctx.needs_input_grad[1]:
-            # the tied vocabulary matrix: its arena slice has zeroed slack rows up to Vp (dp.GradArena pad_rows), so the padded product
-            # accumulates straight into it -- no 196 MB zero fill, and the embedding lookup's gradient (the other producer of the tied
-            # matrix) adds to the same memory in place instead of through a 196 MB autograd add
-            dwp, dw = grad_dest(weight, (V, K), rows=Vp, device=x2.device)
-            gemm(d, x2, dwp, Vp, K, M, Vp, _ld(x2), K, 1, 1, acc=True)
-        if has_bias and ctx.needs_input_grad[2]:
-            db = colsum(d, M, Vp, Vp)[:V]
-        return dx, dw, db, None, None
+        # the tied vocabulary matrix: its arena slice has zeroed slack rows up to Vp (dp.GradArena pad_rows), so the padded product
+        # accumulates straight into it -- no 196 MB zero fill, and the embedding lookup's gradient (the other producer of the tied
+        # matrix) adds to the same memory in place instead of through a 196 MB autograd add
+        dwp, dw = grad_dest(weight, (V, K), rows=Vp, device=x2.device) if need[1] else (None, None)
+        dx, db = _vocab_bwd(d, x2, ctx.w, V, need[0], has_bias and need[2], dwp)
+        return None if dx is None else dx.view(xshape), dw, db, None, None
 
 
 def vocab_cross_entropy(x, weight, bias, labels, ignore_index=-100):
@@ -848,25 +786,9 @@ def logsoftmax_topk(logits, V, k):
 @torch.no_grad()
 def vocab_topk(x, weight, bias, k):
     """the k most probable tokens of every row of x [n, K] under softmax(x W^T + b), weight [V, K] -> (log-probabilities float32
-    [n, k], token ids int32 [n, k]).  No autograd: the decode step.  The projection is VocabCrossEntropyFn.forward's (bf16 and a ragged
-    vocabulary: the row-padded weight shadow into a column-padded [n, Vp] buffer; else the plain weight), and the kernel reads that
-    buffer with its row stride -- no compaction copy to [n, V], no log-softmax round trip."""
-    x2 = _rows(x)
-    V, K = weight.shape
-    M = x2.shape[0]
-    if x2.dtype == torch.bfloat16 and V % VOCAB_PAD != 0:
-        w = shadows.padded(weight)                     # [Vp, K] bf16, rows >= V zero
-    else:
-        w = as_compute(weight, x2.dtype)
-    Vp = w.shape[0]
-    bp = None
-    if bias is not None:
-        bp = bias.detach()
-        if Vp != V:      # zero-padded once per parameter version, not per decode step (the parameter persists: shadows.derived)
-            bp = shadows.derived(bias, ("vocab_pad", Vp), lambda b: torch.cat((b.float(), b.new_zeros(Vp - V, dtype=torch.float32))))
-    logits = torch.empty((M, Vp), dtype=x2.dtype, device=x2.device)
-    gemm(x2, w, logits, M, Vp, K, _ld(x2), K, Vp, 0, 0, bias=bp)
-    return logsoftmax_topk(logits, V, k)
+    [n, k], token ids int32 [n, k]).  No autograd: the decode step.  The projection is _vocab_logits', its padded bias cached on the
+    Parameter, and the kernel reads the [n, Vp] buffer with its row stride -- no compaction copy to [n, V], no log-softmax round trip."""
+    return logsoftmax_topk(_vocab_logits(_rows(x), weight, bias, cache_bias=True)[0], weight.shape[0], k)
 
 
 class FFNFn(torch.autograd.Function):
@@ -903,11 +825,33 @@ def ffn(x, w1, b1, w2, b2):
 # --------------------------------------------------------------------------------------
 # residual + dropout + LayerNorm
 # --------------------------------------------------------------------------------------
-def ln_workspace(rows, Hd, device):
-    """scratch for the per-workgroup partial column sums of fcmf_add_ln_bwd (stream-ordered reuse is safe:
-    every call fully rewrites the part it reads)"""
-    n = H.lib().fcmf_add_ln_bwd_workspace(rows, Hd)
-    return torch.empty(n, dtype=torch.float32, device=device)
+def ln_fwd(x, res, res_ld, gamma, beta, eps, p, seed, z, quant=False):
+    """y = LN(z), z = dropout(x; p, seed) + res, x [rows, H] dense, res rows at stride res_ld (or None, 0) -> (y, mean, rstd, yq).
+    z: the tensor that receives the pre-LN sum the backward needs (x itself: in place).  quant: the kernel also emits
+    yq = (e4m3 y, row scales), what the fp8 GEMM that consumes y would otherwise quantise in a pass of its own; else yq is None"""
+    rows, Hd = x.shape
+    y = torch.empty_like(x)
+    mean, rstd = (torch.empty(rows, dtype=torch.float32, device=x.device) for _ in range(2))
+    name, yq = ("fcmf_add_ln_fwd_fp8", _fp8_buffers(rows, Hd, x.device)) if quant else ("fcmf_add_ln_fwd", None)
+    H.check(getattr(H.lib(), name)(H.ptr(x), H.ptr(res), res_ld, H.ptr(gamma), H.ptr(beta), H.ptr(y), H.ptr(z), H.ptr(mean),
+                                   H.ptr(rstd), rows, Hd, eps, p, seed, H.dt(x), *map(H.ptr, yq or ()), H.stream()), name)
+    return y, mean, rstd, yq
+
+
+def ln_bwd(dy, z, gamma, mean, rstd, p, seed, dg, db, dxsum=None, quant=False):
+    """backward of ln_fwd -> (dz: the gradient of the sum = of the residual, dx: of the dropout's input -- dz itself when p == 0,
+    dxq: (e4m3 dx, row scales) when `quant`, else None).  The float32 [H] gradients of gamma and beta are ACCUMULATED into dg and
+    db, the column sums of dx (the bias gradient of the Linear that produced x) into dxsum where one is given."""
+    rows, Hd = z.shape
+    dz = torch.empty_like(z)
+    dx = torch.empty_like(z) if p > 0 else None
+    L = H.lib()
+    # scratch for the per-workgroup partial column sums (stream-ordered reuse is safe: every call fully rewrites the part it reads)
+    ws = torch.empty(L.fcmf_add_ln_bwd_workspace(rows, Hd), dtype=torch.float32, device=z.device)
+    name, dxq = ("fcmf_add_ln_bwd_fp8", _fp8_buffers(rows, Hd, z.device)) if quant else ("fcmf_add_ln_bwd", None)
+    H.check(getattr(L, name)(H.ptr(dy), H.ptr(z), H.ptr(gamma), H.ptr(mean), H.ptr(rstd), H.ptr(dz), H.ptr(dx), H.ptr(dg), H.ptr(db),
+                             H.ptr(dxsum), H.ptr(ws), rows, Hd, p, seed, H.dt(z), *map(H.ptr, dxq or ()), H.stream()), name)
+    return dz, (dz if dx is None else dx), dxq
 
 
 class AddLNFn(torch.autograd.Function):
@@ -917,16 +861,10 @@ class AddLNFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, gamma, beta, eps, p, seed):
         x2 = _rows(x).contiguous()
-        rows, Hd = x2.shape
         r2 = None if res is None else _rows(res)
-        y = torch.empty_like(x2)
         z = torch.empty_like(x2)
-        mean = torch.empty(rows, dtype=torch.float32, device=x2.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x2.device)
         H.require_cuda(x2)
-        H.check(H.lib().fcmf_add_ln_fwd(H.ptr(x2), H.ptr(r2), 0 if r2 is None else _ld(r2), H.ptr(gamma), H.ptr(beta),
-                                        H.ptr(y), H.ptr(z), H.ptr(mean), H.ptr(rstd), rows, Hd, eps, p, seed,
-                                        H.dt(x2), H.stream()), "fcmf_add_ln_fwd")
+        y, mean, rstd, _ = ln_fwd(x2, r2, 0 if r2 is None else _ld(r2), gamma, beta, eps, p, seed, z)
         ctx.save_for_backward(z, gamma, mean, rstd, beta)
         ctx.p, ctx.seed, ctx.xshape = p, seed, x.shape
         ctx.res_shape = None if res is None else res.shape
@@ -935,18 +873,10 @@ class AddLNFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         z, gamma, mean, rstd, beta = ctx.saved_tensors
-        rows, Hd = z.shape
-        dy2 = dy.reshape(rows, Hd).contiguous()
-        dz = torch.empty_like(z)
-        dx = torch.empty_like(z) if ctx.p > 0 else None
-        dgbuf, dg = grad_dest(gamma, (Hd,))       # the arena slices (already zero) where an arena is active: no fill launches
-        dbbuf, db = grad_dest(beta, (Hd,))          # (dg / db = None: a later use of shared parameters, accumulated in place)
-        H.check(H.lib().fcmf_add_ln_bwd(H.ptr(dy2), H.ptr(z), H.ptr(gamma), H.ptr(mean), H.ptr(rstd), H.ptr(dz),
-                                        H.ptr(dx), H.ptr(dgbuf), H.ptr(dbbuf), 0, H.ptr(ln_workspace(rows, Hd, z.device)), rows, Hd, ctx.p, ctx.seed, H.dt(z),
-                                        H.stream()), "fcmf_add_ln_bwd")
-        dxo = (dx if dx is not None else dz).view(ctx.xshape)
-        dres = None if ctx.res_shape is None else dz.view(ctx.res_shape)
-        return dxo, dres, dg, db, None, None, None
+        dgbuf, dg = grad_dest(gamma, (z.shape[1],))      # the arena slices (already zero) where an arena is active: no fill launches
+        dbbuf, db = grad_dest(beta, (z.shape[1],))       # (dg / db = None: a later use of shared parameters, accumulated in place)
+        dz, dx, _ = ln_bwd(dy.reshape(z.shape).contiguous(), z, gamma, mean, rstd, ctx.p, ctx.seed, dgbuf, dbbuf)
+        return dx.view(ctx.xshape), (None if ctx.res_shape is None else dz.view(ctx.res_shape)), dg, db, None, None, None
 
 
 def add_layer_norm(x, res, gamma, beta, eps, p=0.0, training=False):
@@ -1022,14 +952,12 @@ class EmbedLNFn(torch.autograd.Function):
             o = torch.empty_like(d)
             H.check(L.fcmf_dropout(H.ptr(d), H.ptr(o), d.numel(), ctx.p, ctx.seed, H.dt(d), H.stream()), "fcmf_dropout")
             d = o
-        dz = torch.empty_like(z)
         word, ptab, ttab, gpar, bpar = ctx.params
         # (arena slices: already zero, no fill launches.  Only the word table accumulates in place -- dword = None: the tied
         #  matrix's slice was claimed by the vocabulary projection; the others get a temporary that autograd adds)
         dg, _ = grad_dest(gpar, (Hd,), in_place=False, device=z.device)
         db, _ = grad_dest(bpar, (Hd,), in_place=False, device=z.device)
-        H.check(L.fcmf_add_ln_bwd(H.ptr(d), H.ptr(z), H.ptr(gamma), H.ptr(mean), H.ptr(rstd), H.ptr(dz), 0, H.ptr(dg),
-                                  H.ptr(db), 0, H.ptr(ln_workspace(ntok, Hd, z.device)), ntok, Hd, 0.0, 0, H.dt(z), H.stream()), "fcmf_add_ln_bwd")
+        dz = ln_bwd(d, z, gamma, mean, rstd, 0.0, 0, dg, db)[0]      # (the dropout, applied AFTER the LayerNorm here, is undone above)
         dwordbuf, dword = grad_dest(word, word.shape, device=z.device)
         dpos, _ = grad_dest(ptab, ptab.shape, in_place=False, device=z.device)
         dtt, _ = grad_dest(ttab, ttab.shape, in_place=False, device=z.device)

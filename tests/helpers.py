@@ -44,12 +44,15 @@ class _CallRecorder:
     `calls` and forwards the call.  Scalar = declared as anything but c_void_p / a POINTER: addresses are left out.
     desc: the record is what the C ABI receives -- a scalar declared `float` is recorded as the float32 it is converted to, and
     a fourth element holds, for every fcmf_attn_desc argument, (its non-pointer fields, which pointer fields are non-null,
-    whether v1 == k1)."""
+    whether v1 == k1).
+    nulls: the record ends with one more element, a tuple that says for every c_void_p argument whether it was NULL ("bias given or
+    not", "dx wanted or not": invisible in the scalars)."""
 
-    def __init__(self, real, signatures, desc=False):
+    def __init__(self, real, signatures, desc=False, nulls=False):
         from fcmf_framework._hip import HOST_ONLY, AttnDesc
         self._AttnDesc, self._host_only = AttnDesc, HOST_ONLY
-        self._real, self.calls, self._desc = real, [], desc
+        self._real, self.calls, self._desc, self._nulls = real, [], desc, nulls
+        self._ptrs = {n: [i for i, t in enumerate(sig) if t is ctypes.c_void_p] for n, sig in signatures.items()}
         self._scalars = {n: [i for i, t in enumerate(sig) if t is not ctypes.c_void_p and not issubclass(t, ctypes._Pointer)]
                          for n, sig in signatures.items()}
         self._floats = {n: {i for i, t in enumerate(sig) if t is ctypes.c_float} for n, sig in signatures.items()}
@@ -58,15 +61,18 @@ class _CallRecorder:
         fn, keep = getattr(self._real, name), self._scalars.get(name)
         if keep is None or name in self._host_only:      # (a cached planning query launches nothing: not part of a pass)
             return fn
-        floats = self._floats[name]
+        floats, ptrs = self._floats[name], self._ptrs[name]
 
         def call(*args):
             rc = fn(*args)
             if self._desc:
                 scalars = tuple(ctypes.c_float(args[i]).value if i in floats else args[i] for i in keep)
-                self.calls.append((name, scalars, rc, tuple(_desc_record(a) for a in args if isinstance(a, self._AttnDesc))))
+                rec = (name, scalars, rc, tuple(_desc_record(a) for a in args if isinstance(a, self._AttnDesc)))
             else:
-                self.calls.append((name, tuple(args[i] for i in keep), rc))
+                rec = (name, tuple(args[i] for i in keep), rc)
+            if self._nulls:
+                rec += (tuple(not args[i] for i in ptrs),)
+            self.calls.append(rec)
             return rc
         return call
 
@@ -88,12 +94,12 @@ def _calls_digest(calls):
     return hashlib.sha256(repr(calls).encode()).hexdigest()
 
 
-def _recorded(fn, desc=False):
-    """fn() with the recorder in place of the library -> its calls"""
+def _recorded(fn, desc=False, nulls=False):
+    """fn() with the recorder in place of the library -> its calls (desc, nulls: see _CallRecorder)"""
     from fcmf_framework import _hip as H
     H.gemm_ctx(workspace=True)                   # (the first use of a stream creates its context and workspace: not part of the pass)
     real = H.lib()
-    H._lib = rec = _CallRecorder(real, H.SIGNATURES, desc)
+    H._lib = rec = _CallRecorder(real, H.SIGNATURES, desc, nulls)
     try:
         fn()
         torch.cuda.synchronize()

@@ -148,7 +148,7 @@ def _bwd(dev, dy, z, gamma, eps, p=0.0, seed=0, workspace=True, prefill=False, w
     if workspace:
         n = L.fcmf_add_ln_bwd_workspace(rows, H_)
         ws = R.guarded((n,), F32, dev)
-        ws.view.fill_(float("nan"))            # every call rewrites what it reads (ops.ln_workspace): NaN must not reach a result
+        ws.view.fill_(float("nan"))            # every call rewrites what it reads (ops.ln_bwd): NaN must not reach a result
     dyd, zd, gd, md, rd = (t.to(dev) for t in (dy, z, gamma, mean, rstd))        # (held until the synchronize below)
     rc = L.fcmf_add_ln_bwd(H.ptr(dyd), H.ptr(zd), H.ptr(gd), H.ptr(md), H.ptr(rd), H.ptr(dz.view),
                            0 if dx is None else H.ptr(dx.view), H.ptr(outs["dgamma"][0].view), H.ptr(outs["dbeta"][0].view), H.ptr(outs["dxsum"][0].view) if want_dxsum else 0,
