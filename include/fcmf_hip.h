@@ -39,6 +39,9 @@ extern "C" {
 #define FCMF_EPI_DGELU 3  /* C = acc * gelu'(aux)      (aux = saved pre-activation)     */
 #define FCMF_EPI_DTANH 4  /* C = acc * (1 - aux^2)     (aux = saved tanh output)        */
 #define FCMF_EPI_ADD 5    /* C = acc + bias + aux      (residual-gradient accumulation)  */
+/* the two below through fcmf_gemm_drop only; m(idx) = 1/(1-p) or 0: the counter-based dropout mask of fcmf_dropout */
+#define FCMF_EPI_GELU_DROP 6   /* C = gelu_erf(acc + bias) * m(i*N + j); aux (if non-NULL) <- acc + bias, unmasked */
+#define FCMF_EPI_DGELU_DROP 7  /* C = acc * gelu'(aux) * m(i*N + j)                                                */
 
 int fcmf_abi_version(void);
 /* human-readable "gfx950 ..." build string (host pointer, static storage) */
@@ -87,6 +90,24 @@ int fcmf_gemm(fcmf_gemm_ctx* ctx, const void* A, const void* B, void* C, const f
               int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
               int trans_a, int trans_b, int in_dtype, int out_dtype,
               int epilogue, int accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * GEMM with the feed-forward dropout of nn.TransformerEncoderLayer in its epilogue: linear2(dropout(gelu(linear1(x)))) and its
+ * backward without a pass of their own over the [M, N] activation.  Arguments as fcmf_gemm (no `accumulate`: C is written);
+ * epilogue is FCMF_EPI_GELU_DROP (forward) or FCMF_EPI_DGELU_DROP (backward: aux = the pre-activation the forward wrote,
+ * required), anything else is FCMF_ERR_ARG, as is dropout_p outside (0, 1).
+ *   mask: element (i, j) of the LOGICAL [M, N] output (row-major index i*N + j, 64-bit, whatever ldc is) is multiplied by
+ *         dropout_mult(seed, i*N + j, p, 1/(1-p)) -- the mask fcmf_dropout applies to a contiguous [M, N] tensor with the same
+ *         seed -- so both epilogues of one layer regenerate the same mask from (seed, p) and nothing is stored for it.  A dropped
+ *         element is an exact zero; a kept bf16 value is rounded once, after the scaling.
+ *   aux of GELU_DROP is the unmasked pre-activation (gelu' needs it); colsum sums the values as stored, after the mask.
+ * Kernels: the generic f32-MFMA kernel (exact erf forms), the 128x128 bf16 kernel and the persistent 256 / 192-row bf16
+ * kernels at both k-tile depths (transposed A: the 128x128 kernel); never the 64x64 kernel.  fcmf_gemm_fp8 answers
+ * FCMF_ERR_UNSUPPORTED for the two epilogues: in fp8 mode these two GEMMs stay bf16. */
+int fcmf_gemm_drop(fcmf_gemm_ctx* ctx, const void* A, const void* B, void* C, const float* bias, void* aux, float* colsum,
+                   int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc,
+                   int trans_a, int trans_b, int in_dtype, int out_dtype,
+                   int epilogue, float dropout_p, uint64_t seed, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * FP8 (OCP e4m3fn) path of BASELINE configs[4] (FCMF-large): forward and dX GEMMs on the block-scaled matrix instruction

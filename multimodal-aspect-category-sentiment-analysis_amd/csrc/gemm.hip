@@ -40,6 +40,10 @@ struct GemmParams {
   // log2 of the element distance between neighbouring pixels of the convolution's input (= cv_logC for an NHWC activation
   // whose k-tiles walk the channels of one tap; smaller for fcmf_conv_gemm_runs, whose "tap" is a run of several whole pixels)
   int cv_logP;
+  // FCMF_EPI_GELU_DROP / FCMF_EPI_DGELU_DROP (fcmf_gemm_drop): the counter-based mask over the logical [M, N] output.  The rate, and
+  // what the kernels use of it -- dropout_threshold(p) and 1 / (1 - p) -- formed once on the host (base_params): on the device
+  // they would be VALU results that the compiler hoists above the persistent kernels' main loop, where every VGPR is spoken for
+  float drop_p; unsigned drop_thr; float drop_scale; uint64_t drop_seed;
 };
 // Weight-gradient work list (gemm_bf16_dw_batched_kernel): `total_items` (tile, k-range) items over matrices of ANY shapes.  The
 // three tables live in device memory (uploaded per launch: fcmf_gemm_dw_list); everything an item needs beyond the main loop's
@@ -134,6 +138,19 @@ __device__ __forceinline__ float apply_epilogue(float v, int epi, float auxv) {
   }
 }
 
+// ---- dropout in the epilogue (FCMF_EPI_GELU_DROP / FCMF_EPI_DGELU_DROP) ---------------------------------------------------
+constexpr bool epi_drops(int epi) { return epi == FCMF_EPI_GELU_DROP || epi == FCMF_EPI_DGELU_DROP; }
+constexpr int epi_math(int epi) { return epi == FCMF_EPI_GELU_DROP ? FCMF_EPI_GELU : epi == FCMF_EPI_DGELU_DROP ? FCMF_EPI_DGELU : epi; }
+// v = 4 consecutive outputs of one row whose first row-major index `base` (over the logical [M, N] output) is a multiple of 4
+// (N % 4 == 0 in every MFMA kernel, fragments start at multiples of 4): exactly the two pairs base/2, base/2 + 1, one hash
+// each, and both share the high word of the pair index.  The same values as dropout_mult4; a dropped element is a +0.
+__device__ __forceinline__ f32x4 dropout_apply4(f32x4 v, uint64_t seed, uint64_t base, uint32_t thr, float inv_keep) {
+  const uint64_t k0 = base >> 1;
+  const uint32_t h0 = fcmf_hash32(seed, k0), h1 = fcmf_hash32(seed, k0 | 1);
+  return f32x4{(h0 & 0xFFFFu) >= thr ? v[0] * inv_keep : 0.f, (h0 >> 16) >= thr ? v[1] * inv_keep : 0.f,
+               (h1 & 0xFFFFu) >= thr ? v[2] * inv_keep : 0.f, (h1 >> 16) >= thr ? v[3] * inv_keep : 0.f};
+}
+
 // =========================================================================================
 // bf16 MFMA kernel: 128x128 block tile, BK = 32, 4 waves (2x2, 64x64 each), 4-stage LDS ring
 // filled by LDS-DMA (buffer_load_dwordx4 ... lds: no staging VGPRs, no ds_write), three k-tiles
@@ -219,7 +236,8 @@ __device__ __forceinline__ bf16x8 read_frag(const char* lds, int x0, int lane) {
   }
 }
 
-template <bool A_TR, bool B_TR, typename TC>
+// DROP: p.epilogue is FCMF_EPI_GELU_DROP / FCMF_EPI_DGELU_DROP -- the GELU / gelu' epilogue, then the mask (two pair hashes per float4)
+template <bool A_TR, bool B_TR, typename TC, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmParams p) {
   // (an 8-stage ring -- seven k-tiles in flight -- was tried for the grids that leave most CUs empty, the IAOG decoder's 768-row
   //  GEMMs: 36 workgroups, 24 k-tiles, 20 us.  No gain: those launches are a serial chain of per-k-tile fixed costs -- wait, barrier,
@@ -327,6 +345,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmParams p) {
   TC* AUX = reinterpret_cast<TC*>(p.aux);
   const bool atomic = (p.ksplit > 1);
   const bool lead = (blockIdx.z == 0);
+  int epi = p.epilogue;
+  if constexpr (DROP) epi = epi_math(p.epilogue);
   float4 cs[4] = {make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
 #pragma unroll
   for (int fi = 0; fi < 4; ++fi) {
@@ -342,17 +362,21 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmParams p) {
         v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
       }
       const int64_t off = (int64_t)i * p.ldc + j;
-      if (p.epilogue != FCMF_EPI_NONE) {
+      if (epi != FCMF_EPI_NONE) {
         float4 a = make_float4(0, 0, 0, 0);
-        if (p.epilogue == FCMF_EPI_GELU) { if (AUX) Vec4<TC>::store(AUX + off, v); }
-        else if (p.epilogue != FCMF_EPI_TANH) a = Vec4<TC>::load(AUX + off);
+        if (epi == FCMF_EPI_GELU) { if (AUX) Vec4<TC>::store(AUX + off, v); }
+        else if (epi != FCMF_EPI_TANH) a = Vec4<TC>::load(AUX + off);
         if constexpr (sizeof(TC) == 2) {
-          v.x = apply_epilogue_fast(v.x, p.epilogue, a.x); v.y = apply_epilogue_fast(v.y, p.epilogue, a.y);
-          v.z = apply_epilogue_fast(v.z, p.epilogue, a.z); v.w = apply_epilogue_fast(v.w, p.epilogue, a.w);
+          v.x = apply_epilogue_fast(v.x, epi, a.x); v.y = apply_epilogue_fast(v.y, epi, a.y);
+          v.z = apply_epilogue_fast(v.z, epi, a.z); v.w = apply_epilogue_fast(v.w, epi, a.w);
         } else {
-          v.x = apply_epilogue(v.x, p.epilogue, a.x); v.y = apply_epilogue(v.y, p.epilogue, a.y);
-          v.z = apply_epilogue(v.z, p.epilogue, a.z); v.w = apply_epilogue(v.w, p.epilogue, a.w);
+          v.x = apply_epilogue(v.x, epi, a.x); v.y = apply_epilogue(v.y, epi, a.y);
+          v.z = apply_epilogue(v.z, epi, a.z); v.w = apply_epilogue(v.w, epi, a.w);
         }
+      }
+      if constexpr (DROP) {      // index over the logical [M, N] output; i * N + j is a multiple of 4
+        const f32x4 m = dropout_apply4(f32x4{v.x, v.y, v.z, v.w}, p.drop_seed, (uint64_t)i * (uint64_t)p.N + (uint64_t)j, p.drop_thr, p.drop_scale);
+        v = make_float4(m[0], m[1], m[2], m[3]);
       }
       if constexpr (sizeof(TC) == 4) {
         float* cf = reinterpret_cast<float*>(C) + off;
@@ -367,6 +391,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmParams p) {
         }
       } else {
         Vec4<TC>::store(C + off, v);
+      }
+      if constexpr (DROP && sizeof(TC) == 2) {      // the column sums are those of the values as stored
+        v.x = (float)(bf16_t)v.x; v.y = (float)(bf16_t)v.y; v.z = (float)(bf16_t)v.z; v.w = (float)(bf16_t)v.w;
       }
       if (p.colsum) { cs[fj].x += v.x; cs[fj].y += v.y; cs[fj].z += v.z; cs[fj].w += v.w; }
     }
@@ -522,6 +549,12 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
                                EPI == FCMF_EPI_NONE,
                 "256-row tiles (192 rows: row-major A, bf16 output); narrow tiles: 4 x 2 / 8 x 1 waves, plain bf16 NT GEMM");
   static_assert(KB == 32 || KB == 64, "k-tile depth");
+  // FCMF_EPI_GELU_DROP / FCMF_EPI_DGELU_DROP: the arithmetic of GELU / DGELU (EPIM), then the dropout mask on the f32 values in
+  // the fragment layout, before they are rounded (drop4 in the bf16 epilogue).  Everything downstream -- the transposition, the
+  // stores, the column sums of the values as stored -- sees masked values; the aux pass of GELU is packed before the mask.
+  constexpr bool DROP = epi_drops(EPI);
+  constexpr int EPIM = epi_math(EPI);
+  static_assert(!DROP || (sizeof(TC) == 2 && !FP8 && !BATCH && WNW == 4), "dropout epilogues: the bf16 256 / 192-row tiles");
   static_assert(!FP8 || (KB == 64 && !A_TR && !B_TR && sizeof(TC) == 2), "fp8: K-contiguous operands, bf16 output");
   constexpr int KE = FP8 ? 2 * KB : KB;       // contraction elements per k-tile
   constexpr int NW = 8;
@@ -802,7 +835,7 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
   // 128x64 sub-tile per instruction, 4 instructions per 32-row round.  Rounds 0 and 1 are requested before the
   // LAST block of MFMAs of the main loop, the rest right after it (into the dead fragment registers), so the
   // whole operand is in flight before the epilogue starts.
-  constexpr bool HAS_AUX = sizeof(TC) == 2 && (EPI == FCMF_EPI_DGELU || EPI == FCMF_EPI_ADD);
+  constexpr bool HAS_AUX = sizeof(TC) == 2 && (EPIM == FCMF_EPI_DGELU || EPIM == FCMF_EPI_ADD);
   constexpr int NRND = MI / 2;
   constexpr bool EARLY_AUX = HAS_AUX && MI == 6;   // the 256-row tile has no registers to spare inside the main loop
   constexpr int NAX = !HAS_AUX ? 1 : (EARLY_AUX ? NRND : 2);   // 256-row tile: a ring of two rounds, refilled as consumed
@@ -898,6 +931,13 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
     int lane_e = lane;                          // (laundered: keeps the epilogue's per-lane constants from being
     asm volatile("" : "+v"(lane_e));            //  hoisted above the main loop, where every VGPR is spoken for)
     const int er = lane_e & 15, eg = lane_e >> 4;
+    // DROP: fragment (fi, fj) of this lane = row i0 + wm*WM + 16 fi + er, columns j0 + wn*64 + 16 fj + 4 eg .. + 3 of the LOGICAL
+    // [M, N] output (64-bit row-major index, a multiple of 4).  Rows past M and columns past N get a mask too; they are not stored.
+    [[maybe_unused]] uint64_t drop_idx0 = 0;      // fragment (0, 0); the others lie a wave-uniform distance away
+    if constexpr (DROP) drop_idx0 = (uint64_t)(i0 + wm * WM + er) * (uint64_t)p.N + (uint64_t)(j0 + wn * 64 + eg * 4);
+    [[maybe_unused]] auto drop4 = [&](f32x4 v, int fi, int fj) __attribute__((always_inline)) -> f32x4 {
+      return dropout_apply4(v, p.drop_seed, drop_idx0 + ((uint64_t)(fi * 16) * (uint64_t)p.N + (uint64_t)(fj * 16)), p.drop_thr, p.drop_scale);
+    };
     const unsigned ldc2 = (unsigned)p.ldc * 2u;
     const unsigned tile_off = (unsigned)(i0 + wm * WM) * ldc2 + (unsigned)(j0 + wn * 64) * 2u;   // wave's sub-tile
     // transposition slice: fragment-layout accesses are 8 B per lane, row-layout accesses 16 B per lane (whole
@@ -1021,8 +1061,9 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
             const bf16x4 a4 = __builtin_bit_cast(bf16x4, *reinterpret_cast<const u32x2*>(frag_addr(h, fj)));
             const f32x4 a{(float)a4[0], (float)a4[1], (float)a4[2], (float)a4[3]};
             f32x4 v = acc[fj][rnd * 2 + h];
-            if constexpr (EPI == FCMF_EPI_ADD) v = v + a;
+            if constexpr (EPIM == FCMF_EPI_ADD) v = v + a;
             else v = v * dgelu_poly4(a);
+            if constexpr (DROP) v = drop4(v, rnd * 2 + h, fj);
             o[h * 4 + fj] = pack(v);
           }
 #pragma unroll
@@ -1033,19 +1074,20 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
         __builtin_amdgcn_sched_barrier(0);
       }
     } else {
-      const bool two_pass = (EPI == FCMF_EPI_GELU) && p.aux != nullptr;
+      const bool two_pass = (EPIM == FCMF_EPI_GELU) && p.aux != nullptr;
       // accumulators -> finished bf16 values (straight-line code; the accumulator registers die as it goes).
       // o1 = the C values, o0 = the pre-activations that FCMF_EPI_GELU also writes to aux.
-      u32x2 o0[EPI == FCMF_EPI_GELU ? 4 * MI : 1], o1[4 * MI];
+      u32x2 o0[EPIM == FCMF_EPI_GELU ? 4 * MI : 1], o1[4 * MI];
 #pragma unroll
       for (int fi = 0; fi < MI; ++fi) {
 #pragma unroll
         for (int fj = 0; fj < 4; ++fj) {
           f32x4 v = acc[fj][fi];
-          if constexpr (EPI == FCMF_EPI_GELU) {
+          if constexpr (EPIM == FCMF_EPI_GELU) {
             o0[fi * 4 + fj] = pack(v);
             v = v * phi_poly4(v);
           }
+          if constexpr (DROP) v = drop4(v, fi, fj);
           o1[fi * 4 + fj] = pack(v);
         }
         __builtin_amdgcn_sched_barrier(0);   // one fragment row at a time: short live ranges
@@ -1060,7 +1102,7 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
           store_round(rnd, rD, sums);
         }
       };
-      if constexpr (EPI == FCMF_EPI_GELU) {
+      if constexpr (EPIM == FCMF_EPI_GELU) {
         if (two_pass) write_out(o0, __builtin_amdgcn_make_buffer_rsrc(p.aux, 0, p.c_bytes, 0x00020000), false);
       }
       write_out(o1, rC, p.colsum != nullptr || p.colstats != nullptr);
@@ -1392,9 +1434,11 @@ struct GenericParams {
   int kchunk;   // > 0: blockIdx.z owns the contraction range [z kchunk, (z + 1) kchunk) and ADDS its part into the float32 C with
                 // atomics (accumulating outputs of a few tiles: the classifier's 4 x 768 weight gradient walked K = 384 in 24
                 // dependent steps on 12 lone workgroups, 85 us for 1.2 MFLOP)
+  float drop_p; unsigned drop_thr; float drop_scale; uint64_t drop_seed;   // DROP: the mask of FCMF_EPI_GELU_DROP / FCMF_EPI_DGELU_DROP (see GemmParams)
 };
 
-template <typename TI, typename TC>
+// DROP: p.epilogue is FCMF_EPI_GELU_DROP / FCMF_EPI_DGELU_DROP -- the exact erf forms, then dropout_mult per element
+template <typename TI, typename TC, bool DROP = false>
 __global__ __launch_bounds__(256) void gemm_generic_kernel(GenericParams p) {
   constexpr int GT = 64, GK = 16, LDT = GT + 4;
   __shared__ float As[GK][LDT];
@@ -1448,6 +1492,8 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(GenericParams p) {
   }
   TC* C = reinterpret_cast<TC*>(p.C);
   TC* AUX = reinterpret_cast<TC*>(p.aux);
+  int epi = p.epilogue;
+  if constexpr (DROP) epi = epi_math(p.epilogue);
 #pragma unroll
   for (int fi = 0; fi < 2; ++fi)
 #pragma unroll
@@ -1460,11 +1506,15 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(GenericParams p) {
         float v = acc[fi][fj][r];
         if (p.bias) v += p.bias[j];
         int64_t off = (int64_t)i * p.ldc + j;
-        if (p.epilogue != FCMF_EPI_NONE) {
+        if (epi != FCMF_EPI_NONE) {
           float a = 0.f;
-          if (p.epilogue == FCMF_EPI_GELU) { if (AUX) AUX[off] = from_f32<TC>(v); }
-          else if (p.epilogue != FCMF_EPI_TANH) a = to_f32<TC>(AUX[off]);
-          v = apply_epilogue(v, p.epilogue, a);
+          if (epi == FCMF_EPI_GELU) { if (AUX) AUX[off] = from_f32<TC>(v); }
+          else if (epi != FCMF_EPI_TANH) a = to_f32<TC>(AUX[off]);
+          v = apply_epilogue(v, epi, a);
+        }
+        if constexpr (DROP) {      // (the product form, as fcmf_dropout; index over the logical [M, N] output)
+          v *= dropout_mult(p.drop_seed, (uint64_t)i * (uint64_t)p.N + (uint64_t)j, p.drop_p, p.drop_scale);
+          if constexpr (sizeof(TC) == 2) v = to_f32<TC>(from_f32<TC>(v));      // colsum: the value as stored
         }
         if constexpr (sizeof(TC) == 4) {
           if (p.kchunk > 0) { atomicAdd(reinterpret_cast<float*>(C) + off, v); continue; }      // (host: accumulate, no epilogue / bias / colsum)
@@ -1677,6 +1727,7 @@ struct GemmArgs {
   const ConvGeom* cv;              // implicit-GEMM convolution: A is the NHWC activation
   float* colstats;                 // block statistics of the output (fcmf_gemm_colstats)
   int cblk; int64_t cblk_stride;   // column-blocked output (fcmf_gemm_colblocks)
+  float drop_p; uint64_t drop_seed;   // FCMF_EPI_GELU_DROP / FCMF_EPI_DGELU_DROP (fcmf_gemm_drop)
 };
 
 enum GemmKernel { GK_NONE, GK_GENERIC, GK_TILE128, GK_SMALL, GK_NARROW, GK_PERSISTENT, GK_FP8, GK_DW_BATCHED };
@@ -1700,13 +1751,16 @@ struct GemmPlan {
 constexpr size_t PERSIST_SMEM = (size_t)RING_BYTES + 8 * 4096;   // ring + per-wave transposition slices = 160 KiB
 
 static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-static const char* const epi_names[] = {"NONE", "GELU", "TANH", "DGELU", "DTANH", "ADD"};
+static const char* const epi_names[] = {"NONE", "GELU", "TANH", "DGELU", "DTANH", "ADD", "GELU_DROP", "DGELU_DROP"};
 
 static void plan_begin(GemmPlan* pl, const GemmArgs& a, GemmKernel kernel) {
   pl->kernel = kernel; pl->tm = 0; pl->kb = 32;
   pl->trans_a = a.trans_a; pl->trans_b = a.trans_b; pl->in_dtype = a.in_dtype; pl->out_dtype = a.out_dtype; pl->epilogue = a.epilogue;
   pl->dw = DwList{nullptr, nullptr}; pl->dw_red = nullptr; pl->reduce_entries = 0; pl->reduce = RED_NONE; pl->reduce_blocks = 0; pl->cblk = a.cblk; pl->cblk_stride = a.cblk_stride;
 }
+
+// dropout_threshold (common.h) on the host: the same float32 expression (p * 65536 is exact)
+static unsigned drop_threshold_host(float p) { return (unsigned)(p * 65536.0f + 0.5f); }
 
 static int64_t c_extent_bytes(const GemmArgs& a) { return (((int64_t)a.M - 1) * a.ldc + a.N) * 2; }   // (of a 2-byte output)
 
@@ -1716,6 +1770,7 @@ static GemmParams base_params(const GemmArgs& a, int elem_bytes) {
   p.A = a.A; p.B = a.B; p.C = a.C; p.bias = a.bias; p.aux = a.aux; p.colsum = a.colsum; p.colstats = a.colstats;
   p.M = a.M; p.N = a.N; p.K = a.K; p.lda = a.lda; p.ldb = a.ldb; p.ldc = a.ldc;
   p.epilogue = a.epilogue; p.accumulate = a.accumulate; p.ksplit = 1;
+  p.drop_p = a.drop_p; p.drop_thr = drop_threshold_host(a.drop_p); p.drop_scale = 1.0f / (1.0f - a.drop_p); p.drop_seed = a.drop_seed;
   if (const ConvGeom* cv = a.cv) {
     p.cv_C = cv->C; p.cv_logC = cv->logC; p.cv_Hp = cv->Hp; p.cv_Wp = cv->Wp; p.cv_Ho = cv->Ho; p.cv_Wo = cv->Wo;
     p.cv_kw = cv->kw; p.cv_inv_kw = (65536 + cv->kw - 1) / cv->kw; p.cv_stride = cv->stride; p.cv_logP = cv->logP;
@@ -1800,8 +1855,14 @@ static int plan_narrow(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl
 
 // block tile rows of the persistent kernel: 256, or 192 where that removes a nearly empty last round (cost model: rounds x
 // (k-loop time scaled by the tile rows + a fixed per-tile cost of ~8 k-tiles))
-static int persistent_tile_rows(const fcmf_gemm_ctx& cfg, const GemmArgs& a) {
+// 256-row instantiations that the compiler cannot fit into 256 registers: gelu' + mask on 64-deep k-tiles or with a transposed B
+// (28 / 36 bytes of scratch per lane; their FCMF_EPI_DGELU siblings keep 20 / 28).  They are not built; the 192-row tile, which
+// has the registers, takes those GEMMs.
+constexpr bool tile256_spills(int epi, bool trans_b, int kb) { return epi == FCMF_EPI_DGELU_DROP && (kb == 64 || trans_b); }
+
+static int persistent_tile_rows(const fcmf_gemm_ctx& cfg, const GemmArgs& a, int kb) {
   if (a.trans_a || a.out_dtype != FCMF_BF16 || a.accumulate || a.colstats) return 256;
+  if (tile256_spills(a.epilogue, a.trans_b, kb)) return 192;      // (whatever force_tile says: that instantiation does not exist)
   if (cfg.force_tile == 192) return 192;
   auto cost = [&](int rows) {
     const int64_t t = (int64_t)((a.M + rows - 1) / rows) * ((a.N + GB - 1) / GB);
@@ -1816,11 +1877,11 @@ static int plan_persistent(const fcmf_gemm_ctx& cfg, const GemmArgs& a, bool spl
   plan_begin(pl, a, GK_PERSISTENT);
   GemmParams& p = pl->p;
   p = base_params(a, 2);
-  const int slots = cfg.num_cus, tm = persistent_tile_rows(cfg, a);
-  const int tiles = ((a.M + tm - 1) / tm) * ((a.N + GB - 1) / GB);
   // 64-deep k-tiles where both operands are K-contiguous (whole-line DMA), the output is bf16 and K allows it
   // (weight gradients -- token-major operands, 512-B DMA rows already -- measured 4-8 % SLOWER on 64-deep k-tiles)
   const int kb = (cfg.kb64 && !a.trans_a && !a.trans_b && a.out_dtype == FCMF_BF16 && !a.accumulate && a.K % 64 == 0) ? 64 : 32;
+  const int slots = cfg.num_cus, tm = persistent_tile_rows(cfg, a, kb);
+  const int tiles = ((a.M + tm - 1) / tm) * ((a.N + GB - 1) / GB);
   const int nk = (a.K + kb - 1) / kb;      // (the kernel counts k-tiles of ITS depth)
   const int ksplit = splittable && tiles < slots ? persistent_ksplit(slots, tiles, nk, kb) : 1;
   const dim3 grid = persistent_list(cfg, p, tiles, nk, ksplit, a.out_dtype == FCMF_BF16);
@@ -1864,6 +1925,9 @@ static int plan_mfma(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl) 
                ((int64_t)M * N >= (int64_t)256 * 256 * 64 || (splittable && K >= 512));
   if (cfg.force_tile == 128) large = false;
   if (cfg.force_tile == 256 || cfg.force_tile == 192) large = tile_ok;
+  // dropout epilogues: the persistent kernels carry them for row-major A; the 64 x 64 kernel does not carry them at all
+  const bool drop = epi_drops(a.epilogue);
+  if (drop && a.trans_a) large = false;
   if (a.cblk) {      // column-blocked output: written by the fragment-layout reduce pass only (f32, split K through the workspace)
     if (!(tile_ok && splittable && a.out_dtype == FCMF_F32 && cfg.ws && M >= 256 && N >= 256 && a.cblk % 4 == 0 && N % a.cblk == 0)) return FCMF_ERR_UNSUPPORTED;
     large = true;
@@ -1881,7 +1945,7 @@ static int plan_mfma(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl) 
   p = base_params(a, 2);
   const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN), nk = (K + BK - 1) / BK;
   // small outputs (128 x 128 tiles would leave more than half of the CUs without a workgroup): the 64 x 64 kernel
-  if (cfg.force_tile == 0 && cfg.kb64 && !a.trans_a && !a.trans_b && !a.cv && K % 64 == 0 && tiles <= cfg.num_cus / 2 &&
+  if (cfg.force_tile == 0 && cfg.kb64 && !drop && !a.trans_a && !a.trans_b && !a.cv && K % 64 == 0 && tiles <= cfg.num_cus / 2 &&
       (int64_t)M * N >= 64 * 64 && !(a.accumulate && a.epilogue == FCMF_EPI_NONE && nk >= 64)) {      // (long-K accumulations: split-K below)
     plan_begin(pl, a, GK_SMALL);
     pl->tm = SMALL_T; pl->kb = SMALL_KB;
@@ -1899,7 +1963,7 @@ static int plan_mfma(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl) 
   p.ksplit = (nk + p.ktiles_per_split - 1) / p.ktiles_per_split;
   pl->grid = dim3(tiles, 1, p.ksplit); pl->block = dim3(256);
   pl->smem = NSTAGE * STAGE_BYTES;
-  snprintf(pl->name, sizeof pl->name, "gemm_bf16_kernel<%d,%d,%s>", a.trans_a, a.trans_b, a.out_dtype == FCMF_F32 ? "f32" : "bf16");
+  snprintf(pl->name, sizeof pl->name, "gemm_bf16_kernel<%d,%d,%s%s>", a.trans_a, a.trans_b, a.out_dtype == FCMF_F32 ? "f32" : "bf16", drop ? ",drop" : "");
   return FCMF_OK;
 }
 
@@ -1912,6 +1976,7 @@ static int plan_generic(const GemmArgs& a, GemmPlan* pl) {
   g.M = a.M; g.N = a.N; g.K = a.K;
   g.a_si = a.trans_a ? 1 : a.lda; g.a_sk = a.trans_a ? a.lda : 1; g.b_sj = a.trans_b ? 1 : a.ldb; g.b_sk = a.trans_b ? a.ldb : 1; g.ldc = a.ldc;
   g.epilogue = a.epilogue; g.accumulate = a.accumulate;
+  g.drop_p = a.drop_p; g.drop_thr = drop_threshold_host(a.drop_p); g.drop_scale = 1.0f / (1.0f - a.drop_p); g.drop_seed = a.drop_seed;
   pl->grid = dim3((a.N + 63) / 64, (a.M + 63) / 64); pl->block = dim3(256);
   pl->smem = 0;
   const int blocks = (int)(pl->grid.x * pl->grid.y);
@@ -1919,7 +1984,7 @@ static int plan_generic(const GemmArgs& a, GemmPlan* pl) {
     g.kchunk = generic_kchunk(a.K, blocks);
     if (g.kchunk) pl->grid.z = (a.K + g.kchunk - 1) / g.kchunk;
   }
-  snprintf(pl->name, sizeof pl->name, "gemm_generic_kernel");
+  snprintf(pl->name, sizeof pl->name, epi_drops(a.epilogue) ? "gemm_generic_kernel<drop>" : "gemm_generic_kernel");
   return FCMF_OK;
 }
 
@@ -1930,6 +1995,8 @@ static int plan_gemm(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl) 
   if (a.M == 0 || a.N == 0) return FCMF_OK;
   if (a.accumulate && a.out_dtype != FCMF_F32) return FCMF_ERR_ARG;
   if ((a.epilogue == FCMF_EPI_DGELU || a.epilogue == FCMF_EPI_DTANH || a.epilogue == FCMF_EPI_ADD) && !a.aux) return FCMF_ERR_ARG;
+  // the dropout epilogues come with a rate (fcmf_gemm_drop: fcmf_gemm has none to give) and write C
+  if (epi_drops(a.epilogue) && (!(a.drop_p > 0.f && a.drop_p < 1.f) || a.accumulate || (a.epilogue == FCMF_EPI_DGELU_DROP && !a.aux))) return FCMF_ERR_ARG;
   if (a.colsum && a.accumulate) return FCMF_ERR_ARG;   // column sums are those of the final C, not of split-K partials
   if (a.in_dtype != FCMF_F32 && a.in_dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
   if (a.out_dtype != FCMF_F32 && a.out_dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
@@ -1943,12 +2010,15 @@ template <bool A_TR, bool B_TR, typename TC, int EPI>
 static int launch_persistent_typed(const GemmPlan& pl, hipStream_t st) {
   if constexpr (!A_TR && !B_TR && sizeof(TC) == 2) {
     if (pl.kb == 64 && pl.tm == 192) return fcmf_launch(gemm_bf16_tile192k64_kernel<EPI>, pl.grid, pl.block, pl.smem, st, pl.p);
-    if (pl.kb == 64) return fcmf_launch(gemm_bf16_tile256k64_kernel<EPI>, pl.grid, pl.block, pl.smem, st, pl.p);
+    if constexpr (!tile256_spills(EPI, false, 64)) {
+      if (pl.kb == 64) return fcmf_launch(gemm_bf16_tile256k64_kernel<EPI>, pl.grid, pl.block, pl.smem, st, pl.p);
+    }
   }
   if constexpr (!A_TR && sizeof(TC) == 2) {
     if (pl.tm == 192) return fcmf_launch(gemm_bf16_tile192_kernel<B_TR, EPI>, pl.grid, pl.block, pl.smem, st, pl.p);
   }
-  return fcmf_launch(gemm_bf16_tile256_kernel<A_TR, B_TR, TC, EPI>, pl.grid, pl.block, pl.smem, st, pl.p);
+  if constexpr (tile256_spills(EPI, B_TR, 32)) return FCMF_ERR_UNSUPPORTED;      // (persistent_tile_rows: never planned)
+  else return fcmf_launch(gemm_bf16_tile256_kernel<A_TR, B_TR, TC, EPI>, pl.grid, pl.block, pl.smem, st, pl.p);
 }
 template <bool A_TR, bool B_TR>
 static int launch_persistent(const GemmPlan& pl, hipStream_t st) {
@@ -1957,11 +2027,21 @@ static int launch_persistent(const GemmPlan& pl, hipStream_t st) {
     case FCMF_EPI_NONE: return launch_persistent_typed<A_TR, B_TR, bf16_t, FCMF_EPI_NONE>(pl, st);
     case FCMF_EPI_GELU: return launch_persistent_typed<A_TR, B_TR, bf16_t, FCMF_EPI_GELU>(pl, st);
     case FCMF_EPI_DGELU: return launch_persistent_typed<A_TR, B_TR, bf16_t, FCMF_EPI_DGELU>(pl, st);
+    case FCMF_EPI_GELU_DROP:      // (plan_mfma: row-major A only)
+      if constexpr (!A_TR) return launch_persistent_typed<false, B_TR, bf16_t, FCMF_EPI_GELU_DROP>(pl, st);
+      return FCMF_ERR_UNSUPPORTED;
+    case FCMF_EPI_DGELU_DROP:
+      if constexpr (!A_TR) return launch_persistent_typed<false, B_TR, bf16_t, FCMF_EPI_DGELU_DROP>(pl, st);
+      return FCMF_ERR_UNSUPPORTED;
     default: return launch_persistent_typed<A_TR, B_TR, bf16_t, FCMF_EPI_ADD>(pl, st);
   }
 }
 template <bool A_TR, bool B_TR>
 static int launch_tile128(const GemmPlan& pl, hipStream_t st) {
+  if (epi_drops(pl.epilogue)) {
+    if (pl.out_dtype == FCMF_F32) return fcmf_launch(gemm_bf16_kernel<A_TR, B_TR, float, true>, pl.grid, pl.block, pl.smem, st, pl.p);
+    return fcmf_launch(gemm_bf16_kernel<A_TR, B_TR, bf16_t, true>, pl.grid, pl.block, pl.smem, st, pl.p);
+  }
   if (pl.out_dtype == FCMF_F32) return fcmf_launch(gemm_bf16_kernel<A_TR, B_TR, float>, pl.grid, pl.block, pl.smem, st, pl.p);
   return fcmf_launch(gemm_bf16_kernel<A_TR, B_TR, bf16_t>, pl.grid, pl.block, pl.smem, st, pl.p);
 }
@@ -1974,6 +2054,12 @@ static int launch_fp8(const GemmPlan& pl, hipStream_t st) {
   }
 }
 static int launch_generic(const GemmPlan& pl, hipStream_t st) {
+  if (epi_drops(pl.epilogue)) {
+    if (pl.in_dtype == FCMF_F32 && pl.out_dtype == FCMF_F32) return fcmf_launch(gemm_generic_kernel<float, float, true>, pl.grid, pl.block, 0, st, pl.g);
+    if (pl.in_dtype == FCMF_BF16 && pl.out_dtype == FCMF_BF16) return fcmf_launch(gemm_generic_kernel<bf16_t, bf16_t, true>, pl.grid, pl.block, 0, st, pl.g);
+    if (pl.in_dtype == FCMF_BF16 && pl.out_dtype == FCMF_F32) return fcmf_launch(gemm_generic_kernel<bf16_t, float, true>, pl.grid, pl.block, 0, st, pl.g);
+    return fcmf_launch(gemm_generic_kernel<float, bf16_t, true>, pl.grid, pl.block, 0, st, pl.g);
+  }
   if (pl.in_dtype == FCMF_F32 && pl.out_dtype == FCMF_F32) return fcmf_launch(gemm_generic_kernel<float, float>, pl.grid, pl.block, 0, st, pl.g);
   if (pl.in_dtype == FCMF_BF16 && pl.out_dtype == FCMF_BF16) return fcmf_launch(gemm_generic_kernel<bf16_t, bf16_t>, pl.grid, pl.block, 0, st, pl.g);
   if (pl.in_dtype == FCMF_BF16 && pl.out_dtype == FCMF_F32) return fcmf_launch(gemm_generic_kernel<bf16_t, float>, pl.grid, pl.block, 0, st, pl.g);
@@ -2061,7 +2147,7 @@ extern "C" int fcmf_gemm_fp8(fcmf_gemm_ctx* ctx, const void* A, const float* sa,
   if (!A || !B || !C || !sa || !sb || M < 0 || N < 0 || K <= 0) return FCMF_ERR_ARG;
   if (M == 0 || N == 0) return FCMF_OK;
   if ((epilogue == FCMF_EPI_DGELU || epilogue == FCMF_EPI_ADD) && !aux) return FCMF_ERR_ARG;
-  if (epilogue == FCMF_EPI_TANH || epilogue == FCMF_EPI_DTANH) return FCMF_ERR_UNSUPPORTED;
+  if (epilogue == FCMF_EPI_TANH || epilogue == FCMF_EPI_DTANH || epi_drops(epilogue)) return FCMF_ERR_UNSUPPORTED;
   GemmArgs a{};
   a.A = A; a.B = B; a.C = C; a.bias = bias; a.aux = aux; a.colsum = colsum;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
@@ -2178,6 +2264,19 @@ extern "C" int fcmf_gemm(fcmf_gemm_ctx* ctx, const void* A, const void* B, void*
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
   a.trans_a = trans_a; a.trans_b = trans_b; a.in_dtype = in_dtype; a.out_dtype = out_dtype;
   a.epilogue = epilogue; a.accumulate = accumulate;
+  return gemm_impl(ctx, a, stream);
+}
+
+// fcmf_gemm with the feed-forward dropout mask in the epilogue (include/fcmf_hip.h); plan_gemm checks the rate and the operands
+extern "C" int fcmf_gemm_drop(fcmf_gemm_ctx* ctx, const void* A, const void* B, void* C, const float* bias, void* aux, float* colsum,
+                              int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int trans_a, int trans_b, int in_dtype,
+                              int out_dtype, int epilogue, float dropout_p, uint64_t seed, void* stream) {
+  if (!epi_drops(epilogue)) return FCMF_ERR_ARG;
+  GemmArgs a{};
+  a.A = A; a.B = B; a.C = C; a.bias = bias; a.aux = aux; a.colsum = colsum;
+  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+  a.trans_a = trans_a; a.trans_b = trans_b; a.in_dtype = in_dtype; a.out_dtype = out_dtype;
+  a.epilogue = epilogue; a.drop_p = dropout_p; a.drop_seed = seed;
   return gemm_impl(ctx, a, stream);
 }
 

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libfcmf_hip.so")
 F32, BF16, F64 = 0, 1, 2
 BOX_FAST_TRIG = 0x100      # OR-ed into fcmf_box_bias_*'s coord_dtype (include/fcmf_hip.h FCMF_BOX_FAST_TRIG)
 EPI_NONE, EPI_GELU, EPI_TANH, EPI_DGELU, EPI_DTANH, EPI_ADD = 0, 1, 2, 3, 4, 5
+EPI_GELU_DROP, EPI_DGELU_DROP = 6, 7      # fcmf_gemm_drop only: GELU / gelu' with the feed-forward dropout mask
 ERR_UNSUPPORTED = -3      # FCMF_ERR_UNSUPPORTED: callers with a documented fallback entry point test for it
 
 _c = ctypes
@@ -46,6 +47,7 @@ SIGNATURES = {
     "fcmf_abi_version": [],
     "fcmf_build_info": [],
     "fcmf_gemm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp],
+    "fcmf_gemm_drop": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _f, _u64, _vp],
     "fcmf_gemm_ctx_create": [_c.POINTER(_vp)],
     "fcmf_gemm_ctx_destroy": [_vp],
     "fcmf_gemm_ctx_set_workspace": [_vp, _vp, _i64],

@@ -117,39 +117,49 @@ def self_attention_bwd(qkv, mask, out, lse, dout, G, T, Hd, heads, p, seed, bias
 # --------------------------------------------------------------------------------------
 # shared tail: out-proj -> add+LN -> FFN -> add+LN
 # --------------------------------------------------------------------------------------
-def _want_q(rows, Hd, dtype):
-    """the fp8 mode quantises the LayerNorm output inside the LayerNorm kernel when an fp8 GEMM will consume it"""
-    return ops.fp8_enabled() and dtype == torch.bfloat16 and Hd % 128 == 0 and rows >= 256
+def _want_q(rows, Hd, dtype, bf16_consumer=False):
+    """the fp8 mode quantises the LayerNorm output inside the LayerNorm kernel when an fp8 GEMM will consume it
+    (bf16_consumer: the GEMM that reads it carries the feed-forward dropout and stays bf16 -- nothing would read the e4m3 copy)"""
+    return ops.fp8_enabled() and dtype == torch.bfloat16 and Hd % 128 == 0 and rows >= 256 and not bf16_consumer
 
 
-def _post_fwd(c, res, res_ld, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2, eps, p, seeds):
-    """c [M,H] attention context; res rows at stride res_ld.  Returns y and the tensors the backward needs."""
+def _post_fwd(c, res, res_ld, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2, eps, p, seeds, p_f=0.0, seed_f=0):
+    """c [M,H] attention context; res rows at stride res_ld.  Returns y and the tensors the backward needs.
+    p_f > 0: nn.TransformerEncoderLayer's dropout between the feed-forward's gelu and its second Linear, applied by the first
+    GEMM's epilogue (mask over [M, I] from seed_f); the saved `a` is then the dropped activation."""
     dt = c.dtype
     M, Hd = c.shape
     I = w1.shape[0]
     co, c1, c2 = ops.as_compute(wo, dt), ops.as_compute(w1, dt), ops.as_compute(w2, dt)
     h = torch.empty((M, Hd), dtype=dt, device=c.device)
     ops.gemm_nt(c, wo, co, h, M, Hd, Hd, Hd, bias=bo.detach())
-    h1, m1, r1, h1q = ops.ln_fwd(h, res, res_ld, g1, be1, eps, p, seeds[0], h, quant=_want_q(M, Hd, dt))     # (the pre-LN sum z1 overwrites h)
+    h1, m1, r1, h1q = ops.ln_fwd(h, res, res_ld, g1, be1, eps, p, seeds[0], h, quant=_want_q(M, Hd, dt, p_f > 0))     # (the pre-LN sum z1 overwrites h)
     u = torch.empty((M, I), dtype=dt, device=c.device)
     a = torch.empty((M, I), dtype=dt, device=c.device)
-    ops.gemm_nt(h1, w1, c1, a, M, I, Hd, Hd, bias=b1.detach(), aux=u, epi=H.EPI_GELU, xq=h1q)
+    if p_f > 0:
+        ops.gemm_nt(h1, w1, c1, a, M, I, Hd, Hd, bias=b1.detach(), aux=u, epi=H.EPI_GELU_DROP, drop=(p_f, seed_f))
+    else:
+        ops.gemm_nt(h1, w1, c1, a, M, I, Hd, Hd, bias=b1.detach(), aux=u, epi=H.EPI_GELU, xq=h1q)
     f = torch.empty((M, Hd), dtype=dt, device=c.device)
     ops.gemm_nt(a, w2, c2, f, M, Hd, I, I, bias=b2.detach())
     y, m2, r2, _ = ops.ln_fwd(f, h1, Hd, g2, be2, eps, p, seeds[1], f)                                       # (z2 overwrites f)
     return y, (h, m1, r1, h1, u, a, f, m2, r2)
 
 
-def _post_bwd(dy, c, saved, wo, w1, w2, g1, g2, p, seeds, G):
-    """-> dc [M,H], dres (= dz1) [M,H]; weight / bias / LN gradients are accumulated into the views in G"""
+def _post_bwd(dy, c, saved, wo, w1, w2, g1, g2, p, seeds, G, p_f=0.0, seed_f=0):
+    """-> dc [M,H], dres (= dz1) [M,H]; weight / bias / LN gradients are accumulated into the views in G.
+    p_f > 0: the gelu' GEMM regenerates the forward's feed-forward mask (both write [M, I]) and its column sums are masked"""
     z1, m1, r1, h1, u, a, z2, m2, r2 = saved
     dt = c.dtype
     M, Hd = c.shape
     I = w1.shape[0]
     co, c1, c2 = ops.as_compute(wo, dt), ops.as_compute(w1, dt), ops.as_compute(w2, dt)
-    dz2, df, dfq = ops.ln_bwd(dy, z2, g2, m2, r2, p, seeds[1], G["g2"], G["be2"], G["b2"], quant=_want_q(M, Hd, dt))
+    dz2, df, dfq = ops.ln_bwd(dy, z2, g2, m2, r2, p, seeds[1], G["g2"], G["be2"], G["b2"], quant=_want_q(M, Hd, dt, p_f > 0))
     du = torch.empty((M, I), dtype=dt, device=c.device)
-    ops.gemm_dx(df, w2, c2, du, M, I, Hd, aux=u, epi=H.EPI_DGELU, colsum=G["b1"], dyq=dfq)      # (df W2) * gelu'(u); db1
+    if p_f > 0:
+        ops.gemm_dx(df, w2, c2, du, M, I, Hd, aux=u, epi=H.EPI_DGELU_DROP, colsum=G["b1"], drop=(p_f, seed_f))      # (df W2) * gelu'(u) * mask; db1
+    else:
+        ops.gemm_dx(df, w2, c2, du, M, I, Hd, aux=u, epi=H.EPI_DGELU, colsum=G["b1"], dyq=dfq)      # (df W2) * gelu'(u); db1
     ops.gemm(df, a, G["w2"], Hd, I, M, Hd, I, I, 1, 1, acc=True)                   # dW2 = df^T a
     dh1 = torch.empty((M, Hd), dtype=dt, device=c.device)
     ops.gemm_dx(du, w1, c1, dh1, M, Hd, I, aux=dz2, epi=H.EPI_ADD)                             # du W1 + dz2 (residual)
@@ -215,11 +225,12 @@ class PostAttentionFn(torch.autograd.Function):
 class SelfLayerFn(torch.autograd.Function):
     """the whole self-attention layer: fused QKV GEMM -> attention -> PostAttention tail.
     probs (optional, float32 [G, heads, T, T]): filled with the layer's pre-dropout attention probabilities from the node's own
-    q|k|v buffer (one more launch; nothing is saved for it and the backward does not know about it)."""
+    q|k|v buffer (one more launch; nothing is saved for it and the backward does not know about it).
+    p_f, seed_f: the feed-forward dropout of nn.TransformerEncoderLayer (see _post_fwd); 0 = HF's RobertaLayer, which has none."""
 
     @staticmethod
     def forward(ctx, x, mask, wq, bq, wk, bk, wv, bv, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2, heads, eps, p_h, p_a,
-                seed_a, seed0, seed1, probs=None):
+                seed_a, seed0, seed1, probs=None, p_f=0.0, seed_f=0):
         G_, T, Hd = x.shape
         M = G_ * T
         x2 = x.reshape(M, Hd)
@@ -235,21 +246,21 @@ class SelfLayerFn(torch.autograd.Function):
         c, lse = self_attention_fwd(qkv, mk, G_, T, Hd, heads, p_a, seed_a)
         if probs is not None:
             self_attention_probs(qkv, mk, G_, T, Hd, heads, probs)
-        y, saved = _post_fwd(c, x2, Hd, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2, eps, p_h, (seed0, seed1))
+        y, saved = _post_fwd(c, x2, Hd, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2, eps, p_h, (seed0, seed1), p_f, seed_f)
         ctx.save_for_backward(x2, mk, qkv, c, lse, wq, wk, wv, wo, w1, w2, g1, g2, bq, bk, bv, bo, be1, b1, b2, be2, *saved)
-        ctx.cfg = (heads, p_h, p_a, seed_a, seed0, seed1, x.shape)
+        ctx.cfg = (heads, p_h, p_a, seed_a, seed0, seed1, x.shape, p_f, seed_f)
         return y.view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
         x2, mk, qkv, c, lse, wq, wk, wv, wo, w1, w2, g1, g2, bq, bk, bv, bo, be1, b1, b2, be2, *saved = ctx.saved_tensors
-        heads, p_h, p_a, seed_a, s0, s1, xshape = ctx.cfg
+        heads, p_h, p_a, seed_a, s0, s1, xshape, p_f, seed_f = ctx.cfg
         G_, T, Hd = xshape
         M, dt = G_ * T, x2.dtype
         G, R = _layer_grads(x2.device, Hd, w1.shape[0],
                             dict(wqkv=[wq, wk, wv], bqkv=[bq, bk, bv], wo=wo, w1=w1, w2=w2, bo=bo, b1=b1, b2=b2, g1=g1, be1=be1,
                                  g2=g2, be2=be2))
-        dc, dz1 = _post_bwd(dy.reshape(M, Hd).contiguous(), c, saved, wo, w1, w2, g1, g2, p_h, (s0, s1), G)
+        dc, dz1 = _post_bwd(dy.reshape(M, Hd).contiguous(), c, saved, wo, w1, w2, g1, g2, p_h, (s0, s1), G, p_f, seed_f)
         dqkv = self_attention_bwd(qkv, mk, c, lse, dc, G_, T, Hd, heads, p_a, seed_a, bias_grad=G["bqkv"])
         wqkv = _fused_weight([wq, wk, wv], dt)
         dx = torch.empty((M, Hd), dtype=dt, device=x2.device)
@@ -259,4 +270,4 @@ class SelfLayerFn(torch.autograd.Function):
         Ws, bs = _split3(R["wqkv"], Hd), _split3(R["bqkv"], Hd)
         return (dx.view(xshape), None, Ws[0], bs[0], Ws[1], bs[1], Ws[2], bs[2], R["wo"], R["bo"],
                 R["g1"], R["be1"], R["w1"], R["b1"], R["w2"], R["b2"], R["g2"], R["be2"],
-                None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None)

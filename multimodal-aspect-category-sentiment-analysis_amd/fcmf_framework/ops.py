@@ -80,6 +80,22 @@ def output_fusion_attentions():
     return _output_fusion_attentions
 
 
+_ffn_dropout = False
+
+
+def set_ffn_dropout(on):
+    """Opt-in feed-forward dropout of torch_layers.TransformerEncoderLayer: linear2(dropout(gelu(linear1(x)))), as
+    nn.TransformerEncoderLayer trains it, with the mask inside the two FFN GEMMs' epilogues (fcmf_gemm_drop: no pass of its own
+    over the [M, dim_feedforward] activation, nothing saved for it).  Off (the default): linear2(gelu(linear1(x))), and no launch,
+    seed draw or argument differs.  The FCMF and IAOG layers have no such dropout and do not look at the switch."""
+    global _ffn_dropout
+    _ffn_dropout = bool(on)
+
+
+def ffn_dropout():
+    return _ffn_dropout
+
+
 _seed_base = 0x5DEECE66D
 _seed_ctr = 0
 
@@ -350,8 +366,21 @@ def flush_deferred_dw(lo=None, hi=None):
         deferred_dw.flush(final=False, lo=lo, hi=hi)
 
 
-def gemm(A, B, C, M, N, K, lda, ldb, ldc, ta, tb, bias=None, aux=None, epi=H.EPI_NONE, acc=False, colsum=None):
+_DROP_EPI = (H.EPI_GELU_DROP, H.EPI_DGELU_DROP)
+
+
+def gemm(A, B, C, M, N, K, lda, ldb, ldc, ta, tb, bias=None, aux=None, epi=H.EPI_NONE, acc=False, colsum=None, drop=None):
+    """drop = (p, seed) with epi = H.EPI_GELU_DROP / H.EPI_DGELU_DROP: fcmf_gemm_drop (the dropout mask over the [M, N] output in
+    the epilogue); the two belong together"""
     H.require_cuda(A, B, C)
+    if (drop is not None) != (epi in _DROP_EPI) or (drop is not None and acc):
+        raise H.HipLibraryError("gemm: drop=(p, seed) goes with EPI_GELU_DROP / EPI_DGELU_DROP, only with them, and writes C")
+    if drop is not None:
+        with trace_launch(2.0 * M * N * K):
+            H.check(H.lib().fcmf_gemm_drop(H.gemm_ctx(), H.ptr(A), H.ptr(B), H.ptr(C), H.ptr(bias), H.ptr(aux), H.ptr(colsum), M, N, K,
+                                           lda, ldb, ldc, int(ta), int(tb), H.dt(A), H.dt(C), epi, float(drop[0]), int(drop[1]),
+                                           H.stream()), "fcmf_gemm_drop")
+        return
     if deferred_dw.wanted(A, B, C, ta, tb, bias, aux, epi, colsum) and deferred_dw.push(A, B, C, M, N, K, lda, ldb, ldc, acc):
         return
     ctx = H.gemm_ctx(workspace=acc or C.dtype == torch.float32)   # (weight-gradient GEMMs: the context owns the split-K scratch of this stream)
@@ -417,13 +446,16 @@ def gemm_fp8(xq, sx, wq, sw, C, M, N, K, bias=None, aux=None, epi=H.EPI_NONE, co
                                       M, N, K, K, K, N, epi, H.stream()), "fcmf_gemm_fp8")
 
 
-def gemm_nt(x, weight, w_compute, y, M, N, K, ldx, bias=None, aux=None, epi=H.EPI_NONE, colsum=None, owner=None, xq=None):
+def gemm_nt(x, weight, w_compute, y, M, N, K, ldx, bias=None, aux=None, epi=H.EPI_NONE, colsum=None, owner=None, xq=None, drop=None):
     """y [M, N] = epilogue(x [M, K] W^T + bias), W [N, K]: the forward GEMM of nn.Linear.  `weight` = the float32 master (or a
     view of it; `owner` = its Parameter) when there is one: the fp8 mode then multiplies e4m3 copies (x quantised per row here,
-    W per output row, cached); otherwise the bf16 / f32 kernel on `w_compute`."""
+    W per output row, cached); otherwise the bf16 / f32 kernel on `w_compute`.  drop = (p, seed): see gemm; such a GEMM stays on
+    the bf16 / f32 kernel in fp8 mode too (the e4m3 kernel has no dropout epilogue)."""
     if _grad_arena is not None and (owner is not None or weight is not None):
         _grad_arena.note_forward((owner if owner is not None else weight).data_ptr())     # (see deferred_dw.wanted)
-    if weight is not None and weight.dtype == torch.float32 and weight.dim() == 2 and _fp8_ok(M, N, K, N, x, y, aux):
+    if drop is not None:
+        gemm(x, w_compute, y, M, N, K, ldx, K, N, 0, 0, bias=bias, aux=aux, epi=epi, colsum=colsum, drop=drop)
+    elif weight is not None and weight.dtype == torch.float32 and weight.dim() == 2 and _fp8_ok(M, N, K, N, x, y, aux):
         xq, sx = quant_fp8_rows(x, M, K, ldx) if xq is None else xq       # (xq: already quantised by the producing LayerNorm)
         wq, sw = shadows.get_fp8(weight, owner)
         gemm_fp8(xq, sx, wq, sw, y, M, N, K, bias=bias, aux=aux, epi=epi, colsum=colsum)
@@ -441,19 +473,20 @@ def _ld(x):
     return x.stride(0) if x.shape[0] > 1 else x.shape[1]
 
 
-def gemm_dx(dy, weight, w_compute, dx, M, K_in, N_out, aux=None, epi=H.EPI_NONE, colsum=None, owner=None, dyq=None):
+def gemm_dx(dy, weight, w_compute, dx, M, K_in, N_out, aux=None, epi=H.EPI_NONE, colsum=None, owner=None, dyq=None, drop=None):
     """dx [M,K_in] = dy [M,N_out] @ W [N_out,K_in] (+ epilogue).  bf16 mode multiplies by the transposed bf16 copy of the
-    float32 master `weight` (an NT GEMM); f32 mode, or a weight without a master, uses `w_compute` as it lies (NN)."""
-    if (weight is not None and weight.dtype == torch.float32 and weight.dim() == 2 and dy.is_contiguous()
+    float32 master `weight` (an NT GEMM); f32 mode, or a weight without a master, uses `w_compute` as it lies (NN).
+    drop = (p, seed): see gemm; never the e4m3 kernel."""
+    if (drop is None and weight is not None and weight.dtype == torch.float32 and weight.dim() == 2 and dy.is_contiguous()
             and _fp8_ok(M, K_in, N_out, K_in, dy, dx, aux)):
         dyq, sdy = quant_fp8_rows(dy, M, N_out, N_out) if dyq is None else dyq
         wq, sw = shadows.get_fp8_t(weight, owner)                    # [K_in, N_out] e4m3, scales per input row
         gemm_fp8(dyq, sdy, wq, sw, dx, M, K_in, N_out, aux=aux, epi=epi, colsum=colsum)
     elif dy.dtype == torch.bfloat16 and weight is not None and weight.dtype == torch.float32 and weight.dim() == 2:
         wt = shadows.get_t(weight, owner)                            # [K_in, N_out]; owner: the Parameter behind a temporary view
-        gemm(dy, wt, dx, M, K_in, N_out, N_out, N_out, K_in, 0, 0, aux=aux, epi=epi, colsum=colsum)
+        gemm(dy, wt, dx, M, K_in, N_out, N_out, N_out, K_in, 0, 0, aux=aux, epi=epi, colsum=colsum, drop=drop)
     else:
-        gemm(dy, w_compute, dx, M, K_in, N_out, N_out, K_in, K_in, 0, 1, aux=aux, epi=epi, colsum=colsum)
+        gemm(dy, w_compute, dx, M, K_in, N_out, N_out, K_in, K_in, 0, 1, aux=aux, epi=epi, colsum=colsum, drop=drop)
 
 
 def gemm_dx_long_k(dy, w, M, K_in, N_out, ldw):

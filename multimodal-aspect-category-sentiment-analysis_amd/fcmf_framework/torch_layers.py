@@ -12,9 +12,11 @@ for the text encoder's `output_attentions`: in train() mode they are the softmax
 key is uniform where torch gives NaN.  `need_weights` defaults to False here (torch: True).
 
 Only what the baselines use is built -- batch_first=True, post-norm, gelu, biases, no attn_mask; anything else raises
-NotImplementedError.  One difference under training: torch drops activations once more between the feed-forward's gelu and
-its second Linear; the fused layer (HF's RobertaLayer) does not, so a train()-mode step regularises slightly less.  In
-eval() mode the two are the same function.
+NotImplementedError.  Under training torch drops activations once more between the feed-forward's gelu and its second
+Linear, which HF's RobertaLayer (the fused layer's origin) does not: `ops.set_ffn_dropout(True)` (run_baselines.py
+--ffn_dropout) turns that dropout on, inside the epilogues of the two feed-forward GEMMs (fcmf_gemm_drop), and the
+train()-mode step is then the function torch trains.  It is off by default (a step then regularises slightly less, and is
+launch for launch what it was before the switch existed); in eval() mode the two are the same function either way.
 """
 import copy
 
@@ -120,10 +122,13 @@ class TransformerEncoderLayer(nn.Module):
         p = self.p if self.training else 0.0
         seed_a = ops.next_seed() if p > 0 else 0
         s0, s1 = (ops.next_seed(), ops.next_seed()) if p > 0 else (0, 0)
+        # feed-forward dropout (ops.set_ffn_dropout): probs=None, p_f, seed_f -- the seed drawn last, so the other three masks of
+        # the step are those of a run with the switch off; off, the call is argument for argument what it was
+        ffn = (None, p, ops.next_seed()) if p > 0 and ops.ffn_dropout() else ()
         return SelfLayerFn.apply(src, padding_to_additive(src_key_padding_mask), *sa.qkv_params(), sa.out_proj.weight,
                                  sa.out_proj.bias, self.norm1.weight, self.norm1.bias, self.linear1.weight, self.linear1.bias,
                                  self.linear2.weight, self.linear2.bias, self.norm2.weight, self.norm2.bias, sa.num_heads,
-                                 float(self.norm1.eps), p, p, seed_a, s0, s1)
+                                 float(self.norm1.eps), p, p, seed_a, s0, s1, *ffn)
 
 
 class TransformerEncoder(nn.Module):

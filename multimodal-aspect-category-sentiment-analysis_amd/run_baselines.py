@@ -73,6 +73,8 @@ def build_parser():
     p.add_argument('--synthetic_steps', type=int, default=0, help="train on N seeded synthetic batches per epoch; no dataset needed")
     p.add_argument('--precomputed_features', action='store_true', help="the dataset yields ResNet-152 features instead of pixels")
     p.add_argument('--resnet_checkpoint', default=None, type=str, help="torchvision resnet152 state dict for the HIP trunk")
+    p.add_argument('--ffn_dropout', action='store_true',
+                   help="nn.TransformerEncoderLayer's dropout between the feed-forward's gelu and its second Linear (ops.set_ffn_dropout)")
     p.set_defaults(ddp=False)
     return p
 
@@ -203,6 +205,8 @@ def main(argv=None):
     _, _, _, device, _, logger = init_run(args, "baselines", f"training_{tag}.log", formatter=fmt, script="run_baselines.py")
     args.train_batch_size = int(args.train_batch_size / args.gradient_accumulation_steps)
     logger.info("model: %s device: %s bf16: %s", cls_name, device, args.bf16 or args.fp16)
+    ops.set_ffn_dropout(args.ffn_dropout)        # (before the model is built; the encoder layers read it at every forward)
+    logger.info("feed-forward dropout of the torch encoder layers: %s", "on" if args.ffn_dropout else "off")
 
     aspects = args.list_aspect
     model = getattr(baselines, cls_name)(args.pretrained_hf_model, num_labels=args.num_polarity)
