@@ -42,6 +42,10 @@ extern "C" {
 /* the two below through fcmf_gemm_drop only; m(idx) = 1/(1-p) or 0: the counter-based dropout mask of fcmf_dropout */
 #define FCMF_EPI_GELU_DROP 6   /* C = gelu_erf(acc + bias) * m(i*N + j); aux (if non-NULL) <- acc + bias, unmasked */
 #define FCMF_EPI_DGELU_DROP 7  /* C = acc * gelu'(aux) * m(i*N + j)                                                */
+/* eval-mode BatchNorm folded into a convolution: its scale lives in the weights, its shift is the bias (fcmf_gemm, fcmf_conv_gemm_epi;
+ * fcmf_gemm_fp8 and fcmf_gemm_drop answer FCMF_ERR_UNSUPPORTED) */
+#define FCMF_EPI_RELU 8        /* C = max(acc + bias, 0)                                      */
+#define FCMF_EPI_ADD_RELU 9    /* C = max(acc + bias + aux, 0)  (aux = the block's identity)   */
 
 int fcmf_abi_version(void);
 /* human-readable "gfx950 ..." build string (host pointer, static storage) */
@@ -544,6 +548,11 @@ int fcmf_bn_finalize_apply(const void* x, const void* res, void* y, const double
  * bf16, C a power of two >= 64, w [Cout, kh*kw*C] row-major in (ky, kx, c) order, y [n*Ho*Wo, Cout]. */
 int fcmf_conv_gemm(fcmf_gemm_ctx* ctx, const void* x, const void* w, void* y, int n, int Hp, int Wp, int C, int Ho, int Wo,
                    int kh, int kw, int stride, int Cout, void* stream);
+/* fcmf_conv_gemm with an epilogue: y = epi(conv(x, w) + bias[co] (+ aux[(n, oy, ox), co])), bias float32 [Cout] (required), aux bf16
+ * [n*Ho*Wo, Cout] (required by the two ADD epilogues, ignored otherwise), epilogue one of FCMF_EPI_NONE / _RELU / _ADD / _ADD_RELU
+ * (anything else: FCMF_ERR_ARG).  The convolutions of an eval-mode trunk whose BatchNorm is folded into w and bias. */
+int fcmf_conv_gemm_epi(fcmf_gemm_ctx* ctx, const void* x, const void* w, void* y, const float* bias, void* aux, int epilogue,
+                       int n, int Hp, int Wp, int C, int Ho, int Wo, int kh, int kw, int stride, int Cout, void* stream);
 /* f32 C (+)= op(A) op(B) of bf16 operands with a COLUMN-BLOCKED output: element (i, j) is stored at
  *   C + (j / col_block) * col_block_stride + i * ldc + j % col_block          (col_block % 4 == 0, N % col_block == 0).
  * The per-head projection weights of the IAOG decoder's Attention are [n_head, E, d] tensors (mm_modeling.py:57-58); their gradient

@@ -116,6 +116,7 @@ __device__ __forceinline__ f32x2 phi_poly2(f32x2 x) { const f32x4 r = phi_poly4(
 __device__ __forceinline__ f32x2 dgelu_poly2(f32x2 x) { const f32x4 r = dgelu_poly4(f32x4{x[0], x[1], x[0], x[1]}); return f32x2{r[0], r[1]}; }
 __device__ __forceinline__ float gelu_poly(float x) { const f32x2 v{x, x}; return (v * phi_poly2(v))[0]; }
 __device__ __forceinline__ float dgelu_poly(float x) { return dgelu_poly2(f32x2{x, x})[0]; }
+__device__ __forceinline__ f32x4 relu4(f32x4 v) { return f32x4{fmaxf(v[0], 0.0f), fmaxf(v[1], 0.0f), fmaxf(v[2], 0.0f), fmaxf(v[3], 0.0f)}; }
 __device__ __forceinline__ float apply_epilogue_fast(float v, int epi, float auxv) {
   switch (epi) {
     case FCMF_EPI_GELU: return gelu_poly(v);
@@ -123,6 +124,8 @@ __device__ __forceinline__ float apply_epilogue_fast(float v, int epi, float aux
     case FCMF_EPI_DGELU: return v * dgelu_poly(auxv);
     case FCMF_EPI_DTANH: return v * (1.0f - auxv * auxv);
     case FCMF_EPI_ADD: return v + auxv;
+    case FCMF_EPI_RELU: return fmaxf(v, 0.0f);
+    case FCMF_EPI_ADD_RELU: return fmaxf(v + auxv, 0.0f);
     default: return v;
   }
 }
@@ -134,12 +137,18 @@ __device__ __forceinline__ float apply_epilogue(float v, int epi, float auxv) {
     case FCMF_EPI_DGELU: return v * dgelu_f(auxv);
     case FCMF_EPI_DTANH: return v * (1.0f - auxv * auxv);
     case FCMF_EPI_ADD: return v + auxv;
+    case FCMF_EPI_RELU: return fmaxf(v, 0.0f);
+    case FCMF_EPI_ADD_RELU: return fmaxf(v + auxv, 0.0f);
     default: return v;
   }
 }
 
 // ---- dropout in the epilogue (FCMF_EPI_GELU_DROP / FCMF_EPI_DGELU_DROP) ---------------------------------------------------
 constexpr bool epi_drops(int epi) { return epi == FCMF_EPI_GELU_DROP || epi == FCMF_EPI_DGELU_DROP; }
+// epilogues whose arithmetic reads aux (GELU only writes it; TANH and RELU never touch it)
+__host__ __device__ constexpr bool epi_reads_aux(int epi) {
+  return epi == FCMF_EPI_DGELU || epi == FCMF_EPI_DTANH || epi == FCMF_EPI_ADD || epi == FCMF_EPI_ADD_RELU;
+}
 constexpr int epi_math(int epi) { return epi == FCMF_EPI_GELU_DROP ? FCMF_EPI_GELU : epi == FCMF_EPI_DGELU_DROP ? FCMF_EPI_DGELU : epi; }
 // v = 4 consecutive outputs of one row whose first row-major index `base` (over the logical [M, N] output) is a multiple of 4
 // (N % 4 == 0 in every MFMA kernel, fragments start at multiples of 4): exactly the two pairs base/2, base/2 + 1, one hash
@@ -365,7 +374,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmParams p) {
       if (epi != FCMF_EPI_NONE) {
         float4 a = make_float4(0, 0, 0, 0);
         if (epi == FCMF_EPI_GELU) { if (AUX) Vec4<TC>::store(AUX + off, v); }
-        else if (epi != FCMF_EPI_TANH) a = Vec4<TC>::load(AUX + off);
+        else if (epi_reads_aux(epi)) a = Vec4<TC>::load(AUX + off);
         if constexpr (sizeof(TC) == 2) {
           v.x = apply_epilogue_fast(v.x, epi, a.x); v.y = apply_epilogue_fast(v.y, epi, a.y);
           v.z = apply_epilogue_fast(v.z, epi, a.z); v.w = apply_epilogue_fast(v.w, epi, a.w);
@@ -546,8 +555,8 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
   static_assert(!BATCH || (A_TR && B_TR && sizeof(TC) == 4 && MI == 8 && KB == 32), "batched: the weight-gradient kernel");
   static_assert(WNW == 4 ? (MI == 8 || (MI == 6 && !A_TR && sizeof(TC) == 2))
                          : ((WNW == 2 && MI == 4) || (WNW == 1 && MI == 2)) && !A_TR && !B_TR && sizeof(TC) == 2 && KB == 64 && !FP8 &&
-                               EPI == FCMF_EPI_NONE,
-                "256-row tiles (192 rows: row-major A, bf16 output); narrow tiles: 4 x 2 / 8 x 1 waves, plain bf16 NT GEMM");
+                               (EPI == FCMF_EPI_NONE || EPI == FCMF_EPI_RELU),
+                "256-row tiles (192 rows: row-major A, bf16 output); narrow tiles: 4 x 2 / 8 x 1 waves, bf16 NT GEMM, no aux operand");
   static_assert(KB == 32 || KB == 64, "k-tile depth");
   // FCMF_EPI_GELU_DROP / FCMF_EPI_DGELU_DROP: the arithmetic of GELU / DGELU (EPIM), then the dropout mask on the f32 values in
   // the fragment layout, before they are rounded (drop4 in the bf16 epilogue).  Everything downstream -- the transposition, the
@@ -835,7 +844,7 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
   // 128x64 sub-tile per instruction, 4 instructions per 32-row round.  Rounds 0 and 1 are requested before the
   // LAST block of MFMAs of the main loop, the rest right after it (into the dead fragment registers), so the
   // whole operand is in flight before the epilogue starts.
-  constexpr bool HAS_AUX = sizeof(TC) == 2 && (EPIM == FCMF_EPI_DGELU || EPIM == FCMF_EPI_ADD);
+  constexpr bool HAS_AUX = sizeof(TC) == 2 && (EPIM == FCMF_EPI_DGELU || EPIM == FCMF_EPI_ADD || EPIM == FCMF_EPI_ADD_RELU);
   constexpr int NRND = MI / 2;
   constexpr bool EARLY_AUX = HAS_AUX && MI == 6;   // the 256-row tile has no registers to spare inside the main loop
   constexpr int NAX = !HAS_AUX ? 1 : (EARLY_AUX ? NRND : 2);   // 256-row tile: a ring of two rounds, refilled as consumed
@@ -1062,6 +1071,7 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
             const f32x4 a{(float)a4[0], (float)a4[1], (float)a4[2], (float)a4[3]};
             f32x4 v = acc[fj][rnd * 2 + h];
             if constexpr (EPIM == FCMF_EPI_ADD) v = v + a;
+            else if constexpr (EPIM == FCMF_EPI_ADD_RELU) v = relu4(v + a);
             else v = v * dgelu_poly4(a);
             if constexpr (DROP) v = drop4(v, rnd * 2 + h, fj);
             o[h * 4 + fj] = pack(v);
@@ -1087,6 +1097,7 @@ __device__ __forceinline__ void gemm_bf16_tile256_body(const GemmParams& p, cons
             o0[fi * 4 + fj] = pack(v);
             v = v * phi_poly4(v);
           }
+          if constexpr (EPIM == FCMF_EPI_RELU) v = relu4(v);
           if constexpr (DROP) v = drop4(v, fi, fj);
           o1[fi * 4 + fj] = pack(v);
         }
@@ -1382,7 +1393,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_small_kernel(GemmParams p) {
       if (p.epilogue != FCMF_EPI_NONE) {
         float4 a = make_float4(0, 0, 0, 0);
         if (p.epilogue == FCMF_EPI_GELU) { if (AUX) Vec4<TC>::store(AUX + off, v); }
-        else if (p.epilogue != FCMF_EPI_TANH) a = Vec4<TC>::load(AUX + off);
+        else if (epi_reads_aux(p.epilogue)) a = Vec4<TC>::load(AUX + off);
         if constexpr (sizeof(TC) == 2) {
           v.x = apply_epilogue_fast(v.x, p.epilogue, a.x); v.y = apply_epilogue_fast(v.y, p.epilogue, a.y);
           v.z = apply_epilogue_fast(v.z, p.epilogue, a.z); v.w = apply_epilogue_fast(v.w, p.epilogue, a.w);
@@ -1509,7 +1520,7 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(GenericParams p) {
         if (epi != FCMF_EPI_NONE) {
           float a = 0.f;
           if (epi == FCMF_EPI_GELU) { if (AUX) AUX[off] = from_f32<TC>(v); }
-          else if (epi != FCMF_EPI_TANH) a = to_f32<TC>(AUX[off]);
+          else if (epi_reads_aux(epi)) a = to_f32<TC>(AUX[off]);
           v = apply_epilogue(v, epi, a);
         }
         if constexpr (DROP) {      // (the product form, as fcmf_dropout; index over the logical [M, N] output)
@@ -1547,6 +1558,13 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_tile256k64_n128_kernel(GemmP
 }
 __global__ __launch_bounds__(512, 1) void gemm_bf16_tile256k64_n64_kernel(GemmParams p) {
   gemm_bf16_tile256_body<false, false, bf16_t, FCMF_EPI_NONE, 2, 64, false, false, 1>(p);
+}
+// ... with the ReLU of a folded eval-mode BatchNorm (bias = its shift) in the epilogue: the trunk's 64- / 128-channel 3x3 convolutions
+__global__ __launch_bounds__(512, 1) void gemm_bf16_tile256k64_n128_relu_kernel(GemmParams p) {
+  gemm_bf16_tile256_body<false, false, bf16_t, FCMF_EPI_RELU, 4, 64, false, false, 2>(p);
+}
+__global__ __launch_bounds__(512, 1) void gemm_bf16_tile256k64_n64_relu_kernel(GemmParams p) {
+  gemm_bf16_tile256_body<false, false, bf16_t, FCMF_EPI_RELU, 2, 64, false, false, 1>(p);
 }
 // the weight gradients dW_i (+)= dY_i^T X_i of a whole flush in ONE launch: the tiles of all matrices, of any shapes, form one work
 // list (a layer's 768 x 768 gradient alone is 9 tiles: it filled the chip only through a 28-way split of K, whose partial tiles
@@ -1751,7 +1769,7 @@ struct GemmPlan {
 constexpr size_t PERSIST_SMEM = (size_t)RING_BYTES + 8 * 4096;   // ring + per-wave transposition slices = 160 KiB
 
 static bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-static const char* const epi_names[] = {"NONE", "GELU", "TANH", "DGELU", "DTANH", "ADD", "GELU_DROP", "DGELU_DROP"};
+static const char* const epi_names[] = {"NONE", "GELU", "TANH", "DGELU", "DTANH", "ADD", "GELU_DROP", "DGELU_DROP", "RELU", "ADD_RELU"};
 
 static void plan_begin(GemmPlan* pl, const GemmArgs& a, GemmKernel kernel) {
   pl->kernel = kernel; pl->tm = 0; pl->kb = 32;
@@ -1849,7 +1867,8 @@ static int plan_narrow(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl
   pl->tm = 256; pl->kb = 64;
   pl->p = base_params(a, 2);
   plan_persistent_launch(pl, persistent_list(cfg, pl->p, (a.M + GB - 1) / GB, a.K / 64, 1, true));
-  snprintf(pl->name, sizeof pl->name, "gemm_bf16_tile256k64_n%d_kernel", a.N <= 64 ? 64 : 128);
+  if (a.epilogue == FCMF_EPI_RELU) snprintf(pl->name, sizeof pl->name, "gemm_bf16_tile256k64_n%d_relu_kernel", a.N <= 64 ? 64 : 128);
+  else snprintf(pl->name, sizeof pl->name, "gemm_bf16_tile256k64_n%d_kernel", a.N <= 64 ? 64 : 128);
   return FCMF_OK;
 }
 
@@ -1858,7 +1877,12 @@ static int plan_narrow(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl
 // 256-row instantiations that the compiler cannot fit into 256 registers: gelu' + mask on 64-deep k-tiles or with a transposed B
 // (28 / 36 bytes of scratch per lane; their FCMF_EPI_DGELU siblings keep 20 / 28).  They are not built; the 192-row tile, which
 // has the registers, takes those GEMMs.
-constexpr bool tile256_spills(int epi, bool trans_b, int kb) { return epi == FCMF_EPI_DGELU_DROP && (kb == 64 || trans_b); }
+// The ReLU epilogues follow the same rule: RELU with a transposed B (8 bytes), ADD_RELU on 64-deep k-tiles or with a transposed B
+// (24 / 20 bytes, as their FCMF_EPI_ADD siblings) go to the 192-row tile; with a transposed A (every one spills, and the 192-row
+// tile needs a row-major A) they are not persistent at all: plan_mfma sends them to the run-time-epilogue kernels.
+constexpr bool tile256_spills(int epi, bool trans_b, int kb) {
+  return ((epi == FCMF_EPI_DGELU_DROP || epi == FCMF_EPI_ADD_RELU) && (kb == 64 || trans_b)) || (epi == FCMF_EPI_RELU && trans_b);
+}
 
 static int persistent_tile_rows(const fcmf_gemm_ctx& cfg, const GemmArgs& a, int kb) {
   if (a.trans_a || a.out_dtype != FCMF_BF16 || a.accumulate || a.colstats) return 256;
@@ -1928,11 +1952,14 @@ static int plan_mfma(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl) 
   // dropout epilogues: the persistent kernels carry them for row-major A; the 64 x 64 kernel does not carry them at all
   const bool drop = epi_drops(a.epilogue);
   if (drop && a.trans_a) large = false;
+  if ((a.epilogue == FCMF_EPI_RELU || a.epilogue == FCMF_EPI_ADD_RELU) && a.trans_a) large = false;      // (tile256_spills)
   if (a.cblk) {      // column-blocked output: written by the fragment-layout reduce pass only (f32, split K through the workspace)
     if (!(tile_ok && splittable && a.out_dtype == FCMF_F32 && cfg.ws && M >= 256 && N >= 256 && a.cblk % 4 == 0 && N % a.cblk == 0)) return FCMF_ERR_UNSUPPORTED;
     large = true;
   }
-  if (cfg.force_tile == 0 && cfg.kb64 && tile_ok && !a.colsum && plain_bf16 && narrow_shape(M, N, K)) return plan_narrow(cfg, a, pl);
+  // (narrow layouts carry no aux operand: RELU rides on them, ADD_RELU of such a shape goes to the 64 x 64 / 128 x 128 kernels below)
+  const bool plain_relu = a.out_dtype == FCMF_BF16 && !a.trans_a && !a.trans_b && a.epilogue == FCMF_EPI_RELU && !a.accumulate;      // (RELU never touches aux)
+  if (cfg.force_tile == 0 && cfg.kb64 && tile_ok && !a.colsum && (plain_bf16 || plain_relu) && narrow_shape(M, N, K)) return plan_narrow(cfg, a, pl);
   if (a.colstats) {       // block statistics exist in the 256-row bf16 kernels only: the caller falls back to a statistics pass
     // (they were built into the 128 x 128 kernel too -- the trunk's 64 / 128-channel layers -- and measured: its epilogue, a
     //  fragment-layout one, pays as much for the rounding, the 128 shuffles and two barriers as the separate pass costs)
@@ -1994,7 +2021,7 @@ static int plan_gemm(const fcmf_gemm_ctx& cfg, const GemmArgs& a, GemmPlan* pl) 
   plan_begin(pl, a, GK_NONE);
   if (a.M == 0 || a.N == 0) return FCMF_OK;
   if (a.accumulate && a.out_dtype != FCMF_F32) return FCMF_ERR_ARG;
-  if ((a.epilogue == FCMF_EPI_DGELU || a.epilogue == FCMF_EPI_DTANH || a.epilogue == FCMF_EPI_ADD) && !a.aux) return FCMF_ERR_ARG;
+  if (epi_reads_aux(a.epilogue) && !a.aux) return FCMF_ERR_ARG;
   // the dropout epilogues come with a rate (fcmf_gemm_drop: fcmf_gemm has none to give) and write C
   if (epi_drops(a.epilogue) && (!(a.drop_p > 0.f && a.drop_p < 1.f) || a.accumulate || (a.epilogue == FCMF_EPI_DGELU_DROP && !a.aux))) return FCMF_ERR_ARG;
   if (a.colsum && a.accumulate) return FCMF_ERR_ARG;   // column sums are those of the final C, not of split-K partials
@@ -2032,6 +2059,12 @@ static int launch_persistent(const GemmPlan& pl, hipStream_t st) {
       return FCMF_ERR_UNSUPPORTED;
     case FCMF_EPI_DGELU_DROP:
       if constexpr (!A_TR) return launch_persistent_typed<false, B_TR, bf16_t, FCMF_EPI_DGELU_DROP>(pl, st);
+      return FCMF_ERR_UNSUPPORTED;
+    case FCMF_EPI_RELU:           // (plan_mfma: row-major A only)
+      if constexpr (!A_TR) return launch_persistent_typed<false, B_TR, bf16_t, FCMF_EPI_RELU>(pl, st);
+      return FCMF_ERR_UNSUPPORTED;
+    case FCMF_EPI_ADD_RELU:
+      if constexpr (!A_TR) return launch_persistent_typed<false, B_TR, bf16_t, FCMF_EPI_ADD_RELU>(pl, st);
       return FCMF_ERR_UNSUPPORTED;
     default: return launch_persistent_typed<A_TR, B_TR, bf16_t, FCMF_EPI_ADD>(pl, st);
   }
@@ -2082,8 +2115,12 @@ static int run_plan(const GemmPlan& pl, hipStream_t st) {
                                     : fcmf_launch(gemm_bf16_small_kernel<bf16_t>, pl.grid, pl.block, pl.smem, st, p);
       break;
     case GK_NARROW:
-      rc = p.N <= 64 ? fcmf_launch(gemm_bf16_tile256k64_n64_kernel, pl.grid, pl.block, pl.smem, st, p)
-                     : fcmf_launch(gemm_bf16_tile256k64_n128_kernel, pl.grid, pl.block, pl.smem, st, p);
+      if (pl.epilogue == FCMF_EPI_RELU)
+        rc = p.N <= 64 ? fcmf_launch(gemm_bf16_tile256k64_n64_relu_kernel, pl.grid, pl.block, pl.smem, st, p)
+                       : fcmf_launch(gemm_bf16_tile256k64_n128_relu_kernel, pl.grid, pl.block, pl.smem, st, p);
+      else
+        rc = p.N <= 64 ? fcmf_launch(gemm_bf16_tile256k64_n64_kernel, pl.grid, pl.block, pl.smem, st, p)
+                       : fcmf_launch(gemm_bf16_tile256k64_n128_kernel, pl.grid, pl.block, pl.smem, st, p);
       break;
     case GK_PERSISTENT: rc = FCMF_BY_TRANS(launch_persistent, pl, st); break;
     case GK_FP8: rc = launch_fp8(pl, st); break;
@@ -2147,7 +2184,8 @@ extern "C" int fcmf_gemm_fp8(fcmf_gemm_ctx* ctx, const void* A, const float* sa,
   if (!A || !B || !C || !sa || !sb || M < 0 || N < 0 || K <= 0) return FCMF_ERR_ARG;
   if (M == 0 || N == 0) return FCMF_OK;
   if ((epilogue == FCMF_EPI_DGELU || epilogue == FCMF_EPI_ADD) && !aux) return FCMF_ERR_ARG;
-  if (epilogue == FCMF_EPI_TANH || epilogue == FCMF_EPI_DTANH || epi_drops(epilogue)) return FCMF_ERR_UNSUPPORTED;
+  if (epilogue == FCMF_EPI_TANH || epilogue == FCMF_EPI_DTANH || epi_drops(epilogue) || epilogue == FCMF_EPI_RELU || epilogue == FCMF_EPI_ADD_RELU)
+    return FCMF_ERR_UNSUPPORTED;
   GemmArgs a{};
   a.A = A; a.B = B; a.C = C; a.bias = bias; a.aux = aux; a.colsum = colsum;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
@@ -2271,6 +2309,7 @@ extern "C" int fcmf_gemm(fcmf_gemm_ctx* ctx, const void* A, const void* B, void*
 extern "C" int fcmf_gemm_drop(fcmf_gemm_ctx* ctx, const void* A, const void* B, void* C, const float* bias, void* aux, float* colsum,
                               int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int trans_a, int trans_b, int in_dtype,
                               int out_dtype, int epilogue, float dropout_p, uint64_t seed, void* stream) {
+  if (epilogue == FCMF_EPI_RELU || epilogue == FCMF_EPI_ADD_RELU) return FCMF_ERR_UNSUPPORTED;
   if (!epi_drops(epilogue)) return FCMF_ERR_ARG;
   GemmArgs a{};
   a.A = A; a.B = B; a.C = C; a.bias = bias; a.aux = aux; a.colsum = colsum;
@@ -2695,7 +2734,8 @@ extern "C" int fcmf_gemm_dw_batched(fcmf_gemm_ctx* ctx, int count, const void* c
 // receptive field straight from the activation (per-lane offset = the field's origin, fixed per work item; the tap is a
 // wave-uniform scalar offset).
 struct ConvShape { int n, Hp, Wp, C, Ho, Wo, kh, kw, stride, Cout; };
-static int conv_gemm_impl(fcmf_gemm_ctx* ctx, const void* x, const void* w, void* y, float* colstats, const ConvShape& s, void* stream) {
+static int conv_gemm_impl(fcmf_gemm_ctx* ctx, const void* x, const void* w, void* y, float* colstats, const ConvShape& s, void* stream,
+                          const float* bias = nullptr, void* aux = nullptr, int epilogue = FCMF_EPI_NONE) {
   const int n = s.n, Hp = s.Hp, Wp = s.Wp, C = s.C, Ho = s.Ho, Wo = s.Wo, kh = s.kh, kw = s.kw, stride = s.stride, Cout = s.Cout;
   if (!x || !w || !y || n <= 0 || Hp <= 0 || Wp <= 0 || C <= 0 || Ho <= 0 || Wo <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || Cout <= 0)
     return FCMF_ERR_ARG;
@@ -2707,12 +2747,21 @@ static int conv_gemm_impl(fcmf_gemm_ctx* ctx, const void* x, const void* w, void
   while ((1 << logC) < C) ++logC;
   const ConvGeom cv{C, logC, Hp, Wp, Ho, Wo, kw, stride, in_bytes, logC};
   GemmArgs a = plain_bf16_args(x, w, y, (int)M, Cout, kh * kw * C);
-  a.cv = &cv; a.colstats = colstats;
+  a.cv = &cv; a.colstats = colstats; a.bias = bias; a.aux = aux; a.epilogue = epilogue;
   return gemm_impl(ctx, a, stream);
 }
 extern "C" int fcmf_conv_gemm(fcmf_gemm_ctx* ctx, const void* x, const void* w, void* y, int n, int Hp, int Wp, int C, int Ho,
                               int Wo, int kh, int kw, int stride, int Cout, void* stream) {
   return conv_gemm_impl(ctx, x, w, y, nullptr, ConvShape{n, Hp, Wp, C, Ho, Wo, kh, kw, stride, Cout}, stream);
+}
+
+// fcmf_conv_gemm with a per-channel bias, an optional residual and a ReLU in the epilogue (include/fcmf_hip.h): the convolutions
+// of an eval-mode trunk whose BatchNorm scale is folded into w and whose shift is `bias`
+extern "C" int fcmf_conv_gemm_epi(fcmf_gemm_ctx* ctx, const void* x, const void* w, void* y, const float* bias, void* aux, int epilogue,
+                                  int n, int Hp, int Wp, int C, int Ho, int Wo, int kh, int kw, int stride, int Cout, void* stream) {
+  if (epilogue != FCMF_EPI_NONE && epilogue != FCMF_EPI_RELU && epilogue != FCMF_EPI_ADD && epilogue != FCMF_EPI_ADD_RELU) return FCMF_ERR_ARG;
+  if (!bias) return FCMF_ERR_ARG;
+  return conv_gemm_impl(ctx, x, w, y, nullptr, ConvShape{n, Hp, Wp, C, Ho, Wo, kh, kw, stride, Cout}, stream, bias, aux, epilogue);
 }
 
 // The same two products with the BatchNorm statistics of the output as a by-product (ResNet trunks: every convolution feeds a

@@ -16,7 +16,8 @@ F32, BF16, F64 = 0, 1, 2
 BOX_FAST_TRIG = 0x100      # OR-ed into fcmf_box_bias_*'s coord_dtype (include/fcmf_hip.h FCMF_BOX_FAST_TRIG)
 EPI_NONE, EPI_GELU, EPI_TANH, EPI_DGELU, EPI_DTANH, EPI_ADD = 0, 1, 2, 3, 4, 5
 EPI_GELU_DROP, EPI_DGELU_DROP = 6, 7      # fcmf_gemm_drop only: GELU / gelu' with the feed-forward dropout mask
-ERR_UNSUPPORTED = -3      # FCMF_ERR_UNSUPPORTED: callers with a documented fallback entry point test for it
+EPI_RELU, EPI_ADD_RELU = 8, 9      # folded eval-mode BatchNorm: bias = its shift, aux = the bottleneck's identity
+ERR_UNSUPPORTED = -3     # FCMF_ERR_UNSUPPORTED: callers with a documented fallback entry point test for it
 
 _c = ctypes
 _vp, _i, _i64, _f, _u64 = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_uint64
@@ -115,6 +116,7 @@ SIGNATURES = {
     "fcmf_bn_apply": [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i64, _i, _i, _vp],
     "fcmf_bn_apply_pad": [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i64, _i, _i, _i, _i, _i, _vp],
     "fcmf_conv_gemm": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "fcmf_conv_gemm_epi": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "fcmf_gemm_dw_batched": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i64, _i, _vp],
     "fcmf_gemm_dw_list": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "fcmf_gemm_dw_list_plan": [_i, _vp, _vp, _vp, _vp, _i, _i64, _vp, _i, _vp, _i, _vp],

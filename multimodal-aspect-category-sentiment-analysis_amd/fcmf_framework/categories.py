@@ -39,7 +39,10 @@ class _CategoryModel(nn.Module):
     def forward(self, x):
         """x [N, 3, H, W] crops -> logits [N, num_classes] in the compute dtype.  train(): the trunk is fine-tuned with batch
         statistics (TrunkFn); eval(): running statistics, forward only"""
-        feat = self.feature_extractor.trunk_nhwc(x, fine_tune=self.training)
+        return self.head(self.feature_extractor.trunk_nhwc(x, fine_tune=self.training))
+
+    def head(self, feat):
+        """trunk output NHWC [N, h, w, C] -> logits: global average pool + linear (also fed by predict.Predictor's eval trunks)"""
         if feat.requires_grad:
             pooled = R.AvgPoolFn.apply(feat, 1, 1, False)
         else:

@@ -288,3 +288,21 @@ class IdTokenizer:
             mask += [0] * (max_length - len(ids))
             ids = ids + [self.pad_token_id] * (max_length - len(ids))
         return {"input_ids": ids, "attention_mask": mask}
+
+
+class BytePairTokenizer:
+    """A tokenizer for TEXT PAIRS in synthetic mode (IdTokenizer takes one text of decimal ids): ids = byte values of both segments
+    between <s> ... </s></s> ... </s>, the first segment truncated (truncation='only_first'), padded to max_length.  What
+    `review_batches.ReviewProducer.encode` calls, so that a prompt can be compared position by position without a vocabulary file."""
+    pad_token_id = 1
+
+    def __len__(self):
+        return 203
+
+    def __call__(self, first, second=None, max_length=170, truncation=None, padding=None, return_token_type_ids=False):
+        a, b = [3 + c % 200 for c in first.encode()], [3 + c % 200 for c in (second or "").encode()]
+        a = a[:max(0, max_length - 4 - len(b))]
+        ids = ([0] + a + [2, 2] + b + [2])[:max_length]
+        n = len(ids)
+        return {"input_ids": ids + [self.pad_token_id] * (max_length - n), "token_type_ids": [0] * max_length,
+                "attention_mask": [1] * n + [0] * (max_length - n)}
