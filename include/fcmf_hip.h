@@ -317,6 +317,33 @@ int fcmf_logsoftmax_topk(const void* logits, int64_t ld, int rows, int V, int k,
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Single-query attention with indexed keys, one launch for n rows x `heads` slots: the two attentions of an IAOG decode step
+ * that sees its whole prefix (the decoder `Attention` of mm_modeling.py:66-132 for ONE query row per sequence: values are the
+ * projected keys :129, plain slot -> head pairing, which is the reference's at batch size 1).  All strides in elements.
+ *   q     [n, heads*d] in `dtype`, row r at q + r*q_sr (q_sr may exceed heads*d: the query half of a [kx | qx] buffer);
+ *   keys  the key of position p for row r is the heads*d elements at keys + p*k_sp + idx[r*idx_sr + p*idx_sp]*k_si, int64 idx:
+ *           - a self-attention cache [Tmax, rows, heads*d] (k_sp, k_si = its strides) with idx the row's ancestor table
+ *             [n, >= T]: which cache row held position p of this row's sequence;
+ *           - hoisted encoder keys [samples, Tk, heads*d] (k_si, k_sp = its strides) with idx the row's sample index and
+ *             idx_sp = 0 -- no [n, Tk, heads*d] gather per block and step;
+ *         idx_n = the extent of the indexed axis: an index outside [0, idx_n) reads nothing and makes that row's output NaN;
+ *   score_p = scale * <q[r, h], key_p[h]> for p < live and EXACTLY -1e4 for live <= p < T -- the reference's masked_fill
+ *         (:115-124): a filled key still takes part in the softmax and in the sum, it is not excluded;
+ *   out[r, h*d + j] = sum_{p < T} softmax(score)_p * key_p[h*d + j], row r at out + r*o_sr, in `dtype`; float32 accumulation.
+ *   Append (k_new != NULL): row r's own key, position append_at, is k_new + r*kn_sr.  The kernel uses it from there -- neither
+ *         the cache nor idx is read at position append_at -- and stores it to keys + append_at*k_sp + r*k_si.  No other element
+ *         of `keys` is written, and the launch never loads position append_at, so there is no hazard inside a launch whatever
+ *         the ancestor tables hold.  idx may be NULL when T == 1 (the appended key is the only one).
+ * One wave per (row, slot), keys straight to registers with 16-byte loads, in-wave shuffles, no LDS, no atomics: two launches
+ * give the same bits.
+ * Limits: d a multiple of 8 in 8 .. 128, 1 <= T <= 512, FCMF_F32 / FCMF_BF16 -- FCMF_ERR_UNSUPPORTED otherwise.  q, keys, k_new,
+ * out and every stride of theirs must be multiples of 16 bytes; 0 <= live <= T; with k_new 0 <= append_at < T and n <= idx_n --
+ * FCMF_ERR_ARG otherwise.  n == 0 succeeds without a launch.  The caller guarantees that T positions exist behind `keys`. */
+int fcmf_attn_decode(const void* q, int64_t q_sr, void* keys, int64_t k_sp, int64_t k_si, const int64_t* idx, int64_t idx_sr,
+                     int64_t idx_sp, int64_t idx_n, const void* k_new, int64_t kn_sr, int append_at, void* out, int64_t o_sr,
+                     int n, int heads, int d, int T, int live, float scale, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * y = LayerNorm(dropout(x) + res) * gamma + beta   (eps inside the sqrt, biased variance)
  * Replaces BertSelfOutput/BertOutput/AddNorm + FCMFLayerNorm (mm_modeling.py:158-171,
  * 276-280,324-328,566-573) and HF nn.LayerNorm(eps=1e-5).

@@ -21,21 +21,43 @@ does not hold yet go through ONE `IAOGDecoder.decode_step` with the plain pairin
 vocabulary GEMM with M = rows, log-softmax + top-k in one HIP kernel (csrc/topk.hip: no eager log_softmax / topk), one host read per
 round.  The beam rules per sample are `beam_search_ids`'s, unchanged: `beam_rounds` is that loop over many samples with the
 device step behind a callable.
+
+context="prefix" (every entry point; the default "last" is the reference's loop above, unchanged): a step is conditioned on the
+beam's whole prefix instead -- the function the decoder is trained as (is_train=True: token p at position p, causal self
+attention, the tril rule on the cross attention), at batch size 1 and in eval mode.  The step's logits for seq = [start .. tok_t]
+are row t of the teacher-forced decoder call on tensor([seq]).  There is no (sample, token) memo: every live beam is a row of its
+round, all rows of round t have length t + 1, and `IAOGDecoder.decode_step_prefix` runs them in one pass over a per-block KEY cache
+[max_len, B * beam, n_head * d] (values are the keys: no value cache).  The host carries per beam the ANCESTOR TABLE -- which row
+of round p held position p of this beam -- and uploads it with the tokens and sample indices in the round's one host-to-device
+tensor; csrc/attn_decode.hip reads the cache through it and appends the round's keys, so beams that share or reorder history copy
+nothing on the device.  One host read per round, as in "last" mode; the beam rules are the same code (`_advance`).
 """
 import torch
 import torch.nn.functional as F
 
 __all__ = ["beam_search", "beam_search_ids", "beam_search_batch", "beam_search_ids_batch", "beam_rounds"]
 
+CONTEXTS = ("last", "prefix")
+
+
+def _check_context(context):
+    if context not in CONTEXTS:
+        raise ValueError(f"context must be one of {CONTEXTS}, got {context!r}")
+
 
 @torch.no_grad()
 def beam_search_ids(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                    beam_size=3, max_len=20):
-    """-> (token ids of the best sequence incl. the start token, its log-likelihood, [(score, ids)] of the finished beams)"""
+                    beam_size=3, max_len=20, context="last"):
+    """-> (token ids of the best sequence incl. the start token, its log-likelihood, [(score, ids)] of the finished beams)
+    context="prefix": the batched path with this one sample (see the module header)"""
+    _check_context(context)
     model.eval()
     if enc_ids.dim() == 1:                                    # one sample without a batch axis (:395-402)
         enc_ids, enc_mask, enc_type, add_mask = (t.unsqueeze(0) for t in (enc_ids, enc_mask, enc_type, add_mask))
         vis_embeds, roi_embeds, roi_coors = (t.unsqueeze(0) for t in (vis_embeds, roi_embeds, roi_coors))
+    if context == "prefix":
+        return beam_search_ids_batch(model, start_id, sep_id, enc_ids[:1], enc_mask[:1], enc_type[:1], add_mask[:1], vis_embeds[:1],
+                                     roi_embeds[:1], roi_coors[:1], beam_size=beam_size, max_len=max_len, context=context)[0]
     enc = model.encoder(enc_ids, vis_embeds, roi_embeds, roi_coors, enc_type, enc_mask, add_mask)
     enc = enc[0] if isinstance(enc, tuple) else enc
     dec = model.decoder
@@ -77,52 +99,84 @@ def beam_search_ids(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_ma
 
 
 def beam_search(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                beam_size=3, num_preds=1, max_len=20, device='cuda'):
+                beam_size=3, num_preds=1, max_len=20, device='cuda', context="last"):
     """the reference's signature and result: [decoded text of the best sequence] (fcmf_pretraining.py:383-517)"""
     start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
     ids, _, _ = beam_search_ids(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds,
-                                roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len)
+                                roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len, context=context)
     return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip()]
 
 
-def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=20):
+def _advance(beams, final, tops, sep_id, beam_size):
+    """one round of one sample by `beam_search_ids`'s rules: finished beams move to `final` (:444-447), every other beam j is
+    expanded by tops(j, seq) -> (top log-probabilities, top ids), the candidates are sorted by score, descending and stable (:493).
+    -> None when no beam was live, else (the surviving beams [(score, seq)], for each the position j of its parent in `beams`)"""
+    cands = []
+    for j, (score, seq) in enumerate(beams):
+        if seq[-1] == sep_id:                                 # finished beams leave the search (:444-447)
+            final.append((score, seq))
+            continue
+        top_s, top_i = tops(j, seq)
+        for k in range(beam_size):
+            cands.append((score + top_s[k], seq + [top_i[k]], j))
+    if not cands:
+        return None
+    best = sorted(cands, key=lambda c: c[0], reverse=True)[:beam_size]
+    return [(score, seq) for score, seq, _ in best], [j for _, _, j in best]
+
+
+def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=20, context="last"):
     """the loop of `beam_search_ids` for `num_samples` samples side by side, on the host alone.  Per round: the (sample, last token)
     pairs of every live beam of every unfinished sample that the memo does not hold are collected (each once, in order of first
     appearance) and handed to ONE call step_many(pairs) -> {pair: (top log-probabilities, top ids)} (Python lists of at least
     beam_size entries); then every sample advances by exactly `beam_search_ids`'s rules: the same candidate order, the same stable
     sort, the same finishing rules, Python-float sums in the same order.  A sample whose beams are finished drops out.
+    context="prefix": no memo.  Round t hands every live beam of every unfinished sample, in (sample, beam) order, to ONE call
+    step_many(rows, t) -> [(top log-probabilities, top ids)] in row order, rows = [(sample, token at position t, ancestors)]:
+    ancestors[p] is the index that the beam's position p had among the rows of round p (p < t) -- the step keeps what it needs of a
+    row under (round, row index) and finds a beam's history there.  At most num_samples * beam_size rows per round.
     -> [(ids of the best sequence incl. the start token, its score, the finished list [(score, ids)])], one entry per sample"""
+    _check_context(context)
+    prefix = context == "prefix"
     memo = {}
     beams = [[(0.0, [int(start_id)])] for _ in range(num_samples)]
+    anc = [[[]] for _ in range(num_samples)]                  # prefix mode: per beam, the rows that held its earlier positions
     final = [[] for _ in range(num_samples)]
     live = list(range(num_samples))
-    for _ in range(max_len):
+    for t in range(max_len):
         if not live:
             break
-        need = []
-        for b in live:
-            for _, seq in beams[b]:
-                pair = (b, seq[-1])
-                if seq[-1] != sep_id and pair not in memo and pair not in need:
-                    need.append(pair)
-        if need:
-            memo.update(step_many(need))
+        if prefix:
+            rows, row_of = [], {}
+            for b in live:
+                for j, (_, seq) in enumerate(beams[b]):
+                    if seq[-1] != sep_id:
+                        row_of[(b, j)] = len(rows)
+                        rows.append((b, seq[-1], anc[b][j]))
+            tops_all = step_many(rows, t) if rows else []
+        else:
+            need = []
+            for b in live:
+                for _, seq in beams[b]:
+                    pair = (b, seq[-1])
+                    if seq[-1] != sep_id and pair not in memo and pair not in need:
+                        need.append(pair)
+            if need:
+                memo.update(step_many(need))
         still = []
         for b in live:
-            cands = []
-            for score, seq in beams[b]:
-                if seq[-1] == sep_id:                         # finished beams leave the search (:444-447)
-                    final[b].append((score, seq))
-                    continue
-                top_s, top_i = memo[(b, seq[-1])]
-                for k in range(beam_size):
-                    cands.append((score + top_s[k], seq + [top_i[k]]))
-            if not cands:
+            if prefix:
+                adv = _advance(beams[b], final[b], lambda j, seq: tops_all[row_of[(b, j)]], sep_id, beam_size)
+            else:
+                adv = _advance(beams[b], final[b], lambda j, seq: memo[(b, seq[-1])], sep_id, beam_size)
+            if adv is None:
                 continue
-            beams[b] = sorted(cands, key=lambda c: c[0], reverse=True)[:beam_size]
+            beams[b], parents = adv
             if all(seq[-1] == sep_id for _, seq in beams[b]):  # (:500-502)
                 final[b].extend(beams[b])
                 continue
+            if prefix:
+                anc[b] = [anc[b][j] + [row_of[(b, j)]] for j in parents]
             still.append(b)
         live = still
     out = []
@@ -135,9 +189,11 @@ def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=2
 
 @torch.no_grad()
 def beam_search_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                          beam_size=3, max_len=20):
+                          beam_size=3, max_len=20, context="last"):
     """`beam_search_ids` of every sample of a batch ([B, ...] tensors), one decoder call per beam round for all of them: the encoder
-    and `project_encoder` run once for the batch.  -> [(ids, score, final)], one entry per sample"""
+    and `project_encoder` run once for the batch.  context="prefix": every step sees its beam's whole prefix (module header); the
+    key cache is allocated here, once per batch.  -> [(ids, score, final)], one entry per sample"""
+    _check_context(context)
     model.eval()
     enc = model.encoder(enc_ids, vis_embeds, roi_embeds, roi_coors, enc_type, enc_mask, add_mask)
     enc = enc[0] if isinstance(enc, tuple) else enc
@@ -152,13 +208,26 @@ def beam_search_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, 
         top_s, top_i = both[:, :beam_size].tolist(), both[:, beam_size:].contiguous().view(torch.int32).tolist()
         return {p: (s, i) for p, s, i in zip(pairs, top_s, top_i)}
 
+    if context == "prefix":
+        cache = dec.init_cache(max_len, enc_ids.shape[0] * beam_size, device)
+
+        def step_rows(rows, t):
+            # ONE upload, [2 + t, n]: the samples, the tokens, then the ancestor table position by position (its transpose is the
+            # kernel's [n, t] view: it takes any strides)
+            buf = torch.tensor([[r[0] for r in rows], [r[1] for r in rows]] + [[r[2][p] for r in rows] for p in range(t)],
+                               device=device, dtype=torch.long)
+            logp, ids = dec.decode_step_prefix(buf[1], buf[0], buf[2:].t(), t, cache, enc, keys, beam_size)
+            both = torch.cat((logp, ids.view(torch.float32)), dim=1).cpu()      # ONE host read, as above
+            return list(zip(both[:, :beam_size].tolist(), both[:, beam_size:].contiguous().view(torch.int32).tolist()))
+
+        return beam_rounds(step_rows, enc_ids.shape[0], start_id, sep_id, beam_size, max_len, context)
     return beam_rounds(step_many, enc_ids.shape[0], start_id, sep_id, beam_size, max_len)
 
 
 def beam_search_batch(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                      beam_size=3, max_len=20):
+                      beam_size=3, max_len=20, context="last"):
     """-> [decoded text of the best sequence], one per sample of the batch (what `beam_search` returns per sample, [0])"""
     start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
     res = beam_search_ids_batch(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds,
-                                roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len)
+                                roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len, context=context)
     return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip() for ids, _, _ in res]

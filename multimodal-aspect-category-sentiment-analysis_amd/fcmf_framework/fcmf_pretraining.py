@@ -20,9 +20,17 @@ import torch.nn as nn
 from . import layers, ops
 from .mm_modeling import *  # noqa: F401,F403  (reference does the same; exposes the constants)
 from .mm_modeling import BertCrossEncoder, BertPooler, FeatureExtractor, IAOGDecoder, MultimodalEncoder
-from .decoding import beam_search  # noqa: F401  (the reference keeps it in this module, :383-517, commented out)
+from . import decoding as _decoding
 from .roi_modeling import *  # noqa: F401,F403
 from .roi_modeling import BoxMultiHeadedAttention
+
+
+def beam_search(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
+                beam_size=3, num_preds=1, max_len=20, device='cuda'):
+    """the reference keeps this function in this module (:383-517, commented out): its signature exactly, its decode (a step sees
+    the beam's last token).  `decoding.beam_search` is the same function with `context=` beside it."""
+    return _decoding.beam_search(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
+                                 beam_size=beam_size, num_preds=num_preds, max_len=max_len, device=device)
 
 
 class FCMFEncoder(nn.Module):

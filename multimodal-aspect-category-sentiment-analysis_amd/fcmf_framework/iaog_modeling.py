@@ -358,6 +358,54 @@ class IAOGDecoder(nn.Module):
             X = add_norm(blk.add_norm3, Z, blk.ffn(Z))
         return ops.vocab_topk(X.view(n, -1), self.dense.weight, self.dense.bias, k)
 
+    def init_cache(self, max_len, rows, device=None):
+        """the self-attention key cache of a prefix decode (decode_step_prefix): per block [max_len, rows, n_head*d] in the compute
+        dtype -- position-major, so a round's appends are one contiguous slab.  Values are the keys: there is no value cache."""
+        if not 1 <= max_len <= min(self.pos_encoding.P.shape[1], ops.DECODE_ATTN_MAX_T):
+            raise ValueError(f"prefix decode of {max_len} positions: the positional table has {self.pos_encoding.P.shape[1]} rows, "
+                             f"the decode-attention kernel reads at most {ops.DECODE_ATTN_MAX_T} keys")
+        device = device or self.embedding.weight.device
+        return [torch.empty((max_len, rows, blk.attention1.n_head * blk.attention1.hidden_dim), dtype=ops.compute_dtype(), device=device)
+                for blk in self.blks]
+
+    @torch.no_grad()
+    def decode_step_prefix(self, tokens, sample_idx, anc, t, cache, enc, keys, k):
+        """round t of a decode that sees the whole prefix, n rows in one pass.  Row i is the sequence whose token at position t is
+        tokens[i], of sample sample_idx[i], whose earlier positions p < t went through this method as row anc[i, p] of round p with
+        the same `cache`.  Its result is row t of forward(tensor([seq]), init_state(enc[s:s+1], <2-D mask>), is_train=True) at batch
+        size 1 in eval mode: token p embedded at position p, causal self attention, the tril rule on the cross attention (row t
+        scores the encoder keys > t as -1e4, mm_modeling.py:115-124), the plain slot -> head pairing.  Causality makes row p of every
+        block's input a function of the tokens <= p, so block i needs of the past only the w_kx projection of its input rows: each
+        round appends the n rows' keys at cache[i][t, row] (inside the attention launch) and reads positions < t through `anc` --
+        beams share and reorder history by index, no block's keys are ever copied.
+        tokens, sample_idx int64 [n]; anc int64 [n, >= t] (any strides); cache = init_cache(max_len > t, rows >= n);
+        keys = project_encoder(enc), formed here when None.  -> (log-probabilities float32 [n, k], token ids int32 [n, k]).
+        Dropout is off whatever the module's mode, as in decode_step."""
+        n = tokens.shape[0]
+        if not (0 <= t < cache[0].shape[0] and n <= cache[0].shape[1]):
+            raise ValueError(f"decode_step_prefix: round {t} with {n} rows does not fit a cache of {tuple(cache[0].shape[:2])}")
+        if keys is None:
+            keys = self.project_encoder(enc)
+        X = _ScaledEmbedding.apply(tokens.view(n, 1), self.embedding.weight, self.pos_encoding.P[:, t:t + 1], math.sqrt(self.num_hiddens),
+                                   ops.compute_dtype()).view(n, -1)                  # every row at position t
+
+        def add_norm(an, x, y):                                                      # AddNorm in eval mode, whatever self.training says
+            return ops.add_layer_norm(y, x, an.ln.weight, an.ln.bias, an.ln.variance_epsilon, 0.0, False)
+
+        for blk, kc, kx in zip(self.blks, cache, keys):
+            a1, a2 = blk.attention1, blk.attention2
+            nh = a1.n_head
+            kq = ops.head_project(X, [a1.w_kx, a1.w_qx])                             # [kx | qx] of the n rows, as _SelfQuirkAttentionFn forms it
+            HD = kq.shape[1] // 2
+            o = ops.decode_attention(kq[:, HD:], kc, anc, nh, t + 1, t + 1, k_new=kq[:, :HD], append_at=t)
+            Y = add_norm(blk.addnorm1, X, ops.linear(o, a1.proj.weight, a1.proj.bias))
+            qx = ops.head_project(Y, [a2.w_qx])
+            Tk = kx.shape[1]
+            o = ops.decode_attention(qx, kx, sample_idx, nh, Tk, min(t + 1, Tk), pos_dim=1)      # the sample's keys in place: no gather
+            Z = add_norm(blk.addnorm2, Y, ops.linear(o, a2.proj.weight, a2.proj.bias))
+            X = add_norm(blk.add_norm3, Z, blk.ffn(Z))
+        return ops.vocab_topk(X, self.dense.weight, self.dense.bias, k)
+
     @property
     def attention_weights(self):
         return self._attention_weights

@@ -824,6 +824,40 @@ def vocab_topk(x, weight, bias, k):
     return logsoftmax_topk(_vocab_logits(_rows(x), weight, bias, cache_bias=True)[0], weight.shape[0], k)
 
 
+DECODE_ATTN_MAX_T = 512    # fcmf_attn_decode's limit on the number of keys (include/fcmf_hip.h)
+
+
+@torch.no_grad()
+def decode_attention(q, keys, idx, heads, T, live, pos_dim=0, k_new=None, append_at=None, scale=None):
+    """one query row per sequence against keys read through an index (fcmf_attn_decode, include/fcmf_hip.h): values are the keys,
+    plain slot -> head pairing, scores of the positions live .. T-1 filled with -1e4.  No autograd: the decode step.
+    q [n, heads*d] (unit inner stride, any row stride); keys 3-D with heads*d innermost, `pos_dim` (0 or 1) its position axis and
+    the other leading axis the indexed one: a cache [Tmax, rows, heads*d] with idx int64 [n, >= T] (the ancestor table; any
+    strides), or hoisted encoder keys [samples, Tk, heads*d] (pos_dim=1) with idx int64 [n] (the sample of every row).
+    k_new [n, heads*d] with append_at: row r's own key at that position, also stored to the cache row r.  -> out [n, heads*d]"""
+    H.require_cuda(q, keys, idx, k_new)
+    n, HD = q.shape
+    d = HD // heads
+    ok = (q.dim() == 2 and keys.dim() == 3 and pos_dim in (0, 1) and keys.shape[2] == HD == heads * d and keys.dtype == q.dtype and
+          q.stride(1) == 1 and keys.stride(2) == 1 and 1 <= T <= keys.shape[pos_dim] and idx.dtype == torch.int64 and idx.shape[0] == n and
+          (idx.dim() == 1 or (idx.dim() == 2 and (idx.shape[1] >= T or (k_new is not None and idx.shape[1] >= T - 1 == append_at)))))
+    if k_new is not None:
+        ok = ok and k_new.shape == q.shape and k_new.dtype == q.dtype and k_new.stride(1) == 1 and append_at is not None
+    if not ok:
+        raise H.HipLibraryError(f"decode_attention: q {tuple(q.shape)} {q.dtype}, keys {tuple(keys.shape)} {keys.dtype} (positions on axis "
+                                f"{pos_dim}), idx {tuple(idx.shape)} {idx.dtype}, T {T}, append_at {append_at} do not fit together")
+    out = torch.empty((n, HD), dtype=q.dtype, device=q.device)
+    if n == 0:
+        return out
+    idx_sp = idx.stride(1) if idx.dim() == 2 else 0
+    H.check(H.lib().fcmf_attn_decode(H.ptr(q), q.stride(0), H.ptr(keys), keys.stride(pos_dim), keys.stride(1 - pos_dim),
+                                     H.ptr(idx) if idx.numel() else None, idx.stride(0), idx_sp, keys.shape[1 - pos_dim],
+                                     H.ptr(k_new), 0 if k_new is None else k_new.stride(0), int(append_at or 0), H.ptr(out), HD,
+                                     n, heads, d, T, live, 1.0 / math.sqrt(d) if scale is None else float(scale), H.dt(q),
+                                     H.stream()), "fcmf_attn_decode")
+    return out
+
+
 class FFNFn(torch.autograd.Function):
     """y = gelu_erf(x W1^T + b1) W2^T + b2   (BertIntermediate + BertOutput.dense,
     mm_modeling.py:305-314,320; decoder PositionWiseFFN :558-565).  GELU is the epilogue of the

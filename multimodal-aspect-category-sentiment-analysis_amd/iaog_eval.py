@@ -21,11 +21,12 @@ def decode_label(tokenizer, labels):
 
 
 @torch.no_grad()
-def generate(model, tokenizer, batches, features, beam_size, max_len, aspects=(), batched=False):
+def generate(model, tokenizer, batches, features, beam_size, max_len, aspects=(), batched=False, context="last"):
     """decode every sample of every batch (:385-426, :499-557).  A batch is the dataset's 11-tuple (images, ROI crops, boxes,
     labels, decoder ids, encoder ids / type / mask / added mask, aspect names, texts) on any device; `features` is
     train_harness.make_features' closure, called once per batch; the beam search runs per sample, or -- batched=True -- once per
     batch, every sample advancing one beam round per decoder call (decoding.beam_search_batch: the same beam rules per sample).
+    context="prefix": every decode step is conditioned on the beam's whole prefix instead of its last token (decoding.py's header).
     -> (preds, refs, results): {aspect: [text]} twice (every name of `aspects` present, in that order, then any other in order of
     appearance) and the per-text grouping [{'text': ..., 'aspects': {aspect: {'predict', 'label'}}}] in order of first appearance."""
     device = next(model.parameters()).device
@@ -38,12 +39,12 @@ def generate(model, tokenizer, batches, features, beam_size, max_len, aspects=()
             t.to(device) for t in (t_img, roi_img, coors, enc_ids, enc_type, enc_mask, added))
         vis, roi = features(t_img, roi_img)
         texts_b = beam_search_batch(model, tokenizer, enc_ids, enc_mask, enc_type, added, vis, roi, coors.float(),
-                                    beam_size=beam_size, max_len=max_len) if batched else None
+                                    beam_size=beam_size, max_len=max_len, context=context) if batched else None
         for i in range(enc_ids.shape[0]):
             pred = texts_b[i] if batched else beam_search(
                 model=model, tokenizer=tokenizer, enc_ids=enc_ids[i], enc_mask=enc_mask[i], enc_type=enc_type[i],
                 add_mask=added[i], vis_embeds=vis[i], roi_embeds=roi[i], roi_coors=coors[i].float(),
-                beam_size=beam_size, max_len=max_len, device=device)[0]
+                beam_size=beam_size, max_len=max_len, device=device, context=context)[0]
             pred = strip_rule(pred)
             label = decode_label(tokenizer, labels[i])
             name, text = names[i], texts[i]

@@ -74,6 +74,9 @@ def build_parser():
     p.add_argument("--eval_batch_size", default=16, type=int)
     p.add_argument("--batched_decode", action='store_true',
                    help="--do_eval: decode a whole eval batch per decoder call (decoding.beam_search_batch) instead of sample by sample")
+    p.add_argument("--decode_context", default="last", choices=("last", "prefix"),
+                   help="--do_eval: what a decode step sees.  last: the beam's last token at position 0 (the reference's loop); prefix: "
+                        "the whole prefix, as the decoder is trained (key cache + csrc/attn_decode.hip; implies the batched step)")
     p.add_argument("--learning_rate", default=3e-5, type=float)
     p.add_argument("--adam_epsilon", default=1e-8, type=float)
     p.add_argument("--num_train_epochs", default=8.0, type=float)
@@ -117,6 +120,12 @@ def main(argv=None):
     if args.do_eval and args.batched_decode and not 1 <= args.beam_size <= ops.TOPK_MAX:      # before anything is trained
         raise ValueError(f"--batched_decode: --beam_size {args.beam_size} is outside the top-k kernel's 1 .. {ops.TOPK_MAX}; "
                          f"decode without --batched_decode")
+    if args.do_eval and args.decode_context == "prefix":
+        if not 1 <= args.beam_size <= ops.TOPK_MAX:
+            raise ValueError(f"--decode_context prefix: --beam_size {args.beam_size} is outside the top-k kernel's 1 .. {ops.TOPK_MAX}")
+        if not 1 <= args.max_len_decoder <= ops.DECODE_ATTN_MAX_T:
+            raise ValueError(f"--decode_context prefix: --max_len_decoder {args.max_len_decoder} is outside the decode-attention "
+                             f"kernel's 1 .. {ops.DECODE_ATTN_MAX_T} keys")
     rank, _, world, device, master, logger = init_run(args, "iaog", "pretraining_iaog.log", script="run_pretraining_fcmf.py")
 
     tokenizer = None
@@ -295,7 +304,8 @@ def main(argv=None):
             if r_img is not None:
                 r_img.eval(); r_roi.eval()
             preds, refs, results = generate(model, tokenizer, batches, features, args.beam_size, args.max_len_decoder, aspects,
-                                               batched=args.batched_decode)
+                                               batched=args.batched_decode or args.decode_context == "prefix",
+                                               context=args.decode_context)
             per_aspect, macro = macro_bertscore(preds, refs, aspects, score_fn)
             return per_aspect, macro, results
     elif args.do_eval and master:

@@ -3,7 +3,11 @@
 whole eval batch), on a synthetic FCMFSeq2Seq at the real geometry: H 768, 12 heads, 12 blocks, V 64001, 7 images, bf16,
 --beam_size 2, --max_len_decoder 20, at 16 and 64 samples per batch.  Also the kernel alone: fcmf_logsoftmax_topk next to eager
 log_softmax + topk on the same [n, 64032] bf16 buffer (V = 64001 columns valid).
-Usage (GPU box, repo root):  python tools/decode_bench.py [--samples 16 64] [--beam_size 2] [--max_len_decoder 20]
+"prefix": the batched path in both contexts (decoding.beam_search_ids_batch(context="last" | "prefix"): the memoised last-token
+decode next to the decode on the whole prefix, which runs every live beam every round), and one cross-attention step of the prefix
+decode fused (ops.decode_attention reading the hoisted keys through the sample index) next to composed (index_select of the rows'
+keys + the attention forward the last-token step uses).  --only_prefix skips the other sections.
+Usage (GPU box, repo root):  python tools/decode_bench.py [--samples 16 64] [--beam_size 2] [--max_len_decoder 20] [--only_prefix]
 Prints one JSON line.  Decode: wall time per eval batch between device synchronisations, median of 5 (min, max beside it), both
 paths warmed up once per batch size and alternating, the number of decoder calls of each path, and whether the two paths decoded
 the same token sequences.  Kernel: median microseconds of 9 windows of 50 calls between device events, alternating."""
@@ -30,6 +34,7 @@ p.add_argument("--beam_size", type=int, default=2)
 p.add_argument("--max_len_decoder", type=int, default=20)
 p.add_argument("--seq_len", type=int, default=64)
 p.add_argument("--num_rois", type=int, default=4)
+p.add_argument("--only_prefix", action="store_true")
 args = p.parse_args()
 
 assert torch.cuda.is_available(), "decode_bench.py measures on the MI355X: no GPU, no number"
@@ -86,8 +91,8 @@ def stats(ts):
 
 
 res = {"geometry": dict(H=cfg["hidden_size"], heads=cfg["num_attention_heads"], blocks=cfg["num_hidden_layers"], V=V, num_imgs=NI,
-                        dtype="bf16", beam_size=args.beam_size, max_len=args.max_len_decoder), "decode": [], "kernel": []}
-for B in args.samples:
+                        dtype="bf16", beam_size=args.beam_size, max_len=args.max_len_decoder), "decode": [], "kernel": [], "prefix": []}
+for B in ([] if args.only_prefix else args.samples):
     a = batch_args(B)
     ids_one, ids_many = per_sample(a), batched(a)                         # warm-up of every shape of both paths
     times = {"per_sample": [], "batched": []}
@@ -118,7 +123,7 @@ def window(fn, reps=50):
     return s.elapsed_time(e) / reps * 1e3
 
 
-for n in sorted({B * args.beam_size for B in args.samples}):
+for n in ([] if args.only_prefix else sorted({B * args.beam_size for B in args.samples})):
     x = (torch.randn(n, Vp, generator=torch.Generator().manual_seed(n)) * 3).to(dev).bfloat16()
     kernel = lambda: ops.logsoftmax_topk(x, V, args.beam_size)
     eager = lambda: torch.topk(F.log_softmax(x[:, :V].float(), dim=-1), args.beam_size)
@@ -135,4 +140,45 @@ for n in sorted({B * args.beam_size for B in args.samples}):
                           "kernel_us": round(statistics.median(t["kernel"]), 1), "kernel_us_min_max": [round(min(t["kernel"]), 1), round(max(t["kernel"]), 1)],
                           "eager_us": round(statistics.median(t["eager"]), 1), "eager_us_min_max": [round(min(t["eager"]), 1), round(max(t["eager"]), 1)],
                           "same_ids": bool(torch.equal(ki.long(), ei)), "max_abs_diff": float((kl - el).abs().max())})
+
+# ---- the whole prefix next to the last token
+def in_context(context):
+    return lambda a: [r[0] for r in decoding.beam_search_ids_batch(model, 0, SEP, *a, beam_size=args.beam_size,
+                                                                   max_len=args.max_len_decoder, context=context)]
+
+
+for B in args.samples:
+    a = batch_args(B)
+    fns = {c: in_context(c) for c in ("last", "prefix")}
+    ids = {c: fn(a) for c, fn in fns.items()}                             # warm-up of every shape of both
+    times = {c: [] for c in fns}
+    for _ in range(5):
+        for c, fn in fns.items():
+            times[c].append(timed(fn, a)[0])
+    res["prefix"].append({"samples_per_batch": B, **{c: stats(t) for c, t in times.items()},
+                          "same_sequences": sum(x == y for x, y in zip(ids["last"], ids["prefix"])),
+                          "mean_len": {c: sum(map(len, v)) / B for c, v in ids.items()}})
+
+from fcmf_framework.iaog_modeling import _quirk_attn_fwd
+nh, Tk = cfg["num_attention_heads"], 1 + 2 * NI
+for B in args.samples:
+    n, g = B * args.beam_size, torch.Generator().manual_seed(B)
+    kx = torch.randn(B, Tk, cfg["hidden_size"], generator=g).to(dev).bfloat16()
+    qx = torch.randn(n, cfg["hidden_size"], generator=g).to(dev).bfloat16()
+    sample = torch.arange(n, device=dev) // args.beam_size
+    fused = lambda: ops.decode_attention(qx, kx, sample, nh, Tk, Tk, pos_dim=1)
+    composed = lambda: _quirk_attn_fwd(qx.view(n, 1, -1), kx.index_select(0, sample), nh, False, head_quirk=0)
+    for fn in (fused, composed):
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    t = {"fused": [], "composed": []}
+    for _ in range(9):
+        t["fused"].append(window(fused))
+        t["composed"].append(window(composed))
+    res["prefix"].append({"cross_attention_rows": n, "keys": Tk,
+                          "fused_us": round(statistics.median(t["fused"]), 1), "fused_us_min_max": [round(min(t["fused"]), 1), round(max(t["fused"]), 1)],
+                          "composed_us": round(statistics.median(t["composed"]), 1),
+                          "composed_us_min_max": [round(min(t["composed"]), 1), round(max(t["composed"]), 1)],
+                          "max_abs_diff": float((fused().float() - composed()[0].view(n, -1).float()).abs().max())})
 print(json.dumps(res))
