@@ -317,6 +317,32 @@ int fcmf_logsoftmax_topk(const void* logits, int64_t ld, int rows, int V, int k,
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * One sampled token per row of a logits matrix, one launch: the sampling tail of an IAOG decode step, beside the beam tail above
+ * (temperature, top-k and nucleus filtering in the order and with the tie rules of Hugging Face's TopKLogitsWarper /
+ * TopPLogitsWarper, then a Gumbel-max draw), for `rows` independent rows at once.
+ *   logits [rows, ld] in `dtype` (FCMF_F32 / FCMF_BF16), row r at logits + r*ld (elements); only columns 0 .. V-1 are ever
+ *   loaded (the column padding and any guard band may hold anything, NaN included).  For a row r, x_j its stored values:
+ *   K  (top-k)   every column when top_k == 0 or top_k >= V; else { j : x_j >= v }, v the top_k-th largest stored value of the
+ *                row: ties at v are ALL kept.  The comparison is on stored values and carries no rounding (-0 equals +0);
+ *   z_j = x_j / temperature for j in K, p = softmax of z over K;
+ *   N  (nucleus) j in N iff M(x_j) < top_p, M(v) = sum of p_i over the i in K with x_i > v, the mass STRICTLY above the value:
+ *                ties stand or fall together, the row maximum is always kept, top_p == 1 keeps all of K;
+ *   ids  int32   [rows]: argmax over j in N of z_j + g_j, the LOWER column on an exact tie; g_j = -log(-log(u_j)),
+ *                u_j = ((h_j >> 9) + 0.5) * 2^-23 (exact in float32, never 0 or 1), h_j = fcmf_hash32(seed, ((ctr[r] & (2^44 - 1))
+ *                << 20) | j), the hash of csrc/common.h.  A column holding -inf is never drawn;
+ *   logp float32 [rows]: x[r, ids[r]] - lse[r], lse[r] = log sum_{j<V} exp(x[r,j]): the draw's log-probability under the model's
+ *                own distribution (temperature 1, unfiltered) -- fcmf_logsoftmax_topk's definition, so that the score of a sampled
+ *                chain is comparable with a beam's.  The log-probability under the filtered distribution is not returned.
+ * ctr int64 [rows] on the device: a row's draw depends on (seed, ctr[r]) and its logits only -- not on its row index nor on the
+ * other rows of the launch.  A row of only -inf, or one holding NaN inside V, is undefined.  No floating-point atomics,
+ * fixed-order reductions (the nucleus masses are integer sums): two launches give the same bits.  Rows that are 16-byte aligned
+ * are read 16 bytes per lane, any other layout one element per lane.
+ * Limits: 1 <= V <= 2^20, dtype FCMF_F32 / FCMF_BF16 -- FCMF_ERR_UNSUPPORTED otherwise; temperature finite and > 0, top_k >= 0,
+ * 0 < top_p <= 1, no NULL pointer, rows >= 0, ld >= V -- FCMF_ERR_ARG otherwise; rows == 0 succeeds without a launch. */
+int fcmf_sample_token(const void* logits, int64_t ld, int rows, int V, float temperature, int top_k, float top_p, uint64_t seed,
+                      const int64_t* ctr, int32_t* ids, float* logp, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Single-query attention with indexed keys, one launch for n rows x `heads` slots: the two attentions of an IAOG decode step
  * that sees its whole prefix (the decoder `Attention` of mm_modeling.py:66-132 for ONE query row per sequence: values are the
  * projected keys :129, plain slot -> head pairing, which is the reference's at batch size 1).  All strides in elements.

@@ -17,6 +17,7 @@ BOX_FAST_TRIG = 0x100      # OR-ed into fcmf_box_bias_*'s coord_dtype (include/f
 EPI_NONE, EPI_GELU, EPI_TANH, EPI_DGELU, EPI_DTANH, EPI_ADD = 0, 1, 2, 3, 4, 5
 EPI_GELU_DROP, EPI_DGELU_DROP = 6, 7      # fcmf_gemm_drop only: GELU / gelu' with the feed-forward dropout mask
 EPI_RELU, EPI_ADD_RELU = 8, 9      # folded eval-mode BatchNorm: bias = its shift, aux = the bottleneck's identity
+ERR_ARG = -1             # FCMF_ERR_ARG
 ERR_UNSUPPORTED = -3     # FCMF_ERR_UNSUPPORTED: callers with a documented fallback entry point test for it
 
 _c = ctypes
@@ -73,6 +74,7 @@ SIGNATURES = {
     "fcmf_attn_mfma_probs": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _f, _vp],
     "fcmf_bertscore": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i, _vp],
     "fcmf_logsoftmax_topk": [_vp, _i64, _i, _i, _i, _vp, _vp, _i, _vp],
+    "fcmf_sample_token": [_vp, _i64, _i, _i, _f, _i, _f, _u64, _vp, _vp, _vp, _i, _vp],
     "fcmf_attn_decode": [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i, _vp, _i64, _i, _i, _i, _i, _i, _f, _i, _vp],
     "fcmf_add_ln_fwd": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _u64, _i, _vp],
     "fcmf_add_ln_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _i, _vp],

@@ -31,11 +31,25 @@ round, all rows of round t have length t + 1, and `IAOGDecoder.decode_step_prefi
 of round p held position p of this beam -- and uploads it with the tokens and sample indices in the round's one host-to-device
 tensor; csrc/attn_decode.hip reads the cache through it and appends the round's keys, so beams that share or reorder history copy
 nothing on the device.  One host read per round, as in "last" mode; the beam rules are the same code (`_advance`).
+
+length_penalty (every entry point, default 0): the FINAL choice among the finished hypotheses (or, when none finished, among the
+live beams) ranks by score / max(len(seq) - 1, 1) ** length_penalty instead of the raw log-likelihood sum, which always prefers the
+shortest.  The per-round pruning and every returned score stay the raw sum; 0 takes the reference's code path, with no division.
+
+Sampling (`sample_rounds`, `sample_ids_batch`, `sample_batch`): instead of a beam, every sample runs `num_chains` independent
+chains; per round every unfinished chain is one row of the batched step of either context and draws ONE token from the step's
+distribution after temperature / top-k / nucleus filtering (csrc/sample.hip: no eager softmax / sort / cumsum / multinomial).  The
+draw of (sample, chain, round) is a function of the sampler's seed and the counter ((sample_offset + b) * num_chains + c) * max_len + t
+alone, so a sample's text does not depend on the eval batch it is decoded in.  A chain's score is the sum of its tokens'
+log-probabilities under the model's own distribution, the quantity a beam's score is.
 """
 import torch
 import torch.nn.functional as F
 
-__all__ = ["beam_search", "beam_search_ids", "beam_search_batch", "beam_search_ids_batch", "beam_rounds"]
+from . import ops
+
+__all__ = ["beam_search", "beam_search_ids", "beam_search_batch", "beam_search_ids_batch", "beam_rounds",
+           "sample_rounds", "sample_ids_batch", "sample_batch"]
 
 CONTEXTS = ("last", "prefix")
 
@@ -45,9 +59,17 @@ def _check_context(context):
         raise ValueError(f"context must be one of {CONTEXTS}, got {context!r}")
 
 
+def _best(fin, length_penalty=0.0):
+    """the final choice among [(score, seq)]: the highest score, the first among equals; with a length penalty the score is
+    divided by (tokens after the start token) ** length_penalty first"""
+    if length_penalty == 0:
+        return sorted(fin, key=lambda c: c[0], reverse=True)[0]
+    return sorted(fin, key=lambda c: c[0] / max(len(c[1]) - 1, 1) ** length_penalty, reverse=True)[0]
+
+
 @torch.no_grad()
 def beam_search_ids(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                    beam_size=3, max_len=20, context="last"):
+                    beam_size=3, max_len=20, context="last", length_penalty=0.0):
     """-> (token ids of the best sequence incl. the start token, its log-likelihood, [(score, ids)] of the finished beams)
     context="prefix": the batched path with this one sample (see the module header)"""
     _check_context(context)
@@ -57,7 +79,8 @@ def beam_search_ids(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_ma
         vis_embeds, roi_embeds, roi_coors = (t.unsqueeze(0) for t in (vis_embeds, roi_embeds, roi_coors))
     if context == "prefix":
         return beam_search_ids_batch(model, start_id, sep_id, enc_ids[:1], enc_mask[:1], enc_type[:1], add_mask[:1], vis_embeds[:1],
-                                     roi_embeds[:1], roi_coors[:1], beam_size=beam_size, max_len=max_len, context=context)[0]
+                                     roi_embeds[:1], roi_coors[:1], beam_size=beam_size, max_len=max_len, context=context,
+                                     length_penalty=length_penalty)[0]
     enc = model.encoder(enc_ids, vis_embeds, roi_embeds, roi_coors, enc_type, enc_mask, add_mask)
     enc = enc[0] if isinstance(enc, tuple) else enc
     dec = model.decoder
@@ -94,16 +117,17 @@ def beam_search_ids(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_ma
             break
     if not final:                                             # nothing finished within max_len (:505-506)
         final = list(beams)
-    best_score, best_seq = sorted(final, key=lambda c: c[0], reverse=True)[0]
+    best_score, best_seq = _best(final, length_penalty)
     return best_seq, best_score, final
 
 
 def beam_search(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                beam_size=3, num_preds=1, max_len=20, device='cuda', context="last"):
+                beam_size=3, num_preds=1, max_len=20, device='cuda', context="last", length_penalty=0.0):
     """the reference's signature and result: [decoded text of the best sequence] (fcmf_pretraining.py:383-517)"""
     start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
     ids, _, _ = beam_search_ids(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds,
-                                roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len, context=context)
+                                roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len, context=context,
+                                length_penalty=length_penalty)
     return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip()]
 
 
@@ -125,7 +149,7 @@ def _advance(beams, final, tops, sep_id, beam_size):
     return [(score, seq) for score, seq, _ in best], [j for _, _, j in best]
 
 
-def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=20, context="last"):
+def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=20, context="last", length_penalty=0.0):
     """the loop of `beam_search_ids` for `num_samples` samples side by side, on the host alone.  Per round: the (sample, last token)
     pairs of every live beam of every unfinished sample that the memo does not hold are collected (each once, in order of first
     appearance) and handed to ONE call step_many(pairs) -> {pair: (top log-probabilities, top ids)} (Python lists of at least
@@ -182,14 +206,58 @@ def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=2
     out = []
     for b in range(num_samples):
         fin = final[b] if final[b] else list(beams[b])        # nothing finished within max_len (:505-506)
-        best_score, best_seq = sorted(fin, key=lambda c: c[0], reverse=True)[0]
+        best_score, best_seq = _best(fin, length_penalty)
         out.append((best_seq, best_score, fin))
+    return out
+
+
+def sample_rounds(step_many, num_samples, start_id, sep_id, num_chains=1, max_len=20, context="last", sample_offset=0,
+                  length_penalty=0.0):
+    """the sampling loop for `num_samples` samples side by side, on the host alone: every sample runs `num_chains` independent chains
+    from [start_id]; round t hands every unfinished chain, in (sample, chain) order, to ONE call of the step and appends the token it
+    draws; a chain ends at sep_id or after max_len draws.  A row carries its counter ((sample_offset + b) * num_chains + c) * max_len
+    + t (sample_offset: the running index of sample 0 in the eval set), on which -- with the sampler's seed -- the draw depends.
+    context="last":   step_many(rows) -> [(log-probability, token)] in row order, rows = [(sample, last token, counter)]; no memo, a
+                      draw is no function of (sample, token).
+    context="prefix": step_many(rows, t), rows = [(sample, token at position t, ancestors, counter)], ancestors[p] the index the
+                      chain had among the rows of round p (as in `beam_rounds`; chains never branch).  At most num_samples *
+                      num_chains rows per round.
+    A chain's score is the Python-float sum of the returned log-probabilities, in order.
+    -> [(ids of the best chain incl. the start token, its score, [(score, ids)] of all chains in chain order)], one entry per sample;
+    best = `_best` (the highest score, or the highest length-penalised one; the first chain among equals)"""
+    _check_context(context)
+    prefix = context == "prefix"
+    seqs = [[[int(start_id)] for _ in range(num_chains)] for _ in range(num_samples)]
+    scores = [[0.0] * num_chains for _ in range(num_samples)]
+    anc = [[[] for _ in range(num_chains)] for _ in range(num_samples)]
+    live = [(b, c) for b in range(num_samples) for c in range(num_chains)]
+    for t in range(max_len):
+        if not live:
+            break
+        ctr = [((sample_offset + b) * num_chains + c) * max_len + t for b, c in live]
+        if prefix:
+            res = step_many([(b, seqs[b][c][-1], anc[b][c], n) for (b, c), n in zip(live, ctr)], t)
+        else:
+            res = step_many([(b, seqs[b][c][-1], n) for (b, c), n in zip(live, ctr)])
+        still = []
+        for i, ((b, c), (lp, tok)) in enumerate(zip(live, res)):
+            scores[b][c] += lp
+            seqs[b][c].append(int(tok))
+            anc[b][c].append(i)
+            if tok != sep_id:
+                still.append((b, c))
+        live = still
+    out = []
+    for b in range(num_samples):
+        chains = [(scores[b][c], seqs[b][c]) for c in range(num_chains)]
+        best_score, best_seq = _best(chains, length_penalty)
+        out.append((best_seq, best_score, chains))
     return out
 
 
 @torch.no_grad()
 def beam_search_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                          beam_size=3, max_len=20, context="last"):
+                          beam_size=3, max_len=20, context="last", length_penalty=0.0):
     """`beam_search_ids` of every sample of a batch ([B, ...] tensors), one decoder call per beam round for all of them: the encoder
     and `project_encoder` run once for the batch.  context="prefix": every step sees its beam's whole prefix (module header); the
     key cache is allocated here, once per batch.  -> [(ids, score, final)], one entry per sample"""
@@ -220,14 +288,76 @@ def beam_search_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, 
             both = torch.cat((logp, ids.view(torch.float32)), dim=1).cpu()      # ONE host read, as above
             return list(zip(both[:, :beam_size].tolist(), both[:, beam_size:].contiguous().view(torch.int32).tolist()))
 
-        return beam_rounds(step_rows, enc_ids.shape[0], start_id, sep_id, beam_size, max_len, context)
-    return beam_rounds(step_many, enc_ids.shape[0], start_id, sep_id, beam_size, max_len)
+        return beam_rounds(step_rows, enc_ids.shape[0], start_id, sep_id, beam_size, max_len, context, length_penalty)
+    return beam_rounds(step_many, enc_ids.shape[0], start_id, sep_id, beam_size, max_len, length_penalty=length_penalty)
 
 
 def beam_search_batch(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                      beam_size=3, max_len=20, context="last"):
+                      beam_size=3, max_len=20, context="last", length_penalty=0.0):
     """-> [decoded text of the best sequence], one per sample of the batch (what `beam_search` returns per sample, [0])"""
     start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
     res = beam_search_ids_batch(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds,
-                                roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len, context=context)
+                                roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len, context=context,
+                                length_penalty=length_penalty)
+    return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip() for ids, _, _ in res]
+
+
+def make_sampler(sampler=None):
+    """the sampler settings of the sampling entry points as a checked dict: seed (0), temperature (1), top_k (0 = off), top_p (1 = off)"""
+    out = dict(seed=0, temperature=1.0, top_k=0, top_p=1.0)
+    extra = set(sampler or ()) - set(out)
+    if extra:
+        raise ValueError(f"sampler: unknown settings {sorted(extra)} (known: {sorted(out)})")
+    out.update(sampler or {})
+    ops.check_sampler(out["temperature"], out["top_k"], out["top_p"])
+    return out
+
+
+@torch.no_grad()
+def sample_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
+                     num_chains=1, max_len=20, context="last", sampler=None, sample_offset=0, length_penalty=0.0):
+    """`sample_rounds` of every sample of a batch ([B, ...] tensors) over the batched decode steps: the encoder and `project_encoder`
+    run once for the batch, every round is ONE upload (samples, tokens, counters and, in prefix mode, the ancestor table), one decoder
+    call ending in csrc/sample.hip and ONE host read.  sampler: `make_sampler`'s settings; sample_offset: the running index of the
+    batch's first sample in the eval set.  -> [(ids of the best chain, its score, [(score, ids)] of all chains)], one entry per sample"""
+    _check_context(context)
+    if num_chains < 1:
+        raise ValueError(f"num_chains must be >= 1, got {num_chains}")
+    cfg = make_sampler(sampler)
+    model.eval()
+    enc = model.encoder(enc_ids, vis_embeds, roi_embeds, roi_coors, enc_type, enc_mask, add_mask)
+    enc = enc[0] if isinstance(enc, tuple) else enc
+    dec = model.decoder
+    keys = dec.project_encoder(enc)
+    device = enc.device
+
+    def read(logp, ids):
+        both = torch.cat((logp, ids.view(torch.float32)), dim=1).cpu()      # ONE host read: the ids ride along as their bits
+        return list(zip(both[:, 0].tolist(), both[:, 1].contiguous().view(torch.int32).tolist()))
+
+    if context == "prefix":
+        cache = dec.init_cache(max_len, enc_ids.shape[0] * num_chains, device)
+
+        def step_rows(rows, t):
+            # ONE upload, [3 + t, n]: the samples, the tokens, the counters, then the ancestor table position by position
+            buf = torch.tensor([[r[0] for r in rows], [r[1] for r in rows], [r[3] for r in rows]] + [[r[2][p] for r in rows] for p in range(t)],
+                               device=device, dtype=torch.long)
+            return read(*dec.decode_step_prefix(buf[1], buf[0], buf[3:].t(), t, cache, enc, keys, 1, sampler=dict(cfg, ctr=buf[2])))
+
+        return sample_rounds(step_rows, enc_ids.shape[0], start_id, sep_id, num_chains, max_len, context, sample_offset, length_penalty)
+
+    def step_many(rows):
+        buf = torch.tensor(rows, device=device, dtype=torch.long).t().contiguous()      # ONE upload, [3, n]: samples, tokens, counters
+        return read(*dec.decode_step(buf[1], buf[0], enc, keys, 1, sampler=dict(cfg, ctr=buf[2])))
+
+    return sample_rounds(step_many, enc_ids.shape[0], start_id, sep_id, num_chains, max_len, context, sample_offset, length_penalty)
+
+
+def sample_batch(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
+                 num_chains=1, max_len=20, context="last", sampler=None, sample_offset=0, length_penalty=0.0):
+    """-> [decoded text of the best chain], one per sample of the batch: `beam_search_batch`'s result from `sample_ids_batch`"""
+    start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
+    res = sample_ids_batch(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds,
+                           roi_coors, num_chains=num_chains, max_len=max_len, context=context, sampler=sampler,
+                           sample_offset=sample_offset, length_penalty=length_penalty)
     return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip() for ids, _, _ in res]

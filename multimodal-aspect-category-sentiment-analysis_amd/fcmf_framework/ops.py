@@ -116,6 +116,7 @@ def next_seed():
 
 
 TOPK_MAX = 16    # fcmf_logsoftmax_topk's limit on k (include/fcmf_hip.h)
+SAMPLE_MAX_V = 1 << 20    # fcmf_sample_token's limit on the number of columns (include/fcmf_hip.h)
 
 # --------------------------------------------------------------------------------------
 # flat gradient arena (dp.GradArena): weight-gradient buffers come out of the parameter's slice of ONE zeroed
@@ -822,6 +823,50 @@ def vocab_topk(x, weight, bias, k):
     [n, k], token ids int32 [n, k]).  No autograd: the decode step.  The projection is _vocab_logits', its padded bias cached on the
     Parameter, and the kernel reads the [n, Vp] buffer with its row stride -- no compaction copy to [n, V], no log-softmax round trip."""
     return logsoftmax_topk(_vocab_logits(_rows(x), weight, bias, cache_bias=True)[0], weight.shape[0], k)
+
+
+def check_sampler(temperature=1.0, top_k=0, top_p=1.0):
+    """the value limits of fcmf_sample_token (include/fcmf_hip.h), raised as a ValueError that names the argument"""
+    if not (math.isfinite(temperature) and temperature > 0):
+        raise ValueError(f"temperature must be finite and > 0, got {temperature}")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0 (0 = off), got {top_k}")
+    if not 0 < top_p <= 1:
+        raise ValueError(f"top_p must be in (0, 1] (1 = off), got {top_p}")
+
+
+def sample_token(logits, V, ctr, seed, temperature=1.0, top_k=0, top_p=1.0):
+    """logits [n, >= V] (unit inner stride, any row stride; columns >= V are never read), ctr int64 [n] on the device -> (token ids
+    int32 [n], log-probabilities float32 [n]): one token per row drawn from softmax(logits / temperature) restricted to the top_k
+    largest entries (0 = off; ties kept) and then to the nucleus of mass top_p (1 = off), by Gumbel-max over the counter-based hash
+    of (seed, ctr[r], column); the log-probability is the drawn token's under the unfiltered distribution at temperature 1.  One
+    launch (fcmf_sample_token, include/fcmf_hip.h)"""
+    H.require_cuda(logits, ctr)
+    check_sampler(temperature, top_k, top_p)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] < V:
+        raise H.HipLibraryError(f"sample_token: want [n, >= {V}] rows with unit inner stride, got {tuple(logits.shape)} / {logits.stride()}")
+    n = logits.shape[0]
+    ld = logits.stride(0) if n > 1 else max(logits.stride(0), V)      # (one row: its stride means nothing)
+    if ld < V:
+        raise H.HipLibraryError(f"sample_token: rows overlap (row stride {ld} < {V} columns)")
+    if ctr.dtype != torch.int64 or ctr.shape != (n,):
+        raise H.HipLibraryError(f"sample_token: want one int64 counter per row, got {ctr.dtype} {tuple(ctr.shape)}")
+    ctr = ctr.contiguous()
+    ids = torch.empty((n,), dtype=torch.int32, device=logits.device)
+    logp = torch.empty((n,), dtype=torch.float32, device=logits.device)
+    if n == 0:
+        return ids, logp
+    H.check(H.lib().fcmf_sample_token(H.ptr(logits), ld, n, V, float(temperature), int(top_k), float(top_p),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, H.ptr(ctr), H.ptr(ids), H.ptr(logp), H.dt(logits),
+                                      H.stream()), "fcmf_sample_token")
+    return ids, logp
+
+
+@torch.no_grad()
+def vocab_sample(x, weight, bias, ctr, seed, temperature=1.0, top_k=0, top_p=1.0):
+    """one sampled token for every row of x [n, K] under softmax(x W^T + b), weight [V, K] -> (token ids int32 [n], log-probabilities
+    float32 [n]) (`sample_token`).  No autograd: the sampling decode step, on the projection and the [n, Vp] buffer of `vocab_topk`."""
+    return sample_token(_vocab_logits(_rows(x), weight, bias, cache_bias=True)[0], weight.shape[0], ctr, seed, temperature, top_k, top_p)
 
 
 DECODE_ATTN_MAX_T = 512    # fcmf_attn_decode's limit on the number of keys (include/fcmf_hip.h)

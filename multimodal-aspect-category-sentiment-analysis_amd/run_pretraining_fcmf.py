@@ -18,12 +18,16 @@ epoch the master rank beam-search decodes the dev set (`dev_with_iaog.json`, or 
 the labels with BERTScore (`fcmf_framework/bertscore.py`: --bert_score_model must be a LOCAL model directory), keeps
 `seed_{seed}_{iaog,resimg,resroi}_model_best.pth` by macro F1 and carries `best_score` in the `last` checkpoints; after training
 the best checkpoint decodes the test set into `iaog_test_predictions_formatted.txt`.  Without --do_eval nothing of this runs.
+--decode_strategy sample decodes --num_chains sampled chains per sample instead of a beam (--temperature, --top_k, --top_p,
+--sample_seed; csrc/sample.hip) and keeps the best-scoring one; --length_penalty ranks the final choice of either strategy by
+score / length ** penalty.  The defaults (beam, 0) are the reference's decode.
 Process set-up, the checkpoint code, the extractors and the loop of one epoch are `train_harness.py`'s, shared with
 run_multimodal_fcmf.py; this file keeps the parser, the model and data, the 2 parameter groups and the loss.
 With real data the driver imports the user's `iaog_dataset.IAOGDataset` (host-side producer,
 SURVEY.md section 8(f) "next") and torchvision, as the reference does.
 """
 import argparse
+import math
 import os
 import sys
 
@@ -77,6 +81,16 @@ def build_parser():
     p.add_argument("--decode_context", default="last", choices=("last", "prefix"),
                    help="--do_eval: what a decode step sees.  last: the beam's last token at position 0 (the reference's loop); prefix: "
                         "the whole prefix, as the decoder is trained (key cache + csrc/attn_decode.hip; implies the batched step)")
+    p.add_argument("--decode_strategy", default="beam", choices=("beam", "sample"),
+                   help="--do_eval: beam search (the reference's), or --num_chains sampled chains per sample, the best-scoring one kept "
+                        "(csrc/sample.hip; implies the batched step)")
+    p.add_argument("--temperature", default=1.0, type=float, help="--decode_strategy sample: logits are divided by it (> 0)")
+    p.add_argument("--top_k", default=0, type=int, help="--decode_strategy sample: keep the k most probable tokens, ties included (0 = off)")
+    p.add_argument("--top_p", default=1.0, type=float, help="--decode_strategy sample: keep the nucleus of this mass, in (0, 1] (1 = off)")
+    p.add_argument("--num_chains", default=1, type=int, help="--decode_strategy sample: independent chains per sample")
+    p.add_argument("--sample_seed", default=0, type=int, help="--decode_strategy sample: seed of the counter-based draws")
+    p.add_argument("--length_penalty", default=0.0, type=float,
+                   help="--do_eval: the final choice among the finished beams / the chains ranks by score / length ** this (0 = the raw score)")
     p.add_argument("--learning_rate", default=3e-5, type=float)
     p.add_argument("--adam_epsilon", default=1e-8, type=float)
     p.add_argument("--num_train_epochs", default=8.0, type=float)
@@ -126,6 +140,19 @@ def main(argv=None):
         if not 1 <= args.max_len_decoder <= ops.DECODE_ATTN_MAX_T:
             raise ValueError(f"--decode_context prefix: --max_len_decoder {args.max_len_decoder} is outside the decode-attention "
                              f"kernel's 1 .. {ops.DECODE_ATTN_MAX_T} keys")
+    if args.do_eval and not math.isfinite(args.length_penalty):
+        raise ValueError(f"--length_penalty {args.length_penalty} must be finite")
+    if args.do_eval and args.decode_strategy == "sample":
+        try:
+            ops.check_sampler(args.temperature, args.top_k, args.top_p)
+        except ValueError as e:
+            raise ValueError(f"--decode_strategy sample: --temperature / --top_k / --top_p: {e}") from None
+        if args.num_chains < 1:
+            raise ValueError(f"--decode_strategy sample: --num_chains {args.num_chains} must be >= 1")
+        if args.sample_seed < 0:
+            raise ValueError(f"--decode_strategy sample: --sample_seed {args.sample_seed} must be >= 0")
+        if args.vocab_size > ops.SAMPLE_MAX_V:
+            raise ValueError(f"--decode_strategy sample: --vocab_size {args.vocab_size} is beyond the sampling kernel's {ops.SAMPLE_MAX_V} columns")
     rank, _, world, device, master, logger = init_run(args, "iaog", "pretraining_iaog.log", script="run_pretraining_fcmf.py")
 
     tokenizer = None
@@ -305,7 +332,10 @@ def main(argv=None):
                 r_img.eval(); r_roi.eval()
             preds, refs, results = generate(model, tokenizer, batches, features, args.beam_size, args.max_len_decoder, aspects,
                                                batched=args.batched_decode or args.decode_context == "prefix",
-                                               context=args.decode_context)
+                                               context=args.decode_context, strategy=args.decode_strategy,
+                                               sampler=dict(seed=args.sample_seed, temperature=args.temperature, top_k=args.top_k,
+                                                            top_p=args.top_p),
+                                               num_chains=args.num_chains, length_penalty=args.length_penalty)
             per_aspect, macro = macro_bertscore(preds, refs, aspects, score_fn)
             return per_aspect, macro, results
     elif args.do_eval and master:

@@ -7,7 +7,13 @@ log_softmax + topk on the same [n, 64032] bf16 buffer (V = 64001 columns valid).
 decode next to the decode on the whole prefix, which runs every live beam every round), and one cross-attention step of the prefix
 decode fused (ops.decode_attention reading the hoisted keys through the sample index) next to composed (index_select of the rows'
 keys + the attention forward the last-token step uses).  --only_prefix skips the other sections.
+--strategy sample runs the sampling legs INSTEAD of the sections above: the kernel alone (fcmf_sample_token with top-k 50 + top-p 0.9,
+with top-p 0.9 only and unfiltered, next to fcmf_logsoftmax_topk at k = beam_size and to an eager softmax / sort / cumsum / Gumbel
+argmax composition, a yardstick only, all alternating on one [n, 64032] bf16 buffer), and in the decode: the prefix beam search
+next to prefix sampling with num_chains = beam_size (decoding.sample_ids_batch) -- the same rows through the same blocks per round,
+another tail kernel -- alternating, with sampling's median over the beam's.
 Usage (GPU box, repo root):  python tools/decode_bench.py [--samples 16 64] [--beam_size 2] [--max_len_decoder 20] [--only_prefix]
+                                                          [--strategy sample]
 Prints one JSON line.  Decode: wall time per eval batch between device synchronisations, median of 5 (min, max beside it), both
 paths warmed up once per batch size and alternating, the number of decoder calls of each path, and whether the two paths decoded
 the same token sequences.  Kernel: median microseconds of 9 windows of 50 calls between device events, alternating."""
@@ -35,6 +41,7 @@ p.add_argument("--max_len_decoder", type=int, default=20)
 p.add_argument("--seq_len", type=int, default=64)
 p.add_argument("--num_rois", type=int, default=4)
 p.add_argument("--only_prefix", action="store_true")
+p.add_argument("--strategy", default="beam", choices=("beam", "sample"))
 args = p.parse_args()
 
 assert torch.cuda.is_available(), "decode_bench.py measures on the MI355X: no GPU, no number"
@@ -92,7 +99,10 @@ def stats(ts):
 
 res = {"geometry": dict(H=cfg["hidden_size"], heads=cfg["num_attention_heads"], blocks=cfg["num_hidden_layers"], V=V, num_imgs=NI,
                         dtype="bf16", beam_size=args.beam_size, max_len=args.max_len_decoder), "decode": [], "kernel": [], "prefix": []}
-for B in ([] if args.only_prefix else args.samples):
+sampling = args.strategy == "sample"
+if sampling:
+    res["sample_kernel"], res["sample_decode"] = [], []
+for B in ([] if args.only_prefix or sampling else args.samples):
     a = batch_args(B)
     ids_one, ids_many = per_sample(a), batched(a)                         # warm-up of every shape of both paths
     times = {"per_sample": [], "batched": []}
@@ -122,6 +132,53 @@ def window(fn, reps=50):
     torch.cuda.synchronize()
     return s.elapsed_time(e) / reps * 1e3
 
+
+def med(ts):
+    return dict(us=round(statistics.median(ts), 1), us_min_max=[round(min(ts), 1), round(max(ts), 1)])
+
+
+for n in (sorted({B * args.beam_size for B in args.samples}) if sampling else []):
+    x = (torch.randn(n, Vp, generator=torch.Generator().manual_seed(n)) * 3).to(dev).bfloat16()
+    ctr = torch.arange(n, device=dev)
+
+    def eager_sample():                                   # temperature 1, top-p 0.9, one Gumbel draw: what the kernel replaces
+        p_sorted, order = torch.sort(torch.softmax(x[:, :V].float(), dim=-1), dim=-1, descending=True)
+        keep = torch.cumsum(p_sorted, dim=-1) - p_sorted < 0.9
+        g = -torch.log(-torch.log(torch.rand_like(p_sorted)))
+        return order.gather(1, torch.argmax(torch.where(keep, torch.log(p_sorted) + g, float("-inf")), dim=-1, keepdim=True))
+
+    legs = {"sample_k50_p0.9": lambda: ops.sample_token(x, V, ctr, 1, top_k=50, top_p=0.9),
+            "sample_p0.9": lambda: ops.sample_token(x, V, ctr, 1, top_p=0.9),
+            "sample_unfiltered": lambda: ops.sample_token(x, V, ctr, 1),
+            "topk": lambda: ops.logsoftmax_topk(x, V, args.beam_size), "eager": eager_sample}
+    for fn in legs.values():
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    t = {k: [] for k in legs}
+    for _ in range(9):
+        for k, fn in legs.items():
+            t[k].append(window(fn))
+    res["sample_kernel"].append({"rows": n, "ld": Vp, **{k: med(v) for k, v in t.items()}})
+
+for B in (args.samples if sampling else []):
+    a = batch_args(B)
+    fns = {"beam_prefix": lambda a: [r[0] for r in decoding.beam_search_ids_batch(model, 0, SEP, *a, beam_size=args.beam_size,
+                                                                                  max_len=args.max_len_decoder, context="prefix")],
+           "sample_prefix": lambda a: [r[0] for r in decoding.sample_ids_batch(model, 0, SEP, *a, num_chains=args.beam_size,
+                                                                               max_len=args.max_len_decoder, context="prefix",
+                                                                               sampler=dict(seed=1, top_k=50, top_p=0.9))]}
+    ids = {c: fn(a) for c, fn in fns.items()}             # warm-up of every shape of both
+    times = {c: [] for c in fns}
+    for _ in range(5):
+        for c, fn in fns.items():
+            times[c].append(timed(fn, a)[0])
+    st = {c: stats(t) for c, t in times.items()}
+    res["sample_decode"].append({"samples_per_batch": B, **st, "mean_len": {c: sum(map(len, v)) / B for c, v in ids.items()},
+                                 "sample_over_beam": round(st["sample_prefix"]["median_ms"] / st["beam_prefix"]["median_ms"], 3)})
+if sampling:
+    print(json.dumps(res))
+    sys.exit(0)
 
 for n in ([] if args.only_prefix else sorted({B * args.beam_size for B in args.samples})):
     x = (torch.randn(n, Vp, generator=torch.Generator().manual_seed(n)) * 3).to(dev).bfloat16()
