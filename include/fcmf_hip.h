@@ -343,6 +343,36 @@ int fcmf_sample_token(const void* logits, int64_t ld, int rows, int V, float tem
                       const int64_t* ctr, int32_t* ids, float* logp, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Generation constraints on the logits of a decode step, in place, one launch for `rows` independent rows: repetition penalty,
+ * no-repeat n-gram bans, a minimum length and always-suppressed ids (the rules of Hugging Face's RepetitionPenaltyLogitsProcessor,
+ * NoRepeatNGramLogitsProcessor, MinLengthLogitsProcessor and SuppressTokensLogitsProcessor).
+ * The edit is made on the LOGITS, before fcmf_logsoftmax_topk / fcmf_sample_token: the constrained logits ARE the step's
+ * distribution.  The log-probabilities those return, beam and chain scores, temperature, top-k and top-p all see them; a banned
+ * token has log-probability -inf and the mass is renormalised over the rest.  (Hugging Face's beam search applies its processors
+ * after the log-softmax instead; one definition for both strategies keeps a chain's score and a beam's the same quantity.)
+ *   logits [rows, ld] in `dtype` (FCMF_F32 / FCMF_BF16), row r at logits + r*ld (elements); only columns 0 .. V-1 are touched.
+ *   hist   int64 on the device: the sequence of row r is h[p] = hist[r*hist_sr + p*hist_sp], p = 0 .. L-1, L = hist_len: the start
+ *          token first, the token the step was run on last.  All rows of a call have the same L.  Entries are vocabulary ids and
+ *          are held as int: a value beyond int is out of range like any other and equals only other such values.
+ * Per row, x its stored values, in this order:
+ *   1. repetition penalty theta (finite, > 0; 1 = off): for every DISTINCT v among h[0 .. L-1] with 0 <= v < V,
+ *      x[v] <- x[v] < 0 ? x[v] * theta : x[v] / theta, in float32 with a correctly rounded divide, rounded once to nearest-even
+ *      into the storage type.  A token that occurs five times is penalised once;
+ *   2. no_repeat_ngram n (0 = off): for every i in 0 .. L-n with h[i .. i+n-2] == h[L-n+1 .. L-1]: x[h[i+n-1]] <- -inf.  n = 1 bans
+ *      every token of the sequence, L < n bans nothing;
+ *   3. min_length m (0 = off): if L < m, x[sep_id] <- -inf (L is the length penalty's len(seq) - 1 of the resulting sequence);
+ *   4. x[ban_ids[j]] <- -inf for j < n_ban; ban_ids int32 on the device, or NULL with n_ban == 0.
+ * A ban wins over a penalty on the same column.  An id outside [0, V) -- from hist, sep_id or ban_ids -- writes nothing.  Every
+ * other column, every column >= V and every byte outside the rows keep their bits (bf16 columns are 2-byte stores).  No atomics,
+ * one rounding: two launches give the same bits.
+ * Limits: hist_len <= 512, n_ban <= 1024, dtype FCMF_F32 / FCMF_BF16 -- FCMF_ERR_UNSUPPORTED otherwise; logits and hist not
+ * NULL, rows >= 0, 1 <= V <= ld, hist_len >= 1, theta finite and > 0, no_repeat_ngram / min_length / n_ban >= 0, ban_ids not NULL when n_ban > 0
+ * -- FCMF_ERR_ARG otherwise; rows == 0, or nothing to do (theta == 1, n == 0, L >= m, n_ban == 0), succeeds without a launch. */
+int fcmf_logits_constrain(void* logits, int64_t ld, int rows, int V, const int64_t* hist, int64_t hist_sr, int64_t hist_sp,
+                          int hist_len, float repetition_penalty, int no_repeat_ngram, int min_length, int sep_id,
+                          const int32_t* ban_ids, int n_ban, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Single-query attention with indexed keys, one launch for n rows x `heads` slots: the two attentions of an IAOG decode step
  * that sees its whole prefix (the decoder `Attention` of mm_modeling.py:66-132 for ONE query row per sequence: values are the
  * projected keys :129, plain slot -> head pairing, which is the reference's at batch size 1).  All strides in elements.

@@ -42,6 +42,16 @@ distribution after temperature / top-k / nucleus filtering (csrc/sample.hip: no 
 draw of (sample, chain, round) is a function of the sampler's seed and the counter ((sample_offset + b) * num_chains + c) * max_len + t
 alone, so a sample's text does not depend on the eval batch it is decoded in.  A chain's score is the sum of its tokens'
 log-probabilities under the model's own distribution, the quantity a beam's score is.
+
+Constraints (every entry point, `constraints=` a dict of `make_constraints`' settings, default None): repetition_penalty,
+no_repeat_ngram_size, min_length and suppress_tokens, by the rules of Hugging Face's logits processors, applied to the step's LOGITS
+on the device (csrc/constrain.hip, between the vocabulary GEMM and either tail) -- the constrained logits are the step's
+distribution, so every returned log-probability, beam and chain score is under it, in both strategies alike.  A constrained step is
+a function of the row's whole sequence: the rows handed to the step carry the beam's or chain's `seq` (the host has it), the step
+puts it into the round's one upload tensor and the kernel takes the [n, L] view by strides; beam search in context "last" loses its
+(sample, last token) memo and runs every live beam as a row of its round, as sampling does.  Still one upload and one host read per
+round; the suppressed ids are uploaded once per call.  None, or all settings off, takes the paths above unchanged: the step
+callables receive exactly the same tuples and no new code runs.
 """
 import torch
 import torch.nn.functional as F
@@ -49,7 +59,7 @@ import torch.nn.functional as F
 from . import ops
 
 __all__ = ["beam_search", "beam_search_ids", "beam_search_batch", "beam_search_ids_batch", "beam_rounds",
-           "sample_rounds", "sample_ids_batch", "sample_batch"]
+           "sample_rounds", "sample_ids_batch", "sample_batch", "make_sampler", "make_constraints"]
 
 CONTEXTS = ("last", "prefix")
 
@@ -69,18 +79,19 @@ def _best(fin, length_penalty=0.0):
 
 @torch.no_grad()
 def beam_search_ids(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                    beam_size=3, max_len=20, context="last", length_penalty=0.0):
+                    beam_size=3, max_len=20, context="last", length_penalty=0.0, constraints=None):
     """-> (token ids of the best sequence incl. the start token, its log-likelihood, [(score, ids)] of the finished beams)
-    context="prefix": the batched path with this one sample (see the module header)"""
+    context="prefix", or constraints on: the batched path with this one sample (see the module header)"""
     _check_context(context)
+    constraints = make_constraints(constraints)
     model.eval()
     if enc_ids.dim() == 1:                                    # one sample without a batch axis (:395-402)
         enc_ids, enc_mask, enc_type, add_mask = (t.unsqueeze(0) for t in (enc_ids, enc_mask, enc_type, add_mask))
         vis_embeds, roi_embeds, roi_coors = (t.unsqueeze(0) for t in (vis_embeds, roi_embeds, roi_coors))
-    if context == "prefix":
+    if context == "prefix" or constraints is not None:
         return beam_search_ids_batch(model, start_id, sep_id, enc_ids[:1], enc_mask[:1], enc_type[:1], add_mask[:1], vis_embeds[:1],
                                      roi_embeds[:1], roi_coors[:1], beam_size=beam_size, max_len=max_len, context=context,
-                                     length_penalty=length_penalty)[0]
+                                     length_penalty=length_penalty, constraints=constraints)[0]
     enc = model.encoder(enc_ids, vis_embeds, roi_embeds, roi_coors, enc_type, enc_mask, add_mask)
     enc = enc[0] if isinstance(enc, tuple) else enc
     dec = model.decoder
@@ -122,12 +133,12 @@ def beam_search_ids(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_ma
 
 
 def beam_search(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                beam_size=3, num_preds=1, max_len=20, device='cuda', context="last", length_penalty=0.0):
+                beam_size=3, num_preds=1, max_len=20, device='cuda', context="last", length_penalty=0.0, constraints=None):
     """the reference's signature and result: [decoded text of the best sequence] (fcmf_pretraining.py:383-517)"""
     start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
     ids, _, _ = beam_search_ids(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds,
                                 roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len, context=context,
-                                length_penalty=length_penalty)
+                                length_penalty=length_penalty, constraints=constraints)
     return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip()]
 
 
@@ -149,7 +160,8 @@ def _advance(beams, final, tops, sep_id, beam_size):
     return [(score, seq) for score, seq, _ in best], [j for _, _, j in best]
 
 
-def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=20, context="last", length_penalty=0.0):
+def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=20, context="last", length_penalty=0.0,
+                constraints=None):
     """the loop of `beam_search_ids` for `num_samples` samples side by side, on the host alone.  Per round: the (sample, last token)
     pairs of every live beam of every unfinished sample that the memo does not hold are collected (each once, in order of first
     appearance) and handed to ONE call step_many(pairs) -> {pair: (top log-probabilities, top ids)} (Python lists of at least
@@ -159,9 +171,15 @@ def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=2
     step_many(rows, t) -> [(top log-probabilities, top ids)] in row order, rows = [(sample, token at position t, ancestors)]:
     ancestors[p] is the index that the beam's position p had among the rows of round p (p < t) -- the step keeps what it needs of a
     row under (round, row index) and finds a beam's history there.  At most num_samples * beam_size rows per round.
+    constraints not None (only whether it is None is read here): a step is a function of the beam's whole sequence, so there is no
+    memo in either context -- every live beam is a row, in (sample, beam) order -- and every row carries the beam's own `seq` (all of
+    length t + 1 in round t) as one more, last entry: "last" rows = [(sample, last token, seq)] with step_many(rows) -> a list in
+    row order, "prefix" rows = [(sample, token, ancestors, seq)].
     -> [(ids of the best sequence incl. the start token, its score, the finished list [(score, ids)])], one entry per sample"""
     _check_context(context)
     prefix = context == "prefix"
+    on = constraints is not None
+    by_row = prefix or on                                     # every live beam is a row of its round: no memo
     memo = {}
     beams = [[(0.0, [int(start_id)])] for _ in range(num_samples)]
     anc = [[[]] for _ in range(num_samples)]                  # prefix mode: per beam, the rows that held its earlier positions
@@ -170,14 +188,14 @@ def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=2
     for t in range(max_len):
         if not live:
             break
-        if prefix:
+        if by_row:
             rows, row_of = [], {}
             for b in live:
                 for j, (_, seq) in enumerate(beams[b]):
                     if seq[-1] != sep_id:
                         row_of[(b, j)] = len(rows)
-                        rows.append((b, seq[-1], anc[b][j]))
-            tops_all = step_many(rows, t) if rows else []
+                        rows.append((b, seq[-1]) + ((anc[b][j],) if prefix else ()) + ((seq,) if on else ()))
+            tops_all = (step_many(rows, t) if prefix else step_many(rows)) if rows else []
         else:
             need = []
             for b in live:
@@ -189,7 +207,7 @@ def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=2
                 memo.update(step_many(need))
         still = []
         for b in live:
-            if prefix:
+            if by_row:
                 adv = _advance(beams[b], final[b], lambda j, seq: tops_all[row_of[(b, j)]], sep_id, beam_size)
             else:
                 adv = _advance(beams[b], final[b], lambda j, seq: memo[(b, seq[-1])], sep_id, beam_size)
@@ -212,7 +230,7 @@ def beam_rounds(step_many, num_samples, start_id, sep_id, beam_size=3, max_len=2
 
 
 def sample_rounds(step_many, num_samples, start_id, sep_id, num_chains=1, max_len=20, context="last", sample_offset=0,
-                  length_penalty=0.0):
+                  length_penalty=0.0, constraints=None):
     """the sampling loop for `num_samples` samples side by side, on the host alone: every sample runs `num_chains` independent chains
     from [start_id]; round t hands every unfinished chain, in (sample, chain) order, to ONE call of the step and appends the token it
     draws; a chain ends at sep_id or after max_len draws.  A row carries its counter ((sample_offset + b) * num_chains + c) * max_len
@@ -222,6 +240,8 @@ def sample_rounds(step_many, num_samples, start_id, sep_id, num_chains=1, max_le
     context="prefix": step_many(rows, t), rows = [(sample, token at position t, ancestors, counter)], ancestors[p] the index the
                       chain had among the rows of round p (as in `beam_rounds`; chains never branch).  At most num_samples *
                       num_chains rows per round.
+    constraints not None (only whether it is None is read here): every row carries a copy of the chain's whole sequence as one
+    more, last entry -- (sample, last token, counter, seq) / (sample, token, ancestors, counter, seq).
     A chain's score is the Python-float sum of the returned log-probabilities, in order.
     -> [(ids of the best chain incl. the start token, its score, [(score, ids)] of all chains in chain order)], one entry per sample;
     best = `_best` (the highest score, or the highest length-penalised one; the first chain among equals)"""
@@ -235,10 +255,11 @@ def sample_rounds(step_many, num_samples, start_id, sep_id, num_chains=1, max_le
         if not live:
             break
         ctr = [((sample_offset + b) * num_chains + c) * max_len + t for b, c in live]
+        own = (lambda b, c: (list(seqs[b][c]),)) if constraints is not None else (lambda b, c: ())
         if prefix:
-            res = step_many([(b, seqs[b][c][-1], anc[b][c], n) for (b, c), n in zip(live, ctr)], t)
+            res = step_many([(b, seqs[b][c][-1], anc[b][c], n) + own(b, c) for (b, c), n in zip(live, ctr)], t)
         else:
-            res = step_many([(b, seqs[b][c][-1], n) for (b, c), n in zip(live, ctr)])
+            res = step_many([(b, seqs[b][c][-1], n) + own(b, c) for (b, c), n in zip(live, ctr)])
         still = []
         for i, ((b, c), (lp, tok)) in enumerate(zip(live, res)):
             scores[b][c] += lp
@@ -257,17 +278,25 @@ def sample_rounds(step_many, num_samples, start_id, sep_id, num_chains=1, max_le
 
 @torch.no_grad()
 def beam_search_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                          beam_size=3, max_len=20, context="last", length_penalty=0.0):
+                          beam_size=3, max_len=20, context="last", length_penalty=0.0, constraints=None):
     """`beam_search_ids` of every sample of a batch ([B, ...] tensors), one decoder call per beam round for all of them: the encoder
     and `project_encoder` run once for the batch.  context="prefix": every step sees its beam's whole prefix (module header); the
-    key cache is allocated here, once per batch.  -> [(ids, score, final)], one entry per sample"""
+    key cache is allocated here, once per batch.  constraints: `make_constraints`' settings (module header): the rows' sequences
+    ride in the round's one upload.  -> [(ids, score, final)], one entry per sample"""
     _check_context(context)
+    constraints = make_constraints(constraints)
+    _check_room(constraints, model.decoder.dense.weight.shape[0], max_len, beam_size)
     model.eval()
     enc = model.encoder(enc_ids, vis_embeds, roi_embeds, roi_coors, enc_type, enc_mask, add_mask)
     enc = enc[0] if isinstance(enc, tuple) else enc
     dec = model.decoder
     keys = dec.project_encoder(enc)
     device = enc.device
+    cons = _device_constraints(constraints, sep_id, device)   # the suppressed ids: ONE upload per call
+
+    def read(logp, ids):
+        both = torch.cat((logp, ids.view(torch.float32)), dim=1).cpu()      # ONE host read: the ids ride along as their bits
+        return list(zip(both[:, :beam_size].tolist(), both[:, beam_size:].contiguous().view(torch.int32).tolist()))
 
     def step_many(pairs):
         idx = torch.tensor(pairs, device=device, dtype=torch.long)          # [n, 2]: (sample, token)
@@ -288,18 +317,75 @@ def beam_search_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, 
             both = torch.cat((logp, ids.view(torch.float32)), dim=1).cpu()      # ONE host read, as above
             return list(zip(both[:, :beam_size].tolist(), both[:, beam_size:].contiguous().view(torch.int32).tolist()))
 
-        return beam_rounds(step_rows, enc_ids.shape[0], start_id, sep_id, beam_size, max_len, context, length_penalty)
-    return beam_rounds(step_many, enc_ids.shape[0], start_id, sep_id, beam_size, max_len, length_penalty=length_penalty)
+        def step_rows_seq(rows, t):
+            # ONE upload, [2 + t + (t + 1), n]: as above, then the rows' own sequences position by position (the kernel's [n, t + 1] view)
+            buf = torch.tensor([[r[0] for r in rows], [r[1] for r in rows]] + [[r[2][p] for r in rows] for p in range(t)] +
+                               [[r[3][p] for r in rows] for p in range(t + 1)], device=device, dtype=torch.long)
+            return read(*dec.decode_step_prefix(buf[1], buf[0], buf[2:2 + t].t(), t, cache, enc, keys, beam_size,
+                                                constraints=dict(cons, hist=buf[2 + t:].t())))
+
+        return beam_rounds(step_rows if cons is None else step_rows_seq, enc_ids.shape[0], start_id, sep_id, beam_size, max_len, context,
+                           length_penalty, constraints)
+
+    def step_seq(rows):
+        # ONE upload, [2 + L, n]: the samples, the tokens, then the rows' own sequences position by position
+        buf = torch.tensor([[r[0] for r in rows], [r[1] for r in rows]] + [[r[2][p] for r in rows] for p in range(len(rows[0][2]))],
+                           device=device, dtype=torch.long)
+        return read(*dec.decode_step(buf[1], buf[0], enc, keys, beam_size, constraints=dict(cons, hist=buf[2:].t())))
+
+    return beam_rounds(step_many if cons is None else step_seq, enc_ids.shape[0], start_id, sep_id, beam_size, max_len,
+                       length_penalty=length_penalty, constraints=constraints)
 
 
 def beam_search_batch(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                      beam_size=3, max_len=20, context="last", length_penalty=0.0):
+                      beam_size=3, max_len=20, context="last", length_penalty=0.0, constraints=None):
     """-> [decoded text of the best sequence], one per sample of the batch (what `beam_search` returns per sample, [0])"""
     start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
     res = beam_search_ids_batch(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds,
                                 roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len, context=context,
-                                length_penalty=length_penalty)
+                                length_penalty=length_penalty, constraints=constraints)
     return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip() for ids, _, _ in res]
+
+
+def make_constraints(constraints=None, **settings):
+    """the constraint settings of every entry point as a checked dict -- repetition_penalty (1 = off), no_repeat_ngram_size (0 = off),
+    min_length (0 = off), suppress_tokens (a tuple of ids, () = off) -- from a dict and / or keywords; None when all are off"""
+    out = dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=())
+    given = dict(constraints or {}, **settings)
+    extra = set(given) - set(out)
+    if extra:
+        raise ValueError(f"constraints: unknown settings {sorted(extra)} (known: {sorted(out)})")
+    out.update(given)
+    if isinstance(out["suppress_tokens"], (str, bytes)) or not hasattr(out["suppress_tokens"], "__iter__"):
+        raise ValueError(f"suppress_tokens must be a sequence of token ids, got {out['suppress_tokens']!r}")
+    out["suppress_tokens"] = tuple(out["suppress_tokens"])
+    ops.check_constraints(**out)
+    if out["repetition_penalty"] == 1 and not out["no_repeat_ngram_size"] and not out["min_length"] and not out["suppress_tokens"]:
+        return None
+    return out
+
+
+def _check_room(constraints, V, max_len, width):
+    """constraints on: a round's sequence must fit the kernel, and `width` columns must stay unbanned whatever is decoded -- at most
+    max_len n-gram bans, the separator and the suppressed ids can be -inf"""
+    if constraints is None:
+        return
+    if max_len > ops.CONSTRAIN_MAX_T:
+        raise ValueError(f"constraints: max_len {max_len} is beyond the constraint kernel's {ops.CONSTRAIN_MAX_T} tokens")
+    n_ban = len(constraints["suppress_tokens"])
+    if V < max_len + 1 + n_ban + width:
+        raise ValueError(f"constraints: a vocabulary of {V} cannot keep {width} tokens unbanned beside up to {max_len} n-gram bans, the "
+                         f"separator and {n_ban} suppressed ids (needs >= {max_len + 1 + n_ban + width})")
+
+
+def _device_constraints(constraints, sep_id, device):
+    """`make_constraints`' dict as ops.logits_constrain's keyword arguments but `hist`: the suppressed ids go to the device here, once"""
+    if constraints is None:
+        return None
+    ban = constraints["suppress_tokens"]
+    return dict(repetition_penalty=constraints["repetition_penalty"], no_repeat_ngram_size=constraints["no_repeat_ngram_size"],
+                min_length=constraints["min_length"], sep_id=int(sep_id),
+                ban_ids=torch.tensor(ban, device=device, dtype=torch.int32) if ban else None)
 
 
 def make_sampler(sampler=None):
@@ -315,21 +401,24 @@ def make_sampler(sampler=None):
 
 @torch.no_grad()
 def sample_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                     num_chains=1, max_len=20, context="last", sampler=None, sample_offset=0, length_penalty=0.0):
+                     num_chains=1, max_len=20, context="last", sampler=None, sample_offset=0, length_penalty=0.0, constraints=None):
     """`sample_rounds` of every sample of a batch ([B, ...] tensors) over the batched decode steps: the encoder and `project_encoder`
     run once for the batch, every round is ONE upload (samples, tokens, counters and, in prefix mode, the ancestor table), one decoder
     call ending in csrc/sample.hip and ONE host read.  sampler: `make_sampler`'s settings; sample_offset: the running index of the
-    batch's first sample in the eval set.  -> [(ids of the best chain, its score, [(score, ids)] of all chains)], one entry per sample"""
+    batch's first sample in the eval set; constraints: `make_constraints`' settings (module header).  -> [(ids of the best chain, its score, [(score, ids)] of all chains)], one entry per sample"""
     _check_context(context)
     if num_chains < 1:
         raise ValueError(f"num_chains must be >= 1, got {num_chains}")
     cfg = make_sampler(sampler)
+    constraints = make_constraints(constraints)
+    _check_room(constraints, model.decoder.dense.weight.shape[0], max_len, 1)
     model.eval()
     enc = model.encoder(enc_ids, vis_embeds, roi_embeds, roi_coors, enc_type, enc_mask, add_mask)
     enc = enc[0] if isinstance(enc, tuple) else enc
     dec = model.decoder
     keys = dec.project_encoder(enc)
     device = enc.device
+    cons = _device_constraints(constraints, sep_id, device)   # the suppressed ids: ONE upload per call
 
     def read(logp, ids):
         both = torch.cat((logp, ids.view(torch.float32)), dim=1).cpu()      # ONE host read: the ids ride along as their bits
@@ -344,20 +433,35 @@ def sample_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_m
                                device=device, dtype=torch.long)
             return read(*dec.decode_step_prefix(buf[1], buf[0], buf[3:].t(), t, cache, enc, keys, 1, sampler=dict(cfg, ctr=buf[2])))
 
-        return sample_rounds(step_rows, enc_ids.shape[0], start_id, sep_id, num_chains, max_len, context, sample_offset, length_penalty)
+        def step_rows_seq(rows, t):
+            # ONE upload, [3 + t + (t + 1), n]: as above, then the chains' own sequences position by position
+            buf = torch.tensor([[r[0] for r in rows], [r[1] for r in rows], [r[3] for r in rows]] + [[r[2][p] for r in rows] for p in range(t)] +
+                               [[r[4][p] for r in rows] for p in range(t + 1)], device=device, dtype=torch.long)
+            return read(*dec.decode_step_prefix(buf[1], buf[0], buf[3:3 + t].t(), t, cache, enc, keys, 1, sampler=dict(cfg, ctr=buf[2]),
+                                                constraints=dict(cons, hist=buf[3 + t:].t())))
+
+        return sample_rounds(step_rows if cons is None else step_rows_seq, enc_ids.shape[0], start_id, sep_id, num_chains, max_len, context,
+                             sample_offset, length_penalty, constraints)
 
     def step_many(rows):
         buf = torch.tensor(rows, device=device, dtype=torch.long).t().contiguous()      # ONE upload, [3, n]: samples, tokens, counters
         return read(*dec.decode_step(buf[1], buf[0], enc, keys, 1, sampler=dict(cfg, ctr=buf[2])))
 
-    return sample_rounds(step_many, enc_ids.shape[0], start_id, sep_id, num_chains, max_len, context, sample_offset, length_penalty)
+    def step_seq(rows):
+        # ONE upload, [3 + L, n]: samples, tokens, counters, then the chains' own sequences position by position
+        buf = torch.tensor([[r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows]] +
+                           [[r[3][p] for r in rows] for p in range(len(rows[0][3]))], device=device, dtype=torch.long)
+        return read(*dec.decode_step(buf[1], buf[0], enc, keys, 1, sampler=dict(cfg, ctr=buf[2]), constraints=dict(cons, hist=buf[3:].t())))
+
+    return sample_rounds(step_many if cons is None else step_seq, enc_ids.shape[0], start_id, sep_id, num_chains, max_len, context,
+                         sample_offset, length_penalty, constraints)
 
 
 def sample_batch(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                 num_chains=1, max_len=20, context="last", sampler=None, sample_offset=0, length_penalty=0.0):
+                 num_chains=1, max_len=20, context="last", sampler=None, sample_offset=0, length_penalty=0.0, constraints=None):
     """-> [decoded text of the best chain], one per sample of the batch: `beam_search_batch`'s result from `sample_ids_batch`"""
     start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
     res = sample_ids_batch(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds,
                            roi_coors, num_chains=num_chains, max_len=max_len, context=context, sampler=sampler,
-                           sample_offset=sample_offset, length_penalty=length_penalty)
+                           sample_offset=sample_offset, length_penalty=length_penalty, constraints=constraints)
     return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip() for ids, _, _ in res]

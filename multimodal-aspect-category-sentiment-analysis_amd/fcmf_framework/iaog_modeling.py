@@ -325,17 +325,18 @@ class IAOGDecoder(nn.Module):
         X = self.hidden_states(X, state, enc_attention_mask, True)
         return ops.vocab_cross_entropy(X, self.dense.weight, self.dense.bias, labels, ignore_index)
 
-    def _decode_tail(self, X, k, sampler):
+    def _decode_tail(self, X, k, sampler, constraints=None):
         """the end of a decode step on the rows X [n, H] of the last block: the k best tokens (ops.vocab_topk), or -- `sampler` a dict of
         ops.vocab_sample's arguments ctr (int64 [n] on the device), seed, temperature, top_k, top_p -- one sampled token per row,
-        as ([n, 1], [n, 1]) in the same order (log-probabilities, ids); k is not read then"""
+        as ([n, 1], [n, 1]) in the same order (log-probabilities, ids); k is not read then.  constraints: ops.logits_constrain's
+        keyword arguments as a dict (hist int64 [n, L]: every row's whole sequence), applied to the logits before either tail"""
         if sampler is None:
-            return ops.vocab_topk(X, self.dense.weight, self.dense.bias, k)
-        ids, logp = ops.vocab_sample(X, self.dense.weight, self.dense.bias, **sampler)
+            return ops.vocab_topk(X, self.dense.weight, self.dense.bias, k, constraints=constraints)
+        ids, logp = ops.vocab_sample(X, self.dense.weight, self.dense.bias, constraints=constraints, **sampler)
         return logp.view(-1, 1), ids.view(-1, 1)
 
     @torch.no_grad()
-    def decode_step(self, tokens, sample_idx, enc, keys, k, sampler=None):
+    def decode_step(self, tokens, sample_idx, enc, keys, k, sampler=None, constraints=None):
         """the is_train=False step of n INDEPENDENT rows in one pass: row i is what forward(tensor([[tokens[i]]]),
         init_state(enc[s:s+1], None), is_train=False, hoisted = keys of sample s) computes for s = sample_idx[i] -- position 0, no
         mask on either attention -- followed by log_softmax + topk(k).  At batch size 1 the reference's slot -> head pairing is the
@@ -343,7 +344,8 @@ class IAOGDecoder(nn.Module):
         head_quirk 0 (the one-key self attention needs no launch); stacking them into an ordinary batch would pair slots with other heads (mm_modeling.py:79-85).
         tokens, sample_idx: int64 [n] on the device; enc [Bs, T, H]; keys = project_encoder(enc), formed here when None.
         -> (log-probabilities float32 [n, k], token ids int32 [n, k]) (ops.vocab_topk); no attention weights are kept.  Dropout is
-        off whatever the module's mode: this is the evaluation step.  sampler (see _decode_tail): one sampled token per row instead."""
+        off whatever the module's mode: this is the evaluation step.  sampler (see _decode_tail): one sampled token per row instead;
+        constraints (see there): the step still sees the last token only, the constraints the row's whole sequence."""
         n = tokens.shape[0]
         if keys is None:
             keys = self.project_encoder(enc)
@@ -365,7 +367,7 @@ class IAOGDecoder(nn.Module):
             o, _ = _quirk_attn_fwd(qx, kx.index_select(0, sample_idx), nh, False, head_quirk=0)      # [n, T, HD] gather: T = 1 + 2*num_imgs rows each
             Z = add_norm(blk.addnorm2, Y, ops.linear(o, a2.proj.weight, a2.proj.bias))
             X = add_norm(blk.add_norm3, Z, blk.ffn(Z))
-        return self._decode_tail(X.view(n, -1), k, sampler)
+        return self._decode_tail(X.view(n, -1), k, sampler, constraints)
 
     def init_cache(self, max_len, rows, device=None):
         """the self-attention key cache of a prefix decode (decode_step_prefix): per block [max_len, rows, n_head*d] in the compute
@@ -378,7 +380,7 @@ class IAOGDecoder(nn.Module):
                 for blk in self.blks]
 
     @torch.no_grad()
-    def decode_step_prefix(self, tokens, sample_idx, anc, t, cache, enc, keys, k, sampler=None):
+    def decode_step_prefix(self, tokens, sample_idx, anc, t, cache, enc, keys, k, sampler=None, constraints=None):
         """round t of a decode that sees the whole prefix, n rows in one pass.  Row i is the sequence whose token at position t is
         tokens[i], of sample sample_idx[i], whose earlier positions p < t went through this method as row anc[i, p] of round p with
         the same `cache`.  Its result is row t of forward(tensor([seq]), init_state(enc[s:s+1], <2-D mask>), is_train=True) at batch
@@ -389,7 +391,7 @@ class IAOGDecoder(nn.Module):
         beams share and reorder history by index, no block's keys are ever copied.
         tokens, sample_idx int64 [n]; anc int64 [n, >= t] (any strides); cache = init_cache(max_len > t, rows >= n);
         keys = project_encoder(enc), formed here when None.  -> (log-probabilities float32 [n, k], token ids int32 [n, k]).
-        Dropout is off whatever the module's mode, as in decode_step; sampler as there."""
+        Dropout is off whatever the module's mode, as in decode_step; sampler and constraints as there."""
         n = tokens.shape[0]
         if not (0 <= t < cache[0].shape[0] and n <= cache[0].shape[1]):
             raise ValueError(f"decode_step_prefix: round {t} with {n} rows does not fit a cache of {tuple(cache[0].shape[:2])}")
@@ -413,7 +415,7 @@ class IAOGDecoder(nn.Module):
             o = ops.decode_attention(qx, kx, sample_idx, nh, Tk, min(t + 1, Tk), pos_dim=1)      # the sample's keys in place: no gather
             Z = add_norm(blk.addnorm2, Y, ops.linear(o, a2.proj.weight, a2.proj.bias))
             X = add_norm(blk.add_norm3, Z, blk.ffn(Z))
-        return self._decode_tail(X, k, sampler)
+        return self._decode_tail(X, k, sampler, constraints)
 
     @property
     def attention_weights(self):

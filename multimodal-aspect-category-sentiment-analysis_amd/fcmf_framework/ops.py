@@ -817,12 +817,66 @@ def logsoftmax_topk(logits, V, k):
     return logp, ids
 
 
+CONSTRAIN_MAX_T = 512      # fcmf_logits_constrain's limit on the sequence length (include/fcmf_hip.h)
+CONSTRAIN_MAX_BAN = 1024   # ... and on the number of suppressed ids
+
+
+def check_constraints(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, suppress_tokens=()):
+    """the value limits of fcmf_logits_constrain (include/fcmf_hip.h), raised as a ValueError that names the argument"""
+    if not (isinstance(repetition_penalty, (int, float)) and math.isfinite(repetition_penalty) and repetition_penalty > 0):
+        raise ValueError(f"repetition_penalty must be finite and > 0 (1 = off), got {repetition_penalty}")
+    for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_length", min_length)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{name} must be an integer >= 0 (0 = off), got {v}")
+    ids = list(suppress_tokens)
+    if any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 31 for v in ids):
+        raise ValueError(f"suppress_tokens must be token ids (integers >= 0), got {ids}")
+    if len(ids) > CONSTRAIN_MAX_BAN:
+        raise ValueError(f"suppress_tokens holds {len(ids)} ids, the kernel takes at most {CONSTRAIN_MAX_BAN}")
+
+
+def logits_constrain(logits, V, hist, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, sep_id=-1, ban_ids=None):
+    """edits the first V columns of logits [n, >= V] (unit inner stride, any row stride) IN PLACE, before `logsoftmax_topk` /
+    `sample_token`: repetition penalty once per distinct token of the row's sequence, -inf on every token that would complete an
+    n-gram the sequence already holds, on sep_id while the sequence is shorter than min_length, and on ban_ids (int32 on the
+    device, or None).  hist int64 [n, L] (any strides), L <= CONSTRAIN_MAX_T: row r's sequence, the start token first.  Ids outside
+    [0, V) write nothing.  One launch, none when nothing is on (fcmf_logits_constrain, include/fcmf_hip.h).  Returns nothing."""
+    H.require_cuda(logits, hist, ban_ids)
+    check_constraints(repetition_penalty, no_repeat_ngram_size, min_length)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] < V:
+        raise H.HipLibraryError(f"logits_constrain: want [n, >= {V}] rows with unit inner stride, got {tuple(logits.shape)} / {logits.stride()}")
+    n = logits.shape[0]
+    ld = logits.stride(0) if n > 1 else max(logits.stride(0), V)      # (one row: its stride means nothing)
+    if ld < V:
+        raise H.HipLibraryError(f"logits_constrain: rows overlap (row stride {ld} < {V} columns)")
+    if hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != n or hist.shape[1] < 1:
+        raise H.HipLibraryError(f"logits_constrain: want an int64 history [{n}, L >= 1], got {hist.dtype} {tuple(hist.shape)}")
+    if hist.shape[1] > CONSTRAIN_MAX_T:
+        raise H.HipLibraryError(f"logits_constrain: a sequence of {hist.shape[1]} tokens is beyond the kernel's {CONSTRAIN_MAX_T}")
+    n_ban = 0
+    if ban_ids is not None:
+        if ban_ids.dtype != torch.int32 or ban_ids.dim() != 1 or ban_ids.shape[0] > CONSTRAIN_MAX_BAN:
+            raise H.HipLibraryError(f"logits_constrain: want at most {CONSTRAIN_MAX_BAN} int32 ban_ids, got {ban_ids.dtype} {tuple(ban_ids.shape)}")
+        ban_ids = ban_ids.contiguous()
+        n_ban = ban_ids.shape[0]
+    if n == 0:
+        return
+    H.check(H.lib().fcmf_logits_constrain(H.ptr(logits), ld, n, V, H.ptr(hist), hist.stride(0), hist.stride(1), hist.shape[1],
+                                          float(repetition_penalty), int(no_repeat_ngram_size), int(min_length), int(sep_id),
+                                          H.ptr(ban_ids) if n_ban else None, n_ban, H.dt(logits), H.stream()), "fcmf_logits_constrain")
+
+
 @torch.no_grad()
-def vocab_topk(x, weight, bias, k):
+def vocab_topk(x, weight, bias, k, constraints=None):
     """the k most probable tokens of every row of x [n, K] under softmax(x W^T + b), weight [V, K] -> (log-probabilities float32
     [n, k], token ids int32 [n, k]).  No autograd: the decode step.  The projection is _vocab_logits', its padded bias cached on the
-    Parameter, and the kernel reads the [n, Vp] buffer with its row stride -- no compaction copy to [n, V], no log-softmax round trip."""
-    return logsoftmax_topk(_vocab_logits(_rows(x), weight, bias, cache_bias=True)[0], weight.shape[0], k)
+    Parameter, and the kernel reads the [n, Vp] buffer with its row stride -- no compaction copy to [n, V], no log-softmax round trip.
+    constraints: `logits_constrain`'s keyword arguments as a dict (hist, repetition_penalty, no_repeat_ngram_size, min_length, sep_id,
+    ban_ids), applied to the [n, Vp] buffer before the tail: the log-probabilities are those of the constrained logits."""
+    logits = _vocab_logits(_rows(x), weight, bias, cache_bias=True)[0]
+    if constraints is not None:
+        logits_constrain(logits, weight.shape[0], **constraints)
+    return logsoftmax_topk(logits, weight.shape[0], k)
 
 
 def check_sampler(temperature=1.0, top_k=0, top_p=1.0):
@@ -863,10 +917,14 @@ def sample_token(logits, V, ctr, seed, temperature=1.0, top_k=0, top_p=1.0):
 
 
 @torch.no_grad()
-def vocab_sample(x, weight, bias, ctr, seed, temperature=1.0, top_k=0, top_p=1.0):
+def vocab_sample(x, weight, bias, ctr, seed, temperature=1.0, top_k=0, top_p=1.0, constraints=None):
     """one sampled token for every row of x [n, K] under softmax(x W^T + b), weight [V, K] -> (token ids int32 [n], log-probabilities
-    float32 [n]) (`sample_token`).  No autograd: the sampling decode step, on the projection and the [n, Vp] buffer of `vocab_topk`."""
-    return sample_token(_vocab_logits(_rows(x), weight, bias, cache_bias=True)[0], weight.shape[0], ctr, seed, temperature, top_k, top_p)
+    float32 [n]) (`sample_token`).  No autograd: the sampling decode step, on the projection and the [n, Vp] buffer of `vocab_topk`;
+    constraints as there: the draw and its log-probability are those of the constrained logits."""
+    logits = _vocab_logits(_rows(x), weight, bias, cache_bias=True)[0]
+    if constraints is not None:
+        logits_constrain(logits, weight.shape[0], **constraints)
+    return sample_token(logits, weight.shape[0], ctr, seed, temperature, top_k, top_p)
 
 
 DECODE_ATTN_MAX_T = 512    # fcmf_attn_decode's limit on the number of keys (include/fcmf_hip.h)

@@ -21,6 +21,8 @@ the best checkpoint decodes the test set into `iaog_test_predictions_formatted.t
 --decode_strategy sample decodes --num_chains sampled chains per sample instead of a beam (--temperature, --top_k, --top_p,
 --sample_seed; csrc/sample.hip) and keeps the best-scoring one; --length_penalty ranks the final choice of either strategy by
 score / length ** penalty.  The defaults (beam, 0) are the reference's decode.
+--repetition_penalty, --no_repeat_ngram_size, --min_length_decoder and --suppress_tokens constrain the logits of every decode step
+of either strategy on the device (csrc/constrain.hip; they imply the batched step); their defaults (1, 0, 0, none) run no new code.
 Process set-up, the checkpoint code, the extractors and the loop of one epoch are `train_harness.py`'s, shared with
 run_multimodal_fcmf.py; this file keeps the parser, the model and data, the 2 parameter groups and the loss.
 With real data the driver imports the user's `iaog_dataset.IAOGDataset` (host-side producer,
@@ -38,6 +40,7 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 from fcmf_framework import ops  # noqa: E402
+from fcmf_framework.decoding import make_constraints  # noqa: E402
 from fcmf_framework.dp import GradArena, GradReducer  # noqa: E402
 from fcmf_framework.fcmf_pretraining import FCMFSeq2Seq  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
@@ -91,6 +94,12 @@ def build_parser():
     p.add_argument("--sample_seed", default=0, type=int, help="--decode_strategy sample: seed of the counter-based draws")
     p.add_argument("--length_penalty", default=0.0, type=float,
                    help="--do_eval: the final choice among the finished beams / the chains ranks by score / length ** this (0 = the raw score)")
+    p.add_argument("--repetition_penalty", default=1.0, type=float,
+                   help="--do_eval: logits of the tokens a sequence already holds are divided by it (multiplied when negative); > 0, 1 = off")
+    p.add_argument("--no_repeat_ngram_size", default=0, type=int, help="--do_eval: no n-gram of this size occurs twice in a decoded sequence (0 = off)")
+    p.add_argument("--min_length_decoder", default=0, type=int,
+                   help="--do_eval: the separator cannot be decoded before this many tokens (0 = off; at most --max_len_decoder)")
+    p.add_argument("--suppress_tokens", default=[], type=int, nargs="+", metavar="ID", help="--do_eval: token ids that are never decoded")
     p.add_argument("--learning_rate", default=3e-5, type=float)
     p.add_argument("--adam_epsilon", default=1e-8, type=float)
     p.add_argument("--num_train_epochs", default=8.0, type=float)
@@ -153,6 +162,33 @@ def main(argv=None):
             raise ValueError(f"--decode_strategy sample: --sample_seed {args.sample_seed} must be >= 0")
         if args.vocab_size > ops.SAMPLE_MAX_V:
             raise ValueError(f"--decode_strategy sample: --vocab_size {args.vocab_size} is beyond the sampling kernel's {ops.SAMPLE_MAX_V} columns")
+    constraints = None
+    if args.do_eval:
+        try:
+            constraints = make_constraints(repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
+                                           min_length=args.min_length_decoder, suppress_tokens=args.suppress_tokens)
+        except ValueError as e:
+            msg = str(e)                       # the argument's name opens the message: say the flag's instead
+            for name, flag in (("repetition_penalty", "--repetition_penalty"), ("no_repeat_ngram_size", "--no_repeat_ngram_size"),
+                               ("min_length", "--min_length_decoder"), ("suppress_tokens", "--suppress_tokens")):
+                if msg.startswith(name + " "):
+                    msg = flag + msg[len(name):]
+            raise ValueError(msg) from None
+        if args.min_length_decoder > args.max_len_decoder:
+            raise ValueError(f"--min_length_decoder {args.min_length_decoder} is beyond --max_len_decoder {args.max_len_decoder}: no "
+                             f"sequence could end")
+        if constraints is not None:
+            if not 1 <= args.max_len_decoder <= ops.CONSTRAIN_MAX_T:
+                raise ValueError(f"--repetition_penalty / --no_repeat_ngram_size / --min_length_decoder / --suppress_tokens: "
+                                 f"--max_len_decoder {args.max_len_decoder} is outside the constraint kernel's 1 .. {ops.CONSTRAIN_MAX_T} tokens")
+            if args.decode_strategy == "beam" and not 1 <= args.beam_size <= ops.TOPK_MAX:      # constraints imply the batched step
+                raise ValueError(f"--repetition_penalty / --no_repeat_ngram_size / --min_length_decoder / --suppress_tokens: --beam_size "
+                                 f"{args.beam_size} is outside the top-k kernel's 1 .. {ops.TOPK_MAX}")
+            width = args.beam_size if args.decode_strategy == "beam" else 1
+            need = args.max_len_decoder + 1 + len(args.suppress_tokens) + width
+            if 0 < args.vocab_size < need:     # (0: the tokenizer's size, known later; the decode checks it again)
+                raise ValueError(f"--suppress_tokens / --max_len_decoder: --vocab_size {args.vocab_size} cannot keep {width} tokens "
+                                 f"unbanned (needs >= {need})")
     rank, _, world, device, master, logger = init_run(args, "iaog", "pretraining_iaog.log", script="run_pretraining_fcmf.py")
 
     tokenizer = None
@@ -335,7 +371,8 @@ def main(argv=None):
                                                context=args.decode_context, strategy=args.decode_strategy,
                                                sampler=dict(seed=args.sample_seed, temperature=args.temperature, top_k=args.top_k,
                                                             top_p=args.top_p),
-                                               num_chains=args.num_chains, length_penalty=args.length_penalty)
+                                               num_chains=args.num_chains, length_penalty=args.length_penalty,
+                                               constraints=constraints)
             per_aspect, macro = macro_bertscore(preds, refs, aspects, score_fn)
             return per_aspect, macro, results
     elif args.do_eval and master:

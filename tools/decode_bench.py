@@ -12,8 +12,13 @@ with top-p 0.9 only and unfiltered, next to fcmf_logsoftmax_topk at k = beam_siz
 argmax composition, a yardstick only, all alternating on one [n, 64032] bf16 buffer), and in the decode: the prefix beam search
 next to prefix sampling with num_chains = beam_size (decoding.sample_ids_batch) -- the same rows through the same blocks per round,
 another tail kernel -- alternating, with sampling's median over the beam's.
+--constraints runs the constraint legs INSTEAD of the sections above: the kernel alone (fcmf_logits_constrain with repetition penalty
+1.3, no-repeat bigrams and a minimum length on sequences of 20 and of 512 tokens, next to fcmf_logsoftmax_topk, alternating on one
+[n, 64032] bf16 buffer), and the prefix beam decode with constraints off next to the same decode with no_repeat_ngram_size=2,
+repetition_penalty=1.3, min_length=5, alternating: constrained beams run longer by design, so the rounds run (decode_step_prefix
+calls) and the time per round are reported beside the time per batch.
 Usage (GPU box, repo root):  python tools/decode_bench.py [--samples 16 64] [--beam_size 2] [--max_len_decoder 20] [--only_prefix]
-                                                          [--strategy sample]
+                                                          [--strategy sample] [--constraints]
 Prints one JSON line.  Decode: wall time per eval batch between device synchronisations, median of 5 (min, max beside it), both
 paths warmed up once per batch size and alternating, the number of decoder calls of each path, and whether the two paths decoded
 the same token sequences.  Kernel: median microseconds of 9 windows of 50 calls between device events, alternating."""
@@ -42,6 +47,7 @@ p.add_argument("--seq_len", type=int, default=64)
 p.add_argument("--num_rois", type=int, default=4)
 p.add_argument("--only_prefix", action="store_true")
 p.add_argument("--strategy", default="beam", choices=("beam", "sample"))
+p.add_argument("--constraints", action="store_true")
 args = p.parse_args()
 
 assert torch.cuda.is_available(), "decode_bench.py measures on the MI355X: no GPU, no number"
@@ -177,6 +183,45 @@ for B in (args.samples if sampling else []):
     res["sample_decode"].append({"samples_per_batch": B, **st, "mean_len": {c: sum(map(len, v)) / B for c, v in ids.items()},
                                  "sample_over_beam": round(st["sample_prefix"]["median_ms"] / st["beam_prefix"]["median_ms"], 3)})
 if sampling:
+    print(json.dumps(res))
+    sys.exit(0)
+
+if args.constraints:
+    res["constrain_kernel"], res["constrain_decode"] = [], []
+    CONS = dict(no_repeat_ngram_size=2, repetition_penalty=1.3, min_length=5)
+    for n in sorted({B * args.beam_size for B in args.samples}):
+        x = (torch.randn(n, Vp, generator=torch.Generator().manual_seed(n)) * 3).to(dev).bfloat16()
+        y = x.clone()                                     # the constraint legs edit in place: their own buffer
+        hist = {L: torch.randint(0, V, (n, L), generator=torch.Generator().manual_seed(L)).to(dev) for L in (20, 512)}
+        legs = {f"constrain_L{L}": (lambda L=L: ops.logits_constrain(y, V, hist[L], repetition_penalty=1.3, no_repeat_ngram_size=2,
+                                                                     min_length=L + 1, sep_id=SEP)) for L in (20, 512)}
+        legs["topk"] = lambda: ops.logsoftmax_topk(x, V, args.beam_size)
+        for fn in legs.values():
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        t = {k: [] for k in legs}
+        for _ in range(9):
+            for k, fn in legs.items():
+                t[k].append(window(fn))
+        res["constrain_kernel"].append({"rows": n, "ld": Vp, **{k: med(v) for k, v in t.items()}})
+    rounds = {"n": 0}
+    dec.decode_step_prefix = (lambda *a, _fn=dec.decode_step_prefix, **k: (rounds.__setitem__("n", rounds["n"] + 1), _fn(*a, **k))[1])
+    for B in args.samples:
+        a = batch_args(B)
+        fns = {c: (lambda a, k=k: [r[0] for r in decoding.beam_search_ids_batch(model, 0, SEP, *a, beam_size=args.beam_size,
+                                                                                 max_len=args.max_len_decoder, context="prefix", constraints=k)])
+               for c, k in (("off", None), ("on", CONS))}
+        ids = {c: fn(a) for c, fn in fns.items()}         # warm-up of every shape of both
+        times, nr = {c: [] for c in fns}, {}
+        for _ in range(5):
+            for c, fn in fns.items():
+                rounds["n"] = 0
+                times[c].append(timed(fn, a)[0])
+                nr[c] = rounds["n"]
+        st = {c: dict(stats(t), rounds=nr[c], ms_per_round=round(statistics.median(t) * 1e3 / nr[c], 3)) for c, t in times.items()}
+        res["constrain_decode"].append({"samples_per_batch": B, **st, "mean_len": {c: sum(map(len, v)) / B for c, v in ids.items()},
+                                        "on_over_off_per_round": round(st["on"]["ms_per_round"] / st["off"]["ms_per_round"], 3)})
     print(json.dumps(res))
     sys.exit(0)
 
