@@ -400,6 +400,62 @@ int fcmf_attn_decode(const void* q, int64_t q_sr, void* keys, int64_t k_sp, int6
                      int n, int heads, int d, int T, int live, float scale, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Beam bookkeeping of an IAOG decode on the device: round t of the beam search (decoding._advance and the rules of
+ * decoding.beam_rounds around it) for B samples in one launch, on state that stays on the device from the start token to the
+ * final hypotheses.  R = B * W rows; slot r = b*W + j is beam j of sample b, W = the beam size.
+ * State (all on the device, allocated and initialised by the caller: see decoding.beam_rounds_device):
+ *   seq    int64 [max_len + 1, R], position-major: seq[p*R + r] is token p of slot r.  seq + t*R is the contiguous token vector of
+ *          round t; (seq, row stride 1, position stride R) is the [R, t + 1] history fcmf_logits_constrain takes.  Initially
+ *          seq[0, :] = the start token in EVERY slot;
+ *   anc    int64 [max_len, R], position-major: anc[p*R + r] is the slot that ran position p of slot r's sequence in round p -- the
+ *          [R, t] ancestor table of fcmf_attn_decode (idx_sr = 1, idx_sp = R, idx_n = R) over a key cache of R rows;
+ *   score  float64 [R], initially 0;
+ *   state  int32 [R]: 0 empty, 1 live, 2 ended (the last token is sep_id and the slot is still among the beams).  Initially slot
+ *          b*W is live and the other W - 1 slots of the sample are empty;
+ *   fin_*  the finished list of sample b, entries e = 0 .. fin_count[b] - 1 in the host's append order: fin_score float64
+ *          [B, cap], fin_len int32 [B, cap] (tokens, the start token included), fin_seq int64 [B, cap, max_len + 1] (the first
+ *          fin_len entries), fin_count int32 [B] initially 0.  cap = W * (max_len + 1): a round appends at most the W ended beams
+ *          of its input, the round that finishes the sample at most W more, and there are at most max_len rounds -- so
+ *          beam_rounds' `final` never holds more than W * max_len + W entries;
+ *   done   int32 [B], initially 0.
+ * Inputs: logp float32 / ids int32 [R, >= W], row r at logp + r*ld / ids + r*ld (elements): fcmf_logsoftmax_topk's outputs of
+ * the step run on seq[t] (k >= W).  Per sample b with done[b] == 0, in this order:
+ *   1. every ended beam is appended to the finished list, in beam order, with its score and length t + 1, and gives no
+ *      candidates;
+ *   2. the candidates are, for every live beam j ascending and k = 0 .. W-1 ascending, (score[j] + (double)logp[j, k], ids[j, k]);
+ *   3. no candidates: done[b] = 1, score / state / history of the slots stay as they are;
+ *   4. the W best candidates by score descending, STABLE: among equal scores the earlier candidate wins (a live beam gives W
+ *      candidates, so there are always W).  -inf compares as doubles do; NaN is undefined, as in fcmf_logsoftmax_topk;
+ *   5. candidate i of that order becomes slot b*W + i: seq[0 .. t] and anc[0 .. t-1] of its parent slot, seq[t + 1] = its id,
+ *      anc[t] = the parent's slot, score = the candidate's, state = ended when id == sep_id, else live;
+ *   6. if all W new beams are ended they are appended to the finished list in slot order with length t + 2, and done[b] = 1.
+ * The sum is one float64 addition per round, so scores are bit-equal to the host loop's Python-float sums.
+ * Rows that do not advance -- every slot of a done sample, and of a sample that became done by rule 3 -- get seq[t + 1] = seq[t]
+ * and anc[t] = their own slot; an ended beam keeps sep_id as its token and is replaced in the next round: the step can run all
+ * R rows every round on valid tokens and ancestor indices.  Their step outputs are never read.
+ * Children are written into the slots their parents are read from, and parents may permute or repeat: one wave owns a sample,
+ * a lane owns whole positions, loads the W parent entries of a position into registers and only then stores the W children.
+ * No atomics; one workgroup owns a sample's finished list and done[b]; fixed order: two launches give the same bits.
+ * Limits: 1 <= W <= 8 (the W*W candidates are one per lane of a wave), 1 <= max_len and max_len + 1 <= 512 --
+ * FCMF_ERR_UNSUPPORTED otherwise; a NULL pointer, a negative size, ld < W or t outside [0, max_len) -- FCMF_ERR_ARG; B == 0
+ * succeeds without a launch.  The checks are made in this order: negative sizes, limits, t and ld. */
+int fcmf_beam_advance(const float* logp, const int32_t* ids, int64_t ld, int B, int W, int t, int max_len, int sep_id,
+                      int64_t* seq, int64_t* anc, double* score, int32_t* state, double* fin_score, int64_t* fin_seq,
+                      int32_t* fin_len, int32_t* fin_count, int32_t* done, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The sampling counterpart (decoding.sample_rounds): round t of B samples x W independent chains, slot r = b*W + c.  seq, anc,
+ * score, state and done as in fcmf_beam_advance, every slot live initially; len int32 [R], initially 1: the tokens of the chain,
+ * the start token included.  logp float32 [R] and ids int32 [R]: fcmf_sample_token's outputs of the step run on seq[t].
+ *   live chain r:  score[r] += (double)logp[r]; seq[t + 1, r] = ids[r]; anc[t, r] = r; len[r] = t + 2; state = ended when
+ *                  ids[r] == sep_id.  Chains never branch;
+ *   ended chain r: seq[t + 1, r] = seq[t, r], anc[t, r] = r (a valid row for the step, its outputs unread); score, len stay;
+ *   done[b] = 1 once no chain of sample b is live.
+ * No atomics, fixed order.  Limits and error codes as for fcmf_beam_advance (1 <= W <= 8, max_len + 1 <= 512). */
+int fcmf_chain_advance(const float* logp, const int32_t* ids, int B, int W, int t, int max_len, int sep_id, int64_t* seq,
+                       int64_t* anc, double* score, int32_t* state, int32_t* len, int32_t* done, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * y = LayerNorm(dropout(x) + res) * gamma + beta   (eps inside the sqrt, biased variance)
  * Replaces BertSelfOutput/BertOutput/AddNorm + FCMFLayerNorm (mm_modeling.py:158-171,
  * 276-280,324-328,566-573) and HF nn.LayerNorm(eps=1e-5).

@@ -77,6 +77,8 @@ SIGNATURES = {
     "fcmf_sample_token": [_vp, _i64, _i, _i, _f, _i, _f, _u64, _vp, _vp, _vp, _i, _vp],
     "fcmf_logits_constrain": [_vp, _i64, _i, _i, _vp, _i64, _i64, _i, _f, _i, _i, _i, _vp, _i, _i, _vp],
     "fcmf_attn_decode": [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i, _vp, _i64, _i, _i, _i, _i, _i, _f, _i, _vp],
+    "fcmf_beam_advance": [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "fcmf_chain_advance": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fcmf_add_ln_fwd": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _u64, _i, _vp],
     "fcmf_add_ln_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _u64, _i, _vp],
     "fcmf_add_ln_fwd_fp8": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _u64, _i, _vp, _vp, _vp],

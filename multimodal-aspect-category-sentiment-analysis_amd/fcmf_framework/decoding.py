@@ -52,6 +52,21 @@ puts it into the round's one upload tensor and the kernel takes the [n, L] view 
 (sample, last token) memo and runs every live beam as a row of its round, as sampling does.  Still one upload and one host read per
 round; the suppressed ids are uploaded once per call.  None, or all settings off, takes the paths above unchanged: the step
 callables receive exactly the same tuples and no new code runs.
+
+loop="device" (the batched entry points and, through them, `beam_search_ids` / `beam_search`; default "host": everything above,
+untouched): the search itself moves to the device.  The state -- sequences and ancestor table position-major, float64 scores, slot
+states, per sample a finished list and a done flag -- is allocated once per call in fixed shape, R = samples * beams (or chains)
+slots; a round runs the step on ALL R rows (tokens = seq[t], the ancestor table and the rows' own sequences as strided views of the
+state: the kernels already take them) and then ONE launch of csrc/beam.hip, which applies `_advance` and the finishing rules of
+`beam_rounds` (or the chain rules of `sample_rounds`) in place.  Nothing is uploaded and nothing is read per round; every
+`poll_every` rounds the B done flags are read so that a batch whose samples have all finished stops early (0 = never), and the
+result does not depend on that.  A fixed number of reads at the end brings the state back and `rebuild_beams` / `rebuild_chains`
+apply the final rules (`fin = final or beams`, `_best`) on the host.  The price is that rows of finished samples, ended beams and
+the empty slots of round 0 still run (their outputs are ignored), and that context "last" has no (sample, token) memo: for
+unconstrained "last" the memoised host loop stays the cheaper choice.  Beam size / chain count <= 8 and max_len <= 511 (ValueError
+before any launch otherwise).  Scores are float64 sums in the host's order, ties break as the host's stable sort does: on equal step
+outputs the results are equal; the step's GEMMs see other row counts than the host loop's, so on a real model scores may differ in
+the last bits.
 """
 import torch
 import torch.nn.functional as F
@@ -59,7 +74,8 @@ import torch.nn.functional as F
 from . import ops
 
 __all__ = ["beam_search", "beam_search_ids", "beam_search_batch", "beam_search_ids_batch", "beam_rounds",
-           "sample_rounds", "sample_ids_batch", "sample_batch", "make_sampler", "make_constraints"]
+           "sample_rounds", "sample_ids_batch", "sample_batch", "make_sampler", "make_constraints", "beam_rounds_device",
+           "sample_rounds_device", "rebuild_beams", "rebuild_chains"]
 
 CONTEXTS = ("last", "prefix")
 
@@ -79,19 +95,20 @@ def _best(fin, length_penalty=0.0):
 
 @torch.no_grad()
 def beam_search_ids(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                    beam_size=3, max_len=20, context="last", length_penalty=0.0, constraints=None):
+                    beam_size=3, max_len=20, context="last", length_penalty=0.0, constraints=None, loop="host", poll_every=4):
     """-> (token ids of the best sequence incl. the start token, its log-likelihood, [(score, ids)] of the finished beams)
-    context="prefix", or constraints on: the batched path with this one sample (see the module header)"""
+    context="prefix", constraints on, or loop="device": the batched path with this one sample (see the module header)"""
     _check_context(context)
+    _check_loop(loop, beam_size, max_len)
     constraints = make_constraints(constraints)
     model.eval()
     if enc_ids.dim() == 1:                                    # one sample without a batch axis (:395-402)
         enc_ids, enc_mask, enc_type, add_mask = (t.unsqueeze(0) for t in (enc_ids, enc_mask, enc_type, add_mask))
         vis_embeds, roi_embeds, roi_coors = (t.unsqueeze(0) for t in (vis_embeds, roi_embeds, roi_coors))
-    if context == "prefix" or constraints is not None:
+    if context == "prefix" or constraints is not None or loop == "device":
         return beam_search_ids_batch(model, start_id, sep_id, enc_ids[:1], enc_mask[:1], enc_type[:1], add_mask[:1], vis_embeds[:1],
                                      roi_embeds[:1], roi_coors[:1], beam_size=beam_size, max_len=max_len, context=context,
-                                     length_penalty=length_penalty, constraints=constraints)[0]
+                                     length_penalty=length_penalty, constraints=constraints, **_loop_kw(loop, poll_every))[0]
     enc = model.encoder(enc_ids, vis_embeds, roi_embeds, roi_coors, enc_type, enc_mask, add_mask)
     enc = enc[0] if isinstance(enc, tuple) else enc
     dec = model.decoder
@@ -133,12 +150,13 @@ def beam_search_ids(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_ma
 
 
 def beam_search(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                beam_size=3, num_preds=1, max_len=20, device='cuda', context="last", length_penalty=0.0, constraints=None):
+                beam_size=3, num_preds=1, max_len=20, device='cuda', context="last", length_penalty=0.0, constraints=None,
+                loop="host", poll_every=4):
     """the reference's signature and result: [decoded text of the best sequence] (fcmf_pretraining.py:383-517)"""
     start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
     ids, _, _ = beam_search_ids(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds,
                                 roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len, context=context,
-                                length_penalty=length_penalty, constraints=constraints)
+                                length_penalty=length_penalty, constraints=constraints, **_loop_kw(loop, poll_every))
     return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip()]
 
 
@@ -276,14 +294,133 @@ def sample_rounds(step_many, num_samples, start_id, sep_id, num_chains=1, max_le
     return out
 
 
+LOOPS = ("host", "device")
+
+
+def _check_loop(loop, width, max_len, what="beam_size"):
+    if loop not in LOOPS:
+        raise ValueError(f"loop must be one of {LOOPS}, got {loop!r}")
+    if loop == "device":
+        ops.check_advance(width, max_len, what)
+
+
+def _loop_kw(loop, poll_every):
+    """the keywords a wrapper hands on: none for the host loop, so that its callee is called with exactly the arguments it always got"""
+    return {} if loop == "host" else dict(loop=loop, poll_every=poll_every)
+
+
+def _run_device_rounds(st, round_fn, poll_every):
+    """rounds 0 .. max_len-1 of a device loop; every `poll_every` rounds (0 = never) ONE read of `done` ([B] int32) ends the loop
+    once every sample is done -- the rounds it saves change no slot and no finished list.  -> the rounds run"""
+    if isinstance(poll_every, bool) or not isinstance(poll_every, int) or poll_every < 0:
+        raise ValueError(f"poll_every must be an integer >= 0 (0 = never poll), got {poll_every}")
+    for t in range(st["max_len"]):
+        if poll_every and t and t % poll_every == 0 and bool(st["done"].all().item()):
+            return t
+        round_fn(t)
+    return st["max_len"]
+
+
+def rebuild_beams(score, state, seq, fin_count, fin_score, fin_len, fin_seq, beam_size, length_penalty=0.0):
+    """`beam_rounds`' result from the final device state of `beam_rounds_device`, read back as host lists (`.tolist()` of the
+    tensors of ops.advance_state: score / state [R], seq [max_len + 1][R], fin_count [B], fin_score / fin_len [B][>= count],
+    fin_seq [B][>= count][max_len + 1]), by the host loop's rules:
+      fin = final if final else beams -- the finished list in append order; a sample that finished nothing within max_len returns
+      its beams in slot order, all max_len + 1 tokens long.  Beams that ended in the last round are in `fin` only in that second case:
+      when `final` is non-empty they never reached it (slot state 2, not appended), as in the host loop;
+      best = `_best` (first among equals, length penalty on request).
+    -> [(best_seq, best_score, fin)], one entry per sample"""
+    W = int(beam_size)
+    out = []
+    for b in range(len(fin_count)):
+        n = fin_count[b]
+        if n:
+            fin = [(fin_score[b][e], list(fin_seq[b][e][:fin_len[b][e]])) for e in range(n)]
+        else:
+            # nothing finished: the sample ran every round, so every slot is filled (live or ended in the last round)
+            fin = [(score[r], [row[r] for row in seq]) for r in range(b * W, b * W + W) if state[r] != ops.SLOT_EMPTY]
+        best_score, best_seq = _best(fin, length_penalty)
+        out.append((best_seq, best_score, fin))
+    return out
+
+
+def rebuild_chains(score, length, seq, num_chains, length_penalty=0.0):
+    """`sample_rounds`' result from the final device state of `sample_rounds_device` as host lists (score / length [R], seq
+    [max_len + 1][R]): per sample all chains in chain order, each its first `length` tokens, and `_best` among them"""
+    W = int(num_chains)
+    out = []
+    for b in range(len(score) // W):
+        chains = [(score[r], [seq[p][r] for p in range(length[r])]) for r in range(b * W, b * W + W)]
+        best_score, best_seq = _best(chains, length_penalty)
+        out.append((best_seq, best_score, chains))
+    return out
+
+
+@torch.no_grad()
+def beam_rounds_device(step_rows, num_samples, start_id, sep_id, beam_size=3, max_len=20, context="last", length_penalty=0.0,
+                       constraints=None, device=None, poll_every=4, return_state=False):
+    """`beam_rounds` with the search state on the device from the start token to the final hypotheses (ops.advance_state,
+    include/fcmf_hip.h fcmf_beam_advance): R = num_samples * beam_size fixed slots, slot b * beam_size + j beam j of sample b.
+    Round t calls step_rows(tokens, t, anc, hist) -> (log-probabilities float32 [R, >= beam_size], ids int32 alike) on ALL R rows
+    -- tokens = seq[t] (int64 [R], contiguous), anc the strided [R, t] ancestor view (slot indices: the key cache has R rows),
+    hist the strided [R, t + 1] view of every slot's own sequence; all device tensors -- and then ONE launch of the advance
+    kernel.  Rows of done samples, empty slots and ended beams run on valid tokens and their outputs are ignored.  Nothing is
+    uploaded and nothing is read per round, except the poll: every `poll_every` rounds `done` ([B] int32) is read and the loop ends
+    when all are set (0: never, run max_len rounds); the result does not depend on it.  `context` and `constraints` are checked and
+    otherwise left to the step.  At the end a fixed number of reads, whatever max_len, bring back the slots and the finished lists,
+    and `rebuild_beams` applies the host loop's final rules.  -> `beam_rounds`' result; with return_state also the state dict"""
+    _check_context(context)
+    st = ops.advance_state(num_samples, beam_size, max_len, start_id, device)
+    seq, anc = st["seq"], st["anc"]
+
+    def one_round(t):
+        logp, ids = step_rows(seq[t], t, anc[:t].t(), seq[:t + 1].t())
+        ops.beam_advance(logp, ids, st, t, sep_id)
+
+    _run_device_rounds(st, one_round, poll_every)
+    counts = st["fin_count"].cpu()
+    n = max(int(counts.max()) if counts.numel() else 0, 1)
+    res = rebuild_beams(st["score"].cpu().tolist(), st["state"].cpu().tolist(), seq.cpu().tolist(), counts.tolist(),
+                        st["fin_score"][:, :n].cpu().tolist(), st["fin_len"][:, :n].cpu().tolist(),
+                        st["fin_seq"][:, :n].cpu().tolist(), beam_size, length_penalty)
+    return (res, st) if return_state else res
+
+
+@torch.no_grad()
+def sample_rounds_device(step_rows, num_samples, start_id, sep_id, num_chains=1, max_len=20, context="last", sample_offset=0,
+                         length_penalty=0.0, constraints=None, device=None, poll_every=4, return_state=False):
+    """`sample_rounds` with the chains on the device (fcmf_chain_advance), as `beam_rounds_device`: R = num_samples * num_chains
+    slots, every round all R rows.  step_rows(tokens, t, anc, hist, ctr) -> (log-probability float32, id int32) of [R] or [R, 1]:
+    ctr int64 [R] is row t of the counter table ((sample_offset + b) * num_chains + c) * max_len + t, formed ONCE per call as
+    [max_len, R].  A chain that has ended keeps its score and length; its row still runs and is ignored."""
+    _check_context(context)
+    st = ops.advance_state(num_samples, num_chains, max_len, start_id, device, chains=True)
+    seq, anc = st["seq"], st["anc"]
+    R = st["B"] * st["W"]
+    ctr = ((int(sample_offset) * num_chains + torch.arange(R, dtype=torch.int64)).view(1, R) * max_len +
+           torch.arange(max_len, dtype=torch.int64).view(max_len, 1)).to(device)      # the ONE upload of the call
+
+    def one_round(t):
+        logp, ids = step_rows(seq[t], t, anc[:t].t(), seq[:t + 1].t(), ctr[t])
+        ops.chain_advance(logp, ids, st, t, sep_id)
+
+    _run_device_rounds(st, one_round, poll_every)
+    res = rebuild_chains(st["score"].cpu().tolist(), st["len"].cpu().tolist(), seq.cpu().tolist(), num_chains, length_penalty)
+    return (res, st) if return_state else res
+
+
 @torch.no_grad()
 def beam_search_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                          beam_size=3, max_len=20, context="last", length_penalty=0.0, constraints=None):
+                          beam_size=3, max_len=20, context="last", length_penalty=0.0, constraints=None, loop="host", poll_every=4):
     """`beam_search_ids` of every sample of a batch ([B, ...] tensors), one decoder call per beam round for all of them: the encoder
     and `project_encoder` run once for the batch.  context="prefix": every step sees its beam's whole prefix (module header); the
     key cache is allocated here, once per batch.  constraints: `make_constraints`' settings (module header): the rows' sequences
-    ride in the round's one upload.  -> [(ids, score, final)], one entry per sample"""
+    ride in the round's one upload.  loop="device": the search state lives on the device (`beam_rounds_device`; beam_size <= 8),
+    every round runs all B * beam_size rows and nothing is uploaded or read per round but the poll every `poll_every` rounds; in
+    context "last" that is `decode_step` on every row with no memo, as the constrained path -- for unconstrained "last" the memoised
+    host loop remains the cheaper choice.  -> [(ids, score, final)], one entry per sample"""
     _check_context(context)
+    _check_loop(loop, beam_size, max_len)
     constraints = make_constraints(constraints)
     _check_room(constraints, model.decoder.dense.weight.shape[0], max_len, beam_size)
     model.eval()
@@ -293,6 +430,20 @@ def beam_search_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, 
     keys = dec.project_encoder(enc)
     device = enc.device
     cons = _device_constraints(constraints, sep_id, device)   # the suppressed ids: ONE upload per call
+
+    if loop == "device":
+        rows = enc_ids.shape[0] * beam_size
+        sample_idx = torch.arange(rows, device=device) // beam_size          # constant over the rounds, formed on the device
+        cache = dec.init_cache(max_len, rows, device) if context == "prefix" else None
+
+        def step_dev(tokens, t, anc, hist):
+            own = None if cons is None else dict(cons, hist=hist)
+            if cache is None:
+                return dec.decode_step(tokens, sample_idx, enc, keys, beam_size, constraints=own)
+            return dec.decode_step_prefix(tokens, sample_idx, anc, t, cache, enc, keys, beam_size, constraints=own)
+
+        return beam_rounds_device(step_dev, enc_ids.shape[0], start_id, sep_id, beam_size, max_len, context, length_penalty,
+                                  constraints, device, poll_every)
 
     def read(logp, ids):
         both = torch.cat((logp, ids.view(torch.float32)), dim=1).cpu()      # ONE host read: the ids ride along as their bits
@@ -338,12 +489,12 @@ def beam_search_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, 
 
 
 def beam_search_batch(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                      beam_size=3, max_len=20, context="last", length_penalty=0.0, constraints=None):
+                      beam_size=3, max_len=20, context="last", length_penalty=0.0, constraints=None, loop="host", poll_every=4):
     """-> [decoded text of the best sequence], one per sample of the batch (what `beam_search` returns per sample, [0])"""
     start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
     res = beam_search_ids_batch(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds,
                                 roi_embeds, roi_coors, beam_size=beam_size, max_len=max_len, context=context,
-                                length_penalty=length_penalty, constraints=constraints)
+                                length_penalty=length_penalty, constraints=constraints, **_loop_kw(loop, poll_every))
     return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip() for ids, _, _ in res]
 
 
@@ -401,14 +552,18 @@ def make_sampler(sampler=None):
 
 @torch.no_grad()
 def sample_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                     num_chains=1, max_len=20, context="last", sampler=None, sample_offset=0, length_penalty=0.0, constraints=None):
+                     num_chains=1, max_len=20, context="last", sampler=None, sample_offset=0, length_penalty=0.0, constraints=None,
+                     loop="host", poll_every=4):
     """`sample_rounds` of every sample of a batch ([B, ...] tensors) over the batched decode steps: the encoder and `project_encoder`
     run once for the batch, every round is ONE upload (samples, tokens, counters and, in prefix mode, the ancestor table), one decoder
     call ending in csrc/sample.hip and ONE host read.  sampler: `make_sampler`'s settings; sample_offset: the running index of the
-    batch's first sample in the eval set; constraints: `make_constraints`' settings (module header).  -> [(ids of the best chain, its score, [(score, ids)] of all chains)], one entry per sample"""
+    batch's first sample in the eval set; constraints: `make_constraints`' settings (module header).  loop="device": the chains
+    live on the device (`sample_rounds_device`; num_chains <= 8): all B * num_chains rows run every round, the counters are uploaded
+    once per call, nothing is read per round but the poll.  -> [(ids of the best chain, its score, [(score, ids)] of all chains)], one entry per sample"""
     _check_context(context)
     if num_chains < 1:
         raise ValueError(f"num_chains must be >= 1, got {num_chains}")
+    _check_loop(loop, num_chains, max_len, "num_chains")
     cfg = make_sampler(sampler)
     constraints = make_constraints(constraints)
     _check_room(constraints, model.decoder.dense.weight.shape[0], max_len, 1)
@@ -419,6 +574,20 @@ def sample_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_m
     keys = dec.project_encoder(enc)
     device = enc.device
     cons = _device_constraints(constraints, sep_id, device)   # the suppressed ids: ONE upload per call
+
+    if loop == "device":
+        rows = enc_ids.shape[0] * num_chains
+        sample_idx = torch.arange(rows, device=device) // num_chains         # constant over the rounds, formed on the device
+        cache = dec.init_cache(max_len, rows, device) if context == "prefix" else None
+
+        def step_dev(tokens, t, anc, hist, ctr):
+            own = None if cons is None else dict(cons, hist=hist)
+            if cache is None:
+                return dec.decode_step(tokens, sample_idx, enc, keys, 1, sampler=dict(cfg, ctr=ctr), constraints=own)
+            return dec.decode_step_prefix(tokens, sample_idx, anc, t, cache, enc, keys, 1, sampler=dict(cfg, ctr=ctr), constraints=own)
+
+        return sample_rounds_device(step_dev, enc_ids.shape[0], start_id, sep_id, num_chains, max_len, context, sample_offset,
+                                    length_penalty, constraints, device, poll_every)
 
     def read(logp, ids):
         both = torch.cat((logp, ids.view(torch.float32)), dim=1).cpu()      # ONE host read: the ids ride along as their bits
@@ -458,10 +627,12 @@ def sample_ids_batch(model, start_id, sep_id, enc_ids, enc_mask, enc_type, add_m
 
 
 def sample_batch(model, tokenizer, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds, roi_coors,
-                 num_chains=1, max_len=20, context="last", sampler=None, sample_offset=0, length_penalty=0.0, constraints=None):
+                 num_chains=1, max_len=20, context="last", sampler=None, sample_offset=0, length_penalty=0.0, constraints=None,
+                 loop="host", poll_every=4):
     """-> [decoded text of the best chain], one per sample of the batch: `beam_search_batch`'s result from `sample_ids_batch`"""
     start = tokenizer.bos_token_id if tokenizer.bos_token_id is not None else tokenizer.cls_token_id
     res = sample_ids_batch(model, start, tokenizer.sep_token_id, enc_ids, enc_mask, enc_type, add_mask, vis_embeds, roi_embeds,
                            roi_coors, num_chains=num_chains, max_len=max_len, context=context, sampler=sampler,
-                           sample_offset=sample_offset, length_penalty=length_penalty, constraints=constraints)
+                           sample_offset=sample_offset, length_penalty=length_penalty, constraints=constraints,
+                           **_loop_kw(loop, poll_every))
     return [tokenizer.decode(torch.tensor(ids), skip_special_tokens=True).strip() for ids, _, _ in res]

@@ -961,6 +961,85 @@ def decode_attention(q, keys, idx, heads, T, live, pos_dim=0, k_new=None, append
     return out
 
 
+ADVANCE_MAX_W = 8          # fcmf_beam_advance / fcmf_chain_advance: beams or chains per sample (include/fcmf_hip.h)
+ADVANCE_MAX_T = 512        # ... and max_len + 1, the limit of the constraint and decode-attention kernels
+SLOT_EMPTY, SLOT_LIVE, SLOT_ENDED = 0, 1, 2
+
+
+def check_advance(width, max_len, what="beam_size"):
+    """the limits of fcmf_beam_advance / fcmf_chain_advance (include/fcmf_hip.h), raised as a ValueError that names the argument"""
+    if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= ADVANCE_MAX_W:
+        raise ValueError(f"{what} must be an integer in 1 .. {ADVANCE_MAX_W} for the device loop, got {width}")
+    if isinstance(max_len, bool) or not isinstance(max_len, int) or not 1 <= max_len < ADVANCE_MAX_T:
+        raise ValueError(f"max_len must be an integer in 1 .. {ADVANCE_MAX_T - 1} for the device loop, got {max_len}")
+
+
+def advance_state(num_samples, width, max_len, start_id, device, chains=False):
+    """the device-resident state of a decode call as fcmf_beam_advance / fcmf_chain_advance define it (include/fcmf_hip.h), a dict:
+    seq int64 [max_len + 1, R] and anc int64 [max_len, R] (position-major), score float64 [R], state int32 [R], done int32 [B] and
+    -- beams -- the finished lists fin_score / fin_len / fin_seq / fin_count, or -- chains -- len int32 [R].  R = num_samples * width.
+    Beams start with slot 0 of every sample live and the rest empty, chains all live; every slot holds the start token.  No
+    host-to-device copy: fills only."""
+    check_advance(width, max_len, "num_chains" if chains else "beam_size")
+    B, W, S = int(num_samples), int(width), int(max_len) + 1
+    R = B * W
+    st = dict(B=B, W=W, max_len=int(max_len),
+              seq=torch.full((S, R), int(start_id), dtype=torch.int64, device=device),
+              anc=torch.zeros((S - 1, R), dtype=torch.int64, device=device),
+              score=torch.zeros((R,), dtype=torch.float64, device=device),
+              done=torch.zeros((B,), dtype=torch.int32, device=device))
+    if chains:
+        st["state"] = torch.full((R,), SLOT_LIVE, dtype=torch.int32, device=device)
+        st["len"] = torch.ones((R,), dtype=torch.int32, device=device)
+    else:
+        st["state"] = torch.zeros((B, W), dtype=torch.int32, device=device)
+        st["state"][:, 0] = SLOT_LIVE
+        st["state"] = st["state"].view(R)
+        cap = W * S
+        st["fin_score"] = torch.zeros((B, cap), dtype=torch.float64, device=device)
+        st["fin_len"] = torch.zeros((B, cap), dtype=torch.int32, device=device)
+        st["fin_seq"] = torch.zeros((B, cap, S), dtype=torch.int64, device=device)
+        st["fin_count"] = torch.zeros((B,), dtype=torch.int32, device=device)
+    return st
+
+
+def _advance_inputs(name, logp, ids, st, t, shape):
+    H.require_cuda(logp, ids, st["seq"])
+    if logp.dtype != torch.float32 or ids.dtype != torch.int32 or tuple(logp.shape) != shape or tuple(ids.shape) != shape:
+        raise H.HipLibraryError(f"{name}: want float32 log-probabilities and int32 ids of shape {shape}, got {logp.dtype} "
+                                f"{tuple(logp.shape)} / {ids.dtype} {tuple(ids.shape)}")
+    if not 0 <= t < st["max_len"]:
+        raise H.HipLibraryError(f"{name}: round {t} is outside a state of {st['max_len']} rounds")
+
+
+@torch.no_grad()
+def beam_advance(logp, ids, st, t, sep_id):
+    """round t of the beam search on the device, in place on `st` (= advance_state(...)): logp float32 / ids int32 [R, k >= W], the
+    step's `logsoftmax_topk` outputs on st["seq"][t].  `decoding._advance` and the finishing rules of `decoding.beam_rounds` for
+    every sample that is not done, float64 scores, stable ties.  One launch, no host read (fcmf_beam_advance, include/fcmf_hip.h)."""
+    B, W = st["B"], st["W"]
+    if logp.dim() != 2 or logp.shape[1] < W:
+        raise H.HipLibraryError(f"beam_advance: want [{B * W}, >= {W}] step outputs, got {tuple(logp.shape)}")
+    _advance_inputs("beam_advance", logp, ids, st, t, (B * W, logp.shape[1]))
+    logp, ids = logp.contiguous(), ids.contiguous()
+    H.check(H.lib().fcmf_beam_advance(H.ptr(logp), H.ptr(ids), logp.shape[1], B, W, int(t), st["max_len"], int(sep_id),
+                                      H.ptr(st["seq"]), H.ptr(st["anc"]), H.ptr(st["score"]), H.ptr(st["state"]),
+                                      H.ptr(st["fin_score"]), H.ptr(st["fin_seq"]), H.ptr(st["fin_len"]), H.ptr(st["fin_count"]),
+                                      H.ptr(st["done"]), H.stream()), "fcmf_beam_advance")
+
+
+@torch.no_grad()
+def chain_advance(logp, ids, st, t, sep_id):
+    """round t of the sampling chains on the device, in place on `st` (= advance_state(..., chains=True)): logp float32 / ids int32
+    [R] (or [R, 1]), the step's `sample_token` outputs on st["seq"][t].  One launch, no host read (fcmf_chain_advance)."""
+    B, W = st["B"], st["W"]
+    logp, ids = logp.reshape(-1), ids.reshape(-1)
+    _advance_inputs("chain_advance", logp, ids, st, t, (B * W,))
+    H.check(H.lib().fcmf_chain_advance(H.ptr(logp), H.ptr(ids), B, W, int(t), st["max_len"], int(sep_id), H.ptr(st["seq"]),
+                                       H.ptr(st["anc"]), H.ptr(st["score"]), H.ptr(st["state"]), H.ptr(st["len"]), H.ptr(st["done"]),
+                                       H.stream()), "fcmf_chain_advance")
+
+
 class FFNFn(torch.autograd.Function):
     """y = gelu_erf(x W1^T + b1) W2^T + b2   (BertIntermediate + BertOutput.dense,
     mm_modeling.py:305-314,320; decoder PositionWiseFFN :558-565).  GELU is the epilogue of the

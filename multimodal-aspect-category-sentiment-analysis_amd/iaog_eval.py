@@ -22,7 +22,7 @@ def decode_label(tokenizer, labels):
 
 @torch.no_grad()
 def generate(model, tokenizer, batches, features, beam_size, max_len, aspects=(), batched=False, context="last",
-             strategy="beam", sampler=None, num_chains=1, length_penalty=0.0, constraints=None):
+             strategy="beam", sampler=None, num_chains=1, length_penalty=0.0, constraints=None, loop="host", poll_every=4):
     """decode every sample of every batch (:385-426, :499-557).  A batch is the dataset's 11-tuple (images, ROI crops, boxes,
     labels, decoder ids, encoder ids / type / mask / added mask, aspect names, texts) on any device; `features` is
     train_harness.make_features' closure, called once per batch; the beam search runs per sample, or -- batched=True -- once per
@@ -33,6 +33,8 @@ def generate(model, tokenizer, batches, features, beam_size, max_len, aspects=()
     not depend on the batch size.  length_penalty: the final choice among the finished beams / the chains (decoding.py's header).
     constraints: decoding.make_constraints' settings (repetition penalty, n-gram blocking, minimum length, suppressed ids, on the
     step's logits: csrc/constrain.hip); any of them on implies the batched step.
+    loop="device": the beam / chain bookkeeping runs on the device (csrc/beam.hip, decoding.py's header: no upload and no read per
+    round but a poll of the done flags every `poll_every` rounds); implies the batched step.  "host" (default): the host loops.
     -> (preds, refs, results): {aspect: [text]} twice (every name of `aspects` present, in that order, then any other in order of
     appearance) and the per-text grouping [{'text': ..., 'aspects': {aspect: {'predict', 'label'}}}] in order of first appearance."""
     device = next(model.parameters()).device
@@ -40,7 +42,8 @@ def generate(model, tokenizer, batches, features, beam_size, max_len, aspects=()
     if strategy not in ("beam", "sample"):
         raise ValueError(f"strategy must be 'beam' or 'sample', got {strategy!r}")
     constraints = make_constraints(constraints)
-    batched = batched or constraints is not None
+    batched = batched or constraints is not None or loop == "device"
+    loop_kw = {} if loop == "host" else dict(loop=loop, poll_every=poll_every)
     preds, refs = {a: [] for a in aspects}, {a: [] for a in aspects}
     by_text = {}
     seen = 0                                   # samples decoded so far: the sampling counters' sample_offset
@@ -52,11 +55,11 @@ def generate(model, tokenizer, batches, features, beam_size, max_len, aspects=()
         if strategy == "sample":
             texts_b = sample_batch(model, tokenizer, enc_ids, enc_mask, enc_type, added, vis, roi, coors.float(), num_chains=num_chains,
                                    max_len=max_len, context=context, sampler=sampler, sample_offset=seen, length_penalty=length_penalty,
-                                   constraints=constraints)
+                                   constraints=constraints, **loop_kw)
         else:
             texts_b = beam_search_batch(model, tokenizer, enc_ids, enc_mask, enc_type, added, vis, roi, coors.float(), beam_size=beam_size,
                                         max_len=max_len, context=context, length_penalty=length_penalty,
-                                        constraints=constraints) if batched else None
+                                        constraints=constraints, **loop_kw) if batched else None
         seen += enc_ids.shape[0]
         for i in range(enc_ids.shape[0]):
             pred = texts_b[i] if texts_b is not None else beam_search(

@@ -84,6 +84,11 @@ def build_parser():
     p.add_argument("--decode_context", default="last", choices=("last", "prefix"),
                    help="--do_eval: what a decode step sees.  last: the beam's last token at position 0 (the reference's loop); prefix: "
                         "the whole prefix, as the decoder is trained (key cache + csrc/attn_decode.hip; implies the batched step)")
+    p.add_argument("--decode_loop", default="host", choices=("host", "device"),
+                   help="--do_eval: where the beam / chain bookkeeping runs.  host: the Python loops, one upload and one read per round; "
+                        "device: the state stays on the device and csrc/beam.hip advances it (beams / chains <= 8; implies the batched step)")
+    p.add_argument("--decode_poll_every", default=4, type=int,
+                   help="--decode_loop device: read the done flags every N rounds to stop early (0 = never, run --max_len_decoder rounds)")
     p.add_argument("--decode_strategy", default="beam", choices=("beam", "sample"),
                    help="--do_eval: beam search (the reference's), or --num_chains sampled chains per sample, the best-scoring one kept "
                         "(csrc/sample.hip; implies the batched step)")
@@ -149,6 +154,14 @@ def main(argv=None):
         if not 1 <= args.max_len_decoder <= ops.DECODE_ATTN_MAX_T:
             raise ValueError(f"--decode_context prefix: --max_len_decoder {args.max_len_decoder} is outside the decode-attention "
                              f"kernel's 1 .. {ops.DECODE_ATTN_MAX_T} keys")
+    if args.do_eval and args.decode_loop == "device":
+        width = args.num_chains if args.decode_strategy == "sample" else args.beam_size
+        try:
+            ops.check_advance(width, args.max_len_decoder, "--num_chains" if args.decode_strategy == "sample" else "--beam_size")
+        except ValueError as e:
+            raise ValueError(f"--decode_loop device: {e}") from None
+        if args.decode_poll_every < 0:
+            raise ValueError(f"--decode_loop device: --decode_poll_every {args.decode_poll_every} must be >= 0")
     if args.do_eval and not math.isfinite(args.length_penalty):
         raise ValueError(f"--length_penalty {args.length_penalty} must be finite")
     if args.do_eval and args.decode_strategy == "sample":
@@ -367,12 +380,12 @@ def main(argv=None):
             if r_img is not None:
                 r_img.eval(); r_roi.eval()
             preds, refs, results = generate(model, tokenizer, batches, features, args.beam_size, args.max_len_decoder, aspects,
-                                               batched=args.batched_decode or args.decode_context == "prefix",
+                                               batched=args.batched_decode or args.decode_context == "prefix" or args.decode_loop == "device",
                                                context=args.decode_context, strategy=args.decode_strategy,
                                                sampler=dict(seed=args.sample_seed, temperature=args.temperature, top_k=args.top_k,
                                                             top_p=args.top_p),
                                                num_chains=args.num_chains, length_penalty=args.length_penalty,
-                                               constraints=constraints)
+                                               constraints=constraints, loop=args.decode_loop, poll_every=args.decode_poll_every)
             per_aspect, macro = macro_bertscore(preds, refs, aspects, score_fn)
             return per_aspect, macro, results
     elif args.do_eval and master:

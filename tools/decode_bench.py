@@ -17,8 +17,13 @@ another tail kernel -- alternating, with sampling's median over the beam's.
 [n, 64032] bf16 buffer), and the prefix beam decode with constraints off next to the same decode with no_repeat_ngram_size=2,
 repetition_penalty=1.3, min_length=5, alternating: constrained beams run longer by design, so the rounds run (decode_step_prefix
 calls) and the time per round are reported beside the time per batch.
+--loop runs the decode-loop legs INSTEAD of the sections above: the advance kernels alone (fcmf_beam_advance / fcmf_chain_advance on
+the state of samples x beam_size slots, round max_len / 2, between device events), and the prefix decode with loop="host" (the
+baseline: one upload and one blocking read per round) next to loop="device" at poll_every 0 and 4, alternating, for beam search and
+for sampling (num_chains = beam_size): time per batch, rounds run (decode_step_prefix calls), time per round, and whether the legs
+decoded the same sequences.
 Usage (GPU box, repo root):  python tools/decode_bench.py [--samples 16 64] [--beam_size 2] [--max_len_decoder 20] [--only_prefix]
-                                                          [--strategy sample] [--constraints]
+                                                          [--strategy sample] [--constraints] [--loop]
 Prints one JSON line.  Decode: wall time per eval batch between device synchronisations, median of 5 (min, max beside it), both
 paths warmed up once per batch size and alternating, the number of decoder calls of each path, and whether the two paths decoded
 the same token sequences.  Kernel: median microseconds of 9 windows of 50 calls between device events, alternating."""
@@ -48,6 +53,7 @@ p.add_argument("--num_rois", type=int, default=4)
 p.add_argument("--only_prefix", action="store_true")
 p.add_argument("--strategy", default="beam", choices=("beam", "sample"))
 p.add_argument("--constraints", action="store_true")
+p.add_argument("--loop", action="store_true")
 args = p.parse_args()
 
 assert torch.cuda.is_available(), "decode_bench.py measures on the MI355X: no GPU, no number"
@@ -108,7 +114,7 @@ res = {"geometry": dict(H=cfg["hidden_size"], heads=cfg["num_attention_heads"], 
 sampling = args.strategy == "sample"
 if sampling:
     res["sample_kernel"], res["sample_decode"] = [], []
-for B in ([] if args.only_prefix or sampling else args.samples):
+for B in ([] if args.only_prefix or sampling or args.loop else args.samples):
     a = batch_args(B)
     ids_one, ids_many = per_sample(a), batched(a)                         # warm-up of every shape of both paths
     times = {"per_sample": [], "batched": []}
@@ -222,6 +228,56 @@ if args.constraints:
         st = {c: dict(stats(t), rounds=nr[c], ms_per_round=round(statistics.median(t) * 1e3 / nr[c], 3)) for c, t in times.items()}
         res["constrain_decode"].append({"samples_per_batch": B, **st, "mean_len": {c: sum(map(len, v)) / B for c, v in ids.items()},
                                         "on_over_off_per_round": round(st["on"]["ms_per_round"] / st["off"]["ms_per_round"], 3)})
+    print(json.dumps(res))
+    sys.exit(0)
+
+if args.loop:
+    res["advance_kernel"], res["loop_decode"] = [], []
+    W, L = args.beam_size, args.max_len_decoder
+    for B in args.samples:
+        g = torch.Generator().manual_seed(B)
+        t = L // 2
+        logp = -torch.rand(B * W, W, generator=g).to(dev)
+        ids = torch.randint(SEP + 1, V, (B * W, W), generator=g).int().to(dev)        # never sep: no sample is ever done
+        beams, chains = ops.advance_state(B, W, L, 0, dev), ops.advance_state(B, W, L, 0, dev, chains=True)
+        beams["state"].fill_(ops.SLOT_LIVE)
+        logp1, ids1 = logp[:, 0].contiguous(), ids[:, 0].contiguous()
+        legs = {"beam_advance": lambda: ops.beam_advance(logp, ids, beams, t, SEP),
+                "chain_advance": lambda: ops.chain_advance(logp1, ids1, chains, t, SEP)}
+        for fn in legs.values():
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        tm = {k: [] for k in legs}
+        for _ in range(9):
+            for k, fn in legs.items():
+                tm[k].append(window(fn))
+        res["advance_kernel"].append({"samples": B, "rows": B * W, "round": t, **{k: med(v) for k, v in tm.items()}})
+    rounds = {"n": 0}
+    dec.decode_step_prefix = (lambda *a, _fn=dec.decode_step_prefix, **k: (rounds.__setitem__("n", rounds["n"] + 1), _fn(*a, **k))[1])
+
+    def beam_leg(**kw):
+        return lambda a: [r[0] for r in decoding.beam_search_ids_batch(model, 0, SEP, *a, beam_size=W, max_len=L, context="prefix", **kw)]
+
+    def sample_leg(**kw):
+        return lambda a: [r[0] for r in decoding.sample_ids_batch(model, 0, SEP, *a, num_chains=W, max_len=L, context="prefix",
+                                                                  sampler=dict(seed=1, top_k=50, top_p=0.9), **kw)]
+
+    for B in args.samples:
+        a = batch_args(B)
+        for strategy, leg in (("beam", beam_leg), ("sample", sample_leg)):
+            fns = {"host": leg(loop="host"), "device_poll0": leg(loop="device", poll_every=0), "device_poll4": leg(loop="device", poll_every=4)}
+            out = {c: fn(a) for c, fn in fns.items()}     # warm-up of every shape of all three
+            times, nr = {c: [] for c in fns}, {}
+            for _ in range(5):
+                for c, fn in fns.items():
+                    rounds["n"] = 0
+                    times[c].append(timed(fn, a)[0])
+                    nr[c] = rounds["n"]
+            st = {c: dict(stats(tt), rounds=nr[c], ms_per_round=round(statistics.median(tt) * 1e3 / nr[c], 3)) for c, tt in times.items()}
+            res["loop_decode"].append({"strategy": strategy, "samples_per_batch": B, "rows": B * W, **st,
+                                       "same_sequences": {c: sum(x == y for x, y in zip(out["host"], out[c])) for c in fns if c != "host"},
+                                       "device_over_host": {c: round(st[c]["median_ms"] / st["host"]["median_ms"], 3) for c in fns if c != "host"}})
     print(json.dumps(res))
     sys.exit(0)
 
