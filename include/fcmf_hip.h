@@ -547,6 +547,44 @@ int fcmf_xent_bwd(const void* logits, int64_t ld, const int64_t* labels, void* d
 int fcmf_xent_mean(const float* loss_rows, const int64_t* labels, int n, int64_t ignore_index,
                    float mult, float* out2, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Cross entropy with class weights, label smoothing and a focal factor, normalised per SEGMENT (csrc/loss.hip; the plain
+ * entry points above are untouched and stay the path of a loss without options).  Row r of the n rows belongs to segment
+ * r % segments (logits [B, A, C] flattened: the segment is the aspect).  For a live row (label != ignore_index) of
+ * segment s, with p = softmax over the first C columns and w = the segment's weights (ones when weight is NULL):
+ *   l_n  = (1 - eps) w_y (1 - p_y)^gamma (-log p_y) + (eps / C) sum_c w_c (-log p_c)
+ *   loss = mult * sum_s [ sum_{n in s, live} l_n / sum_{n in s, live} w_{y_n} ]
+ * With gamma = 0 a segment's term is torch's F.cross_entropy(x_s, y_s, weight, label_smoothing=eps, ignore_index).
+ *   logits [n, >= C] of `dtype` (FCMF_F32 / FCMF_BF16), row stride ld >= C elements; labels int64 [n];
+ *   weight float32 or NULL: [C] shared by all segments (wstride = 0) or one row per segment, wstride >= C elements apart;
+ *   eps in [0, 1), gamma >= 0 and finite, not both positive.
+ * Every entry point returns before any launch: FCMF_ERR_ARG for a null pointer, segments < 1, n % segments != 0, a
+ * stride below C, eps outside [0, 1) or gamma < 0 / not finite; FCMF_ERR_UNSUPPORTED for eps > 0 together with gamma > 0
+ * and for another dtype.  C < 1024: one wave per row; C >= 1024: one workgroup per row in one pass, 16-byte accesses when
+ * logits (dlogits, weight) and their strides are 16-byte aligned, element accesses otherwise.  1 - p_y is formed from the
+ * other classes' exponentials and log p_y as x_y - lse, never as 1.0f - p_y or log(p_y).
+ *
+ * fcmf_xent_fwd_ex: num[r] = l_r, den[r] = w_{y_r}; both 0 for an ignored row.  A label outside [0, C) that is not
+ * ignore_index reads nothing and gives num = NaN, den = 0 (the loss turns NaN instead of reading out of bounds). */
+int fcmf_xent_fwd_ex(const void* logits, int64_t ld, const int64_t* labels, const float* weight, int64_t wstride,
+                     float* num, float* den, int n, int C, int segments, int64_t ignore_index, float eps, float gamma,
+                     int dtype, void* stream);
+/* The reduction over fcmf_xent_fwd_ex's rows by ONE workgroup in a fixed order with float64 partial sums (no atomics, no
+ * host read): loss[0] = mult * sum_s N_s / D_s with N_s, D_s the segment's sums of num and den (0 / 0 = NaN when a segment
+ * has no live weight, as torch); scales[s] (float32 [segments]) = mult / D_s, the scale of fcmf_xent_bwd_ex -- 0 where
+ * D_s is not positive, so that such a segment's rows get zero gradients. */
+int fcmf_xent_reduce_ex(const float* num, const float* den, int n, int segments, float mult, float* loss, float* scales,
+                        void* stream);
+/* dlogits[r, j] = sc * [(1 - eps) w_y (p_j - [j == y]) + (eps / C) (p_j sum_c w_c - w_j)] for gamma = 0 and
+ *                 sc * w_y [gamma p_y (1 - p_y)^(gamma - 1) log p_y - (1 - p_y)^gamma] ([j == y] - p_j) for gamma > 0,
+ * sc = scales[r % segments] * (grad ? *grad : 1) (grad: device float32 [1], the upstream gradient); zeros for ignored rows,
+ * rows with a label outside [0, C) and rows whose sc is 0.  dlogits has `dtype` and row stride ldd >= C.  For C >= 1024 it
+ * may be the logits themselves (dlogits == logits, ldd == ld: every element is read and written by the same thread).
+ * Columns at or past C are neither read nor written. */
+int fcmf_xent_bwd_ex(const void* logits, int64_t ld, const int64_t* labels, const float* weight, int64_t wstride,
+                     void* dlogits, int64_t ldd, const float* scales, const float* grad, int n, int C, int segments,
+                     int64_t ignore_index, float eps, float gamma, int dtype, void* stream);
+
 /* torch.nn.BCEWithLogitsLoss() (mean over n x C) of the multi-label photo-category head (image_processing/
  * run_image_categories.py:175,186), in one launch of one workgroup (classifier heads: n x C of a few thousand):
  *   logits [n, C] of `dtype` (row stride ld elements), target float32 [n, C] (row stride ldt; may be NULL when only probs

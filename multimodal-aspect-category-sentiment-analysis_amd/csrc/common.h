@@ -83,6 +83,18 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// ---- wide class axes (the cross-entropy kernels of misc.hip and loss.hip): 16 bytes of a row per lane, online softmax sums ----
+template <typename T> struct XVec;
+template <> struct XVec<float> { static constexpr int N = 4; typedef f32x4 type; };
+template <> struct XVec<bf16_t> { static constexpr int N = 8; typedef bf16x8 type; };
+
+// (m, s) <- the (max, sum of exp(x - max)) of two parts that hold (m, s) and (m2, s2)
+__device__ __forceinline__ void online_merge(float& m, float& s, float m2, float s2) {
+  const float mn = fmaxf(m, m2);
+  s = (m == -INFINITY ? 0.f : s * __expf(m - mn)) + (m2 == -INFINITY ? 0.f : s2 * __expf(m2 - mn));
+  m = mn;
+}
+
 // ---- column sums of a row-major matrix (fcmf_colsum, the LayerNorm backward's reduce pass) -----------------------------------
 // out[c] += sum_r X[r, c] for the rows [blockIdx.y * rows_per_block, +rows_per_block) of the 256-column block blockIdx.x, by one
 // workgroup of COLSUM_WAVES waves.  A lane owns V adjacent columns, so one wave instruction reads 256 contiguous columns of

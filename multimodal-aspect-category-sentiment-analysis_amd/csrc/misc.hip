@@ -115,16 +115,6 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const T* __restrict__ log
 // ---- cross entropy over a WIDE class axis (IAOG: the 64001-entry vocabulary, run_pretraining_fcmf.py:322-324):
 // one workgroup per row, 16-byte loads, one online (max, sum-exp) pass; the backward may run IN PLACE
 // (dlogits == logits: every element is read and written by the same thread).
-template <typename T> struct XVec;
-template <> struct XVec<float> { static constexpr int N = 4; typedef f32x4 type; };
-template <> struct XVec<bf16_t> { static constexpr int N = 8; typedef bf16x8 type; };
-
-__device__ __forceinline__ void online_merge(float& m, float& s, float m2, float s2) {
-  const float mn = fmaxf(m, m2);
-  s = (m == -INFINITY ? 0.f : s * __expf(m - mn)) + (m2 == -INFINITY ? 0.f : s2 * __expf(m2 - mn));
-  m = mn;
-}
-
 // block-wide (max, sum exp(x - max)) of lr[0..C): every thread returns the same pair
 template <typename T>
 __device__ __forceinline__ void row_softmax_stats(const T* __restrict__ lr, int C, bool vec, float& m_out, float& s_out) {

@@ -59,10 +59,13 @@ class _Baseline(nn.Module):
         pooled = ops.dropout(pooled.contiguous(), self.dropout.p, self.training)
         return ops.linear(pooled, self.classifier.weight, self.classifier.bias).float()
 
-    def loss_aspects(self, logits, labels):
-        """sum over aspects of the batch-mean cross entropy, as FCMF.loss_aspects"""
+    def loss_aspects(self, logits, labels, weight=None, label_smoothing=0.0, focal_gamma=0.0):
+        """sum over aspects of the batch-mean cross entropy, as FCMF.loss_aspects (the same options: the aspects are the segments)"""
         B, A, C = logits.shape
-        return ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), mult=float(A))
+        if weight is None and label_smoothing == 0.0 and focal_gamma == 0.0:
+            return ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), mult=float(A))
+        return ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), weight=weight, label_smoothing=label_smoothing,
+                                 focal_gamma=focal_gamma, segments=A)
 
 
 class mRoBERTa(_Baseline):

@@ -62,8 +62,12 @@ class FCMF(nn.Module):
                                           attention_mask, added_attention_mask)
         return self._head(seq).float().view(B, A, -1)
 
-    def loss_aspects(self, logits, labels):
+    def loss_aspects(self, logits, labels, weight=None, label_smoothing=0.0, focal_gamma=0.0):
         """sum over aspects of the batch-mean CE (run_multimodal_fcmf.py:463-475), in one kernel:
-        mean over B*A rows times A."""
+        mean over B*A rows times A.  With class weights (float32 [C] or [A, C]), label smoothing or a focal exponent every
+        aspect divides by its own weight sum, so the aspects become the loss's segments (ops.cross_entropy)."""
         B, A, C = logits.shape
-        return ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), mult=float(A))
+        if weight is None and label_smoothing == 0.0 and focal_gamma == 0.0:
+            return ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), mult=float(A))
+        return ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), weight=weight, label_smoothing=label_smoothing,
+                                 focal_gamma=focal_gamma, segments=A)

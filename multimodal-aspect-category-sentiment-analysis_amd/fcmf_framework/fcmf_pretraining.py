@@ -192,13 +192,13 @@ class FCMFSeq2Seq(nn.Module):
         return logits
 
     def forward_loss(self, enc_X, dec_X, labels, visual_embeds_att, roi_embeds_att, roi_coors=None, token_type_ids=None,
-                     attention_mask=None, added_attention_mask=None, ignore_index=-100):
+                     attention_mask=None, added_attention_mask=None, ignore_index=-100, label_smoothing=0.0):
         """the training step's `CrossEntropyLoss(ignore_index=-100)(forward(...).permute(0, 2, 1), labels)`
         (run_pretraining_fcmf.py:309-324) as one call: same value, the 64001-wide logits stay inside the fused
         projection + loss node (ops.VocabCrossEntropyFn)"""
         dec_state, _ = self._decoder_state(enc_X, visual_embeds_att, roi_embeds_att, roi_coors, token_type_ids,
                                            attention_mask, added_attention_mask)
-        return self.decoder.loss(dec_X, dec_state, labels, ignore_index=ignore_index)
+        return self.decoder.loss(dec_X, dec_state, labels, ignore_index=ignore_index, label_smoothing=label_smoothing)
 
     def _init_weights(self, module):
         if isinstance(module, nn.Linear):

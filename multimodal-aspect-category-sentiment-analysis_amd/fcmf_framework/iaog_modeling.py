@@ -319,11 +319,11 @@ class IAOGDecoder(nn.Module):
         X = self.hidden_states(X, state, enc_attention_mask, is_train, hoisted)
         return ops.vocab_linear(X, self.dense.weight, self.dense.bias)
 
-    def loss(self, X, state, labels, enc_attention_mask=None, ignore_index=-100):
-        """CrossEntropyLoss(ignore_index)(forward(X).permute(0, 2, 1), labels) (run_pretraining_fcmf.py:322-324) with
-        the vocabulary projection and the loss fused: the [B, Ld, V] logits are never handed out"""
+    def loss(self, X, state, labels, enc_attention_mask=None, ignore_index=-100, label_smoothing=0.0):
+        """CrossEntropyLoss(ignore_index, label_smoothing)(forward(X).permute(0, 2, 1), labels) (run_pretraining_fcmf.py:322-324)
+        with the vocabulary projection and the loss fused: the [B, Ld, V] logits are never handed out"""
         X = self.hidden_states(X, state, enc_attention_mask, True)
-        return ops.vocab_cross_entropy(X, self.dense.weight, self.dense.bias, labels, ignore_index)
+        return ops.vocab_cross_entropy(X, self.dense.weight, self.dense.bias, labels, ignore_index, label_smoothing=label_smoothing)
 
     def _decode_tail(self, X, k, sampler, constraints=None):
         """the end of a decode step on the rows X [n, H] of the last block: the k best tokens (ops.vocab_topk), or -- `sampler` a dict of

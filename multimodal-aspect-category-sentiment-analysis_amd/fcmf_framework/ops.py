@@ -792,9 +792,56 @@ class VocabCrossEntropyFn(torch.autograd.Function):
         return None if dx is None else dx.view(xshape), dw, db, None, None
 
 
-def vocab_cross_entropy(x, weight, bias, labels, ignore_index=-100):
-    """mean CE of the vocabulary projection of x over the non-ignored positions (torch CrossEntropyLoss semantics)"""
-    return VocabCrossEntropyFn.apply(x, weight, bias, labels, int(ignore_index))
+class VocabCrossEntropyExFn(torch.autograd.Function):
+    """VocabCrossEntropyFn with label smoothing and / or class weights over the V real columns of the padded logits
+    (fcmf_xent_fwd_ex + fcmf_xent_reduce_ex; fcmf_xent_bwd_ex in place): the rows, their weighted mean and the backward's scale
+    stay on the device, with no torch arithmetic between the launches"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, labels, ignore_index, eps, class_weight):
+        x2 = _rows(x)
+        V = weight.shape[0]
+        cw, _ = _loss_weight(class_weight, V, 1, x2.device, "vocab_cross_entropy: class_weight")
+        logits, ctx.w = _vocab_logits(x2, weight, bias)
+        M, Vp = logits.shape
+        lb = labels.reshape(-1).contiguous()
+        rows = torch.empty((2, M), dtype=torch.float32, device=x2.device)
+        out = torch.empty(2, dtype=torch.float32, device=x2.device)          # [loss, 1 / sum of the live rows' weights]
+        L = H.lib()
+        H.check(L.fcmf_xent_fwd_ex(H.ptr(logits), Vp, H.ptr(lb), H.ptr(cw), 0, H.ptr(rows[0]), H.ptr(rows[1]), M, V, 1, ignore_index,
+                                   eps, 0.0, H.dt(logits), H.stream()), "fcmf_xent_fwd_ex")
+        H.check(L.fcmf_xent_reduce_ex(H.ptr(rows[0]), H.ptr(rows[1]), M, 1, 1.0, H.ptr(out), H.ptr(out[1:]), H.stream()),
+                "fcmf_xent_reduce_ex")
+        ctx.save_for_backward(x2, weight, logits, lb, out, *(() if cw is None else (cw,)))
+        ctx.cfg = (ignore_index, bias is not None, x.shape, eps)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x2, weight, logits, lb, out = ctx.saved_tensors[:5]
+        cw = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else None
+        ignore_index, has_bias, xshape, eps = ctx.cfg
+        need = ctx.needs_input_grad
+        V, K = weight.shape
+        M, Vp = logits.shape
+        g = _grad_scalar(g)
+        d = logits                                          # in place: the node owns the buffer
+        H.check(H.lib().fcmf_xent_bwd_ex(H.ptr(logits), Vp, H.ptr(lb), H.ptr(cw), 0, H.ptr(d), Vp, H.ptr(out[1:]), H.ptr(g), M, V, 1,
+                                         ignore_index, eps, 0.0, H.dt(logits), H.stream()), "fcmf_xent_bwd_ex")
+        if Vp != V:
+            d[:, V:].zero_()                                # the padding logits (= bias 0) must not leak into dX / dW
+        dwp, dw = grad_dest(weight, (V, K), rows=Vp, device=x2.device) if need[1] else (None, None)
+        dx, db = _vocab_bwd(d, x2, ctx.w, V, need[0], has_bias and need[2], dwp)
+        return None if dx is None else dx.view(xshape), dw, db, None, None, None, None
+
+
+def vocab_cross_entropy(x, weight, bias, labels, ignore_index=-100, *, label_smoothing=0.0, class_weight=None):
+    """mean CE of the vocabulary projection of x over the non-ignored positions (torch CrossEntropyLoss semantics, its
+    `label_smoothing` and `weight` (here class_weight, float32 [V] on the device) included).  Without either it is the plain node."""
+    eps, _ = check_loss_options(label_smoothing, 0.0)
+    if eps == 0.0 and class_weight is None:
+        return VocabCrossEntropyFn.apply(x, weight, bias, labels, int(ignore_index))
+    return VocabCrossEntropyExFn.apply(x, weight, bias, labels, int(ignore_index), eps, class_weight)
 
 
 def logsoftmax_topk(logits, V, k):
@@ -1663,8 +1710,95 @@ def additive_mask(m, value):
     return out
 
 
-def cross_entropy(logits, labels, ignore_index=-100, mult=1.0):
-    return XentFn.apply(logits, labels, int(ignore_index), float(mult))
+def check_loss_options(label_smoothing=0.0, focal_gamma=0.0):
+    """the value limits of fcmf_xent_*_ex (include/fcmf_hip.h), raised as a ValueError that names the argument -> (eps, gamma)"""
+    for name, v in (("label_smoothing", label_smoothing), ("focal_gamma", focal_gamma)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing}")
+    if focal_gamma < 0.0:
+        raise ValueError(f"focal_gamma must be >= 0 (0 = off), got {focal_gamma}")
+    if label_smoothing > 0.0 and focal_gamma > 0.0:
+        raise ValueError(f"focal_gamma ({focal_gamma}) and label_smoothing ({label_smoothing}) cannot both be set")
+    return float(label_smoothing), float(focal_gamma)
+
+
+def _loss_weight(weight, C, segments, device, what):
+    """class weights of a loss -> (contiguous float32 tensor or None, fcmf_xent_*_ex's wstride: 0 = [C] shared, C = [segments, C])"""
+    if weight is None:
+        return None, 0
+    if not torch.is_tensor(weight):
+        raise H.HipLibraryError(f"{what} must be a tensor, got {type(weight).__name__}")
+    if weight.device != device:
+        raise H.HipLibraryError(f"{what} is on {weight.device}, the logits are on {device}")
+    if weight.dtype != torch.float32:
+        raise H.HipLibraryError(f"{what} must be float32, got {weight.dtype}")
+    if tuple(weight.shape) == (C,):
+        return weight.contiguous(), 0
+    if tuple(weight.shape) == (segments, C):
+        return weight.contiguous(), C
+    raise H.HipLibraryError(f"{what} must have shape [{C}] or [{segments}, {C}] (segments, classes), got {tuple(weight.shape)}")
+
+
+def _grad_scalar(g):
+    """the upstream gradient of a scalar loss as the device float32 [1] that fcmf_xent_bwd_ex reads"""
+    g = g.reshape(1)
+    return g if g.dtype == torch.float32 else g.float()
+
+
+class XentExFn(torch.autograd.Function):
+    """cross entropy with class weights, label smoothing or a focal factor, each segment (row r -> segment r % segments) divided
+    by its own live weight sum, x `mult`: fcmf_xent_fwd_ex + fcmf_xent_reduce_ex forward, fcmf_xent_bwd_ex backward, no torch
+    arithmetic between them (include/fcmf_hip.h states the function)"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, ignore_index, mult, eps, gamma, segments):
+        lg = _rows2d(logits)
+        lb = labels.reshape(-1).contiguous()
+        H.require_cuda(lg, lb)
+        n, C = lg.shape
+        if segments < 1 or n % segments != 0:
+            raise H.HipLibraryError(f"cross_entropy: {n} rows do not divide into {segments} segments")
+        if lb.numel() != n:
+            raise H.HipLibraryError(f"cross_entropy: {n} rows of logits but {lb.numel()} labels")
+        w, wstride = _loss_weight(weight, C, segments, lg.device, "cross_entropy: weight")
+        ld = lg.stride(0) if n > 1 else max(lg.stride(0), C)              # (one row: its stride means nothing)
+        rows = torch.empty((2, n), dtype=torch.float32, device=lg.device)
+        out = torch.empty(1 + segments, dtype=torch.float32, device=lg.device)      # [loss, mult / D_s ...]
+        L = H.lib()
+        H.check(L.fcmf_xent_fwd_ex(H.ptr(lg), ld, H.ptr(lb), H.ptr(w), wstride, H.ptr(rows[0]), H.ptr(rows[1]), n, C, segments,
+                                   ignore_index, eps, gamma, H.dt(lg), H.stream()), "fcmf_xent_fwd_ex")
+        H.check(L.fcmf_xent_reduce_ex(H.ptr(rows[0]), H.ptr(rows[1]), n, segments, mult, H.ptr(out), H.ptr(out[1:]), H.stream()),
+                "fcmf_xent_reduce_ex")
+        ctx.save_for_backward(lg, lb, out, *(() if w is None else (w,)))
+        ctx.cfg = (ignore_index, eps, gamma, segments, wstride, ld, logits.shape)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lg, lb, out = ctx.saved_tensors[:3]
+        w = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        ignore_index, eps, gamma, segments, wstride, ld, lshape = ctx.cfg
+        n, C = lg.shape
+        d = torch.empty((n, C), dtype=lg.dtype, device=lg.device)
+        g = _grad_scalar(g)
+        H.check(H.lib().fcmf_xent_bwd_ex(H.ptr(lg), ld, H.ptr(lb), H.ptr(w), wstride, H.ptr(d), C, H.ptr(out[1:]), H.ptr(g), n, C,
+                                         segments, ignore_index, eps, gamma, H.dt(lg), H.stream()), "fcmf_xent_bwd_ex")
+        return d.view(lshape), None, None, None, None, None, None, None
+
+
+def cross_entropy(logits, labels, ignore_index=-100, mult=1.0, *, weight=None, label_smoothing=0.0, focal_gamma=0.0, segments=1):
+    """torch.nn.CrossEntropyLoss semantics x `mult`.  Options (any of them selects XentExFn; none leaves the plain XentFn):
+    `weight` float32 [C] or [segments, C] on the device, `label_smoothing` in [0, 1), `focal_gamma` >= 0 (not with smoothing),
+    `segments`: row r of the flattened logits belongs to segment r % segments, and the result is the SUM over the segments of each
+    segment's own weighted mean (logits [B, A, C]: segments=A is the drivers' sum over aspects of per-aspect batch means)."""
+    eps, gamma = check_loss_options(label_smoothing, focal_gamma)
+    if isinstance(segments, bool) or not isinstance(segments, int) or segments < 1:
+        raise ValueError(f"segments must be a positive integer, got {segments!r}")
+    if weight is None and eps == 0.0 and gamma == 0.0 and segments == 1:
+        return XentFn.apply(logits, labels, int(ignore_index), float(mult))
+    return XentExFn.apply(logits, labels, weight, int(ignore_index), float(mult), eps, gamma, segments)
 
 
 def _rows2d(logits):

@@ -31,7 +31,8 @@ from fcmf_framework import baselines, ops  # noqa: E402
 from fcmf_framework.dp import GradArena  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
-from train_harness import build_extractors, init_run, make_features, save_model, split_decay, train_epoch  # noqa: E402
+from train_harness import (add_loss_arguments, build_extractors, check_loss_arguments, class_weight_tensor, init_run,  # noqa: E402
+                           make_features, save_model, split_decay, train_epoch, train_label_table)
 from run_multimodal_fcmf import POLARITY_MAP, macro_f1  # noqa: E402
 
 #            model class, checkpoint name before _best / _last (seed filled in), name in the log and result files
@@ -75,6 +76,7 @@ def build_parser():
     p.add_argument('--resnet_checkpoint', default=None, type=str, help="torchvision resnet152 state dict for the HIP trunk")
     p.add_argument('--ffn_dropout', action='store_true',
                    help="nn.TransformerEncoderLayer's dropout between the feed-forward's gelu and its second Linear (ops.set_ffn_dropout)")
+    add_loss_arguments(p)
     p.set_defaults(ddp=False)
     return p
 
@@ -199,6 +201,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.gradient_accumulation_steps < 1:
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
+    weight_request = check_loss_arguments(args)
     cls_name, ckpt, tag = MODELS[args.model]
     ckpt = ckpt.format(seed=args.seed)
     fmt = logging.Formatter('%(asctime)s - %(levelname)s - %(name)s - %(message)s', datefmt='%m/%d/%Y %H:%M:%S')
@@ -250,9 +253,16 @@ def main(argv=None):
     f32_fields = () if args.model == "ef_captr" else (1,)
     last_loss = [float("nan")]
 
+    class_weight = class_weight_tensor(weight_request, lambda: train_label_table(train_loader, first_wins=args.model != "ef_captr"),
+                                       len(aspects), args.num_polarity, device, args.output_dir, logger, True) if args.do_train else None
+    if args.do_train:
+        logger.info("training loss: label_smoothing %g focal_gamma %g class_weights %s", args.label_smoothing, args.focal_gamma,
+                    args.class_weights)
+
     def loss_fn(batch):
         logits, labels, _ = forward_batch(args.model, model, batch, features)
-        return model.loss_aspects(logits, labels)
+        return model.loss_aspects(logits, labels, weight=class_weight, label_smoothing=args.label_smoothing,
+                                  focal_gamma=args.focal_gamma)
 
     def log(step, loss):
         last_loss[0] = loss

@@ -42,8 +42,8 @@ from fcmf_framework.dp import GradArena, GradReducer  # noqa: E402
 from fcmf_framework.fcmf_multimodal import FCMF  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
-from train_harness import (build_extractors, init_run, load_resnets, make_features, save_extractors, save_model,  # noqa: E402
-                           split_decay, train_epoch)
+from train_harness import (add_loss_arguments, build_extractors, check_loss_arguments, class_weight_tensor, init_run,  # noqa: E402
+                           load_resnets, make_features, save_extractors, save_model, split_decay, train_epoch, train_label_table)
 
 
 POLARITY_MAP = {0: 'None', 1: 'Negative', 2: 'Neutral', 3: 'Positive'}      # reference :28
@@ -101,6 +101,7 @@ def build_parser():
     parser.add_argument('--dump_attention_maps', action='store_true',
                         help="with --do_eval: the test-set pass also writes test_attention_maps.npz (head-averaged [CLS] "
                              "attention over each photo's patches and ROIs, per review and aspect) into --output_dir")
+    add_loss_arguments(parser)
     return parser
 
 
@@ -146,6 +147,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.gradient_accumulation_steps < 1:
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
+    weight_request = check_loss_arguments(args)
     fmt = logging.Formatter('%(asctime)s - %(levelname)s - %(name)s - %(message)s', datefmt='%m/%d/%Y %H:%M:%S')
     rank, _, world, device, master, logger = init_run(args, "fcmf", "training_fcmf.log", formatter=fmt, script="run_multimodal_fcmf.py")
     args.train_batch_size = int(args.train_batch_size / args.gradient_accumulation_steps)
@@ -241,10 +243,19 @@ def main(argv=None):
         ops.shadows.clear()
 
     features = make_features(resnet_img, resnet_roi)
+    # the training loss's options; the synthetic label table is rank 0's, so that every rank holds the same weights
+    counted = synthetic(args.synthetic_steps, args.train_batch_size, args.seed) if args.synthetic_steps > 0 else train_loader
+    class_weight = class_weight_tensor(weight_request, lambda: train_label_table(counted), len(ASPECT), args.num_polarity, device,
+                                       args.output_dir, logger, master) if args.do_train else None
+    if master and args.do_train:
+        logger.info("training loss: label_smoothing %g focal_gamma %g class_weights %s", args.label_smoothing, args.focal_gamma,
+                    args.class_weights)
 
     def loss_fn(batch):
         logits, labels, _ = forward_batch(model, batch, features)
-        return model.loss_aspects(logits, labels)                     # sum over aspects of the batch-mean CE
+        # sum over aspects of the batch-mean CE (each aspect over its own weight sum once an option is set)
+        return model.loss_aspects(logits, labels, weight=class_weight, label_smoothing=args.label_smoothing,
+                                  focal_gamma=args.focal_gamma)
 
     if args.do_train:
         for epoch in range(start_epoch, int(args.num_train_epochs)):

@@ -45,8 +45,8 @@ from fcmf_framework.dp import GradArena, GradReducer  # noqa: E402
 from fcmf_framework.fcmf_pretraining import FCMFSeq2Seq  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
-from train_harness import (build_extractors, init_run, load_resnets, make_features, save_extractors, save_model,  # noqa: E402
-                           split_decay, train_epoch)
+from train_harness import (add_loss_arguments, build_extractors, check_loss_arguments, init_run, load_resnets,  # noqa: E402
+                           make_features, save_extractors, save_model, split_decay, train_epoch)
 
 
 DEFAULT_BERT_SCORE_MODEL = 'uitnlp/visobert'      # the reference's default (:53), a hub name
@@ -128,6 +128,7 @@ def build_parser():
                    help="with --synthetic_steps: batches carry SIZE x SIZE pixel crops and the ResNet-152 trunks run inside the step")
     p.add_argument('--synthetic_eval_samples', type=int, default=0,
                    help="with --synthetic_steps and --do_eval: dev and test sets of N seeded synthetic samples each")
+    add_loss_arguments(p, class_weights=False)
     return p
 
 
@@ -202,6 +203,7 @@ def main(argv=None):
             if 0 < args.vocab_size < need:     # (0: the tokenizer's size, known later; the decode checks it again)
                 raise ValueError(f"--suppress_tokens / --max_len_decoder: --vocab_size {args.vocab_size} cannot keep {width} tokens "
                                  f"unbanned (needs >= {need})")
+    check_loss_arguments(args)
     rank, _, world, device, master, logger = init_run(args, "iaog", "pretraining_iaog.log", script="run_pretraining_fcmf.py")
 
     tokenizer = None
@@ -365,7 +367,8 @@ def main(argv=None):
         vis, roi, coors, enc_X, tt, am, added, dec_X, labels = batch
         vis, roi = features(vis, roi)
         # model(...) -> logits -> CrossEntropyLoss(ignore_index=-100) (reference :309-324) as one fused call
-        return model.forward_loss(enc_X, dec_X, labels, vis, roi, coors, tt, am, added, ignore_index=-100)
+        return model.forward_loss(enc_X, dec_X, labels, vis, roi, coors, tt, am, added, ignore_index=-100,
+                                  label_smoothing=args.label_smoothing)
 
     evaluate = None
     if args.do_eval and master and dev_set is not None:

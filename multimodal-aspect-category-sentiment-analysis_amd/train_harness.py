@@ -2,7 +2,9 @@
 ResNet-152 extractors with their checkpoints beside the model's, the weight-decay split and the loop of one epoch.  Each
 driver keeps its parser, model, data, parameter groups, loss call and (fine-tuning) evaluation.  File:line citations are
 into the reference's two drivers."""
+import json
 import logging
+import math
 import os
 import random
 
@@ -21,6 +23,88 @@ def split_decay(named):
     for n, p in named:
         (exempt if any(nd in n for nd in NO_DECAY) else decay).append(p)
     return decay, exempt
+
+
+# ---- the training loss's options (ops.cross_entropy / ops.vocab_cross_entropy) -----------------------------------------------
+EVAL_LOSS_NOTE = ("evaluation is untouched: a dev / test eval_loss stays plain cross entropy, so result files compare across runs "
+                  "with and without it")
+
+
+def add_loss_arguments(parser, class_weights=True):
+    """--label_smoothing, and for the aspect classifiers --class_weights / --focal_gamma (values are checked by check_loss_arguments)"""
+    if class_weights:
+        parser.add_argument('--class_weights', default='none', type=str,
+                            help="training-loss class weights: none | balanced (per aspect N / (C * max(count, 1)) over the training "
+                                 "split's labels) | a comma list of --num_polarity floats; every aspect is divided by its own weight "
+                                 "sum; written to output_dir/class_weights.json; " + EVAL_LOSS_NOTE)
+        parser.add_argument('--focal_gamma', default=0.0, type=float,
+                            help="focal exponent of the training loss, (1 - p_y)^gamma; 0 = off, not together with --label_smoothing; "
+                                 + EVAL_LOSS_NOTE)
+    parser.add_argument('--label_smoothing', default=0.0, type=float,
+                        help="label smoothing of the training loss, in [0, 1); " + EVAL_LOSS_NOTE)
+
+
+def check_loss_arguments(args):
+    """refuses bad loss flags with a ValueError that names the flag (call before anything is created or written)
+    -> the class-weight request: None, "balanced" or a list of num_polarity floats"""
+    eps, gamma = args.label_smoothing, getattr(args, "focal_gamma", 0.0)
+    if not (math.isfinite(eps) and 0.0 <= eps < 1.0):
+        raise ValueError(f"--label_smoothing must lie in [0, 1), got {eps}")
+    if not (math.isfinite(gamma) and gamma >= 0.0):
+        raise ValueError(f"--focal_gamma must be finite and >= 0, got {gamma}")
+    if eps > 0.0 and gamma > 0.0:
+        raise ValueError(f"--focal_gamma {gamma} and --label_smoothing {eps} cannot both be set")
+    spec = getattr(args, "class_weights", "none").strip()
+    if spec.lower() in ("none", "balanced"):
+        return None if spec.lower() == "none" else "balanced"
+    try:
+        values = [float(v) for v in spec.split(",")]
+    except ValueError:
+        raise ValueError(f"--class_weights must be none, balanced or a comma list of {args.num_polarity} floats, got {spec!r}") from None
+    if len(values) != args.num_polarity:
+        raise ValueError(f"--class_weights lists {len(values)} values, --num_polarity is {args.num_polarity}")
+    if not all(math.isfinite(v) and v >= 0.0 for v in values) or sum(values) <= 0.0:
+        raise ValueError(f"--class_weights must be finite, >= 0 and not all zero, got {spec!r}")
+    return values
+
+
+def balanced_class_weights(labels, num_classes):
+    """labels: integers [N, A] (one column per aspect) -> float32 [A, num_classes], w[a, c] = N / (C * max(count[a, c], 1)):
+    scikit-learn's class_weight="balanced" per aspect, a class that an aspect never shows counted once"""
+    labels = np.asarray(labels, dtype=np.int64)
+    if labels.ndim != 2 or labels.shape[0] == 0:
+        raise ValueError(f"balanced class weights need a non-empty [reviews, aspects] label table, got shape {labels.shape}")
+    if labels.min() < 0 or labels.max() >= num_classes:
+        raise ValueError(f"labels outside [0, {num_classes}) in the training split")
+    N, A = labels.shape
+    counts = np.stack([np.bincount(labels[:, a], minlength=num_classes) for a in range(A)])
+    return (N / (num_classes * np.maximum(counts, 1))).astype(np.float32)
+
+
+def train_label_table(loader, first_wins=True):
+    """the training split's labels [reviews, aspects] without touching a photo: from the dataset's frame where the loader has one
+    (column 3, "Aspect#Polarity" lists, as the datasets read it), else from the (synthetic) batches' label field"""
+    ds = getattr(loader, "dataset", None)
+    if ds is not None and hasattr(ds, "data"):
+        from review_batches import polarity_labels
+        aspects = getattr(ds, "ASPECT")
+        return np.stack([polarity_labels(ann, aspects, first_wins=first_wins).numpy() for ann in ds.data.iloc[:, 3]])
+    return np.concatenate([np.asarray(batch[-2]) for batch in loader])
+
+
+def class_weight_tensor(request, labels_fn, num_aspects, num_classes, device, output_dir, logger, master):
+    """check_loss_arguments' request -> the loss's weight (float32 on the device: [A, C] balanced, [C] listed) or None; logged and
+    written to output_dir/class_weights.json by the master.  labels_fn() returns the training label table (balanced only)."""
+    if request is None:
+        return None
+    w = balanced_class_weights(labels_fn(), num_classes) if request == "balanced" else np.asarray(request, dtype=np.float32)
+    if w.ndim == 2 and w.shape[0] != num_aspects:
+        raise ValueError(f"--class_weights balanced: the label table has {w.shape[0]} aspects, --list_aspect names {num_aspects}")
+    if master:
+        logger.info("class weights (%s): %s", "aspect x polarity" if w.ndim == 2 else "polarity", w.tolist())
+        with open(os.path.join(output_dir, "class_weights.json"), "w") as f:
+            json.dump({"mode": "balanced" if request == "balanced" else "list", "weights": w.tolist()}, f)
+    return torch.from_numpy(w).to(device)
 
 
 def init_run(args, logger_name, log_file, formatter=None, script="this driver"):
