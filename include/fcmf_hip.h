@@ -681,7 +681,8 @@ int fcmf_bertadam(float* p, const float* g, float* m, float* v, int64_t n, float
  * fcmf_conv_im2col: dst[row, (r*kw + s)*C + c] = src(n, ho*stride + r - pad, wo*stride + s - pad, c) or 0,
  * row = (n*Ho + ho)*Wo + wo, Ho = (H + 2*pad - kh)/stride + 1; columns kh*kw*C .. Kpad-1 are zero (the stem's
  * K = 147 is padded to a multiple of 32).  src element (n,h,w,c) at n*sn + h*sh + w*sw + c*sc: NCHW float32
- * crops and NHWC activations alike.  (nn.Conv2d's input gather, torchvision Bottleneck conv2 / downsample.0 / conv1) */
+ * crops and NHWC activations alike.  FCMF_ERR_ARG when the kernel is larger than the padded input (no output row or column).
+ * (nn.Conv2d's input gather, torchvision Bottleneck conv2 / downsample.0 / conv1) */
 int fcmf_conv_im2col(const void* src, int src_dtype, void* dst, int dst_dtype, int N, int H, int W, int C,
                      int64_t sn, int64_t sh, int64_t sw, int64_t sc, int kh, int kw, int stride, int pad,
                      int Kpad, void* stream);
@@ -774,7 +775,8 @@ int fcmf_gemm_dw_batched(fcmf_gemm_ctx* ctx, int count, const void* const* A, co
 int fcmf_conv_gemm_runs(fcmf_gemm_ctx* ctx, const void* x, const void* w, void* y, float* stats, int n, int Hp, int Wp, int pix, int run,
                         int Ho, int Wo, int kh, int stride, int Cout, void* stream);
 /* crops in any layout (element strides of n, h, w, c; float32 / float64 / bf16; 3 channels) -> the interior of dst
- * [N, H + 2 pad, Wp, 4] bf16, Wp >= W + 2 pad (channel 3 = 0; the border is NOT written: zero it once) */
+ * [N, H + 2 pad, Wp, 4] bf16, Wp >= W + 2 pad (channel 3 = 0; the border is NOT written: zero it once).  Every value is rounded
+ * once, to the nearest bf16 with ties to even (a float64 source does not pass through float32). */
 int fcmf_pack_rgb0(const void* src, int src_dtype, void* dst, int N, int H, int W, int64_t sn, int64_t sh, int64_t sw, int64_t sc,
                    int pad, int Wp, void* stream);
 /* The 1x1 (plain GEMM: A [M, K] = the NHWC activation, W [N, K]) and implicit-GEMM convolutions with the statistics of the

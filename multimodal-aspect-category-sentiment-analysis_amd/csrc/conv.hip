@@ -2,7 +2,8 @@
 // resnet152).  Activations are NHWC ([N*H*W, C] row-major), so every convolution is a GEMM of the step's MFMA kernels
 // (gemm.hip): 1x1 / stride 1 directly on the activation matrix, everything else on the patch matrix built here.
 //   im2col_kernel        patch matrix [N*Ho*Wo, Kpad] (k = (r, s, c), zero padding and zero tail columns)
-//   bn_stats_kernel      GROUPED BatchNorm batch statistics: per (call group, channel) sum / sum of squares (double)
+//   bn_stats_kernel      GROUPED BatchNorm batch statistics: per (call group, row chunk, channel) sum / sum of squares (double),
+//                        summed per group by bn_reduce_chunks_kernel (bn_reduce_blocks_kernel: from a GEMM's block statistics)
 //   bn_finalize_kernel   statistics -> per-(group, channel) scale/shift + the running-statistics EMA in call order
 //   bn_apply_kernel      y = relu?(x * scale + shift (+ residual)), in place
 //   maxpool3x3s2_kernel  3x3 / stride 2 / pad 1
@@ -87,15 +88,17 @@ __global__ __launch_bounds__(256) void pack_rgb0_kernel(const TS* __restrict__ s
     const int64_t n = t / H;
     const TS* q = src + n * sn + h * sh + w * sw;
     bf16x4 o;
-    o[0] = (bf16_t)(float)q[0]; o[1] = (bf16_t)(float)q[sc]; o[2] = (bf16_t)(float)q[2 * sc]; o[3] = (bf16_t)0.f;
+    // ONE rounding from the source type, to nearest even: a float64 value is not rounded to float32 first
+    o[0] = (bf16_t)q[0]; o[1] = (bf16_t)q[sc]; o[2] = (bf16_t)q[2 * sc]; o[3] = (bf16_t)0.f;
     *reinterpret_cast<bf16x4*>(dst + ((n * Hp + h + pad) * Wp + w + pad) * 4) = o;
   }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // grouped batch statistics.  grid (channel slabs of 256, row chunks, groups); a thread owns 4 adjacent channels and
-// every (256 / vecs-per-row)-th row of its chunk; waves are reduced through LDS; one double atomic per channel and
-// workgroup.  sums [G, C, 2] (sum, sum of squares) must be zero on entry.
+// every (256 / vecs-per-row)-th row of its chunk; waves are reduced through LDS; the workgroup then STORES its (sum, sum of squares)
+// per channel as the partial [g][chunk][c][2] of `sums` (no atomics: `sums` need not be initialised, every partial is overwritten);
+// bn_reduce_chunks_kernel adds the chunks of a group into the totals behind the partials.
 // ---------------------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, double* __restrict__ sums, int C,
@@ -616,8 +619,9 @@ extern "C" int fcmf_conv_im2col(const void* src, int src_dtype, void* dst, int d
   if (!src || !dst || N <= 0 || H <= 0 || W <= 0 || C <= 0 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 ||
       Kpad < kh * kw * C)
     return FCMF_ERR_ARG;
+  // a kernel larger than the padded input has no output (the division below truncates towards zero: (-1) / 2 + 1 would be 1)
+  if (H + 2 * pad < kh || W + 2 * pad < kw) return FCMF_ERR_ARG;
   const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
-  if (Ho <= 0 || Wo <= 0) return FCMF_ERR_ARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t rows = (int64_t)N * Ho * Wo;
   const bool nhwc = sc == 1 && sw == C && sh == (int64_t)W * C && sn == (int64_t)H * W * C;
