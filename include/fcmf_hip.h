@@ -664,6 +664,28 @@ int fcmf_multi_adamw(const int64_t* p_ptrs, const int64_t* g_ptrs, const int64_t
                      const float* lr /*host[8]*/, const float* wd /*host[8]*/, int ngroups,
                      float beta1, float beta2, float eps, int step, const double* sumsq,
                      float max_norm, void* stream);
+/* fcmf_multi_adamw that also keeps an exponential moving average of the weights.  Every argument of fcmf_multi_adamw in
+ * the same order, then ema_ptrs (device table of float32 addresses, one per tensor, none zero) and ema_decay in [0, 1).
+ * p, m, v and the bf16 shadows come out bit-identical to fcmf_multi_adamw; then, per element, with the updated parameter
+ * p_new,
+ *     e = ema_decay * e + (1.0f - ema_decay) * p_new
+ * in float32, every product and the sum rounded on its own (no fused multiply-add; ema_decay == 0 gives e == p_new).  The
+ * result does not depend on the alignment of any tensor.  FCMF_ERR_ARG before any launch for ema_ptrs == NULL, an
+ * ema_decay that is not finite or lies outside [0, 1), and whatever fcmf_multi_adamw refuses. */
+int fcmf_multi_adamw_ema(const int64_t* p_ptrs, const int64_t* g_ptrs, const int64_t* m_ptrs,
+                         const int64_t* v_ptrs, const int64_t* bf16_ptrs, const int64_t* sizes,
+                         const int32_t* group_of, const int32_t* chunk_tensor,
+                         const int64_t* chunk_offset, int nchunks, int chunk_size,
+                         const float* lr /*host[8]*/, const float* wd /*host[8]*/, int ngroups,
+                         float beta1, float beta2, float eps, int step, const double* sumsq,
+                         float max_norm, void* stream, const int64_t* ema_ptrs, float ema_decay);
+/* Exchange the contents of the float32 tensors a[t] and b[t] of every tensor in one launch (the averaged weights in for
+ * evaluation, and back out).  Where bf16_ptrs is not NULL and bf16_ptrs[t] is not 0 the bf16 copy (round to nearest even)
+ * of what a[t] NOW holds is written there: the shadow convention of fcmf_multi_adamw.  Each element is read from both
+ * sides before either is written, by the lane that writes them, so a[t] == b[t] leaves the data as it is. */
+int fcmf_multi_swap(const int64_t* a_ptrs, const int64_t* b_ptrs, const int64_t* bf16_ptrs,
+                    const int64_t* sizes, const int32_t* chunk_tensor, const int64_t* chunk_offset,
+                    int nchunks, int chunk_size, void* stream);
 /* BertAdam.step for one tensor (optimization.py:94-162): per-parameter clip, no bias
  * correction, weight decay added to the update; `lr_scheduled` is computed by the host
  * from the warmup schedule. `scratch` is a device double[1]. */

@@ -341,7 +341,14 @@ struct AdamArgs {
   float max_norm;
 };
 
-__global__ __launch_bounds__(256) void multi_adamw_kernel(AdamArgs a) {
+// the averaged weights (fcmf_multi_adamw_ema): a second argument block, so that the plain instantiation keeps its kernel arguments
+struct AdamEmaArgs : AdamArgs {
+  const int64_t* ema_ptrs;
+  float ema_decay;
+};
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void multi_adamw_kernel(std::conditional_t<EMA, AdamEmaArgs, AdamArgs> a) {
   // every product and sum rounded on its own: left to the compiler, the 4-wide body and the scalar loop below were contracted
   // into different fused multiply-adds, and a parameter's trajectory depended on whether its storage is 16-byte aligned
   // (arena slices and packed buffers are not always).  The kernel is bound by its 28 bytes per element, not by these few ops.
@@ -353,6 +360,14 @@ __global__ __launch_bounds__(256) void multi_adamw_kernel(AdamArgs a) {
   float* m = reinterpret_cast<float*>(a.m_ptrs[t]) + off;
   float* v = reinterpret_cast<float*>(a.v_ptrs[t]) + off;
   bf16_t* sh = a.bf16_ptrs && a.bf16_ptrs[t] ? reinterpret_cast<bf16_t*>(a.bf16_ptrs[t]) + off : nullptr;
+  // EMA: e = decay * e + (1 - decay) * p_new, one float32 read and one write more per element (36 bytes against 28)
+  float* ema = nullptr;
+  float ema_d = 0.f, ema_1md = 0.f;
+  if constexpr (EMA) {
+    ema = reinterpret_cast<float*>(a.ema_ptrs[t]) + off;
+    ema_d = a.ema_decay;
+    ema_1md = 1.0f - a.ema_decay;
+  }
   int64_t n = a.sizes[t] - off;
   if (n > a.chunk_size) n = a.chunk_size;
   const int grp = a.group_of[t];
@@ -367,7 +382,7 @@ __global__ __launch_bounds__(256) void multi_adamw_kernel(AdamArgs a) {
   typedef float f4 __attribute__((ext_vector_type(4)));
   int64_t i0 = 0;
   if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0 &&
-      (!sh || (reinterpret_cast<uintptr_t>(sh) & 7) == 0)) {
+      (!sh || (reinterpret_cast<uintptr_t>(sh) & 7) == 0) && (!EMA || (reinterpret_cast<uintptr_t>(ema) & 15) == 0)) {
     const int64_t n4 = n >> 2;
     for (int64_t i = threadIdx.x; i < n4; i += 256) {
       const f4 g4 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(g) + i) * coef;
@@ -379,6 +394,10 @@ __global__ __launch_bounds__(256) void multi_adamw_kernel(AdamArgs a) {
       reinterpret_cast<f4*>(p)[i] = p4;
       __builtin_nontemporal_store(m4, reinterpret_cast<f4*>(m) + i);
       __builtin_nontemporal_store(v4, reinterpret_cast<f4*>(v) + i);
+      if constexpr (EMA) {
+        const f4 e4 = ema_d * __builtin_nontemporal_load(reinterpret_cast<const f4*>(ema) + i) + ema_1md * p4;
+        __builtin_nontemporal_store(e4, reinterpret_cast<f4*>(ema) + i);
+      }
       if (sh) {
         bf16x4 o;
         o[0] = (bf16_t)p4[0]; o[1] = (bf16_t)p4[1]; o[2] = (bf16_t)p4[2]; o[3] = (bf16_t)p4[3];
@@ -395,7 +414,46 @@ __global__ __launch_bounds__(256) void multi_adamw_kernel(AdamArgs a) {
     const float denom = sqrtf(vi) / a.bc2_sqrt + a.eps;
     pi -= step_size * (mi / denom);
     p[i] = pi; m[i] = mi; v[i] = vi;
+    if constexpr (EMA) __builtin_nontemporal_store(ema_d * __builtin_nontemporal_load(ema + i) + ema_1md * pi, ema + i);
     if (sh) sh[i] = (bf16_t)pi;
+  }
+}
+
+// a[t] <-> b[t] (float32), and the bf16 copy of what a[t] now holds: both sides are read before either is written, by the
+// lane that writes them, so a[t] == b[t] is harmless
+__global__ __launch_bounds__(256) void multi_swap_kernel(const int64_t* __restrict__ a_ptrs, const int64_t* __restrict__ b_ptrs,
+                                                         const int64_t* __restrict__ bf16_ptrs, const int64_t* __restrict__ sizes,
+                                                         const int32_t* __restrict__ chunk_tensor,
+                                                         const int64_t* __restrict__ chunk_offset, int chunk_size) {
+  const int t = chunk_tensor[blockIdx.x];
+  const int64_t off = chunk_offset[blockIdx.x];
+  float* pa = reinterpret_cast<float*>(a_ptrs[t]) + off;
+  float* pb = reinterpret_cast<float*>(b_ptrs[t]) + off;
+  bf16_t* sh = bf16_ptrs && bf16_ptrs[t] ? reinterpret_cast<bf16_t*>(bf16_ptrs[t]) + off : nullptr;
+  int64_t n = sizes[t] - off;
+  if (n > chunk_size) n = chunk_size;
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  int64_t i0 = 0;
+  if (((reinterpret_cast<uintptr_t>(pa) | reinterpret_cast<uintptr_t>(pb)) & 15) == 0 &&
+      (!sh || (reinterpret_cast<uintptr_t>(sh) & 7) == 0)) {
+    const int64_t n4 = n >> 2;
+    for (int64_t i = threadIdx.x; i < n4; i += 256) {
+      const f4 x = reinterpret_cast<const f4*>(pa)[i];
+      const f4 y = reinterpret_cast<const f4*>(pb)[i];
+      reinterpret_cast<f4*>(pa)[i] = y;
+      reinterpret_cast<f4*>(pb)[i] = x;
+      if (sh) {
+        bf16x4 o;
+        o[0] = (bf16_t)y[0]; o[1] = (bf16_t)y[1]; o[2] = (bf16_t)y[2]; o[3] = (bf16_t)y[3];
+        reinterpret_cast<bf16x4*>(sh)[i] = o;
+      }
+    }
+    i0 = n4 << 2;
+  }
+  for (int64_t i = i0 + threadIdx.x; i < n; i += 256) {
+    const float x = pa[i], y = pb[i];
+    pa[i] = y; pb[i] = x;
+    if (sh) sh[i] = (bf16_t)y;
   }
 }
 
@@ -716,16 +774,13 @@ extern "C" int fcmf_multi_sumsq(const int64_t* g_ptrs, const int64_t* sizes, con
   return FCMF_OK;
 }
 
-extern "C" int fcmf_multi_adamw(const int64_t* p_ptrs, const int64_t* g_ptrs, const int64_t* m_ptrs, const int64_t* v_ptrs,
-                                const int64_t* bf16_ptrs, const int64_t* sizes, const int32_t* group_of,
-                                const int32_t* chunk_tensor, const int64_t* chunk_offset, int nchunks, int chunk_size,
-                                const float* lr, const float* wd, int ngroups, float beta1, float beta2, float eps, int step,
-                                const double* sumsq, float max_norm, void* stream) {
+static int adamw_plan(AdamArgs& a, const int64_t* p_ptrs, const int64_t* g_ptrs, const int64_t* m_ptrs, const int64_t* v_ptrs,
+                      const int64_t* bf16_ptrs, const int64_t* sizes, const int32_t* group_of, const int32_t* chunk_tensor,
+                      const int64_t* chunk_offset, int nchunks, int chunk_size, const float* lr, const float* wd, int ngroups,
+                      float beta1, float beta2, float eps, int step, const double* sumsq, float max_norm) {
   if (!p_ptrs || !g_ptrs || !m_ptrs || !v_ptrs || !sizes || !group_of || !chunk_tensor || !chunk_offset || !lr || !wd)
     return FCMF_ERR_ARG;
   if (ngroups <= 0 || ngroups > 8 || step < 1 || chunk_size <= 0 || nchunks < 0) return FCMF_ERR_ARG;
-  if (nchunks == 0) return FCMF_OK;
-  AdamArgs a{};
   a.p_ptrs = p_ptrs; a.g_ptrs = g_ptrs; a.m_ptrs = m_ptrs; a.v_ptrs = v_ptrs; a.bf16_ptrs = bf16_ptrs; a.sizes = sizes;
   a.group_of = group_of; a.chunk_tensor = chunk_tensor; a.chunk_offset = chunk_offset; a.chunk_size = chunk_size;
   for (int i = 0; i < ngroups; ++i) { a.lr[i] = lr[i]; a.wd[i] = wd[i]; }
@@ -733,7 +788,48 @@ extern "C" int fcmf_multi_adamw(const int64_t* p_ptrs, const int64_t* g_ptrs, co
   a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   a.sumsq = sumsq; a.max_norm = max_norm;
-  hipLaunchKernelGGL(multi_adamw_kernel, dim3(nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return FCMF_OK;
+}
+
+extern "C" int fcmf_multi_adamw(const int64_t* p_ptrs, const int64_t* g_ptrs, const int64_t* m_ptrs, const int64_t* v_ptrs,
+                                const int64_t* bf16_ptrs, const int64_t* sizes, const int32_t* group_of,
+                                const int32_t* chunk_tensor, const int64_t* chunk_offset, int nchunks, int chunk_size,
+                                const float* lr, const float* wd, int ngroups, float beta1, float beta2, float eps, int step,
+                                const double* sumsq, float max_norm, void* stream) {
+  AdamArgs a{};
+  const int rc = adamw_plan(a, p_ptrs, g_ptrs, m_ptrs, v_ptrs, bf16_ptrs, sizes, group_of, chunk_tensor, chunk_offset, nchunks,
+                            chunk_size, lr, wd, ngroups, beta1, beta2, eps, step, sumsq, max_norm);
+  if (rc != FCMF_OK) return rc;
+  if (nchunks == 0) return FCMF_OK;
+  hipLaunchKernelGGL(multi_adamw_kernel<false>, dim3(nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  FCMF_CHECK_LAUNCH();
+  return FCMF_OK;
+}
+
+extern "C" int fcmf_multi_adamw_ema(const int64_t* p_ptrs, const int64_t* g_ptrs, const int64_t* m_ptrs, const int64_t* v_ptrs,
+                                    const int64_t* bf16_ptrs, const int64_t* sizes, const int32_t* group_of,
+                                    const int32_t* chunk_tensor, const int64_t* chunk_offset, int nchunks, int chunk_size,
+                                    const float* lr, const float* wd, int ngroups, float beta1, float beta2, float eps, int step,
+                                    const double* sumsq, float max_norm, void* stream, const int64_t* ema_ptrs, float ema_decay) {
+  AdamEmaArgs a{};
+  const int rc = adamw_plan(a, p_ptrs, g_ptrs, m_ptrs, v_ptrs, bf16_ptrs, sizes, group_of, chunk_tensor, chunk_offset, nchunks,
+                            chunk_size, lr, wd, ngroups, beta1, beta2, eps, step, sumsq, max_norm);
+  if (rc != FCMF_OK) return rc;
+  if (!ema_ptrs || !(ema_decay >= 0.0f && ema_decay < 1.0f)) return FCMF_ERR_ARG;      // (a NaN fails both comparisons)
+  if (nchunks == 0) return FCMF_OK;
+  a.ema_ptrs = ema_ptrs; a.ema_decay = ema_decay;
+  hipLaunchKernelGGL(multi_adamw_kernel<true>, dim3(nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  FCMF_CHECK_LAUNCH();
+  return FCMF_OK;
+}
+
+extern "C" int fcmf_multi_swap(const int64_t* a_ptrs, const int64_t* b_ptrs, const int64_t* bf16_ptrs, const int64_t* sizes,
+                               const int32_t* chunk_tensor, const int64_t* chunk_offset, int nchunks, int chunk_size,
+                               void* stream) {
+  if (!a_ptrs || !b_ptrs || !sizes || !chunk_tensor || !chunk_offset || chunk_size <= 0 || nchunks < 0) return FCMF_ERR_ARG;
+  if (nchunks == 0) return FCMF_OK;
+  hipLaunchKernelGGL(multi_swap_kernel, dim3(nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a_ptrs, b_ptrs,
+                     bf16_ptrs, sizes, chunk_tensor, chunk_offset, chunk_size);
   FCMF_CHECK_LAUNCH();
   return FCMF_OK;
 }

@@ -16,6 +16,8 @@ plus one fcmf_bn_apply pass with (s, t).  No statistics launch (fcmf_bn_stats*, 
 
 The snapshot is explicit: it does not go through the version-keyed shadow cache (BatchNorm buffers changing under an unchanged
 convolution weight would leave a stale entry there); `refresh()` rebuilds it after the module's parameters or buffers changed.
+(One change it learns of by itself: `FusedAdamW.ema_weights()` exchanging parameters and averaged weights counts `shadows.swaps`
+up, and a call that finds the count moved since the snapshot takes a new one first.)
 `resnet.Bottleneck.run`, `ResNet._trunk_pass` and `trunk_nhwc` are untouched: this is a second, opt-in walk.
 """
 import torch
@@ -67,6 +69,7 @@ class FoldedTrunk:
                                         "(train-mode BatchNorm normalises with batch statistics: nothing to fold)")
         H.require_cuda(net.conv1.weight)
         self.dtype = dt = ops.compute_dtype()
+        self._swaps = ops.shadows.swaps
         with torch.no_grad():
             self.stem_scale, self.stem_shift = (v.contiguous() for v in _affine(net.bn1))
             self.blocks = []
@@ -157,6 +160,8 @@ class FoldedTrunk:
     def __call__(self, x):
         """x [N, 3, H, W] (any float dtype / layout) -> NHWC [N, h, w, C], detached"""
         H.require_cuda(x)
+        if self._swaps != ops.shadows.swaps:
+            self.refresh()        # FusedAdamW.ema_weights() exchanged the weights since the snapshot (it cannot mark this copy stale)
         if ops.compute_dtype() != self.dtype:
             raise H.HipLibraryError(f"FoldedTrunk: snapshot taken in {self.dtype}, compute dtype is now {ops.compute_dtype()}: call refresh()")
         with torch.no_grad():

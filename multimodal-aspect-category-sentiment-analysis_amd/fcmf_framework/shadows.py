@@ -50,6 +50,7 @@ class Shadows:
         self._d = {}
         self._owners = {}      # id(owner) -> (weak reference, its address when its first entry was made): what `_prune` walks
         self._mt_tables = None
+        self.swaps = 0         # how often FusedAdamW.ema_weights() exchanged the parameters' contents (never reset)
 
     def __len__(self):
         return len(self._d)

@@ -31,8 +31,9 @@ from fcmf_framework import baselines, ops  # noqa: E402
 from fcmf_framework.dp import GradArena  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
-from train_harness import (add_loss_arguments, build_extractors, check_loss_arguments, class_weight_tensor, init_run,  # noqa: E402
-                           make_features, save_model, split_decay, train_epoch, train_label_table)
+from train_harness import (add_ema_arguments, add_loss_arguments, averaged, build_extractors, check_ema_arguments,  # noqa: E402
+                           check_loss_arguments, class_weight_tensor, init_run, make_features, save_model, setup_ema, split_decay,
+                           train_epoch, train_label_table)
 from run_multimodal_fcmf import POLARITY_MAP, macro_f1  # noqa: E402
 
 #            model class, checkpoint name before _best / _last (seed filled in), name in the log and result files
@@ -77,6 +78,7 @@ def build_parser():
     p.add_argument('--ffn_dropout', action='store_true',
                    help="nn.TransformerEncoderLayer's dropout between the feed-forward's gelu and its second Linear (ops.set_ffn_dropout)")
     add_loss_arguments(p)
+    add_ema_arguments(p)
     p.set_defaults(ddp=False)
     return p
 
@@ -202,6 +204,7 @@ def main(argv=None):
     if args.gradient_accumulation_steps < 1:
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
     weight_request = check_loss_arguments(args)
+    check_ema_arguments(args)
     cls_name, ckpt, tag = MODELS[args.model]
     ckpt = ckpt.format(seed=args.seed)
     fmt = logging.Formatter('%(asctime)s - %(levelname)s - %(name)s - %(message)s', datefmt='%m/%d/%Y %H:%M:%S')
@@ -237,6 +240,7 @@ def main(argv=None):
                                                       args.fine_tune_cnn, device)
     model = model.to(device)
     optimizer = FusedAdamW(param_groups(model), lr=args.learning_rate)
+    ema = setup_ema(optimizer, args, logger, True)          # before a checkpoint's optimizer state is loaded: its 'ema' is kept
     steps_per_epoch = len(train_loader) if train_loader is not None else 0
     num_train_steps = int(steps_per_epoch / args.gradient_accumulation_steps * args.num_train_epochs)
     scheduler = get_linear_schedule_with_warmup(optimizer, int(num_train_steps * args.warmup_proportion), num_train_steps)
@@ -280,11 +284,13 @@ def main(argv=None):
             if dev_loader is not None:
                 if resnet_img is not None:
                     resnet_img.eval(); resnet_roi.eval()
-                f1 = evaluate(args.model, model, dev_loader, device, features, aspects, logger)
+                with averaged(optimizer, ema):
+                    f1 = evaluate(args.model, model, dev_loader, device, features, aspects, logger)
             tags = ['last'] + (['best'] if f1 > max_f1 or not os.path.exists(f'{args.output_dir}/{ckpt}_best.pth') else [])
             max_f1 = max(max_f1, f1)
-            for t in tags:
-                save_model(f'{args.output_dir}/{ckpt}_{t}.pth', model, optimizer, scheduler, epoch, max_f1)
+            for t in tags:      # with --ema_decay `best` holds the averaged weights that earned the score, `last` the raw ones + the average
+                with averaged(optimizer, ema and t == 'best'):
+                    save_model(f'{args.output_dir}/{ckpt}_{t}.pth', model, optimizer, scheduler, epoch, max_f1)
     if args.do_eval and test_loader is not None:
         logger.info("===================== STARTING TEST EVALUATION =====================")
         best_path = f'{args.output_dir}/{ckpt}_best.pth'
@@ -294,7 +300,8 @@ def main(argv=None):
             ops.shadows.clear()
         else:
             logger.warning("No best model found! Using current weights.")
-        evaluate(args.model, model, test_loader, device, features, aspects, logger, output_dir=args.output_dir, tag=tag)
+        with averaged(optimizer, ema and not os.path.exists(best_path)):      # (a best checkpoint already holds the averaged weights)
+            evaluate(args.model, model, test_loader, device, features, aspects, logger, output_dir=args.output_dir, tag=tag)
     arena.deactivate()
     return last_loss[0]
 

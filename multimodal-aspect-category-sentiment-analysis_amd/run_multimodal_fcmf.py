@@ -42,8 +42,9 @@ from fcmf_framework.dp import GradArena, GradReducer  # noqa: E402
 from fcmf_framework.fcmf_multimodal import FCMF  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
-from train_harness import (add_loss_arguments, build_extractors, check_loss_arguments, class_weight_tensor, init_run,  # noqa: E402
-                           load_resnets, make_features, save_extractors, save_model, split_decay, train_epoch, train_label_table)
+from train_harness import (add_ema_arguments, add_loss_arguments, averaged, build_extractors, check_ema_arguments,  # noqa: E402
+                           check_loss_arguments, class_weight_tensor, init_run, load_resnets, make_features, save_extractors,
+                           save_model, setup_ema, split_decay, train_epoch, train_label_table)
 
 
 POLARITY_MAP = {0: 'None', 1: 'Negative', 2: 'Neutral', 3: 'Positive'}      # reference :28
@@ -102,6 +103,7 @@ def build_parser():
                         help="with --do_eval: the test-set pass also writes test_attention_maps.npz (head-averaged [CLS] "
                              "attention over each photo's patches and ROIs, per review and aspect) into --output_dir")
     add_loss_arguments(parser)
+    add_ema_arguments(parser)
     return parser
 
 
@@ -148,6 +150,7 @@ def main(argv=None):
     if args.gradient_accumulation_steps < 1:
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
     weight_request = check_loss_arguments(args)
+    check_ema_arguments(args)
     fmt = logging.Formatter('%(asctime)s - %(levelname)s - %(name)s - %(message)s', datefmt='%m/%d/%Y %H:%M:%S')
     rank, _, world, device, master, logger = init_run(args, "fcmf", "training_fcmf.log", formatter=fmt, script="run_multimodal_fcmf.py")
     args.train_batch_size = int(args.train_batch_size / args.gradient_accumulation_steps)
@@ -217,6 +220,7 @@ def main(argv=None):
         for p in model.encoder.parameters():
             p.requires_grad = False
     optimizer = FusedAdamW(param_groups(model, args), lr=args.classifier_head_learning_rate)
+    ema = setup_ema(optimizer, args, logger, master)        # before a checkpoint's optimizer state is loaded: its 'ema' is kept
     steps_per_epoch = len(train_loader) if train_loader is not None else 0
     num_train_steps = int(steps_per_epoch / args.gradient_accumulation_steps * args.num_train_epochs)
     scheduler = get_linear_schedule_with_warmup(optimizer, int(num_train_steps * args.warmup_proportion), num_train_steps)
@@ -275,15 +279,18 @@ def main(argv=None):
             if dev_loader is not None and master:
                 if resnet_img is not None:
                     resnet_img.eval(); resnet_roi.eval()              # reference :502
-                f1 = evaluate(model, dev_loader, device, features, len(ASPECT), logger)
+                with averaged(optimizer, ema):                        # the master alone swaps: no collective call inside
+                    f1 = evaluate(model, dev_loader, device, features, len(ASPECT), logger)
             if world > 1:
                 torch.distributed.barrier()
             if master:
                 tags = ['last'] + (['best'] if f1 > max_f1 else [])
                 max_f1 = max(max_f1, f1)
                 for tag in tags:                                      # reference :555-563: the model and BOTH extractors
-                    save_model(f'{args.output_dir}/seed_{args.seed}_fcmf_model_{tag}.pth', model, optimizer, scheduler, epoch, max_f1)
-                    save_extractors(args.output_dir, args.seed, tag, resnet_img, resnet_roi, optimizer, scheduler, epoch)
+                    # with --ema_decay `best` holds the averaged weights that earned the score, `last` the raw ones + the average
+                    with averaged(optimizer, ema and tag == 'best'):
+                        save_model(f'{args.output_dir}/seed_{args.seed}_fcmf_model_{tag}.pth', model, optimizer, scheduler, epoch, max_f1)
+                        save_extractors(args.output_dir, args.seed, tag, resnet_img, resnet_roi, optimizer, scheduler, epoch)
     # ---- 7. TEST EVALUATION (reference :567-694) ---------------------------------------------------------------------
     if args.do_eval and master and test_loader is not None:
         logger.info("===================== STARTING TEST EVALUATION =====================")
@@ -295,11 +302,14 @@ def main(argv=None):
             model.load_state_dict(ck['model_state_dict'], strict=False)
             ops.shadows.clear()
             load_resnets(best_path, resnet_img, resnet_roi, device, logger, old="fcmf", strict=False)      # :588-598
+            found = True
         else:
             logger.warning("No best model found! Using current weights.")
+            found = False
         if resnet_img is not None:
             resnet_img.eval(); resnet_roi.eval()
-        test_evaluate(model, test_loader, device, features, ASPECT, args.output_dir, logger, dump_maps=args.dump_attention_maps)
+        with averaged(optimizer, ema and not found):                  # (a best checkpoint already holds the averaged weights)
+            test_evaluate(model, test_loader, device, features, ASPECT, args.output_dir, logger, dump_maps=args.dump_attention_maps)
     arena.deactivate()
     if world > 1:
         torch.distributed.destroy_process_group()

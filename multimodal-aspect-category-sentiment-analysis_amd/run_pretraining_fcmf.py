@@ -45,8 +45,9 @@ from fcmf_framework.dp import GradArena, GradReducer  # noqa: E402
 from fcmf_framework.fcmf_pretraining import FCMFSeq2Seq  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
-from train_harness import (add_loss_arguments, build_extractors, check_loss_arguments, init_run, load_resnets,  # noqa: E402
-                           make_features, save_extractors, save_model, split_decay, train_epoch)
+from train_harness import (add_ema_arguments, add_loss_arguments, averaged, build_extractors, check_ema_arguments,  # noqa: E402
+                           check_loss_arguments, init_run, load_resnets, make_features, save_extractors, save_model, setup_ema,
+                           split_decay, train_epoch)
 
 
 DEFAULT_BERT_SCORE_MODEL = 'uitnlp/visobert'      # the reference's default (:53), a hub name
@@ -129,6 +130,7 @@ def build_parser():
     p.add_argument('--synthetic_eval_samples', type=int, default=0,
                    help="with --synthetic_steps and --do_eval: dev and test sets of N seeded synthetic samples each")
     add_loss_arguments(p, class_weights=False)
+    add_ema_arguments(p)
     return p
 
 
@@ -204,6 +206,7 @@ def main(argv=None):
                 raise ValueError(f"--suppress_tokens / --max_len_decoder: --vocab_size {args.vocab_size} cannot keep {width} tokens "
                                  f"unbanned (needs >= {need})")
     check_loss_arguments(args)
+    check_ema_arguments(args)
     rank, _, world, device, master, logger = init_run(args, "iaog", "pretraining_iaog.log", script="run_pretraining_fcmf.py")
 
     tokenizer = None
@@ -239,6 +242,7 @@ def main(argv=None):
     decay, exempt = split_decay(named)
     groups = [{'params': decay, 'weight_decay': 1e-5}, {'params': exempt, 'weight_decay': 0.0}]
     optimizer = FusedAdamW(groups, lr=args.learning_rate, eps=args.adam_epsilon)
+    ema = setup_ema(optimizer, args, logger, master)        # before a checkpoint's optimizer state is loaded: its 'ema' is kept
 
     if args.synthetic_steps > 0:
         import synthetic_data as synth
@@ -403,18 +407,20 @@ def main(argv=None):
             train_epoch(DevicePrefetcher(make_loader(), device), loss_fn, arena=arena, reducer=reducer, optimizer=optimizer,
                         scheduler=scheduler, accum=args.gradient_accumulation_steps, log=log if master else None)
             if evaluate is not None:                                     # reference :376-452; the other ranks wait at the barrier below
-                logger.info("***** Running evaluation on Dev Set with BEAM SEARCH *****")
-                per_aspect, macro, _ = evaluate(dev_set())
-                logger.info("Computing BERTScore for Dev Set using model: %s ...", bert_score_dir)
-                for a, m in per_aspect.items():
-                    if m is not None:
-                        logger.info("  Aspect: " + aspect_line(a, m))
-                logger.info("Epoch %d [Macro-Avg] F1: %.4f", epoch, macro[2])
-                if macro[2] > best_score:
-                    best_score = macro[2]
-                    logger.info("New Best F1-Score (%.4f)! Saving model...", best_score)
-                    save_model(f'{args.output_dir}/seed_{args.seed}_iaog_model_best.pth', model, optimizer, scheduler, epoch, best_score)
-                    save_extractors(args.output_dir, args.seed, 'best', r_img, r_roi, optimizer, scheduler, epoch, best_score)
+                # (with --ema_decay the decode, the score and the best checkpoint are the averaged weights'; the master alone swaps)
+                with averaged(optimizer, ema):
+                    logger.info("***** Running evaluation on Dev Set with BEAM SEARCH *****")
+                    per_aspect, macro, _ = evaluate(dev_set())
+                    logger.info("Computing BERTScore for Dev Set using model: %s ...", bert_score_dir)
+                    for a, m in per_aspect.items():
+                        if m is not None:
+                            logger.info("  Aspect: " + aspect_line(a, m))
+                    logger.info("Epoch %d [Macro-Avg] F1: %.4f", epoch, macro[2])
+                    if macro[2] > best_score:
+                        best_score = macro[2]
+                        logger.info("New Best F1-Score (%.4f)! Saving model...", best_score)
+                        save_model(f'{args.output_dir}/seed_{args.seed}_iaog_model_best.pth', model, optimizer, scheduler, epoch, best_score)
+                        save_extractors(args.output_dir, args.seed, 'best', r_img, r_roi, optimizer, scheduler, epoch, best_score)
             if world > 1:
                 torch.distributed.barrier()
             if master:
@@ -428,7 +434,8 @@ def main(argv=None):
             ops.shadows.clear()
             load_resnets(best, r_img, r_roi, device, logger, old="iaog_model")
         logger.info("Computing BERTScore for Test Set using model: %s ...", bert_score_dir)
-        per_aspect, macro, results = evaluate(test_set())
+        with averaged(optimizer, ema and not os.path.exists(best)):       # (a best checkpoint already holds the averaged weights)
+            per_aspect, macro, results = evaluate(test_set())
         log_path = f"{args.output_dir}/iaog_test_predictions_formatted.txt"
         write_predictions(log_path, bert_score_dir, per_aspect, macro, results)
         for a, m in per_aspect.items():

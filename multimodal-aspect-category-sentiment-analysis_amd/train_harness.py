@@ -2,6 +2,7 @@
 ResNet-152 extractors with their checkpoints beside the model's, the weight-decay split and the loop of one epoch.  Each
 driver keeps its parser, model, data, parameter groups, loss call and (fine-tuning) evaluation.  File:line citations are
 into the reference's two drivers."""
+import contextlib
 import json
 import logging
 import math
@@ -66,6 +67,44 @@ def check_loss_arguments(args):
     if not all(math.isfinite(v) and v >= 0.0 for v in values) or sum(values) <= 0.0:
         raise ValueError(f"--class_weights must be finite, >= 0 and not all zero, got {spec!r}")
     return values
+
+
+# ---- averaged weights (FusedAdamW.set_ema / ema_weights) ------------------------------------------------------------------------
+def add_ema_arguments(parser):
+    parser.add_argument('--ema_decay', default=0.0, type=float,
+                        help="keep an exponential moving average of the optimizer's parameters, updated inside the AdamW kernel, "
+                             "with this decay in (0, 1); 0 = off.  The dev evaluation of every epoch runs on the averaged weights, "
+                             "*_best.pth is chosen by their score and holds them, *_last.pth holds the raw weights and carries the "
+                             "average in the optimizer state.  BatchNorm running statistics of the ResNet trunks are buffers, not "
+                             "optimizer parameters: they are not averaged")
+    parser.add_argument('--ema_no_warmup', action='store_true',
+                        help="use --ema_decay from the first step on; default: step t uses min(ema_decay, (1 + t) / (10 + t))")
+
+
+def check_ema_arguments(args):
+    """refuses a bad --ema_decay with a ValueError that names the flag (call before anything is created or written)
+    -> the decay, 0.0 = off"""
+    d = args.ema_decay
+    if not (math.isfinite(d) and 0.0 <= d < 1.0):
+        raise ValueError(f"--ema_decay must lie in [0, 1), got {d}")
+    return d
+
+
+def setup_ema(optimizer, args, logger, master):
+    """turn the average on as the flags ask (every rank: all of them take the same steps) -> whether it is on"""
+    if args.ema_decay <= 0.0:
+        return False
+    optimizer.set_ema(args.ema_decay, warmup=not args.ema_no_warmup)
+    if master:
+        logger.info("weight EMA: decay %g, %s; dev evaluation and *_best.pth use the averaged weights", args.ema_decay,
+                    "no warmup" if args.ema_no_warmup else "warmup min(decay, (1 + t) / (10 + t)) at optimizer step t")
+    return True
+
+
+def averaged(optimizer, on):
+    """`with averaged(optimizer, ema and master):` -- the block runs on the averaged weights (one swap launch in, one out; no
+    collective call, so one rank may enter alone), or on the parameters as they are"""
+    return optimizer.ema_weights() if on else contextlib.nullcontext()
 
 
 def balanced_class_weights(labels, num_classes):
