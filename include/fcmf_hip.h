@@ -585,6 +585,36 @@ int fcmf_xent_bwd_ex(const void* logits, int64_t ld, const int64_t* labels, cons
                      void* dlogits, int64_t ldd, const float* scales, const float* grad, int n, int C, int segments,
                      int64_t ignore_index, float eps, float gamma, int dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Symmetric KL divergence of row pairs: the consistency term of R-Drop (Liang et al., 2021; csrc/loss.hip).  For a pair of
+ * logit rows a, b of C columns, with p = softmax(a), q = softmax(b), d_c = a_c - b_c:
+ *   k        = 1/2 [KL(p||q) + KL(q||p)] = 1/2 sum_c (p_c - q_c) d_c      (log p_c - log q_c = d_c - (lse a - lse b), sum(p - q) = 0)
+ *   dk/da_j  =  1/2 [p_j (d_j - E_p d) + p_j - q_j]
+ *   dk/db_j  = -1/2 [q_j (d_j - E_q d) + p_j - q_j]
+ *   loss     = alpha * sum_s [ sum_{r in s, live} k_r / #live pairs of s ]
+ * A constant added to d changes none of the three; the kernels take d around max a - max b (float32: 1/2 (E_p d - E_q d) of the
+ * raw d loses the digits of k to a common offset of the rows).  No log is taken.  Bitwise-equal rows give k == 0 and all-zero
+ * gradients exactly.  Pair r belongs to segment r % segments, as in fcmf_xent_*_ex.  `labels` (int64 [n], may be NULL = all
+ * live) only decides liveness: a pair whose label equals ignore_index is dead.
+ *   a, b [n, >= C] of `dtype` (FCMF_F32 / FCMF_BF16), row strides lda, ldb >= C elements; finite logits.
+ * C < 1024: one wave per pair; C >= 1024: one workgroup per pair in one pass over the rows, 16-byte accesses when both rows (and,
+ * backward, both destinations) and their strides are 16-byte aligned, element accesses otherwise.  float32 arithmetic, no
+ * atomics, a fixed order.  FCMF_ERR_ARG before any launch for a null pointer (labels and grad excepted), n < 0, C < 1,
+ * segments < 1, n % segments != 0 or a stride below C; FCMF_ERR_UNSUPPORTED for another dtype; n == 0 succeeds without a launch.
+ *
+ * fcmf_symkl_fwd: num[r] = k_r, den[r] = 1 for a live pair, both 0 for a dead one.  fcmf_xent_reduce_ex(num, den, n, segments,
+ * mult = alpha) then yields the loss and scales[s] = alpha / #live pairs of s. */
+int fcmf_symkl_fwd(const void* a, int64_t lda, const void* b, int64_t ldb, const int64_t* labels, float* num, float* den, int n,
+                   int C, int segments, int64_t ignore_index, int dtype, void* stream);
+/* da[r, j] = sc dk/da_j, db[r, j] = sc dk/db_j, sc = scales[r % segments] * (grad ? *grad : 1) (grad: device float32 [1], the
+ * upstream gradient).  acc = 0 writes; acc = 1 adds to what da / db hold (each element is read and written by the same thread).
+ * A dead pair, or one whose sc is 0, gets zeros with acc = 0 and is left alone with acc = 1.  da, db have `dtype` and row strides
+ * ldda, lddb >= C; columns at or past C are never touched.  FCMF_ERR_ARG also for acc outside {0, 1} and when the rows of da or
+ * db overlap those of a or b, or each other. */
+int fcmf_symkl_bwd(const void* a, int64_t lda, const void* b, int64_t ldb, const int64_t* labels, void* da, int64_t ldda, void* db,
+                   int64_t lddb, const float* scales, const float* grad, int n, int C, int segments, int64_t ignore_index, int acc,
+                   int dtype, void* stream);
+
 /* torch.nn.BCEWithLogitsLoss() (mean over n x C) of the multi-label photo-category head (image_processing/
  * run_image_categories.py:175,186), in one launch of one workgroup (classifier heads: n x C of a few thousand):
  *   logits [n, C] of `dtype` (row stride ld elements), target float32 [n, C] (row stride ldt; may be NULL when only probs

@@ -13,6 +13,7 @@
 //   * the smoothing sum is W log s - sum_c w_c (x_c - m); the wide kernel, which learns m only at the end of its one pass,
 //     gathers sum w_c (x_c - r_t) around a per-thread reference r_t (its first element) and shifts by (r_t - m) W_t afterwards,
 //     so a common offset of the logits never meets the sum.
+// Below them: the symmetric KL divergence of row pairs (the R-Drop consistency term), in the same two shapes.
 // MODE: 0 = no smoothing (the weight is read at the label only), 1 = smoothing with unit weights, 2 = smoothing with weights.
 #include "common.h"
 
@@ -295,6 +296,232 @@ __global__ __launch_bounds__(256) void xent_ex_bwd_wide_kernel(const T* logits, 
   }
 }
 
+// ---- symmetric KL of row pairs (R-Drop): k = 1/2 [KL(p||q) + KL(q||p)] = 1/2 sum_c (p_c - q_c) d_c, d = a - b ---------------------
+// A constant added to d changes neither k nor its gradients, so d is taken around max a - max b: d'_c = (a_c - max a) -
+// (b_c - max b).  With S_a = sum exp(a - max a), T_a = sum exp(a - max a) d' (S_b, T_b likewise):
+//   k       = 1/2 (T_a / S_a - T_b / S_b)
+//   dk/da_j =  1/2 [p_j (d'_j - T_a / S_a) + p_j - q_j],   dk/db_j = -1/2 [q_j (d'_j - T_b / S_b) + p_j - q_j]
+// Both sides run through the same inlined code, so bitwise-equal rows give S_a == S_b, T_a == T_b == 0, p_j == q_j: k and both
+// gradients are exactly zero.  No log anywhere.  Finite logits are assumed (a -inf column has no d).
+struct PairStats { float ma, mb, ia, ib, Ea, Eb; };      // the maxima, 1 / S and T / S of the two rows
+
+__device__ __forceinline__ PairStats pair_stats(float ma, float mb, float sa, float sb, float ta, float tb) {
+  PairStats p;
+  p.ma = ma; p.mb = mb;
+  p.ia = 1.0f / sa; p.ib = 1.0f / sb;
+  p.Ea = ta / sa; p.Eb = tb / sb;
+  return p;
+}
+
+// one side's share of an element: s += e, t += e * d with e = exp(x - m)
+__device__ __forceinline__ void pair_side(float x, float m, float d, float& s, float& t) {
+  const float e = __expf(x - m);
+  s += e;
+  t += e * d;
+}
+
+// the two gradients of one column: xa, xb the logits, h = 1/2 * scale.  No contraction here: p - q fused into fma(e_a, 1 / S_a, -q)
+// would subtract a rounded q from an unrounded p and leave ~1e-10 where equal rows must give an exact zero.
+__device__ __forceinline__ void pair_grads(const PairStats& st, float xa, float xb, float h, float& ga, float& gb) {
+#pragma clang fp contract(off)
+  const float da = xa - st.ma, db = xb - st.mb, d = da - db;
+  const float p = __expf(da) * st.ia, q = __expf(db) * st.ib, pq = p - q;
+  ga = h * (p * (d - st.Ea) + pq);
+  gb = -h * (q * (d - st.Eb) + pq);
+}
+
+__device__ __forceinline__ bool pair_live(const int64_t* __restrict__ labels, int r, int64_t ignore_index) {
+  return !labels || labels[r] != ignore_index;
+}
+
+// one wave per pair (C < 1024): a pass for the maxima, a pass for the sums; every lane returns the same values
+template <typename T>
+__device__ __forceinline__ PairStats wave_pair_stats(const T* __restrict__ ar, const T* __restrict__ br, int C) {
+  const int lane = threadIdx.x & 63;
+  float ma = -INFINITY, mb = -INFINITY;
+  for (int c = lane; c < C; c += 64) { ma = fmaxf(ma, to_f32<T>(ar[c])); mb = fmaxf(mb, to_f32<T>(br[c])); }
+  ma = wave_max(ma); mb = wave_max(mb);
+  float sa = 0.f, sb = 0.f, ta = 0.f, tb = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float xa = to_f32<T>(ar[c]), xb = to_f32<T>(br[c]);
+    const float d = (xa - ma) - (xb - mb);
+    pair_side(xa, ma, d, sa, ta);
+    pair_side(xb, mb, d, sb, tb);
+  }
+  return pair_stats(ma, mb, wave_sum(sa), wave_sum(sb), wave_sum(ta), wave_sum(tb));
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void symkl_fwd_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b, int64_t ldb,
+                                                        const int64_t* __restrict__ labels, float* __restrict__ num,
+                                                        float* __restrict__ den, int n, int C, int64_t ignore_index) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;
+  if (!pair_live(labels, r, ignore_index)) {
+    if (lane == 0) { num[r] = 0.f; den[r] = 0.f; }
+    return;
+  }
+  const PairStats st = wave_pair_stats<T>(a + (int64_t)r * lda, b + (int64_t)r * ldb, C);
+  if (lane == 0) { num[r] = 0.5f * (st.Ea - st.Eb); den[r] = 1.0f; }
+}
+
+template <typename T, bool ACC>
+__global__ __launch_bounds__(256) void symkl_bwd_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b, int64_t ldb,
+                                                        const int64_t* __restrict__ labels, T* __restrict__ da, int64_t ldda,
+                                                        T* __restrict__ db, int64_t lddb, const float* __restrict__ scales,
+                                                        const float* __restrict__ gptr, int n, int C, int segments,
+                                                        int64_t ignore_index) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;
+  T* dar = da + (int64_t)r * ldda;
+  T* dbr = db + (int64_t)r * lddb;
+  const float sc = scales[r % segments] * (gptr ? *gptr : 1.0f);
+  if (!pair_live(labels, r, ignore_index) || sc == 0.f) {      // sc == 0: a segment without a live pair
+    if (!ACC)
+      for (int c = lane; c < C; c += 64) { dar[c] = from_f32<T>(0.f); dbr[c] = from_f32<T>(0.f); }
+    return;
+  }
+  const T* ar = a + (int64_t)r * lda;
+  const T* br = b + (int64_t)r * ldb;
+  const PairStats st = wave_pair_stats<T>(ar, br, C);
+  const float h = 0.5f * sc;
+  for (int c = lane; c < C; c += 64) {
+    float ga, gb;
+    pair_grads(st, to_f32<T>(ar[c]), to_f32<T>(br[c]), h, ga, gb);
+    if (ACC) { ga += to_f32<T>(dar[c]); gb += to_f32<T>(dbr[c]); }
+    dar[c] = from_f32<T>(ga);
+    dbr[c] = from_f32<T>(gb);
+  }
+}
+
+// one workgroup per pair (C >= 1024), ONE pass over the two rows: a thread learns the maxima only at the end, so it gathers
+// exp(x - running max) d around its own reference rho_t = a_first - b_first (the idea of block_row_stats' smoothing sum) and
+// shifts by (rho_t - (max a - max b)) S_t once the block's maxima are known.  Every thread returns the same values.
+template <typename T>
+__device__ __forceinline__ PairStats block_pair_stats(const T* ar, const T* br, int C, bool vec) {
+  constexpr int VN = XVec<T>::N;
+  typedef typename XVec<T>::type vec_t;
+  __shared__ float red[6][4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int Cv = vec ? (C / VN) * VN : 0;
+  float ma = -INFINITY, mb = -INFINITY, sa = 0.f, sb = 0.f, ta = 0.f, tb = 0.f, ra = 0.f, rb = 0.f;
+  {
+    const int c0 = tid * VN < Cv ? tid * VN : Cv + tid;
+    if (c0 < C) { ra = to_f32<T>(ar[c0]); rb = to_f32<T>(br[c0]); }
+  }
+  for (int c = tid * VN; c < Cv; c += 256 * VN) {
+    const vec_t va = *reinterpret_cast<const vec_t*>(ar + c);
+    const vec_t vb = *reinterpret_cast<const vec_t*>(br + c);
+    float xa[VN], xb[VN], na = ma, nb = mb;
+#pragma unroll
+    for (int e = 0; e < VN; ++e) { xa[e] = (float)va[e]; xb[e] = (float)vb[e]; na = fmaxf(na, xa[e]); nb = fmaxf(nb, xb[e]); }
+    const float fa = ma == -INFINITY ? 0.f : __expf(ma - na), fb = mb == -INFINITY ? 0.f : __expf(mb - nb);
+    sa *= fa; ta *= fa; sb *= fb; tb *= fb;
+    ma = na; mb = nb;
+#pragma unroll
+    for (int e = 0; e < VN; ++e) {
+      const float d = (xa[e] - ra) - (xb[e] - rb);
+      pair_side(xa[e], ma, d, sa, ta);
+      pair_side(xb[e], mb, d, sb, tb);
+    }
+  }
+  for (int c = Cv + tid; c < C; c += 256) {
+    const float xa = to_f32<T>(ar[c]), xb = to_f32<T>(br[c]);
+    const float na = fmaxf(ma, xa), nb = fmaxf(mb, xb);
+    const float fa = ma == -INFINITY ? 0.f : __expf(ma - na), fb = mb == -INFINITY ? 0.f : __expf(mb - nb);
+    sa *= fa; ta *= fa; sb *= fb; tb *= fb;
+    ma = na; mb = nb;
+    const float d = (xa - ra) - (xb - rb);
+    pair_side(xa, ma, d, sa, ta);
+    pair_side(xb, mb, d, sb, tb);
+  }
+  const float wa = wave_max(ma), wb = wave_max(mb);
+  if (lane == 0) { red[0][w] = wa; red[1][w] = wb; }
+  __syncthreads();
+  const float Ma = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+  const float Mb = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+  // to the block's maxima and the block's centre (a thread without elements has s = t = 0 and a factor of 0)
+  const float fa = ma == -INFINITY ? 0.f : __expf(ma - Ma), fb = mb == -INFINITY ? 0.f : __expf(mb - Mb);
+  const float shift = (ra - rb) - (Ma - Mb);
+  ta = (ta + shift * sa) * fa; sa *= fa;
+  tb = (tb + shift * sb) * fb; sb *= fb;
+  sa = wave_sum(sa); sb = wave_sum(sb); ta = wave_sum(ta); tb = wave_sum(tb);
+  if (lane == 0) { red[2][w] = sa; red[3][w] = sb; red[4][w] = ta; red[5][w] = tb; }
+  __syncthreads();
+  return pair_stats(Ma, Mb, (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]), (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]),
+                    (red[4][0] + red[4][1]) + (red[4][2] + red[4][3]), (red[5][0] + red[5][1]) + (red[5][2] + red[5][3]));
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void symkl_fwd_wide_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b, int64_t ldb,
+                                                             const int64_t* __restrict__ labels, float* __restrict__ num,
+                                                             float* __restrict__ den, int C, int64_t ignore_index, int vec) {
+  const int r = blockIdx.x;
+  if (!pair_live(labels, r, ignore_index)) {
+    if (threadIdx.x == 0) { num[r] = 0.f; den[r] = 0.f; }
+    return;
+  }
+  const PairStats st = block_pair_stats<T>(a + (int64_t)r * lda, b + (int64_t)r * ldb, C, vec != 0);
+  if (threadIdx.x == 0) { num[r] = 0.5f * (st.Ea - st.Eb); den[r] = 1.0f; }
+}
+
+// the second pass re-reads the two rows (L2) and, with ACC, the destinations: each element is read and written by the same thread
+template <typename T, bool ACC>
+__global__ __launch_bounds__(256) void symkl_bwd_wide_kernel(const T* __restrict__ a, int64_t lda, const T* __restrict__ b, int64_t ldb,
+                                                             const int64_t* __restrict__ labels, T* __restrict__ da, int64_t ldda,
+                                                             T* __restrict__ db, int64_t lddb, const float* __restrict__ scales,
+                                                             const float* __restrict__ gptr, int C, int segments,
+                                                             int64_t ignore_index, int vec) {
+  constexpr int VN = XVec<T>::N;
+  typedef typename XVec<T>::type vec_t;
+  const int r = blockIdx.x, tid = threadIdx.x;
+  T* dar = da + (int64_t)r * ldda;
+  T* dbr = db + (int64_t)r * lddb;
+  const int Cv = vec ? (C / VN) * VN : 0;
+  const float sc = scales[r % segments] * (gptr ? *gptr : 1.0f);
+  if (!pair_live(labels, r, ignore_index) || sc == 0.f) {
+    if (!ACC) {
+      vec_t z;
+#pragma unroll
+      for (int e = 0; e < VN; ++e) z[e] = from_f32<T>(0.f);
+      for (int c = tid * VN; c < Cv; c += 256 * VN) { *reinterpret_cast<vec_t*>(dar + c) = z; *reinterpret_cast<vec_t*>(dbr + c) = z; }
+      for (int c = Cv + tid; c < C; c += 256) { dar[c] = from_f32<T>(0.f); dbr[c] = from_f32<T>(0.f); }
+    }
+    return;
+  }
+  const T* ar = a + (int64_t)r * lda;
+  const T* br = b + (int64_t)r * ldb;
+  const PairStats st = block_pair_stats<T>(ar, br, C, vec != 0);
+  const float h = 0.5f * sc;
+  for (int c = tid * VN; c < Cv; c += 256 * VN) {
+    const vec_t va = *reinterpret_cast<const vec_t*>(ar + c);
+    const vec_t vb = *reinterpret_cast<const vec_t*>(br + c);
+    float ga[VN], gb[VN];
+#pragma unroll
+    for (int e = 0; e < VN; ++e) pair_grads(st, (float)va[e], (float)vb[e], h, ga[e], gb[e]);
+    if (ACC) {
+      const vec_t pa = *reinterpret_cast<const vec_t*>(dar + c);
+      const vec_t pb = *reinterpret_cast<const vec_t*>(dbr + c);
+#pragma unroll
+      for (int e = 0; e < VN; ++e) { ga[e] += (float)pa[e]; gb[e] += (float)pb[e]; }
+    }
+    vec_t oa, ob;
+#pragma unroll
+    for (int e = 0; e < VN; ++e) { oa[e] = from_f32<T>(ga[e]); ob[e] = from_f32<T>(gb[e]); }
+    *reinterpret_cast<vec_t*>(dar + c) = oa;
+    *reinterpret_cast<vec_t*>(dbr + c) = ob;
+  }
+  for (int c = Cv + tid; c < C; c += 256) {
+    float ga, gb;
+    pair_grads(st, to_f32<T>(ar[c]), to_f32<T>(br[c]), h, ga, gb);
+    if (ACC) { ga += to_f32<T>(dar[c]); gb += to_f32<T>(dbr[c]); }
+    dar[c] = from_f32<T>(ga);
+    dbr[c] = from_f32<T>(gb);
+  }
+}
+
 // ---- reduction: ONE workgroup, fixed order, float64 partial sums -------------------------------------------------------------
 // The segments are taken one after the other; thread t sums the segment's rows s + t segments, s + (t + 256) segments, ...,
 // the waves meet in a fixed butterfly and their four partial sums are added in wave order.  loss[0] = mult * sum_s N_s / D_s
@@ -409,6 +636,81 @@ extern "C" int fcmf_xent_bwd_ex(const void* logits, int64_t ld, const int64_t* l
     xent_ex_bwd_launch<float>(st, mode, vec, (const float*)logits, ld, labels, weight, wstride, (float*)dlogits, ldd, scales, grad, n, C, segments, ignore_index, eps, gamma);
   else
     xent_ex_bwd_launch<bf16_t>(st, mode, vec, (const bf16_t*)logits, ld, labels, weight, wstride, (bf16_t*)dlogits, ldd, scales, grad, n, C, segments, ignore_index, eps, gamma);
+  FCMF_CHECK_LAUNCH();
+  return FCMF_OK;
+}
+
+// ---- symmetric KL: host ----------------------------------------------------------------------------------------------------
+static int symkl_args(const void* a, int64_t lda, const void* b, int64_t ldb, int n, int C, int segments, int dtype) {
+  if (!a || !b || n < 0 || C <= 0 || lda < C || ldb < C || segments < 1 || n % segments != 0) return FCMF_ERR_ARG;
+  if (dtype != FCMF_F32 && dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
+  return FCMF_OK;
+}
+
+// do the n rows of C elements behind p (stride ld) and behind q (stride ldq) share a byte?
+static bool symkl_overlap(const void* p, int64_t ld, const void* q, int64_t ldq, int n, int C, int es) {
+  const uintptr_t p0 = reinterpret_cast<uintptr_t>(p), q0 = reinterpret_cast<uintptr_t>(q);
+  const uintptr_t p1 = p0 + (uintptr_t)(((int64_t)(n - 1) * ld + C) * es), q1 = q0 + (uintptr_t)(((int64_t)(n - 1) * ldq + C) * es);
+  return p0 < q1 && q0 < p1;
+}
+
+template <typename T>
+static void symkl_fwd_launch(hipStream_t st, int vec, const T* a, int64_t lda, const T* b, int64_t ldb, const int64_t* labels, float* num,
+                             float* den, int n, int C, int64_t ignore_index) {
+  if (C >= 1024)
+    hipLaunchKernelGGL((symkl_fwd_wide_kernel<T>), dim3(n), dim3(256), 0, st, a, lda, b, ldb, labels, num, den, C, ignore_index, vec);
+  else
+    hipLaunchKernelGGL((symkl_fwd_kernel<T>), dim3((n + 3) / 4), dim3(256), 0, st, a, lda, b, ldb, labels, num, den, n, C, ignore_index);
+}
+
+template <typename T, bool ACC>
+static void symkl_bwd_launch(hipStream_t st, int vec, const T* a, int64_t lda, const T* b, int64_t ldb, const int64_t* labels, T* da,
+                             int64_t ldda, T* db, int64_t lddb, const float* scales, const float* grad, int n, int C, int segments,
+                             int64_t ignore_index) {
+  if (C >= 1024)
+    hipLaunchKernelGGL((symkl_bwd_wide_kernel<T, ACC>), dim3(n), dim3(256), 0, st, a, lda, b, ldb, labels, da, ldda, db, lddb, scales,
+                       grad, C, segments, ignore_index, vec);
+  else
+    hipLaunchKernelGGL((symkl_bwd_kernel<T, ACC>), dim3((n + 3) / 4), dim3(256), 0, st, a, lda, b, ldb, labels, da, ldda, db, lddb,
+                       scales, grad, n, C, segments, ignore_index);
+}
+
+extern "C" int fcmf_symkl_fwd(const void* a, int64_t lda, const void* b, int64_t ldb, const int64_t* labels, float* num, float* den,
+                              int n, int C, int segments, int64_t ignore_index, int dtype, void* stream) {
+  if (!num || !den) return FCMF_ERR_ARG;
+  const int rc = symkl_args(a, lda, b, ldb, n, C, segments, dtype);
+  if (rc != FCMF_OK) return rc;
+  if (n == 0) return FCMF_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int vec = xent_ex_vec(a, lda, b, ldb, nullptr, 0, 1, dtype);
+  if (dtype == FCMF_F32)
+    symkl_fwd_launch<float>(st, vec, (const float*)a, lda, (const float*)b, ldb, labels, num, den, n, C, ignore_index);
+  else
+    symkl_fwd_launch<bf16_t>(st, vec, (const bf16_t*)a, lda, (const bf16_t*)b, ldb, labels, num, den, n, C, ignore_index);
+  FCMF_CHECK_LAUNCH();
+  return FCMF_OK;
+}
+
+extern "C" int fcmf_symkl_bwd(const void* a, int64_t lda, const void* b, int64_t ldb, const int64_t* labels, void* da, int64_t ldda,
+                              void* db, int64_t lddb, const float* scales, const float* grad, int n, int C, int segments,
+                              int64_t ignore_index, int acc, int dtype, void* stream) {
+  if (!da || !db || !scales || ldda < C || lddb < C || (acc != 0 && acc != 1)) return FCMF_ERR_ARG;
+  const int rc = symkl_args(a, lda, b, ldb, n, C, segments, dtype);
+  if (rc != FCMF_OK) return rc;
+  if (n == 0) return FCMF_OK;
+  const int es = dtype == FCMF_F32 ? 4 : 2;
+  if (symkl_overlap(da, ldda, a, lda, n, C, es) || symkl_overlap(da, ldda, b, ldb, n, C, es) ||
+      symkl_overlap(db, lddb, a, lda, n, C, es) || symkl_overlap(db, lddb, b, ldb, n, C, es) ||
+      symkl_overlap(da, ldda, db, lddb, n, C, es))
+    return FCMF_ERR_ARG;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int vec = xent_ex_vec(a, lda, b, ldb, nullptr, 0, 1, dtype) && xent_ex_vec(da, ldda, db, lddb, nullptr, 0, 1, dtype);
+#define SYMKL_BWD(T, ACC)                                                                                                     \
+  symkl_bwd_launch<T, ACC>(st, vec, (const T*)a, lda, (const T*)b, ldb, labels, (T*)da, ldda, (T*)db, lddb, scales, grad, n, C, \
+                           segments, ignore_index)
+  if (dtype == FCMF_F32) { if (acc) SYMKL_BWD(float, true); else SYMKL_BWD(float, false); }
+  else { if (acc) SYMKL_BWD(bf16_t, true); else SYMKL_BWD(bf16_t, false); }
+#undef SYMKL_BWD
   FCMF_CHECK_LAUNCH();
   return FCMF_OK;
 }

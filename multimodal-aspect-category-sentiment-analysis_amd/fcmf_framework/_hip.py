@@ -98,6 +98,8 @@ SIGNATURES = {
     "fcmf_xent_fwd_ex": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i64, _f, _f, _i, _vp],
     "fcmf_xent_reduce_ex": [_vp, _vp, _i, _i, _f, _vp, _vp, _vp],
     "fcmf_xent_bwd_ex": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i, _i64, _f, _f, _i, _vp],
+    "fcmf_symkl_fwd": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _vp],
+    "fcmf_symkl_bwd": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i, _i64, _i, _i, _vp],
     "fcmf_bce_logits": [_vp, _i64, _vp, _i64, _i, _i, _vp, _vp, _vp, _i64, _vp, _i, _vp],
     "fcmf_crop_resize_normalize": [_vp, _i64, _vp, _i, _i, _i, _c.POINTER(_f), _c.POINTER(_f), _vp, _i64, _vp, _i, _vp],
     "fcmf_additive_mask": [_vp, _i64, _vp, _i, _i, _f, _vp],

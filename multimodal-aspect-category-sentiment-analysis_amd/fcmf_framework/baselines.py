@@ -59,13 +59,19 @@ class _Baseline(nn.Module):
         pooled = ops.dropout(pooled.contiguous(), self.dropout.p, self.training)
         return ops.linear(pooled, self.classifier.weight, self.classifier.bias).float()
 
-    def loss_aspects(self, logits, labels, weight=None, label_smoothing=0.0, focal_gamma=0.0):
-        """sum over aspects of the batch-mean cross entropy, as FCMF.loss_aspects (the same options: the aspects are the segments)"""
+    def loss_aspects(self, logits, labels, weight=None, label_smoothing=0.0, focal_gamma=0.0, rdrop_alpha=0.0):
+        """sum over aspects of the batch-mean cross entropy, as FCMF.loss_aspects (the same options: the aspects are the segments;
+        rdrop_alpha > 0: logits [2B, A, C] of two passes, labels [B, A], + the symmetric-KL term)"""
+        kl = None
+        if rdrop_alpha != 0.0:
+            labels, kl = ops.rdrop_pairs(logits, labels, rdrop_alpha)      # the labels repeated, the symmetric-KL term
         B, A, C = logits.shape
         if weight is None and label_smoothing == 0.0 and focal_gamma == 0.0:
-            return ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), mult=float(A))
-        return ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), weight=weight, label_smoothing=label_smoothing,
-                                 focal_gamma=focal_gamma, segments=A)
+            ce = ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), mult=float(A))
+        else:
+            ce = ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), weight=weight, label_smoothing=label_smoothing,
+                                   focal_gamma=focal_gamma, segments=A)
+        return ce if kl is None else ce + kl
 
 
 class mRoBERTa(_Baseline):

@@ -62,12 +62,21 @@ class FCMF(nn.Module):
                                           attention_mask, added_attention_mask)
         return self._head(seq).float().view(B, A, -1)
 
-    def loss_aspects(self, logits, labels, weight=None, label_smoothing=0.0, focal_gamma=0.0):
+    def loss_aspects(self, logits, labels, weight=None, label_smoothing=0.0, focal_gamma=0.0, rdrop_alpha=0.0):
         """sum over aspects of the batch-mean CE (run_multimodal_fcmf.py:463-475), in one kernel:
         mean over B*A rows times A.  With class weights (float32 [C] or [A, C]), label smoothing or a focal exponent every
-        aspect divides by its own weight sum, so the aspects become the loss's segments (ops.cross_entropy)."""
+        aspect divides by its own weight sum, so the aspects become the loss's segments (ops.cross_entropy).
+        rdrop_alpha > 0 (R-Drop): logits [2B, A, C] holds two passes of the batch under independent dropout masks (copy i and
+        copy i + B of review i), labels stays [B, A]; the result is the loss above over all 2B rows with the labels repeated
+        (= the mean of the two passes' CE) + rdrop_alpha x the sum over aspects of the batch-mean symmetric KL between the
+        two copies (ops.symmetric_kl)."""
+        kl = None
+        if rdrop_alpha != 0.0:
+            labels, kl = ops.rdrop_pairs(logits, labels, rdrop_alpha)      # the labels repeated, the symmetric-KL term
         B, A, C = logits.shape
         if weight is None and label_smoothing == 0.0 and focal_gamma == 0.0:
-            return ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), mult=float(A))
-        return ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), weight=weight, label_smoothing=label_smoothing,
-                                 focal_gamma=focal_gamma, segments=A)
+            ce = ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), mult=float(A))
+        else:
+            ce = ops.cross_entropy(logits.reshape(B * A, C), labels.reshape(B * A), weight=weight, label_smoothing=label_smoothing,
+                                   focal_gamma=focal_gamma, segments=A)
+        return ce if kl is None else ce + kl

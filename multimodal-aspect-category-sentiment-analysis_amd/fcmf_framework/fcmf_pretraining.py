@@ -192,13 +192,19 @@ class FCMFSeq2Seq(nn.Module):
         return logits
 
     def forward_loss(self, enc_X, dec_X, labels, visual_embeds_att, roi_embeds_att, roi_coors=None, token_type_ids=None,
-                     attention_mask=None, added_attention_mask=None, ignore_index=-100, label_smoothing=0.0):
+                     attention_mask=None, added_attention_mask=None, ignore_index=-100, label_smoothing=0.0, rdrop_alpha=0.0):
         """the training step's `CrossEntropyLoss(ignore_index=-100)(forward(...).permute(0, 2, 1), labels)`
         (run_pretraining_fcmf.py:309-324) as one call: same value, the 64001-wide logits stay inside the fused
-        projection + loss node (ops.VocabCrossEntropyFn)"""
+        projection + loss node (ops.VocabCrossEntropyFn).  rdrop_alpha > 0 adds the R-Drop term: encoder and decoder run a
+        second time at the same batch size under fresh dropout seeds (IAOGDecoder.loss)."""
         dec_state, _ = self._decoder_state(enc_X, visual_embeds_att, roi_embeds_att, roi_coors, token_type_ids,
                                            attention_mask, added_attention_mask)
-        return self.decoder.loss(dec_X, dec_state, labels, ignore_index=ignore_index, label_smoothing=label_smoothing)
+        if rdrop_alpha == 0.0:
+            return self.decoder.loss(dec_X, dec_state, labels, ignore_index=ignore_index, label_smoothing=label_smoothing)
+        dec_state2, _ = self._decoder_state(enc_X, visual_embeds_att, roi_embeds_att, roi_coors, token_type_ids,
+                                            attention_mask, added_attention_mask)
+        return self.decoder.loss(dec_X, dec_state, labels, ignore_index=ignore_index, label_smoothing=label_smoothing,
+                                 rdrop_alpha=rdrop_alpha, state2=dec_state2)
 
     def _init_weights(self, module):
         if isinstance(module, nn.Linear):

@@ -319,11 +319,18 @@ class IAOGDecoder(nn.Module):
         X = self.hidden_states(X, state, enc_attention_mask, is_train, hoisted)
         return ops.vocab_linear(X, self.dense.weight, self.dense.bias)
 
-    def loss(self, X, state, labels, enc_attention_mask=None, ignore_index=-100, label_smoothing=0.0):
+    def loss(self, X, state, labels, enc_attention_mask=None, ignore_index=-100, label_smoothing=0.0, rdrop_alpha=0.0, state2=None):
         """CrossEntropyLoss(ignore_index, label_smoothing)(forward(X).permute(0, 2, 1), labels) (run_pretraining_fcmf.py:322-324)
-        with the vocabulary projection and the loss fused: the [B, Ld, V] logits are never handed out"""
-        X = self.hidden_states(X, state, enc_attention_mask, True)
-        return ops.vocab_cross_entropy(X, self.dense.weight, self.dense.bias, labels, ignore_index, label_smoothing=label_smoothing)
+        with the vocabulary projection and the loss fused: the [B, Ld, V] logits are never handed out.
+        rdrop_alpha > 0 (R-Drop): the stack runs TWICE at batch B -- not once at 2B, the slot -> head pairing of the blocks
+        depends on the batch size -- the second time on state2 (a second encoder pass; `state` again when None), each pass under
+        its own dropout seeds, and the two [B, Ld, H] hidden states go stacked into ops.vocab_cross_entropy(rdrop_alpha=)."""
+        H1 = self.hidden_states(X, state, enc_attention_mask, True)
+        if rdrop_alpha == 0.0:
+            return ops.vocab_cross_entropy(H1, self.dense.weight, self.dense.bias, labels, ignore_index, label_smoothing=label_smoothing)
+        H2 = self.hidden_states(X, state if state2 is None else state2, enc_attention_mask, True)
+        return ops.vocab_cross_entropy(torch.cat((H1, H2), dim=0), self.dense.weight, self.dense.bias, labels, ignore_index,
+                                       label_smoothing=label_smoothing, rdrop_alpha=rdrop_alpha)
 
     def _decode_tail(self, X, k, sampler, constraints=None):
         """the end of a decode step on the rows X [n, H] of the last block: the k best tokens (ops.vocab_topk), or -- `sampler` a dict of

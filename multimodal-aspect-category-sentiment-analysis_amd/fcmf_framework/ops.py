@@ -835,10 +835,74 @@ class VocabCrossEntropyExFn(torch.autograd.Function):
         return None if dx is None else dx.view(xshape), dw, db, None, None, None, None
 
 
-def vocab_cross_entropy(x, weight, bias, labels, ignore_index=-100, *, label_smoothing=0.0, class_weight=None):
+class VocabCrossEntropyRDropFn(torch.autograd.Function):
+    """R-Drop on the vocabulary head in ONE node that owns the padded logits [2M, Vp] of the two stacked passes (rows [0, M) and
+    [M, 2M) pair up): loss = CE over all 2M rows with the labels repeated (fcmf_xent_fwd_ex + fcmf_xent_reduce_ex, so label
+    smoothing and class weights apply) + alpha x the live pairs' mean symmetric KL (fcmf_symkl_fwd + the same reduce).
+    Backward: the CE gradient OUT OF PLACE into a second [2M, Vp] buffer (the pair kernel still needs the logits),
+    fcmf_symkl_bwd(acc=1) on top of it, padding columns zeroed, then _vocab_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, labels, ignore_index, eps, class_weight, alpha):
+        x2 = _rows(x)
+        V = weight.shape[0]
+        lb = labels.reshape(-1).contiguous()
+        M = lb.numel()
+        if x2.shape[0] != 2 * M:
+            raise H.HipLibraryError(f"vocab_cross_entropy: rdrop_alpha > 0 takes the two passes stacked, 2 x {M} rows for {M} labels; "
+                                    f"got {x2.shape[0]} rows")
+        cw, _ = _loss_weight(class_weight, V, 1, x2.device, "vocab_cross_entropy: class_weight")
+        logits, ctx.w = _vocab_logits(x2, weight, bias)
+        Vp = logits.shape[1]
+        lb2 = torch.cat((lb, lb))
+        rows = torch.empty((4, 2 * M), dtype=torch.float32, device=x2.device)     # CE num, den [2M]; KL num, den [M]
+        out = torch.empty(4, dtype=torch.float32, device=x2.device)               # [CE, 1 / D, KL term, alpha / N]
+        L = H.lib()
+        H.check(L.fcmf_xent_fwd_ex(H.ptr(logits), Vp, H.ptr(lb2), H.ptr(cw), 0, H.ptr(rows[0]), H.ptr(rows[1]), 2 * M, V, 1,
+                                   ignore_index, eps, 0.0, H.dt(logits), H.stream()), "fcmf_xent_fwd_ex")
+        H.check(L.fcmf_xent_reduce_ex(H.ptr(rows[0]), H.ptr(rows[1]), 2 * M, 1, 1.0, H.ptr(out), H.ptr(out[1:]), H.stream()),
+                "fcmf_xent_reduce_ex")
+        H.check(L.fcmf_symkl_fwd(H.ptr(logits), Vp, H.ptr(logits[M:]), Vp, H.ptr(lb), H.ptr(rows[2]), H.ptr(rows[3]), M, V, 1,
+                                 ignore_index, H.dt(logits), H.stream()), "fcmf_symkl_fwd")
+        H.check(L.fcmf_xent_reduce_ex(H.ptr(rows[2]), H.ptr(rows[3]), M, 1, alpha, H.ptr(out[2:]), H.ptr(out[3:]), H.stream()),
+                "fcmf_xent_reduce_ex")
+        ctx.save_for_backward(x2, weight, logits, lb2, out, *(() if cw is None else (cw,)))
+        ctx.cfg = (ignore_index, bias is not None, x.shape, eps)
+        return out[0] + out[2]
+
+    @staticmethod
+    def backward(ctx, g):
+        x2, weight, logits, lb2, out = ctx.saved_tensors[:5]
+        cw = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else None
+        ignore_index, has_bias, xshape, eps = ctx.cfg
+        need = ctx.needs_input_grad
+        V, K = weight.shape
+        M2, Vp = logits.shape
+        M = M2 // 2
+        g = _grad_scalar(g)
+        d = torch.empty_like(logits)
+        L = H.lib()
+        H.check(L.fcmf_xent_bwd_ex(H.ptr(logits), Vp, H.ptr(lb2), H.ptr(cw), 0, H.ptr(d), Vp, H.ptr(out[1:]), H.ptr(g), M2, V, 1,
+                                   ignore_index, eps, 0.0, H.dt(logits), H.stream()), "fcmf_xent_bwd_ex")
+        H.check(L.fcmf_symkl_bwd(H.ptr(logits), Vp, H.ptr(logits[M:]), Vp, H.ptr(lb2), H.ptr(d), Vp, H.ptr(d[M:]), Vp, H.ptr(out[3:]),
+                                 H.ptr(g), M, V, 1, ignore_index, 1, H.dt(logits), H.stream()), "fcmf_symkl_bwd")
+        if Vp != V:
+            d[:, V:].zero_()                                # the padding logits (= bias 0) must not leak into dX / dW
+        dwp, dw = grad_dest(weight, (V, K), rows=Vp, device=x2.device) if need[1] else (None, None)
+        dx, db = _vocab_bwd(d, x2, ctx.w, V, need[0], has_bias and need[2], dwp)
+        return None if dx is None else dx.view(xshape), dw, db, None, None, None, None, None
+
+
+def vocab_cross_entropy(x, weight, bias, labels, ignore_index=-100, *, label_smoothing=0.0, class_weight=None, rdrop_alpha=0.0):
     """mean CE of the vocabulary projection of x over the non-ignored positions (torch CrossEntropyLoss semantics, its
-    `label_smoothing` and `weight` (here class_weight, float32 [V] on the device) included).  Without either it is the plain node."""
+    `label_smoothing` and `weight` (here class_weight, float32 [V] on the device) included).  Without either it is the plain node.
+    rdrop_alpha > 0: x holds two passes of the same positions stacked along its first axis (rows [0, M) and [M, 2M) of the
+    flattened x pair up; `labels` has M entries) and the result is the CE over all 2M rows (= the mean of the two passes' CE) +
+    rdrop_alpha x the mean over the live positions of the pairs' symmetric KL (VocabCrossEntropyRDropFn)."""
     eps, _ = check_loss_options(label_smoothing, 0.0)
+    alpha = check_rdrop_alpha(rdrop_alpha, "rdrop_alpha")
+    if alpha > 0.0:
+        return VocabCrossEntropyRDropFn.apply(x, weight, bias, labels, int(ignore_index), eps, class_weight, alpha)
     if eps == 0.0 and class_weight is None:
         return VocabCrossEntropyFn.apply(x, weight, bias, labels, int(ignore_index))
     return VocabCrossEntropyExFn.apply(x, weight, bias, labels, int(ignore_index), eps, class_weight)
@@ -1804,6 +1868,86 @@ def cross_entropy(logits, labels, ignore_index=-100, mult=1.0, *, weight=None, l
 def _rows2d(logits):
     lg = logits if logits.stride(-1) == 1 else logits.contiguous()
     return lg.reshape(-1, lg.shape[-1]) if lg.dim() != 2 else lg
+
+
+def check_rdrop_alpha(alpha, name="alpha"):
+    """the weight of the symmetric-KL term: a finite number >= 0 (0 = off), else a ValueError that names the argument -> float"""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not math.isfinite(alpha) or alpha < 0.0:
+        raise ValueError(f"{name} must be a finite number >= 0 (0 = off), got {alpha!r}")
+    return float(alpha)
+
+
+class SymmetricKLFn(torch.autograd.Function):
+    """alpha x sum over segments of the live pairs' mean 1/2 [KL(p||q) + KL(q||p)], p / q = softmax of a pair of rows of a / b
+    (include/fcmf_hip.h states the function): fcmf_symkl_fwd + fcmf_xent_reduce_ex forward, fcmf_symkl_bwd backward"""
+
+    @staticmethod
+    def forward(ctx, a, b, labels, ignore_index, alpha, segments):
+        a2, b2 = _rows2d(a), _rows2d(b)
+        lb = None if labels is None else labels.reshape(-1).contiguous()
+        n, C = a2.shape
+        a2, b2 = (t.contiguous() if n > 1 and t.stride(0) < C else t for t in (a2, b2))      # (an expanded row)
+        lda, ldb = (t.stride(0) if n > 1 else C for t in (a2, b2))               # (one row: its stride means nothing)
+        rows = torch.empty((2, n), dtype=torch.float32, device=a2.device)
+        out = torch.empty(1 + segments, dtype=torch.float32, device=a2.device)     # [loss, alpha / N_s ...]
+        L = H.lib()
+        H.check(L.fcmf_symkl_fwd(H.ptr(a2), lda, H.ptr(b2), ldb, H.ptr(lb), H.ptr(rows[0]), H.ptr(rows[1]), n, C, segments,
+                                 ignore_index, H.dt(a2), H.stream()), "fcmf_symkl_fwd")
+        H.check(L.fcmf_xent_reduce_ex(H.ptr(rows[0]), H.ptr(rows[1]), n, segments, alpha, H.ptr(out), H.ptr(out[1:]), H.stream()),
+                "fcmf_xent_reduce_ex")
+        ctx.save_for_backward(a2, b2, out, *(() if lb is None else (lb,)))
+        ctx.cfg = (ignore_index, segments, lda, ldb, a.shape, b.shape)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        a2, b2, out = ctx.saved_tensors[:3]
+        lb = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+        ignore_index, segments, lda, ldb, ashape, bshape = ctx.cfg
+        n, C = a2.shape
+        d = torch.empty((2, n, C), dtype=a2.dtype, device=a2.device)
+        g = _grad_scalar(g)
+        H.check(H.lib().fcmf_symkl_bwd(H.ptr(a2), lda, H.ptr(b2), ldb, H.ptr(lb), H.ptr(d[0]), C, H.ptr(d[1]), C, H.ptr(out[1:]),
+                                       H.ptr(g), n, C, segments, ignore_index, 0, H.dt(a2), H.stream()), "fcmf_symkl_bwd")
+        need = ctx.needs_input_grad
+        return d[0].view(ashape) if need[0] else None, d[1].view(bshape) if need[1] else None, None, None, None, None
+
+
+def symmetric_kl(a, b, labels=None, ignore_index=-100, *, alpha=1.0, segments=1):
+    """the R-Drop consistency term of two logit tensors of one shape [..., C]: alpha x the SUM over segments (pair r of the
+    flattened rows -> segment r % segments) of the MEAN over the segment's live pairs of 1/2 [KL(softmax a || softmax b) +
+    KL(softmax b || softmax a)].  `labels` (int64, one per pair, optional) only decides liveness: a pair whose label is
+    ignore_index contributes nothing.  Gradients go to whichever of a, b needs one."""
+    alpha = check_rdrop_alpha(alpha)
+    if isinstance(segments, bool) or not isinstance(segments, int) or segments < 1:
+        raise ValueError(f"segments must be a positive integer, got {segments!r}")
+    if not torch.is_tensor(a) or not torch.is_tensor(b):
+        raise H.HipLibraryError("symmetric_kl: a and b must be tensors")
+    H.require_cuda(a, b, labels)
+    if a.shape != b.shape or a.dim() < 1:
+        raise H.HipLibraryError(f"symmetric_kl: a {tuple(a.shape)} and b {tuple(b.shape)} must have one shape [..., C]")
+    if a.dtype != b.dtype or a.dtype not in (torch.float32, torch.bfloat16):
+        raise H.HipLibraryError(f"symmetric_kl: a and b must both be float32 or both bfloat16, got {a.dtype} and {b.dtype}")
+    if a.device != b.device or (labels is not None and labels.device != a.device):
+        raise H.HipLibraryError("symmetric_kl: a, b and labels must be on one device")
+    n = a.numel() // a.shape[-1] if a.shape[-1] else 0
+    if a.shape[-1] < 1 or n % segments != 0:
+        raise H.HipLibraryError(f"symmetric_kl: {n} pairs of {a.shape[-1]} columns do not divide into {segments} segments")
+    if labels is not None and (labels.dtype != torch.int64 or labels.numel() != n):
+        raise H.HipLibraryError(f"symmetric_kl: labels must be int64 with {n} entries, got {labels.dtype} with {labels.numel()}")
+    return SymmetricKLFn.apply(a, b, labels, int(ignore_index), alpha, segments)
+
+
+def rdrop_pairs(logits, labels, rdrop_alpha):
+    """what the R-Drop form of a model's loss_aspects adds: logits [2B, A, C] (copy i and copy i + B of review i), labels [B, A]
+    -> (the labels repeated for the cross entropy over all 2B rows, rdrop_alpha x symmetric_kl of the two halves with the
+    aspects as its segments)"""
+    alpha = check_rdrop_alpha(rdrop_alpha, "rdrop_alpha")
+    B = labels.shape[0]
+    if logits.dim() != 3 or logits.shape[0] != 2 * B:
+        raise H.HipLibraryError(f"loss_aspects: rdrop_alpha > 0 takes the logits of two passes, [2 x {B}, A, C] for labels "
+                                f"{tuple(labels.shape)}; got {tuple(logits.shape)}")
+    return torch.cat((labels, labels), dim=0), symmetric_kl(logits[:B], logits[B:], segments=logits.shape[1], alpha=alpha)
 
 
 class BCELogitsFn(torch.autograd.Function):

@@ -32,8 +32,8 @@ from fcmf_framework.dp import GradArena  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
 from train_harness import (add_ema_arguments, add_loss_arguments, averaged, build_extractors, check_ema_arguments,  # noqa: E402
-                           check_loss_arguments, class_weight_tensor, init_run, make_features, save_model, setup_ema, split_decay,
-                           train_epoch, train_label_table)
+                           check_loss_arguments, class_weight_tensor, init_run, log_rdrop, make_features, save_model, setup_ema, split_decay,
+                           train_epoch, train_label_table, twice)
 from run_multimodal_fcmf import POLARITY_MAP, macro_f1  # noqa: E402
 
 #            model class, checkpoint name before _best / _last (seed filled in), name in the log and result files
@@ -119,14 +119,17 @@ class SyntheticBatches:
                 yield head + (t["input_ids"], t["attention_mask"], b["input_ids"], b["attention_mask"], b["labels"], texts)
 
 
-def forward_batch(name, model, batch, features):
-    """one batch of baselines_dataset.py's layout -> (logits [B, aspects, polarities], labels, texts)"""
+def forward_batch(name, model, batch, features, copies=1):
+    """one batch of baselines_dataset.py's layout -> (logits [B, aspects, polarities], labels, texts).  copies=2 (an R-Drop
+    training step): the model sees every review twice, logits [2B, ...], labels stay [B, ...]; the doubling comes AFTER the
+    feature extractor, so under --fine_tune_cnn the trunks still see each crop once"""
+    rep = twice if copies == 2 else (lambda *t: t)
     if name == "ef_captr":
         ids, mask, labels, texts = batch
-        return model.forward_aspects(ids, mask), labels, texts
+        return model.forward_aspects(*rep(ids, mask)), labels, texts
     vis, roi = features(batch[0], batch[1])
     *text_side, labels, texts = batch[2:]
-    return model.forward_aspects(*text_side, vis, roi), labels, texts
+    return model.forward_aspects(*rep(*text_side, vis, roi)), labels, texts
 
 
 @torch.no_grad()
@@ -262,11 +265,13 @@ def main(argv=None):
     if args.do_train:
         logger.info("training loss: label_smoothing %g focal_gamma %g class_weights %s", args.label_smoothing, args.focal_gamma,
                     args.class_weights)
+        log_rdrop(args, logger)
 
     def loss_fn(batch):
-        logits, labels, _ = forward_batch(args.model, model, batch, features)
+        rdrop = args.rdrop_alpha if model.training else 0.0
+        logits, labels, _ = forward_batch(args.model, model, batch, features, copies=2 if rdrop > 0 else 1)
         return model.loss_aspects(logits, labels, weight=class_weight, label_smoothing=args.label_smoothing,
-                                  focal_gamma=args.focal_gamma)
+                                  focal_gamma=args.focal_gamma, rdrop_alpha=rdrop)
 
     def log(step, loss):
         last_loss[0] = loss

@@ -43,8 +43,8 @@ from fcmf_framework.fcmf_multimodal import FCMF  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
 from train_harness import (add_ema_arguments, add_loss_arguments, averaged, build_extractors, check_ema_arguments,  # noqa: E402
-                           check_loss_arguments, class_weight_tensor, init_run, load_resnets, make_features, save_extractors,
-                           save_model, setup_ema, split_decay, train_epoch, train_label_table)
+                           check_loss_arguments, class_weight_tensor, init_run, load_resnets, log_rdrop, make_features, save_extractors,
+                           save_model, setup_ema, split_decay, train_epoch, train_label_table, twice)
 
 
 POLARITY_MAP = {0: 'None', 1: 'Negative', 2: 'Neutral', 3: 'Positive'}      # reference :28
@@ -254,12 +254,14 @@ def main(argv=None):
     if master and args.do_train:
         logger.info("training loss: label_smoothing %g focal_gamma %g class_weights %s", args.label_smoothing, args.focal_gamma,
                     args.class_weights)
+        log_rdrop(args, logger)
 
     def loss_fn(batch):
-        logits, labels, _ = forward_batch(model, batch, features)
+        rdrop = args.rdrop_alpha if model.training else 0.0
+        logits, labels, _ = forward_batch(model, batch, features, copies=2 if rdrop > 0 else 1)
         # sum over aspects of the batch-mean CE (each aspect over its own weight sum once an option is set)
         return model.loss_aspects(logits, labels, weight=class_weight, label_smoothing=args.label_smoothing,
-                                  focal_gamma=args.focal_gamma)
+                                  focal_gamma=args.focal_gamma, rdrop_alpha=rdrop)
 
     if args.do_train:
         for epoch in range(start_epoch, int(args.num_train_epochs)):
@@ -315,10 +317,14 @@ def main(argv=None):
         torch.distributed.destroy_process_group()
 
 
-def forward_batch(model, batch, features):
-    """one batch of the reference's 9-tuple (vimacsa_dataset.py:202) -> (logits [B, aspects, polarities], labels, texts)"""
+def forward_batch(model, batch, features, copies=1):
+    """one batch of the reference's 9-tuple (vimacsa_dataset.py:202) -> (logits [B, aspects, polarities], labels, texts).
+    copies=2 (an R-Drop training step): the model sees every review twice, logits [2B, ...], labels stay [B, ...]; the doubling
+    comes AFTER the feature extractor, so under --fine_tune_cnn the trunks still see each crop once"""
     t_img, roi_img, roi_coors, ids, tts, ams, added, labels, texts = batch
     vis, roi = features(t_img, roi_img)
+    if copies == 2:
+        vis, roi, roi_coors, ids, tts, ams, added = twice(vis, roi, roi_coors, ids, tts, ams, added)
     logits = model.forward_aspects(input_ids=ids, token_type_ids=tts, attention_mask=ams, added_attention_mask=added,
                                    visual_embeds_att=vis, roi_embeds_att=roi, roi_coors=roi_coors)
     return logits, labels, texts

@@ -46,7 +46,7 @@ from fcmf_framework.fcmf_pretraining import FCMFSeq2Seq  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
 from train_harness import (add_ema_arguments, add_loss_arguments, averaged, build_extractors, check_ema_arguments,  # noqa: E402
-                           check_loss_arguments, init_run, load_resnets, make_features, save_extractors, save_model, setup_ema,
+                           check_loss_arguments, init_run, load_resnets, log_rdrop, make_features, save_extractors, save_model, setup_ema,
                            split_decay, train_epoch)
 
 
@@ -372,7 +372,7 @@ def main(argv=None):
         vis, roi = features(vis, roi)
         # model(...) -> logits -> CrossEntropyLoss(ignore_index=-100) (reference :309-324) as one fused call
         return model.forward_loss(enc_X, dec_X, labels, vis, roi, coors, tt, am, added, ignore_index=-100,
-                                  label_smoothing=args.label_smoothing)
+                                  label_smoothing=args.label_smoothing, rdrop_alpha=args.rdrop_alpha if model.training else 0.0)
 
     evaluate = None
     if args.do_eval and master and dev_set is not None:
@@ -399,6 +399,9 @@ def main(argv=None):
         logger.info("--do_eval: no dev set (--synthetic_eval_samples is 0): nothing is evaluated")
 
     if args.do_train:
+        if master:
+            logger.info("training loss: label_smoothing %g", args.label_smoothing)
+            log_rdrop(args, logger)
         for epoch in range(start_epoch, int(args.num_train_epochs)):
             model.train()
             if r_img is not None:

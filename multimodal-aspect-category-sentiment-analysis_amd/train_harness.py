@@ -43,6 +43,12 @@ def add_loss_arguments(parser, class_weights=True):
                                  + EVAL_LOSS_NOTE)
     parser.add_argument('--label_smoothing', default=0.0, type=float,
                         help="label smoothing of the training loss, in [0, 1); " + EVAL_LOSS_NOTE)
+    parser.add_argument('--rdrop_alpha', default=0.0, type=float,
+                        help="R-Drop (Liang et al., 2021): every training sample runs twice under independent dropout masks and "
+                             "alpha x the bidirectional KL divergence between the two predictions, 1/2 [KL(p||q) + KL(q||p)], is added "
+                             "to the mean of the two cross entropies; 0 = off.  The KL term is the BATCH MEAN (per aspect; per live "
+                             "target position for IAOG), not the sum over the batch of the authors' script.  Activation memory "
+                             "doubles; " + EVAL_LOSS_NOTE)
 
 
 def check_loss_arguments(args):
@@ -55,6 +61,9 @@ def check_loss_arguments(args):
         raise ValueError(f"--focal_gamma must be finite and >= 0, got {gamma}")
     if eps > 0.0 and gamma > 0.0:
         raise ValueError(f"--focal_gamma {gamma} and --label_smoothing {eps} cannot both be set")
+    alpha = getattr(args, "rdrop_alpha", 0.0)
+    if not (math.isfinite(alpha) and alpha >= 0.0):
+        raise ValueError(f"--rdrop_alpha must be finite and >= 0 (0 = off), got {alpha}")
     spec = getattr(args, "class_weights", "none").strip()
     if spec.lower() in ("none", "balanced"):
         return None if spec.lower() == "none" else "balanced"
@@ -67,6 +76,17 @@ def check_loss_arguments(args):
     if not all(math.isfinite(v) and v >= 0.0 for v in values) or sum(values) <= 0.0:
         raise ValueError(f"--class_weights must be finite, >= 0 and not all zero, got {spec!r}")
     return values
+
+
+def log_rdrop(args, logger):
+    """the line that goes beside "training loss:" when training starts"""
+    logger.info("training loss: rdrop_alpha %g%s", args.rdrop_alpha,
+                " (two dropout passes per sample + alpha x the batch-mean symmetric KL)" if args.rdrop_alpha > 0 else " (off)")
+
+
+def twice(*tensors):
+    """every tensor repeated along the batch axis (copy i and copy i + B of sample i): what an R-Drop step feeds the model"""
+    return tuple(None if t is None else torch.cat((t, t), dim=0) for t in tensors)
 
 
 # ---- averaged weights (FusedAdamW.set_ema / ema_weights) ------------------------------------------------------------------------
