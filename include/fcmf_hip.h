@@ -495,6 +495,31 @@ int fcmf_embed_ln_fwd(const int64_t* ids, const int64_t* pos, const int64_t* typ
                       const float* gamma, const float* beta, void* y, void* z, float* mean,
                       float* rstd, int ntok, int H, float eps, float dropout_p, uint64_t seed,
                       int dtype, void* stream);
+/* Adversarial training on the token embeddings (FGM: Miyato et al., "Adversarial Training Methods for Semi-Supervised Text
+ * Classification"), one step per micro-batch: (1) a clean forward and backward; g = dz of fcmf_add_ln_bwd in the embedding's
+ * backward, the gradient at the pre-LayerNorm sum, [nseq, S, H] in `dtype`; (2) fcmf_adv_scale: scale[s] = epsilon /
+ * ||g[s, t, :] over the tokens t with ids[s, t] != pad_id||_2, and 0 where that norm is 0 (every token pad, a zero gradient);
+ * (3) fcmf_embed_ln_adv_fwd: a second forward on z = ((word + type) + pos) + scale[s] * g[s, t, :] at the tokens that are not pad
+ * -- pad tokens get exactly the plain sum -- then LayerNorm and dropout as fcmf_embed_ln_fwd; (4) its backward is the plain
+ * one (the perturbation is a constant) and accumulates onto the first.  The perturbation is never materialised.
+ *
+ * fcmf_adv_scale: one workgroup per sequence, float32 accumulation, no atomics (the same bits every run); rows whose id is
+ * pad_id are not read.  The squares are taken of the values divided by the power of two of the sequence's largest magnitude,
+ * so no gradient scale leaves float32, and dz * 2^k gives scale * 2^-k bit for bit while both stay normal numbers.  scale is
+ * float32 [nseq].  A NaN among the values that are read gives scale 0.
+ * fcmf_embed_ln_adv_fwd: the arguments of fcmf_embed_ln_fwd, then g [ntok, H] in `dtype`, scale [ntok / S] float32, S and
+ * pad_id; row r belongs to sequence r / S.  With every scale 0 and finite g the outputs are fcmf_embed_ln_fwd's.
+ * Both, before any launch: FCMF_ERR_ARG for a NULL required pointer (type_ids and z may be NULL as in fcmf_embed_ln_fwd),
+ * S <= 0, a negative count, ntok no multiple of S, epsilon negative or not finite; FCMF_ERR_UNSUPPORTED for H % 4 != 0, H
+ * above the LayerNorm limit of 2048 (the forward), another dtype than FCMF_F32 / FCMF_BF16, dz / g not aligned to four
+ * elements; FCMF_OK and nothing done for nseq == 0 / ntok == 0. */
+int fcmf_adv_scale(const void* dz, const int64_t* ids, float* scale, int nseq, int S, int H, int pad_id, float epsilon,
+                   int dtype, void* stream);
+int fcmf_embed_ln_adv_fwd(const int64_t* ids, const int64_t* pos, const int64_t* type_ids,
+                          const float* word, const float* pos_table, const float* type_table,
+                          const float* gamma, const float* beta, void* y, void* z, float* mean,
+                          float* rstd, int ntok, int H, float eps, float dropout_p, uint64_t seed,
+                          int dtype, void* stream, const void* g, const float* scale, int S, int pad_id);
 /* scatter-add dz into the float32 table gradients (pad rows of word/pos receive nothing).  dpos may be NULL when
  * the position table is handled by fcmf_embed_pos_bwd. */
 int fcmf_embed_bwd(const void* dz, const int64_t* ids, const int64_t* pos, const int64_t* type_ids,

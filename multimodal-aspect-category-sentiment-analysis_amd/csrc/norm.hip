@@ -291,20 +291,34 @@ __global__ __launch_bounds__(64) void position_ids_kernel(const int64_t* __restr
   }
 }
 
-template <typename T, int NP>
+// ADV (fcmf_embed_ln_adv_fwd): z = ((word + type) + pos) + scale[row / S] * g[row] on the rows whose id is not pad_id -- the FGM
+// perturbation, never materialised.  A compile-time branch on the trailing pack, which is empty (the plain kernel: the argument
+// list ends at `seed`, as it always did) or one EmbedAdvArgs.
+template <typename T> struct EmbedAdvArgs { const T* g; const float* scale; int S; int pad_id; };
+template <typename A> __device__ __forceinline__ const A& embed_adv_args(const A& a) { return a; }
+
+template <typename T, int NP, typename... Adv>
 __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ pos,
                                                            const int64_t* __restrict__ tt, const float* __restrict__ word,
                                                            const float* __restrict__ ptab, const float* __restrict__ ttab,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            T* __restrict__ y, T* __restrict__ z, float* __restrict__ mean,
                                                            float* __restrict__ rstd, int ntok, int H, float eps, float p,
-                                                           uint64_t seed) {
+                                                           uint64_t seed, Adv... adv) {
+  constexpr bool ADV = sizeof...(Adv) == 1;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= ntok) return;
   const float* wr = word + ids[row] * H;
   const float* pr = ptab + pos[row] * H;
   const float* tr = ttab + (tt ? tt[row] : 0) * H;
+  bool perturb = false;
+  float sc = 0.f;
+  if constexpr (ADV) {
+    const auto& a = embed_adv_args(adv...);
+    perturb = ids[row] != a.pad_id;          // (wave-uniform: pad rows read neither scale nor g)
+    if (perturb) sc = a.scale[row / a.S];
+  }
   float4 v[NP];
   float s = 0.f;
 #pragma unroll
@@ -316,6 +330,12 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __rest
       const float4 d = *reinterpret_cast<const float4*>(pr + c);
       // same association as HF: (word + type) + position
       float4 o; o.x = (a.x + b.x) + d.x; o.y = (a.y + b.y) + d.y; o.z = (a.z + b.z) + d.z; o.w = (a.w + b.w) + d.w;
+      if constexpr (ADV) {
+        if (perturb) {
+          const float4 gv = Vec4<T>::load(embed_adv_args(adv...).g + (int64_t)row * H + c);
+          o.x = fmaf(sc, gv.x, o.x); o.y = fmaf(sc, gv.y, o.y); o.z = fmaf(sc, gv.z, o.z); o.w = fmaf(sc, gv.w, o.w);
+        }
+      }
       v[i] = o;
       s += o.x + o.y + o.z + o.w;
     }
@@ -351,6 +371,64 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __rest
       }
       Vec4<T>::store(y + (int64_t)row * H + c, o);
     }
+  }
+}
+
+// scale[s] = epsilon / || dz[s, t, :] over the tokens t with ids[s, t] != pad_id ||_2 (0 where that norm is 0): one workgroup per
+// sequence, a wave per row, V elements (16 bytes; 8 for bf16 rows that are no multiple of 16 bytes) per lane and trip.  Two passes
+// over the sequence: its largest magnitude, then the sum of squares of the values divided by that magnitude's power of two 2^e
+// (v_ldexp_f32: exact), so no square leaves float32 whatever the gradient's scale -- and dz * 2^k gives the same normalised
+// values, the same sum and scale * 2^-k bit for bit.  A lane adds serially, wave_sum adds the lanes, thread 0 adds the four waves
+// from LDS in a fixed order: no atomics.  Rows whose id is pad_id are not read.
+template <typename T, int V> struct AdvVec;
+template <> struct AdvVec<float, 4> { typedef f32x4 type; };
+template <> struct AdvVec<bf16_t, 8> { typedef bf16x8 type; };
+template <> struct AdvVec<bf16_t, 4> { typedef bf16x4 type; };
+
+template <typename T, int V>
+__global__ __launch_bounds__(256) void adv_scale_kernel(const T* __restrict__ dz, const int64_t* __restrict__ ids,
+                                                        float* __restrict__ scale, int S, int H, int pad_id, float epsilon) {
+  typedef typename AdvVec<T, V>::type Vt;
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t* id = ids + (int64_t)blockIdx.x * S;
+  const T* g = dz + (int64_t)blockIdx.x * S * H;
+  float amax = 0.f;
+  for (int t = wave; t < S; t += 4) {
+    if (id[t] == pad_id) continue;
+    const T* r = g + (int64_t)t * H;
+    for (int c = lane * V; c < H; c += 64 * V) {
+      const Vt v = *reinterpret_cast<const Vt*>(r + c);
+#pragma unroll
+      for (int j = 0; j < V; ++j) amax = fmaxf(amax, fabsf((float)v[j]));
+    }
+  }
+  amax = wave_max(amax);
+  if (lane == 0) red[wave] = amax;
+  __syncthreads();
+  amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;      // amax = m * 2^e, 1 <= m < 2 (a denormal: e = -127)
+  float s = 0.f;
+  for (int t = wave; t < S; t += 4) {
+    if (id[t] == pad_id) continue;
+    const T* r = g + (int64_t)t * H;
+    for (int c = lane * V; c < H; c += 64 * V) {
+      const Vt v = *reinterpret_cast<const Vt*>(r + c);
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float x = ldexpf((float)v[j], -e);
+        s += x * x;
+      }
+    }
+  }
+  s = wave_sum(s);
+  if (lane == 0) red[wave] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float tot = ((red[0] + red[1]) + red[2]) + red[3];
+    // (not positive: every row pad, a zero gradient -- or a NaN, which no scale can mend)
+    scale[blockIdx.x] = tot > 0.f ? ldexpf(epsilon / sqrtf(tot), -e) : 0.f;
   }
 }
 
@@ -624,6 +702,48 @@ extern "C" int fcmf_embed_ln_fwd(const int64_t* ids, const int64_t* pos, const i
     pos_table, type_table, gamma, beta, (T*)y, (T*)z, mean, rstd, ntok, H, eps, dropout_p, seed)
   LN_DISPATCH(dtype, H);
 #undef LAUNCH_
+  FCMF_CHECK_LAUNCH();
+  return FCMF_OK;
+}
+
+extern "C" int fcmf_embed_ln_adv_fwd(const int64_t* ids, const int64_t* pos, const int64_t* type_ids, const float* word,
+                                     const float* pos_table, const float* type_table, const float* gamma, const float* beta,
+                                     void* y, void* z, float* mean, float* rstd, int ntok, int H, float eps, float dropout_p,
+                                     uint64_t seed, int dtype, void* stream, const void* g, const float* scale, int S, int pad_id) {
+  if (!ids || !pos || !word || !pos_table || !type_table || !gamma || !beta || !y || !mean || !rstd || !g || !scale) return FCMF_ERR_ARG;
+  if (S <= 0 || ntok < 0 || H < 0 || ntok % S != 0) return FCMF_ERR_ARG;      // (whole sequences: a row's scale is scale[row / S])
+  if (H % 4 != 0 || H > LN_MAXP * 256) return FCMF_ERR_UNSUPPORTED;
+  if (dtype != FCMF_F32 && dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(g) & (dtype == FCMF_F32 ? 15 : 7)) return FCMF_ERR_UNSUPPORTED;
+  if (ntok == 0 || H == 0) return FCMF_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  dim3 grid((ntok + 3) / 4);
+#define LAUNCH_(T, NP) hipLaunchKernelGGL((embed_ln_fwd_kernel<T, NP, EmbedAdvArgs<T>>), grid, dim3(256), 0, st, ids, pos, type_ids, word, \
+    pos_table, type_table, gamma, beta, (T*)y, (T*)z, mean, rstd, ntok, H, eps, dropout_p, seed,                             \
+    EmbedAdvArgs<T>{(const T*)g, scale, S, pad_id})
+  LN_DISPATCH(dtype, H);
+#undef LAUNCH_
+  FCMF_CHECK_LAUNCH();
+  return FCMF_OK;
+}
+
+extern "C" int fcmf_adv_scale(const void* dz, const int64_t* ids, float* scale, int nseq, int S, int H, int pad_id, float epsilon,
+                              int dtype, void* stream) {
+  if (!dz || !ids || !scale || S <= 0 || nseq < 0 || H < 0) return FCMF_ERR_ARG;
+  if (!(epsilon >= 0.f) || epsilon > 3.402823466e+38f) return FCMF_ERR_ARG;      // negative, NaN or infinite
+  if (H % 4 != 0) return FCMF_ERR_UNSUPPORTED;
+  if (dtype != FCMF_F32 && dtype != FCMF_BF16) return FCMF_ERR_UNSUPPORTED;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(dz);
+  if (a & (dtype == FCMF_F32 ? 15 : 7)) return FCMF_ERR_UNSUPPORTED;
+  if (nseq == 0) return FCMF_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  dim3 grid(nseq);
+  if (dtype == FCMF_F32)
+    hipLaunchKernelGGL((adv_scale_kernel<float, 4>), grid, dim3(256), 0, st, (const float*)dz, ids, scale, S, H, pad_id, epsilon);
+  else if (H % 8 == 0 && (a & 15) == 0)
+    hipLaunchKernelGGL((adv_scale_kernel<bf16_t, 8>), grid, dim3(256), 0, st, (const bf16_t*)dz, ids, scale, S, H, pad_id, epsilon);
+  else      // (rows of 8 * odd bytes: every other row starts off a 16-byte boundary)
+    hipLaunchKernelGGL((adv_scale_kernel<bf16_t, 4>), grid, dim3(256), 0, st, (const bf16_t*)dz, ids, scale, S, H, pad_id, epsilon);
   FCMF_CHECK_LAUNCH();
   return FCMF_OK;
 }

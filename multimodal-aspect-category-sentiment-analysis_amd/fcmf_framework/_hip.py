@@ -86,6 +86,9 @@ SIGNATURES = {
     "fcmf_add_ln_bwd_workspace": [_i, _i],
     "fcmf_position_ids": [_vp, _vp, _i, _i, _i, _vp],
     "fcmf_embed_ln_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _u64, _i, _vp],
+    "fcmf_adv_scale": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
+    "fcmf_embed_ln_adv_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _u64, _i, _vp,
+                              _vp, _vp, _i, _i],
     "fcmf_embed_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "fcmf_embed_pos_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "fcmf_embed_pos_type_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],

@@ -1285,7 +1285,7 @@ class EmbedLNFn(torch.autograd.Function):
     """RobertaEmbeddings: LN(word[ids] + type[tt] + pos[pos]) then dropout"""
 
     @staticmethod
-    def forward(ctx, ids, pos, tt, word, ptab, ttab, gamma, beta, eps, p, seed, pad_id, out_dtype):
+    def forward(ctx, ids, pos, tt, word, ptab, ttab, gamma, beta, eps, p, seed, pad_id, out_dtype, g=None, scale=None):
         ids, pos = ids.contiguous(), pos.contiguous()
         tt = None if tt is None else tt.contiguous()
         ntok, Hd = ids.numel(), word.shape[1]
@@ -1294,9 +1294,15 @@ class EmbedLNFn(torch.autograd.Function):
         mean = torch.empty(ntok, dtype=torch.float32, device=word.device)
         rstd = torch.empty(ntok, dtype=torch.float32, device=word.device)
         H.require_cuda(ids, word)
-        H.check(H.lib().fcmf_embed_ln_fwd(H.ptr(ids), H.ptr(pos), H.ptr(tt), H.ptr(word), H.ptr(ptab), H.ptr(ttab),
-                                          H.ptr(gamma), H.ptr(beta), H.ptr(y), H.ptr(z), H.ptr(mean), H.ptr(rstd),
-                                          ntok, Hd, eps, p, seed, H.dt(y), H.stream()), "fcmf_embed_ln_fwd")
+        if g is None:
+            H.check(H.lib().fcmf_embed_ln_fwd(H.ptr(ids), H.ptr(pos), H.ptr(tt), H.ptr(word), H.ptr(ptab), H.ptr(ttab),
+                                              H.ptr(gamma), H.ptr(beta), H.ptr(y), H.ptr(z), H.ptr(mean), H.ptr(rstd),
+                                              ntok, Hd, eps, p, seed, H.dt(y), H.stream()), "fcmf_embed_ln_fwd")
+        else:      # (EmbedLNAdvFn: the sum plus scale[sequence] * g at the tokens that are not pad)
+            H.check(H.lib().fcmf_embed_ln_adv_fwd(H.ptr(ids), H.ptr(pos), H.ptr(tt), H.ptr(word), H.ptr(ptab), H.ptr(ttab),
+                                                  H.ptr(gamma), H.ptr(beta), H.ptr(y), H.ptr(z), H.ptr(mean), H.ptr(rstd),
+                                                  ntok, Hd, eps, p, seed, H.dt(y), H.stream(), H.ptr(g), H.ptr(scale),
+                                                  ids.shape[-1], pad_id), "fcmf_embed_ln_adv_fwd")
         ctx.save_for_backward(ids, pos, tt, z, gamma, mean, rstd)
         ctx.p, ctx.seed, ctx.pad_id = p, seed, pad_id
         ctx.params = (word, ptab, ttab, gamma, beta)       # (the Parameters: grad_dest looks up their arena slices)
@@ -1318,6 +1324,9 @@ class EmbedLNFn(torch.autograd.Function):
         dg, _ = grad_dest(gpar, (Hd,), in_place=False, device=z.device)
         db, _ = grad_dest(bpar, (Hd,), in_place=False, device=z.device)
         dz = ln_bwd(d, z, gamma, mean, rstd, 0.0, 0, dg, db)[0]      # (the dropout, applied AFTER the LayerNorm here, is undone above)
+        rec = getattr(ctx, "adv_record", None)
+        if rec is not None:      # (EmbeddingAdversary.record: dz IS the gradient w.r.t. the token embeddings; kept, not copied)
+            rec[0][rec[1]] = (dz, ids)
         dwordbuf, dword = grad_dest(word, word.shape, device=z.device)
         dpos, _ = grad_dest(ptab, ptab.shape, in_place=False, device=z.device)
         dtt, _ = grad_dest(ttab, ttab.shape, in_place=False, device=z.device)
@@ -1338,8 +1347,114 @@ class EmbedLNFn(torch.autograd.Function):
         return None, None, None, dword, dpos, dtt, dg, db, None, None, None, None, None
 
 
+class EmbedLNAdvFn(EmbedLNFn):
+    """EmbedLNFn on the perturbed sum (EmbeddingAdversary.attack).  g and scale are constants: the backward is EmbedLNFn's"""
+
+    @staticmethod
+    def backward(ctx, dy):
+        return EmbedLNFn.backward(ctx, dy) + (None, None)
+
+
+_adversary = None      # the EmbeddingAdversary whose record() or attack() block is running
+
+
+class EmbeddingAdversary:
+    """FGM on the text embeddings (Miyato et al., "Adversarial Training Methods for Semi-Supervised Text Classification"), in two
+    passes over the same batch:
+
+        with adv.record():  loss = model(batch)        # clean pass: every embed_layer_norm call registers, in forward order
+        loss.backward()                                # ... and its backward deposits (dz, ids): the gradient at the embeddings
+        with adv.attack():  loss_adv = model(batch)    # call k adds epsilon * dz_k / ||dz_k|| (per sequence, pad tokens excluded)
+        loss_adv.backward()                            # accumulates onto the first pass: the step's gradient is the sum
+
+    Only calls made in training mode, with grad enabled and a word table that requires grad take part; all others run the plain
+    kernel in either block.  The perturbation is never materialised: fcmf_adv_scale turns the kept dz into one float per sequence
+    and fcmf_embed_ln_adv_fwd reads dz and that scale.  Nothing flows back through either.  The records (one dz per call: the
+    cost in memory) are released when attack() exits.  ids of any rank: the last axis is the sequence."""
+
+    def __init__(self, epsilon):
+        epsilon = float(epsilon)
+        if not (math.isfinite(epsilon) and epsilon >= 0.0):
+            raise ValueError(f"the adversary's epsilon must be finite and >= 0, got {epsilon}")
+        self.epsilon = epsilon
+        self._records, self._mode, self._next = [], None, 0
+
+    def _enter(self, mode):
+        global _adversary
+        if _adversary is not None:
+            raise RuntimeError("an EmbeddingAdversary block is already running: record() and attack() do not nest")
+        _adversary, self._mode, self._next = self, mode, 0
+
+    def _leave(self):
+        global _adversary
+        _adversary, self._mode = None, None
+
+    def record(self):
+        return _AdversaryBlock(self, "record")
+
+    def attack(self):
+        return _AdversaryBlock(self, "attack")
+
+    def recorded(self):
+        """embed_layer_norm calls registered by the last record() and not yet released"""
+        return len(self._records)
+
+    def _embed(self, args, takes_part):
+        ids, word, pad_id, out_dtype = args[0], args[3], args[11], args[12]
+        if not takes_part:
+            return EmbedLNFn.apply(*args)
+        if self._mode == "record":
+            y = EmbedLNFn.apply(*args)
+            self._records.append(None)
+            y.grad_fn.adv_record = (self._records, len(self._records) - 1)      # (grad_fn is the node's ctx)
+            return y
+        k, self._next = self._next, self._next + 1
+        if k >= len(self._records):
+            raise ValueError(f"the adversarial pass makes more embedding calls than the clean pass recorded ({len(self._records)})")
+        if self._records[k] is None:
+            raise ValueError(f"embedding call {k} of the clean pass has no gradient: run backward() between record() and attack()")
+        dz, rids = self._records[k]
+        if rids.shape != ids.shape or dz.shape[-1] != word.shape[1] or dz.dtype != out_dtype:
+            raise ValueError(f"embedding call {k}: the clean pass saw ids {tuple(rids.shape)} and a {dz.dtype} gradient of width "
+                             f"{dz.shape[-1]}, the adversarial pass ids {tuple(ids.shape)}, {out_dtype} and width {word.shape[1]}")
+        S = ids.shape[-1]
+        nseq = ids.numel() // S if S else 0
+        scale = torch.empty(nseq, dtype=torch.float32, device=dz.device)
+        H.check(H.lib().fcmf_adv_scale(H.ptr(dz), H.ptr(rids), H.ptr(scale), nseq, S, dz.shape[-1], pad_id, self.epsilon, H.dt(dz),
+                                       H.stream()), "fcmf_adv_scale")
+        return EmbedLNAdvFn.apply(*args, dz, scale)
+
+
+class _AdversaryBlock:
+    def __init__(self, adv, mode):
+        self.adv, self.mode = adv, mode
+
+    def __enter__(self):
+        a = self.adv
+        if self.mode == "attack" and not a._records:
+            raise ValueError("attack() with nothing recorded: the text embeddings must be trainable (a word table that requires "
+                             "grad, in training mode, with grad enabled) during record()")
+        a._enter(self.mode)
+        if self.mode == "record":
+            a._records = []      # (a new list: a backward of an older pass still deposits into its own)
+        return a
+
+    def __exit__(self, *exc):
+        a = self.adv
+        a._leave()
+        if self.mode == "attack":
+            used, n = a._next, len(a._records)
+            a._records = []
+            if exc[0] is None and used != n:
+                raise ValueError(f"the adversarial pass made {used} embedding calls, the clean pass recorded {n}")
+        return False
+
+
 def embed_layer_norm(ids, pos, tt, word, ptab, ttab, gamma, beta, eps, p, training, pad_id, out_dtype):
     p = float(p) if training else 0.0
+    if _adversary is not None:
+        return _adversary._embed((ids, pos, tt, word, ptab, ttab, gamma, beta, float(eps), p, next_seed() if p > 0 else 0,
+                                  int(pad_id), out_dtype), bool(training) and torch.is_grad_enabled() and word.requires_grad)
     return EmbedLNFn.apply(ids, pos, tt, word, ptab, ttab, gamma, beta, float(eps), p, next_seed() if p > 0 else 0,
                            int(pad_id), out_dtype)
 

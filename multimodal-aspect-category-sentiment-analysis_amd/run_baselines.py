@@ -31,9 +31,10 @@ from fcmf_framework import baselines, ops  # noqa: E402
 from fcmf_framework.dp import GradArena  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
-from train_harness import (add_ema_arguments, add_loss_arguments, averaged, build_extractors, check_ema_arguments,  # noqa: E402
-                           check_loss_arguments, class_weight_tensor, init_run, log_rdrop, make_features, save_model, setup_ema, split_decay,
-                           train_epoch, train_label_table, twice)
+from train_harness import (add_adv_arguments, add_ema_arguments, add_loss_arguments, averaged, build_extractors,  # noqa: E402
+                           check_adv_arguments, check_ema_arguments, check_loss_arguments, class_weight_tensor, init_run, log_adv,
+                           log_rdrop, make_adversary, make_features, save_model, setup_ema, split_decay, train_epoch, train_label_table,
+                           twice)
 from run_multimodal_fcmf import POLARITY_MAP, macro_f1  # noqa: E402
 
 #            model class, checkpoint name before _best / _last (seed filled in), name in the log and result files
@@ -79,6 +80,7 @@ def build_parser():
                    help="nn.TransformerEncoderLayer's dropout between the feed-forward's gelu and its second Linear (ops.set_ffn_dropout)")
     add_loss_arguments(p)
     add_ema_arguments(p)
+    add_adv_arguments(p)
     p.set_defaults(ddp=False)
     return p
 
@@ -208,6 +210,7 @@ def main(argv=None):
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
     weight_request = check_loss_arguments(args)
     check_ema_arguments(args)
+    check_adv_arguments(args)
     cls_name, ckpt, tag = MODELS[args.model]
     ckpt = ckpt.format(seed=args.seed)
     fmt = logging.Formatter('%(asctime)s - %(levelname)s - %(name)s - %(message)s', datefmt='%m/%d/%Y %H:%M:%S')
@@ -266,6 +269,7 @@ def main(argv=None):
         logger.info("training loss: label_smoothing %g focal_gamma %g class_weights %s", args.label_smoothing, args.focal_gamma,
                     args.class_weights)
         log_rdrop(args, logger)
+        log_adv(args, logger)
 
     def loss_fn(batch):
         rdrop = args.rdrop_alpha if model.training else 0.0
@@ -283,7 +287,8 @@ def main(argv=None):
             if resnet_img is not None:
                 resnet_img.train(); resnet_roi.train()
             train_epoch(DevicePrefetcher(train_loader, device, float32_fields=f32_fields), loss_fn, arena=arena, reducer=None,
-                        optimizer=optimizer, scheduler=scheduler, accum=args.gradient_accumulation_steps, log=log)
+                        optimizer=optimizer, scheduler=scheduler, accum=args.gradient_accumulation_steps, log=log,
+                        adversary=make_adversary(args))
             logger.info("--> Epoch %d Completed. LR %.2e last logged loss %.4f", epoch, optimizer.param_groups[0]['lr'], last_loss[0])
             f1 = 0.0
             if dev_loader is not None:

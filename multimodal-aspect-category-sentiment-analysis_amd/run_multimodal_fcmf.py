@@ -42,9 +42,10 @@ from fcmf_framework.dp import GradArena, GradReducer  # noqa: E402
 from fcmf_framework.fcmf_multimodal import FCMF  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
-from train_harness import (add_ema_arguments, add_loss_arguments, averaged, build_extractors, check_ema_arguments,  # noqa: E402
-                           check_loss_arguments, class_weight_tensor, init_run, load_resnets, log_rdrop, make_features, save_extractors,
-                           save_model, setup_ema, split_decay, train_epoch, train_label_table, twice)
+from train_harness import (add_adv_arguments, add_ema_arguments, add_loss_arguments, averaged, build_extractors,  # noqa: E402
+                           check_adv_arguments, check_ema_arguments, check_loss_arguments, class_weight_tensor, init_run, load_resnets,
+                           log_adv, log_rdrop, make_adversary, make_features, save_extractors, save_model, setup_ema, split_decay,
+                           train_epoch, train_label_table, twice)
 
 
 POLARITY_MAP = {0: 'None', 1: 'Negative', 2: 'Neutral', 3: 'Positive'}      # reference :28
@@ -104,6 +105,7 @@ def build_parser():
                              "attention over each photo's patches and ROIs, per review and aspect) into --output_dir")
     add_loss_arguments(parser)
     add_ema_arguments(parser)
+    add_adv_arguments(parser)
     return parser
 
 
@@ -151,6 +153,7 @@ def main(argv=None):
         raise ValueError("Invalid gradient_accumulation_steps parameter: {}, should be >= 1".format(args.gradient_accumulation_steps))
     weight_request = check_loss_arguments(args)
     check_ema_arguments(args)
+    check_adv_arguments(args)
     fmt = logging.Formatter('%(asctime)s - %(levelname)s - %(name)s - %(message)s', datefmt='%m/%d/%Y %H:%M:%S')
     rank, _, world, device, master, logger = init_run(args, "fcmf", "training_fcmf.log", formatter=fmt, script="run_multimodal_fcmf.py")
     args.train_batch_size = int(args.train_batch_size / args.gradient_accumulation_steps)
@@ -255,6 +258,7 @@ def main(argv=None):
         logger.info("training loss: label_smoothing %g focal_gamma %g class_weights %s", args.label_smoothing, args.focal_gamma,
                     args.class_weights)
         log_rdrop(args, logger)
+        log_adv(args, logger)
 
     def loss_fn(batch):
         rdrop = args.rdrop_alpha if model.training else 0.0
@@ -273,7 +277,8 @@ def main(argv=None):
             log = lambda step, loss: logger.info("epoch %d step %d loss %.4f", epoch, step, loss)
             # next batch: pinned, on the copy stream (field 1 = the float64 ROI crops)
             train_epoch(DevicePrefetcher(train_loader, device, float32_fields=(1,)), loss_fn, arena=arena, reducer=reducer,
-                        optimizer=optimizer, scheduler=scheduler, accum=args.gradient_accumulation_steps, log=log if master else None)
+                        optimizer=optimizer, scheduler=scheduler, accum=args.gradient_accumulation_steps, log=log if master else None,
+                        adversary=make_adversary(args))
             if master:
                 logger.info("--> Epoch %d Completed. Encoder LR %.2e Head LR %.2e", epoch,
                             optimizer.param_groups[0]['lr'], optimizer.param_groups[2]['lr'])

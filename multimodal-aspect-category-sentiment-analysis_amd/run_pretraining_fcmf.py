@@ -45,9 +45,9 @@ from fcmf_framework.dp import GradArena, GradReducer  # noqa: E402
 from fcmf_framework.fcmf_pretraining import FCMFSeq2Seq  # noqa: E402
 from fcmf_framework.optimization import FusedAdamW, get_linear_schedule_with_warmup  # noqa: E402
 from device_prefetch import DevicePrefetcher  # noqa: E402
-from train_harness import (add_ema_arguments, add_loss_arguments, averaged, build_extractors, check_ema_arguments,  # noqa: E402
-                           check_loss_arguments, init_run, load_resnets, log_rdrop, make_features, save_extractors, save_model, setup_ema,
-                           split_decay, train_epoch)
+from train_harness import (add_adv_arguments, add_ema_arguments, add_loss_arguments, averaged, build_extractors,  # noqa: E402
+                           check_adv_arguments, check_ema_arguments, check_loss_arguments, init_run, load_resnets, log_adv, log_rdrop,
+                           make_adversary, make_features, save_extractors, save_model, setup_ema, split_decay, train_epoch)
 
 
 DEFAULT_BERT_SCORE_MODEL = 'uitnlp/visobert'      # the reference's default (:53), a hub name
@@ -131,6 +131,7 @@ def build_parser():
                    help="with --synthetic_steps and --do_eval: dev and test sets of N seeded synthetic samples each")
     add_loss_arguments(p, class_weights=False)
     add_ema_arguments(p)
+    add_adv_arguments(p)
     return p
 
 
@@ -207,6 +208,7 @@ def main(argv=None):
                                  f"unbanned (needs >= {need})")
     check_loss_arguments(args)
     check_ema_arguments(args)
+    check_adv_arguments(args)
     rank, _, world, device, master, logger = init_run(args, "iaog", "pretraining_iaog.log", script="run_pretraining_fcmf.py")
 
     tokenizer = None
@@ -402,13 +404,15 @@ def main(argv=None):
         if master:
             logger.info("training loss: label_smoothing %g", args.label_smoothing)
             log_rdrop(args, logger)
+            log_adv(args, logger)
         for epoch in range(start_epoch, int(args.num_train_epochs)):
             model.train()
             if r_img is not None:
                 r_img.train(); r_roi.train()
             log = lambda step, loss: logger.info("epoch %d step %d loss %.4f", epoch, step, loss)
             train_epoch(DevicePrefetcher(make_loader(), device), loss_fn, arena=arena, reducer=reducer, optimizer=optimizer,
-                        scheduler=scheduler, accum=args.gradient_accumulation_steps, log=log if master else None)
+                        scheduler=scheduler, accum=args.gradient_accumulation_steps, log=log if master else None,
+                        adversary=make_adversary(args))
             if evaluate is not None:                                     # reference :376-452; the other ranks wait at the barrier below
                 # (with --ema_decay the decode, the score and the best checkpoint are the averaged weights'; the master alone swaps)
                 with averaged(optimizer, ema):

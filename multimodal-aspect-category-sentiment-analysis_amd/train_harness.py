@@ -84,6 +84,38 @@ def log_rdrop(args, logger):
                 " (two dropout passes per sample + alpha x the batch-mean symmetric KL)" if args.rdrop_alpha > 0 else " (off)")
 
 
+# ---- adversarial training on the text embeddings (ops.EmbeddingAdversary) ---------------------------------------------------------
+def add_adv_arguments(parser):
+    parser.add_argument('--adv_epsilon', default=0.0, type=float,
+                        help="FGM adversarial training (Miyato et al., 2017) on the text encoder's token embeddings: every micro-batch "
+                             "runs a second forward and backward with epsilon * g / ||g||_2 added to each sequence's embeddings (g: the "
+                             "clean pass's gradient there, pad tokens excluded) and the two gradients are summed; 0 = off.  About two "
+                             "steps of time per step; no value is recommended: accuracy has not been measured.  " + EVAL_LOSS_NOTE)
+
+
+def check_adv_arguments(args):
+    """refuses a bad --adv_epsilon with a ValueError that names the flag (call before anything is created or written)
+    -> epsilon, 0.0 = off"""
+    e = args.adv_epsilon
+    if not (math.isfinite(e) and e >= 0.0):
+        raise ValueError(f"--adv_epsilon must be finite and >= 0 (0 = off), got {e}")
+    if e > 0.0 and getattr(args, "freeze_encoder", False):
+        raise ValueError(f"--adv_epsilon {e} perturbs the text embeddings through their gradient: not together with --freeze_encoder")
+    return e
+
+
+def log_adv(args, logger):
+    """the line that goes beside log_rdrop's"""
+    logger.info("training loss: adv_epsilon %g%s", args.adv_epsilon,
+                " (FGM: a second pass per micro-batch on the text embeddings + epsilon x their normalised gradient)"
+                if args.adv_epsilon > 0 else " (off)")
+
+
+def make_adversary(args):
+    """train_epoch's `adversary` as --adv_epsilon asks: an ops.EmbeddingAdversary, or None (off)"""
+    return ops.EmbeddingAdversary(args.adv_epsilon) if args.adv_epsilon > 0 else None
+
+
 def twice(*tensors):
     """every tensor repeated along the batch axis (copy i and copy i + B of sample i): what an R-Drop step feeds the model"""
     return tuple(None if t is None else torch.cat((t, t), dim=0) for t in tensors)
@@ -244,19 +276,37 @@ def make_features(resnet_img, resnet_roi):
     return features
 
 
-def train_epoch(batches, loss_fn, *, arena, reducer, optimizer, scheduler, accum, log=None):
+def train_epoch(batches, loss_fn, *, arena, reducer, optimizer, scheduler, accum, log=None, adversary=None):
     """one epoch (run_multimodal_fcmf.py:427-489, run_pretraining_fcmf.py:284-337): `loss_fn(batch)` accumulates over `accum`
     steps, then the gradients are reduced across ranks (`reducer`, None on one rank), clipped to norm 1.0 and applied; a trailing
-    partial group gets no optimizer step.  `log(step, loss)`, if given, sees the undivided loss of every 10th step."""
+    partial group gets no optimizer step.  `log(step, loss)`, if given, sees the undivided loss of every 10th step.
+    adversary (ops.EmbeddingAdversary): every micro-step is a clean pass under record(), never reduced, then a pass on the
+    perturbed embeddings under attack() whose backward accumulates onto the first as a further micro-step does (temporaries that
+    autograd adds; each backward flushes its own deferred weight gradients when the engine finishes); the logged loss is the
+    clean one."""
     arena.zero()
     for step, batch in enumerate(batches):
-        loss = loss_fn(batch)
-        if accum > 1:
-            loss = loss / accum
         boundary = (step + 1) % accum == 0
+        if adversary is not None:
+            with adversary.record():
+                loss = loss_fn(batch)
+            if accum > 1:
+                loss = loss / accum
+            if reducer is not None:
+                reducer.enabled = False
+            loss.backward()
+            with adversary.attack():
+                adv_loss = loss_fn(batch)
+            if accum > 1:
+                adv_loss = adv_loss / accum
+        else:
+            loss = loss_fn(batch)
+            if accum > 1:
+                loss = loss / accum
+            adv_loss = loss
         if reducer is not None:
             reducer.enabled = boundary                        # all-reduce only the accumulated gradients
-        loss.backward()
+        adv_loss.backward()
         if boundary:
             if reducer is not None:
                 reducer.finish()
